@@ -145,8 +145,8 @@ extern "C" int igs_rast_profile_read(double* ms_sum, long long* count, double* r
 
 extern "C" int igs_rast_version(void) { return IGS_RAST_VERSION; }
 extern "C" const char* igs_rast_last_error(void) { return g_err; }
-// workspace = 256-byte aligned { gacc[P][32] floats | 64 loss shards one cache line apart (refine step) }
-static inline size_t ws_gacc_bytes(int P) { return ((size_t)(P > 0 ? P : 0) * GACC_F * 4 + 255) & ~(size_t)255; }
+// workspace = 256-byte aligned { gacc[P][32] doubles | 64 loss shards one cache line apart (refine step) }
+static inline size_t ws_gacc_bytes(int P) { return ((size_t)(P > 0 ? P : 0) * GACC_F * 8 + 255) & ~(size_t)255; }
 #define WS_LOSS_BYTES 4096
 extern "C" size_t igs_rast_backward_workspace_bytes(int P) { return ws_gacc_bytes(P) + WS_LOSS_BYTES + 512; }
 
@@ -162,7 +162,7 @@ struct FwdExtra {
     bool defer_status = false;          // igs_rast_forward_async / igs_refine_step: do not wait for {R, overflow}
     bool no_latch = false;              // igs_rast_forward_nowait: ... and do not expect an igs_rast_forward_finish either
     bool raw_activations = false;       // igs_refine_step: opacities / scales / rotations are the raw optimiser leaves
-    float* zero_gacc = nullptr;         // ... backward accumulators / loss shards the preprocess kernel zero-fills on the side
+    double* zero_gacc = nullptr;        // ... backward accumulators / loss shards the preprocess kernel zero-fills on the side
     float* zero_loss = nullptr;
     float* zero_loss2 = nullptr;
     bool scratch_clean = false;         // igs_refine_step_args::scratch_clean: the image buffer's binning counters are known clean
@@ -660,8 +660,8 @@ static int backward_impl(
     if (!fuse && (!dL_dmean2D || !dL_dcolor || !dL_dopacity || !dL_dmean3D || !dL_dcov3D || !dL_dscale || !dL_drot || (M > 0 && !dL_dsh)))
         return fail(IGS_RAST_E_INVALID, "igs_rast_backward: NULL output");
 
-    if ((uint64_t)P * GACC_F * 4 >= (1ull << 32))      // (the blend backward addresses its accumulator rows with 32-bit byte offsets)
-        return fail(IGS_RAST_E_INVALID, "igs_rast_backward: more than 33 million Gaussians are not supported");
+    if ((uint64_t)P * GACC_F * 8 >= (1ull << 32))      // (the blend backward addresses its accumulator rows with 32-bit byte offsets)
+        return fail(IGS_RAST_E_INVALID, "igs_rast_backward: more than 16 million Gaussians are not supported");
     const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
     const size_t Tn = (size_t)gx * gy, HW = (size_t)width * height;
     const GeomLayout GL(P);
@@ -670,7 +670,7 @@ static int backward_impl(
     const char* gbase = align_ptr(geom_buffer);
     const char* ibase = align_ptr(image_buffer);
     const char* bbase = binning_buffer ? align_ptr(binning_buffer) : nullptr;
-    float* gacc = (float*)align_ptr((const char*)workspace);
+    double* gacc = (double*)align_ptr((const char*)workspace);
     const float fy = height / (2.0f * tan_fovy), fx = width / (2.0f * tan_fovx);
 
     // NaN report asked for this backward (one-shot, consumed here even if the call fails later)
@@ -696,7 +696,7 @@ static int backward_impl(
     const bool will_compact = !(require_coord && (dL_dpix_coord || dL_dpix_mcoord)) && !(require_depth && (dL_dpix_depth || dL_dpix_mdepth))
                               && !((require_coord || require_depth) && dL_dpixel_normals);
     if (!(fuse && fuse->prezeroed)) {              // (igs_refine_step: the forward's preprocess kernel zero-filled the accumulators)
-        HIP_TRY(zero_fill_async(s, gacc, (size_t)P * (will_compact ? GACC_COMPACT_F : GACC_F) * 4), "zero gacc");
+        HIP_TRY(zero_fill_async(s, gacc, (size_t)P * (will_compact ? GACC_COMPACT_F : GACC_F) * 8), "zero gacc");
         if (l1_gt) HIP_TRY(zero_fill_async(s, loss_shards, WS_LOSS_BYTES), "zero loss shards");
     }
     prof_mark(s, ST_MEMSET);
@@ -862,7 +862,7 @@ extern "C" int igs_refine_step(const igs_refine_step_args* a)
         g_pending.active = false;
         f.prezeroed = 1;
         FwdExtra ex;
-        ex.zero_gacc = (float*)align_ptr((const char*)a->workspace);
+        ex.zero_gacc = (double*)align_ptr((const char*)a->workspace);
         ex.zero_loss = dssim ? ssim_shards : (float*)((char*)ex.zero_gacc + ws_gacc_bytes(a->P));
         ex.zero_loss2 = dssim ? ssim_shards + 1024 : nullptr;
         ex.defer_status = attempt == 0;            // second attempt: synchronous forward, which sorts out its scratch sizes itself

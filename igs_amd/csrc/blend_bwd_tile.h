@@ -246,8 +246,8 @@ __device__ __forceinline__ void blend_bwd_tile(const BlendBwdArgs& a, const uint
     const int rrow = ADJ ? (int)(lane >> 2) : (int)(lane & (64 / LPR - 1)), rpart = ADJ ? (int)(lane & 3) : (int)(lane / (64 / LPR));
     const int rseg = ADJ ? rpart : LPR == 4 ? ((rpart + (int)((SEG_ROT >> (2 * (rrow & 15))) & 3u)) & 3) : rpart;      // which column segment this lane sums
     // gacc slot of compact row `lane` (rows are emitted in slot order with the dead groups left out)
-    // (the colour-only instance packs its 10 moments into slots 0..9 instead: one 64-byte atomic request per row, not two --
-    //  float atomics execute at the memory side in 64-byte requests, ~20 G requests/s for the whole chip)
+    // (the colour-only instance packs its 10 moments into slots 0..9 instead: one 128-byte row of doubles, the moments of one
+    //  Gaussian in one cache line)
     int slot_of_row = ADJ ? (int)(lane >> 2) : (int)lane;
     constexpr bool COMPACT = !COORD && !DEPTH && !NORMAL;
     if (!COMPACT && !COORD && slot_of_row >= 3) slot_of_row += 9;
@@ -265,7 +265,7 @@ __device__ __forceinline__ void blend_bwd_tile(const BlendBwdArgs& a, const uint
     const float4* const my_row = (const float4*)(myred + rrow_c * RED_STRIDE + rseg * (64 / LPR));
     constexpr uint64_t ATOMIC_LANES = ADJ ? (0x1111111111111111ull & ((NROWS >= 16) ? ~0ull : ((1ull << (4 * NROWS)) - 1ull)))
                                           : ((NROWS >= 64) ? ~0ull : ((1ull << NROWS) - 1ull));
-    const uint32_t slot_bytes = 4u * (uint32_t)slot_of_row;
+    const uint32_t slot_bytes = 8u * (uint32_t)slot_of_row;
     auto reduce_row = [&](const float (&mv)[NROWS], const uint32_t gid) {
                 ColWrite<RED_STRIDE * 4, 0, NROWS>::run(myred_m0, mv);
                 // every lane has written its column; the row sums below read what OTHER lanes wrote.  The wave runs in lockstep and
@@ -294,10 +294,11 @@ __device__ __forceinline__ void blend_bwd_tile(const BlendBwdArgs& a, const uint
                         tot = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
                     }
                 }
-                const uint32_t off = gid * (uint32_t)((COMPACT ? GACC_COMPACT_F : GACC_F) * 4) + slot_bytes;
+                const uint32_t off = gid * (uint32_t)((COMPACT ? GACC_COMPACT_F : GACC_F) * 8) + slot_bytes;
+                const double totd = (double)tot;      // double rows: the sum does not depend on the order the atomics land in
                 uint64_t saved;
-                asm volatile("s_and_saveexec_b64 %0, %1\n\tglobal_atomic_add_f32 %2, %3, %4\n\ts_mov_b64 exec, %0"
-                             : "=&s"(saved) : "s"(ATOMIC_LANES), "v"(off), "v"(tot), "s"(a.gacc) : "memory", "scc");
+                asm volatile("s_and_saveexec_b64 %0, %1\n\tglobal_atomic_add_f64 %2, %3, %4\n\ts_mov_b64 exec, %0"
+                             : "=&s"(saved) : "s"(ATOMIC_LANES), "v"(off), "v"(totd), "s"(a.gacc) : "memory", "scc");
     };
     // ---- one (wave, splat) row: `R` hands out the splat's record (q0 = {x, y, conic.x, conic.y}, q1 = {conic.z, opacity, r, g},
     //      q2 = {b, ...}) and its Gaussian id (LdsRec below: the staged LDS copy)

@@ -30,7 +30,12 @@
 //   18,19 dL_dmean2D.xy (NDC-scaled)  20 dL_dmean2D.z (abs sum)
 //   21..23 dL_dconic (x, y, w)  24 dL_dopacity (before coef)
 #define GACC_F 32
-#define GACC_COMPACT_F 16              // row stride of the colour-only instance's 10 moments: one 64-byte atomic request, two Gaussians per line
+#define GACC_COMPACT_F 16              // row stride of the colour-only instance's 10 moments (one 128-byte line per Gaussian)
+// Rows are doubles: every (wave, splat) adds one float per moment.  In float the sum depended on the order the atomics landed in,
+// and Adam (eps 1e-15) spread those last bits over the steps.  In double the sum of a row is exact, so order-independent, while the
+// addends' spread in binades plus log2 of their count stays within 29 bits; beyond that the order can still move the double's last
+// bit, which survives the reader's rounding to float only at a float rounding boundary.  Not a guarantee, a large reduction:
+// measured bit-identical run to run on the benchmark scenes.
 enum { GA_COLOR = 0, GA_VP = 3, GA_CP = 6, GA_TS = 12, GA_RP = 13, GA_NRM = 15, GA_M2D = 18, GA_M2DZ = 20,
        GA_CONIC = 21, GA_OPA = 24, GA_USED = 25 };
 
@@ -114,8 +119,8 @@ struct FwdParams {
     int prefiltered;
     const float *view, *proj, *campos;      // device pointers (transposed 4x4 matrices, camera centre)
     uint32_t* zero_stats = nullptr;     // slab binning on a buffer whose counters are known clean: workgroup 0 zeroes the four status words here
-    int zero_gacc_stride = GACC_F;      // floats per accumulator row to zero (GACC_COMPACT_F when the colour-only backward will run)
-    float* zero_gacc; float* zero_loss; float* zero_loss2;     // refine step: backward accumulators / loss shards to zero-fill on the side (NULL = no)
+    int zero_gacc_stride = GACC_F;      // doubles per accumulator row to zero (GACC_COMPACT_F when the colour-only backward will run)
+    double* zero_gacc; float* zero_loss; float* zero_loss2;     // refine step: backward accumulators / loss shards to zero-fill on the side (NULL = no)
     int raw_activations;                    // refine step: opacities / scales / rotations are the raw optimiser leaves
                                             // (sigmoid / exp / normalize applied here: gaussian_model.py:90-127)
     float* plane_cache = nullptr; uint32_t plane_tag = 0;      // refine step with a plane / depth / normal gradient to come: keep Sigma^-1 (geom_math.h: PlaneCache)
@@ -170,7 +175,7 @@ struct BlendBwdArgs {
     const uint32_t* ranges; const uint32_t* point_list; const float* rec; const float* colors_precomp;
     const float *alphas, *normalmap, *accum_coord, *accum_depth, *normal_length; const uint32_t* n_contrib;
     const float *dL_dpix, *dL_dcoord, *dL_dmcoord, *dL_ddepth, *dL_dmdepth, *dL_dalpha, *dL_dnormal;
-    float* gacc;
+    double* gacc;
     // refine step: L1 loss fused in -- dL_dpix = l1_scale * sign(l1_color - l1_gt), sum |l1_color - l1_gt| -> 64 shards l1_loss[16*s]
     const float *l1_color, *l1_gt; float l1_scale; float* l1_loss;
     // 0: nobody reads dL_dmean2D.z (the absolute screen-space gradient sum the densification statistics use): the colour-only
@@ -187,7 +192,7 @@ struct GeomBwdArgs {
     const float *means3D, *shs, *scales, *rotations, *cov3D_precomp; const int* radii;
     float scale_modifier, tan_fovx, tan_fovy, fx, fy, kernel_size;
     const float *view, *proj, *campos;
-    const float* rec; const float* gacc;
+    const float* rec; const double* gacc;
     int gacc_compact;                       // gacc rows hold {colour 3, Q0, Qx, Qy, Qxx, Qxy, Qyy, Z} in slots 0..9 (colour-only blend instance)
     float *dL_dmean2D, *dL_dcolor, *dL_dopacity, *dL_dmean3D, *dL_dcov3D, *dL_dsh, *dL_dscale, *dL_drot;
     // NaN report (igs_rast_next_backward_options): a thread that writes a NaN stores nan_seq into *nan_host (pinned host memory, device
@@ -223,7 +228,7 @@ struct RefineFuse {
                                                                            // invisible Gaussians zero): what the N > 1 exchange gathers instead of dL/dSH
 };
 hipError_t launch_geom_bwd_adam(hipStream_t s, const GeomBwdArgs& a, const RefineFuse& f);
-hipError_t launch_extract_view_colors(hipStream_t s, int P, const int* radii, const float* rec, const float* gacc, int gacc_compact, bool have_sh, float* color_out);
+hipError_t launch_extract_view_colors(hipStream_t s, int P, const int* radii, const float* rec, const double* gacc, int gacc_compact, bool have_sh, float* color_out);
 #define IGS_MAX_EXCHANGE_VIEWS 64
 hipError_t launch_sh_grad_views(hipStream_t s, int P, int D, int M, int V, const float* means3D, const float* campos_host, const float* gc,
                                 float clamp, float* dsh_out);

@@ -286,19 +286,20 @@ geom_bwd_kernel(const GBArgs args)
 
     if (active && a.radii[idx] > 0) {
         const float4* R4 = (const float4*)(a.rec + (size_t)idx * REC_F);
-        const float4* G4 = (const float4*)(a.gacc + (size_t)idx * ((COLOUR_ONLY || a.gacc_compact) ? GACC_COMPACT_F : GACC_F));
+        const double2* G2 = (const double2*)(a.gacc + (size_t)idx * ((COLOUR_ONLY || a.gacc_compact) ? GACC_COMPACT_F : GACC_F));
+        auto G4 = [&](int k) { const double2 u = G2[2 * k], v = G2[2 * k + 1]; return make_float4((float)u.x, (float)u.y, (float)v.x, (float)v.y); };
         const float4 r0 = R4[0], r1 = R4[1], r2 = R4[2], r4 = R4[4], r5 = R4[5], r6 = R4[6], r7 = R4[7];
         PlaneCacheEntry pce; pce.have = false;
         if (!COLOUR_ONLY && a.plane_cache) pce = plane_cache_fetch(a.plane_cache + (size_t)idx * PLANE_CACHE_F);      // (kernel-uniform condition)
         float4 g0, g1, g2, g3, g4, g5, g6;
         if (COLOUR_ONLY || a.gacc_compact) {
             // colour-only blend instance: {c0 c1 c2 Q0} {Qx Qy Qxx Qxy} {Qyy Z - -}; every plane / depth / normal moment is zero
-            const float4 c0 = G4[0], c1 = G4[1], c2 = G4[2];
+            const float4 c0 = G4(0), c1 = G4(1), c2 = G4(2);
             const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
             g0 = make_float4(c0.x, c0.y, c0.z, 0.f); g1 = z; g2 = z; g3 = z;
             g4 = make_float4(0.f, 0.f, c0.w, c1.x); g5 = make_float4(c1.y, c1.z, c1.w, c2.x); g6 = make_float4(c2.y, 0.f, 0.f, 0.f);
         } else {
-            g0 = G4[0]; g1 = G4[1]; g2 = G4[2]; g3 = G4[3]; g4 = G4[4]; g5 = G4[5]; g6 = G4[6];
+            g0 = G4(0); g1 = G4(1); g2 = G4(2); g3 = G4(3); g4 = G4(4); g5 = G4(5); g6 = G4(6);
         }
         GTL(1);
         // ---- unpack raw moments ----
@@ -870,20 +871,21 @@ hipError_t launch_geom_bwd_adam(hipStream_t s, const GeomBwdArgs& a, const Refin
 // per-Gaussian kernel's `color_out`: channels the SH evaluation clamped at zero (forward.cu:71-73 -> backward.cu:36-40) and
 // Gaussians the view does not see give zero.  Lets the N > 1 exchange start one kernel earlier (RefineFuse::color_event).
 __global__ void __launch_bounds__(256)
-extract_view_colors_kernel(int P, const int* __restrict__ radii, const float* __restrict__ rec, const float* __restrict__ gacc,
+extract_view_colors_kernel(int P, const int* __restrict__ radii, const float* __restrict__ rec, const double* __restrict__ gacc,
                            int stride, int have_sh, float* __restrict__ color_out)
 {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= P) return;
     float3 c = make_float3(0.f, 0.f, 0.f);
     if (have_sh && radii[idx] > 0) {
-        const float4 g = *(const float4*)(gacc + (size_t)idx * stride);
+        const double* gr = gacc + (size_t)idx * stride;
+        const float3 g = make_float3((float)gr[0], (float)gr[1], (float)gr[2]);
         const uint32_t clamped = __float_as_uint(rec[(size_t)idx * REC_F + 30]);      // record word 7.z (preprocess.hip)
         c = make_float3((clamped & 1u) ? 0.f : g.x, (clamped & 2u) ? 0.f : g.y, (clamped & 4u) ? 0.f : g.z);
     }
     color_out[3 * (size_t)idx] = c.x; color_out[3 * (size_t)idx + 1] = c.y; color_out[3 * (size_t)idx + 2] = c.z;
 }
-hipError_t launch_extract_view_colors(hipStream_t s, int P, const int* radii, const float* rec, const float* gacc, int gacc_compact, bool have_sh,
+hipError_t launch_extract_view_colors(hipStream_t s, int P, const int* radii, const float* rec, const double* gacc, int gacc_compact, bool have_sh,
                                       float* color_out)
 {
     hipLaunchKernelGGL(extract_view_colors_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, radii, rec, gacc,

@@ -201,8 +201,8 @@ preprocess_body(const FwdParams& p, const uint32_t blk, float* __restrict__ rec,
             float4* Z4 = (float4*)(p.zero_gacc + (size_t)idx * p.zero_gacc_stride);
             const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-            for (int k = 0; k < GACC_F / 4; k++)
-                if (4 * k < p.zero_gacc_stride) Z4[k] = z;
+            for (int k = 0; k < GACC_F / 2; k++)            // (16 bytes = two doubles per store)
+                if (2 * k < p.zero_gacc_stride) Z4[k] = z;
         }
         if (blk == 0 && threadIdx.x < 64) {
             p.zero_loss[16 * threadIdx.x] = 0.f;

@@ -27,7 +27,7 @@ gout = R.rasterize_gaussians_backward(bg.to(dev), ad["means3D"], radii, E, ad["s
 gr = co.rasterize_backward(st, bg, a["means3D"], None, a["scales"], a["rotations"], None, cam.world_view_transform, cam.full_proj_transform,
                            cam.camera_center, a["shs"], oo["alpha"], oo["normal"], *[grads[k] for k in KEYS], debug_intermediates=True)
 base = (ws.data_ptr() + 255) // 256 * 256 - ws.data_ptr()
-g = ws[base:base + P * 32 * 4].view(torch.float32).view(P, 32).cpu().numpy().astype(np.float64)
+g = ws[base:base + P * 32 * 8].view(torch.float64).view(P, 32).cpu().numpy()          # accumulator rows are doubles
 compact = not (req[0] or req[1])
 print("seed", seed, "P", P, "req", req, "compact", compact, "radius", oo["radii"][w], "xy", st.intermediates()["means2D"][w], "conic_opacity", st.intermediates()["conic_opacity"][w])
 if compact:     # {c0 c1 c2 Q0} {Qx Qy Qxx Qxy} {Qyy Z}

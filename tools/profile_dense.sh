@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_dense_$TAG
 rm -rf $O && mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --scene dense --steps 50 --warmup 10 --no-cpu-baseline > $O/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --scene dense --steps 50 --warmup 10 --no-cpu-baseline > $O/bench_under_rocprof.log 2>&1
 f=$(ls $O/stats/*/*_kernel_stats.csv | head -1)
 python3 - "$f" "$R/profiles/${TAG}_dense_kernel_stats.csv" <<'PY'
 import csv, sys
