@@ -38,10 +38,18 @@ class RefineStepArgs(C.Structure):
                 ("gt_stats", C.c_void_p), ("gt_stats_valid", C.c_int), ("color_ready_event", C.c_void_p)]
 
 
+class RefineMaskArgs(C.Structure):
+    """igs_refine_mask_args (include/igs_rast.h): Gaussians [0, first_trainable) frozen, whole groups frozen by GROUP_* bit."""
+    _fields_ = [("first_trainable", C.c_int), ("frozen_groups", C.c_uint)]
+
+
+GROUP_XYZ, GROUP_ROT, GROUP_SH, GROUP_OPACITY, GROUP_SCALE = 1, 2, 4, 8, 16      # IGS_GROUP_*
+
 EXPORTS = ["igs_rast_version", "igs_rast_last_error", "igs_rast_forward", "igs_rast_backward_workspace_bytes",
            "igs_rast_forward_async", "igs_rast_forward_finish", "igs_rast_forward_nowait", "igs_rast_last_status", "igs_rast_last_posted_status", "igs_rast_hint_scratch_clean", "igs_rast_set_slab_hint", "igs_rast_get_slab_hint", "igs_rast_backward", "igs_rast_mark_visible", "igs_rast_debug_dump",
            "igs_rast_profile_enable", "igs_rast_profile_read", "igs_adam_step", "igs_adam_step_groups", "igs_adam_step_multi", "igs_adam_step_multi_dev", "igs_adam_step_multi_dev_scratch_words", "igs_densify_stats", "igs_densify_remap", "igs_refine_step", "igs_refine_loss_scratch_bytes", "igs_ssim_l1_scratch_bytes", "igs_ssim_l1_loss_fwd_bwd", "igs_ssim_l1_loss_fwd_bwd_cached", "igs_ssim_mean_fwd_bwd", "igs_ssim_gt_stats_bytes", "igs_depth_normal_loss_fwd_bwd", "igs_l1_loss_fwd_bwd", "igs_l1_mean_fwd_bwd", "igs_activate_fwd", "igs_activate_bwd",
-           "igs_sh_grad_from_view_colors", "igs_adam_sh_from_view_colors", "igs_rast_last_backward_instance", "igs_rast_next_backward_options", "igs_rast_nan_report_wait", "igs_rast_nan_report_handle", "igs_rast_nan_report_wait_at", "igs_refine_step_args_size", "igs_rast_debug_poison_lds", "igs_adam_exchange_step", "igs_morton_order", "igs_morton_order_scratch_bytes", "igs_ply_to_params", "igs_params_to_ply", "igs_debug_tile_sort"]
+           "igs_sh_grad_from_view_colors", "igs_adam_sh_from_view_colors", "igs_rast_last_backward_instance", "igs_rast_next_backward_options", "igs_rast_nan_report_wait", "igs_rast_nan_report_handle", "igs_rast_nan_report_wait_at", "igs_refine_step_args_size", "igs_rast_debug_poison_lds", "igs_adam_exchange_step", "igs_morton_order", "igs_morton_order_scratch_bytes", "igs_ply_to_params", "igs_params_to_ply", "igs_debug_tile_sort",
+           "igs_refine_step_masked", "igs_refine_mask_args_size"]
 
 VERSION = 4       # IGS_RAST_VERSION this binding was written against (include/igs_rast.h)
 
@@ -77,6 +85,11 @@ def lib():
     if L.igs_refine_step_args_size() != C.sizeof(RefineStepArgs):
         raise RuntimeError("igs_amd: igs_refine_step_args is %d bytes in the library, %d in the binding"
                            % (L.igs_refine_step_args_size(), C.sizeof(RefineStepArgs)))
+    L.igs_refine_mask_args_size.restype = C.c_size_t
+    L.igs_refine_mask_args_size.argtypes = []
+    if L.igs_refine_mask_args_size() != C.sizeof(RefineMaskArgs):
+        raise RuntimeError("igs_amd: igs_refine_mask_args is %d bytes in the library, %d in the binding"
+                           % (L.igs_refine_mask_args_size(), C.sizeof(RefineMaskArgs)))
     L.igs_rast_last_backward_instance.restype = _i
     L.igs_rast_last_backward_instance.argtypes = []
     L.igs_rast_next_backward_options.restype = None
@@ -135,6 +148,8 @@ def lib():
         L.igs_densify_remap.argtypes = [_vp, _i, _i] + [_vp] * 13
         L.igs_refine_step.restype = _i
         L.igs_refine_step.argtypes = [C.POINTER(RefineStepArgs)]
+        L.igs_refine_step_masked.restype = _i
+        L.igs_refine_step_masked.argtypes = [C.POINTER(RefineStepArgs), C.POINTER(RefineMaskArgs)]
         L.igs_refine_loss_scratch_bytes.restype = C.c_size_t
         L.igs_refine_loss_scratch_bytes.argtypes = [_i, _i]
         L.igs_ssim_l1_scratch_bytes.restype = C.c_size_t

@@ -166,6 +166,7 @@ struct FwdExtra {
     float* zero_loss = nullptr;
     float* zero_loss2 = nullptr;
     bool scratch_clean = false;         // igs_refine_step_args::scratch_clean: the image buffer's binning counters are known clean
+    int zero_gacc_first = 0;            // ... masked refine step: accumulator rows exist for Gaussians [zero_gacc_first, P) only
     bool skip_bwd_state = false;        // ... the loss is colour-only: blend_fwd need not store the geometry branches' backward state
     uint32_t plane_tag = 0;             // ... nonzero: a plane / depth / normal gradient will come back: keep Sigma^-1 per Gaussian under this tag
     // igs_refine_step with the L1 loss: run the colour-only blend backward inside the forward's tile kernel (blend_step.hip).  The
@@ -239,7 +240,7 @@ static int forward_impl(
     fp.kernel_size = kernel_size; fp.prefiltered = prefiltered;
     fp.view = viewmatrix; fp.proj = projmatrix; fp.campos = cam_pos;
     fp.raw_activations = ex.raw_activations ? 1 : 0;
-    fp.zero_gacc = ex.zero_gacc; fp.zero_loss = ex.zero_loss; fp.zero_loss2 = ex.zero_loss2;
+    fp.zero_gacc = ex.zero_gacc; fp.zero_loss = ex.zero_loss; fp.zero_loss2 = ex.zero_loss2; fp.zero_gacc_first = ex.zero_gacc_first;
     if (ex.plane_tag) { fp.plane_cache = (float*)(gbase + GL.planes); fp.plane_tag = ex.plane_tag; }
     fp.zero_gacc_stride = ex.skip_bwd_state ? GACC_COMPACT_F : GACC_F;      // (colour-only loss <=> compact accumulator rows)
     g_last_fwd = LastFwd();
@@ -714,6 +715,7 @@ static int backward_impl(
     ba.l1_gt = l1_gt; ba.l1_color = l1_color; ba.l1_scale = l1_scale; ba.l1_loss = loss_shards;
     ba.want_absgrad = (fuse && !dL_dmean2D) ? 0 : 1;
     ba.tile_order = (const uint32_t*)(ibase + IL.tile_order);    // the forward's blend kernel ordered the tiles heaviest-first
+    ba.first_trainable = fuse ? fuse->first : 0;                 // (masked refine step: frozen splats form no moments)
     bool gacc_compact = will_compact;
     int inst_bits = -1;
     if (fuse && fuse->blend_done) {
@@ -801,7 +803,32 @@ extern "C" size_t igs_refine_loss_scratch_bytes(int width, int height)
 
 extern "C" size_t igs_refine_step_args_size(void) { return sizeof(igs_refine_step_args); }
 
-extern "C" int igs_refine_step(const igs_refine_step_args* a)
+extern "C" size_t igs_refine_mask_args_size(void) { return sizeof(igs_refine_mask_args); }
+
+static int refine_step_impl(const igs_refine_step_args* a, int first, unsigned frozen);
+
+extern "C" int igs_refine_step(const igs_refine_step_args* a) { return refine_step_impl(a, 0, 0u); }
+
+// igs_refine_step on a partitioned store (include/igs_rast.h): Gaussians [0, first_trainable) frozen, whole groups frozen by bit.
+// Every check comes before any HIP call; m == NULL or {0, 0} is igs_refine_step itself.
+extern "C" int igs_refine_step_masked(const igs_refine_step_args* a, const igs_refine_mask_args* m)
+{
+    if (!a) return fail(IGS_RAST_E_INVALID, "igs_refine_step_masked: NULL args");
+    if (!m || (m->first_trainable == 0 && m->frozen_groups == 0u)) return refine_step_impl(a, 0, 0u);
+    if (m->first_trainable < 0 || m->first_trainable > a->P)
+        return fail(IGS_RAST_E_INVALID, "igs_refine_step_masked: first_trainable outside [0, P]");
+    const unsigned known = IGS_GROUP_XYZ | IGS_GROUP_ROT | IGS_GROUP_SH | IGS_GROUP_OPACITY | IGS_GROUP_SCALE;
+    if (m->frozen_groups & ~known) return fail(IGS_RAST_E_INVALID, "igs_refine_step_masked: unknown group bits");
+    if (m->frozen_groups & (IGS_GROUP_XYZ | IGS_GROUP_ROT))
+        return fail(IGS_RAST_E_INVALID, "igs_refine_step_masked: xyz and rotation are always trained (refine_item cannot freeze them)");
+    if (a->grad_out || a->color_grad_out)
+        return fail(IGS_RAST_E_INVALID, "igs_refine_step_masked: grad_out / color_grad_out (the multi-GPU exchange) cannot be combined with a mask");
+    if (a->dL_dmean2D)
+        return fail(IGS_RAST_E_INVALID, "igs_refine_step_masked: dL_dmean2D (densification) cannot be combined with a mask");
+    return refine_step_impl(a, m->first_trainable, m->frozen_groups);
+}
+
+static int refine_step_impl(const igs_refine_step_args* a, int first, unsigned frozen)
 {
     if (!a) return fail(IGS_RAST_E_INVALID, "igs_refine_step: NULL args");
     if (g_pending.active) return fail(IGS_RAST_E_INVALID, "igs_refine_step: an asynchronous forward is pending on this thread; call igs_rast_forward_finish() first");
@@ -825,6 +852,7 @@ extern "C" int igs_refine_step(const igs_refine_step_args* a)
     f.lr_xyz = (float)(a->lr_xyz / bc1); f.lr_rot = (float)(a->lr_rot / bc1); f.lr_sh = (float)(a->lr_sh / bc1);
     f.lr_opacity = (float)(a->lr_opacity / bc1); f.lr_scale = (float)(a->lr_scale / bc1);
     f.clamp = a->clamp_grads;
+    f.first = first; f.frozen_groups = frozen;
     f.color_out = a->color_grad_out;
     f.color_event = a->color_ready_event;
     f.b1 = a->beta1; f.b2 = a->beta2; f.eps = a->eps; f.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
@@ -865,6 +893,7 @@ extern "C" int igs_refine_step(const igs_refine_step_args* a)
         ex.zero_gacc = (double*)align_ptr((const char*)a->workspace);
         ex.zero_loss = dssim ? ssim_shards : (float*)((char*)ex.zero_gacc + ws_gacc_bytes(a->P));
         ex.zero_loss2 = dssim ? ssim_shards + 1024 : nullptr;
+        ex.zero_gacc_first = first;
         ex.defer_status = attempt == 0;            // second attempt: synchronous forward, which sorts out its scratch sizes itself
         ex.raw_activations = true;
         ex.skip_bwd_state = !dn;                   // (colour-only backward instance: see BlendFwdArgs)
@@ -892,6 +921,7 @@ extern "C" int igs_refine_step(const igs_refine_step_args* a)
             fused_bwd.l1_gt = a->gt; fused_bwd.l1_color = color; fused_bwd.l1_scale = l1_scale;
             fused_bwd.l1_loss = (float*)((char*)ex.zero_gacc + ws_gacc_bytes(a->P));
             fused_bwd.want_absgrad = a->dL_dmean2D ? 1 : 0;
+            fused_bwd.first_trainable = first;
             ex.fused_bwd = &fused_bwd; ex.fused_ran = &fused_ran; ex.fused_instance = &fused_inst;
         }
         const int R = forward_impl(a->stream, capture_alloc, &cg, capture_alloc, &cb, capture_alloc, &ci, a->P, a->D, a->M, a->background,

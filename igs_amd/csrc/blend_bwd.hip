@@ -3,7 +3,7 @@
 // The per-tile work and its design notes live in blend_bwd_tile.h (shared with the fused tile kernel of the refine step).
 #include "blend_bwd_tile.h"
 
-template <bool COORD, bool DEPTH, bool NORMAL, bool ABS = true>
+template <bool COORD, bool DEPTH, bool NORMAL, bool ABS = true, bool MASK = false>
 __global__ void __launch_bounds__(256)
 blend_bwd_kernel(const BlendBwdArgs a)
 {
@@ -20,7 +20,7 @@ blend_bwd_kernel(const BlendBwdArgs a)
         tile = a.tile_order[blockIdx.x];
         if (tile >= (uint32_t)(a.gx * a.gy)) return;      // (a corrupt image buffer must not turn into an out-of-bounds access)
     } else if (!tile_for_block(blockIdx.x, a.gx, a.gy, tile)) return;
-    blend_bwd_tile<COORD, DEPTH, NORMAL, ABS, false>(a, tile, chunk, chunk_id, quad_bits, wave_max, red, nullptr);
+    blend_bwd_tile<COORD, DEPTH, NORMAL, ABS, false, MASK>(a, tile, chunk, chunk_id, quad_bits, wave_max, red, nullptr);
 }
 
 hipError_t launch_blend_bwd(hipStream_t s, const BlendBwdArgs& a, bool coord, bool depth, bool* compact_layout, int* instance_bits)
@@ -35,6 +35,14 @@ hipError_t launch_blend_bwd(hipStream_t s, const BlendBwdArgs& a, bool coord, bo
     const bool N = (coord || depth) && a.dL_dnormal;
     if (compact_layout) *compact_layout = !C && !D && !N;
     if (instance_bits) *instance_bits = (C ? 1 : 0) | (D ? 2 : 0) | (N ? 4 : 0) | ((C || (D && !N) || (!D && N) || a.want_absgrad) ? 8 : 0);
+    if (a.first_trainable > 0) {
+        // masked refine step: its losses reach the colour-only and the <depth, normal> instance, never with the |gradient| moment
+        // (igs_refine_step_masked refuses dL_dmean2D); other combinations are refused rather than computed without the mask
+        if (C || a.want_absgrad || (D != N)) return hipErrorInvalidValue;
+        if (D) hipLaunchKernelGGL((blend_bwd_kernel<false, true, true, false, true>), grid, block, 0, s, a);
+        else   hipLaunchKernelGGL((blend_bwd_kernel<false, false, false, false, true>), grid, block, 0, s, a);
+        return hipGetLastError();
+    }
 #define LAUNCH(c, d, n) hipLaunchKernelGGL((blend_bwd_kernel<c, d, n>), grid, block, 0, s, a)
     if (C) { if (D) { if (N) LAUNCH(true, true, true); else LAUNCH(true, true, false); }
              else   { if (N) LAUNCH(true, false, true); else LAUNCH(true, false, false); } }

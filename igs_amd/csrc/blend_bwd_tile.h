@@ -112,7 +112,10 @@ template <bool COORD, bool DEPTH, bool NORMAL, bool ABS> struct BwdCfg {
 // PRE: the per-pixel results of the forward arrive in registers (`pre`, fused kernel) instead of being loaded from the images.
 // LDS (all provided by the kernel): chunk [BCHUNK * NQ] float4, chunk_id [BCHUNK], quad_bits [4][NSW], wave_max [4], red [RED_FLOATS]
 // (16-byte aligned).  Every thread of the workgroup calls it.
-template <bool COORD, bool DEPTH, bool NORMAL, bool ABS, bool PRE>
+// MASK (masked refine step, a.first_trainable > 0): a splat of a frozen Gaussian (gid < a.first_trainable) still runs the alpha / T / D
+// recurrence -- it occludes the trainable ones -- but forms no moments and issues no atomic; the branch is on the splat's id in an
+// SGPR (s_cmp, wave-uniform), and Gaussian gid's accumulator row is gid - a.first_trainable.  MASK = false compiles exactly as before.
+template <bool COORD, bool DEPTH, bool NORMAL, bool ABS, bool PRE, bool MASK = false>
 __device__ __forceinline__ void blend_bwd_tile(const BlendBwdArgs& a, const uint32_t tile, float4* __restrict__ chunk, uint32_t* __restrict__ chunk_id,
                                                uint64_t (*quad_bits)[BwdCfg<COORD, DEPTH, NORMAL, ABS>::NSW], int* wave_max,
                                                float* __restrict__ red_all, const FwdPix* pre)
@@ -294,7 +297,8 @@ __device__ __forceinline__ void blend_bwd_tile(const BlendBwdArgs& a, const uint
                         tot = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
                     }
                 }
-                const uint32_t off = gid * (uint32_t)((COMPACT ? GACC_COMPACT_F : GACC_F) * 8) + slot_bytes;
+                const uint32_t row = MASK ? gid - (uint32_t)a.first_trainable : gid;      // (MASK: gid >= first_trainable here)
+                const uint32_t off = row * (uint32_t)((COMPACT ? GACC_COMPACT_F : GACC_F) * 8) + slot_bytes;
                 const double totd = (double)tot;      // double rows: the sum does not depend on the order the atomics land in
                 uint64_t saved;
                 asm volatile("s_and_saveexec_b64 %0, %1\n\tglobal_atomic_add_f64 %2, %3, %4\n\ts_mov_b64 exec, %0"
@@ -359,6 +363,12 @@ __device__ __forceinline__ void blend_bwd_tile(const BlendBwdArgs& a, const uint
                 const float Snew = last_alpha * Dprev + (1.f - last_alpha) * S;
                 const float dL_dopa = (D - Snew) * T + (-T_final * inv_one_m) * bg_dot_e;
                 S = Snew; Dprev = D; last_alpha = alpha;
+                if constexpr (MASK) {
+                    // frozen splat: the recurrence above has advanced; no moments, no transpose, no atomic.  gid is wave-uniform (a
+                    // broadcast LDS read): readfirstlane puts it in an SGPR, so the test is an s_cmp and a scalar branch
+                    gid = (uint32_t)__builtin_amdgcn_readfirstlane((int)gid);
+                    if (gid < (uint32_t)a.first_trainable) return;
+                }
                 const float q = valid ? (op * dL_dopa) * G : 0.f;
                 const float qdx = q * dx, qdy = q * dy;
 

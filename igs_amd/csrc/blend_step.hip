@@ -26,7 +26,7 @@ extern "C" int igs_debug_blend_timeline(unsigned long long* host, int n)
 #else
 #define BTL(k, val) do { } while (0)
 #endif
-template <bool COORD, bool DEPTH, bool NORMAL, bool ABS>
+template <bool COORD, bool DEPTH, bool NORMAL, bool ABS, bool MASK = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
 blend_step_kernel(const BlendFwdArgs f, const BlendBwdArgs b)
 {
@@ -68,7 +68,7 @@ blend_step_kernel(const BlendFwdArgs f, const BlendBwdArgs b)
     blend_fwd_tile<COORD, DEPTH, NORMAL, true, false>(f, tile, (float4*)smem, quad_bits_f, wave_done, px);
     tile_barrier();           // every wave is done with the forward's staged records: the backward takes the LDS over
     BTL(1, wall_clock64());
-    blend_bwd_tile<false, false, false, ABS, true>(b, tile, (float4*)smem, nullptr, quad_bits_b, wave_max, (float*)(smem + BWD_CHUNK_BYTES), &px);
+    blend_bwd_tile<false, false, false, ABS, true, MASK>(b, tile, (float4*)smem, nullptr, quad_bits_b, wave_max, (float*)(smem + BWD_CHUNK_BYTES), &px);
     BTL(2, wall_clock64());
 }
 
@@ -80,6 +80,13 @@ hipError_t launch_blend_step(hipStream_t s, const BlendFwdArgs& f, const BlendBw
         return hipErrorInvalidValue;
     const dim3 grid(tile_grid_blocks(f.gx, f.gy)), block(256);
     if (instance_bits) *instance_bits = b.want_absgrad ? 8 : 0;
+    if (b.first_trainable > 0) {          // masked refine step (never with the |gradient| moment: dL_dmean2D is refused with a mask)
+        if (b.want_absgrad) return hipErrorInvalidValue;
+        if (coord && depth) hipLaunchKernelGGL((blend_step_kernel<true, true, true, false, true>), grid, block, 0, s, f, b);
+        else if (!coord && !depth) hipLaunchKernelGGL((blend_step_kernel<false, false, false, false, true>), grid, block, 0, s, f, b);
+        else return hipErrorInvalidValue;
+        return hipGetLastError();
+    }
     if (coord && depth) {
         if (b.want_absgrad) hipLaunchKernelGGL((blend_step_kernel<true, true, true, true>), grid, block, 0, s, f, b);
         else hipLaunchKernelGGL((blend_step_kernel<true, true, true, false>), grid, block, 0, s, f, b);

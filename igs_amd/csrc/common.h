@@ -121,6 +121,7 @@ struct FwdParams {
     uint32_t* zero_stats = nullptr;     // slab binning on a buffer whose counters are known clean: workgroup 0 zeroes the four status words here
     int zero_gacc_stride = GACC_F;      // doubles per accumulator row to zero (GACC_COMPACT_F when the colour-only backward will run)
     double* zero_gacc; float* zero_loss; float* zero_loss2;     // refine step: backward accumulators / loss shards to zero-fill on the side (NULL = no)
+    int zero_gacc_first = 0;            // masked refine step: only Gaussians [zero_gacc_first, P) have accumulator rows (row idx - zero_gacc_first)
     int raw_activations;                    // refine step: opacities / scales / rotations are the raw optimiser leaves
                                             // (sigmoid / exp / normalize applied here: gaussian_model.py:90-127)
     float* plane_cache = nullptr; uint32_t plane_tag = 0;      // refine step with a plane / depth / normal gradient to come: keep Sigma^-1 (geom_math.h: PlaneCache)
@@ -182,6 +183,10 @@ struct BlendBwdArgs {
     // instance then drops that moment (its |.| terms, one LDS row, one atomic lane per row)
     int want_absgrad = 1;
     const uint32_t* tile_order = nullptr;      // [T] tile ids, heaviest first (the forward's blend kernel wrote them); NULL: plain XCD-aware order
+    // masked refine step (igs_refine_step_masked): splats of Gaussians below first_trainable are frozen -- they take part in the
+    // transmittance recurrence but form no moments; Gaussian gid >= first_trainable owns accumulator row gid - first_trainable.
+    // 0 = the unmasked instances
+    int first_trainable = 0;
 };
 hipError_t launch_blend_bwd(hipStream_t s, const BlendBwdArgs& a, bool coord, bool depth, bool* compact_layout, int* instance_bits = nullptr);
 // forward + colour-only backward (L1 fused in) of every tile in one kernel (blend_step.hip): igs_refine_step with the L1 loss
@@ -226,6 +231,10 @@ struct RefineFuse {
     int colors_extracted = 0;                                              // (set by backward_impl for the per-Gaussian kernel: color_out is already written)
     float* color_out = nullptr;                                            // [P][3] non-NULL: also write dL/d(colour) of this view (clamped channels and
                                                                            // invisible Gaussians zero): what the N > 1 exchange gathers instead of dL/dSH
+    // masked refine step: Gaussians [0, first) are frozen (the kernel runs over [first, P), accumulator row = gid - first);
+    // frozen_groups = IGS_GROUP_SH / _OPACITY / _SCALE bits: those groups are neither differentiated nor updated
+    int first = 0;
+    unsigned frozen_groups = 0;
 };
 hipError_t launch_geom_bwd_adam(hipStream_t s, const GeomBwdArgs& a, const RefineFuse& f);
 hipError_t launch_extract_view_colors(hipStream_t s, int P, const int* radii, const float* rec, const double* gacc, int gacc_compact, bool have_sh, float* color_out);

@@ -11,6 +11,7 @@
 //  * the conic backward adds kernel_size to a and c, the forward conic does not (backward.cu:377-379);
 //  * no quaternion-normalisation backward (backward.cu:554).
 #include "geom_math.h"
+#include "../../include/igs_rast.h"      // IGS_GROUP_* (masked refine step)
 
 __constant__ float BSH_C0 = 0.28209479177387814f;
 __constant__ float BSH_C1 = 0.4886025119029199f;
@@ -68,6 +69,38 @@ __device__ __forceinline__ float3 sh_backward(int deg, int M, const float* __res
     }
     const int used = (deg + 1) * (deg + 1);
     for (int k = used; k < M; k++) { dsh[3 * k] = 0.f; dsh[3 * k + 1] = 0.f; dsh[3 * k + 2] = 0.f; }
+    const float3 dL_ddir = make_float3(dot3(dx, g), dot3(dy, g), dot3(dz, g));
+    return dnormvdv(dir_orig, dL_ddir);
+}
+
+// The SH backward's contribution to dL_dmean alone (masked refine step with the SH group frozen: xyz is still trained, so dL/dcolour
+// still reaches the mean through the view direction, but no SH gradient is formed).  Same expressions and order as sh_backward.
+__device__ __forceinline__ float3 sh_backward_dir_only(int deg, const float* __restrict__ sh, float3 dir_orig, uint32_t clamped, float3 dL_dcolor)
+{
+    const float len = sqrtf(dot3(dir_orig, dir_orig));
+    const float x = dir_orig.x / len, y = dir_orig.y / len, z = dir_orig.z / len;
+    const float3 g = make_float3((clamped & 1u) ? 0.f : dL_dcolor.x, (clamped & 2u) ? 0.f : dL_dcolor.y, (clamped & 4u) ? 0.f : dL_dcolor.z);
+    auto L = [&](int k) { return make_float3(sh[3 * k], sh[3 * k + 1], sh[3 * k + 2]); };
+    float3 dx = make_float3(0, 0, 0), dy = make_float3(0, 0, 0), dz = make_float3(0, 0, 0);
+    if (deg > 0) {
+        dx = L(3) * (-BSH_C1); dy = L(1) * (-BSH_C1); dz = L(2) * BSH_C1;
+        if (deg > 1) {
+            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+            dx = dx + (L(4) * (BSH_C2[0] * y) + L(6) * (BSH_C2[2] * 2.f * -x) + L(7) * (BSH_C2[3] * z) + L(8) * (BSH_C2[4] * 2.f * x));
+            dy = dy + (L(4) * (BSH_C2[0] * x) + L(5) * (BSH_C2[1] * z) + L(6) * (BSH_C2[2] * 2.f * -y) + L(8) * (BSH_C2[4] * 2.f * -y));
+            dz = dz + (L(5) * (BSH_C2[1] * y) + L(6) * (BSH_C2[2] * 2.f * 2.f * z) + L(7) * (BSH_C2[3] * x));
+            if (deg > 2) {
+                dx = dx + (L(9) * (BSH_C3[0] * 3.f * 2.f * xy) + L(10) * (BSH_C3[1] * yz) + L(11) * (BSH_C3[2] * -2.f * xy)
+                           + L(12) * (BSH_C3[3] * -3.f * 2.f * xz) + L(13) * (BSH_C3[4] * (-3.f * xx + 4.f * zz - yy))
+                           + L(14) * (BSH_C3[5] * 2.f * xz) + L(15) * (BSH_C3[6] * 3.f * (xx - yy)));
+                dy = dy + (L(9) * (BSH_C3[0] * 3.f * (xx - yy)) + L(10) * (BSH_C3[1] * xz)
+                           + L(11) * (BSH_C3[2] * (-3.f * yy + 4.f * zz - xx)) + L(12) * (BSH_C3[3] * -3.f * 2.f * yz)
+                           + L(13) * (BSH_C3[4] * -2.f * xy) + L(14) * (BSH_C3[5] * -2.f * yz) + L(15) * (BSH_C3[6] * -3.f * 2.f * xy));
+                dz = dz + (L(10) * (BSH_C3[1] * xy) + L(11) * (BSH_C3[2] * 4.f * 2.f * yz) + L(12) * (BSH_C3[3] * 3.f * (2.f * zz - xx - yy))
+                           + L(13) * (BSH_C3[4] * 4.f * 2.f * xz) + L(14) * (BSH_C3[5] * (xx - yy)));
+            }
+        }
+    }
     const float3 dL_ddir = make_float3(dot3(dx, g), dot3(dy, g), dot3(dz, g));
     return dnormvdv(dir_orig, dL_ddir);
 }
@@ -248,7 +281,8 @@ extern "C" int igs_debug_geom_timeline(unsigned long long* host, int n)
 // COLOUR_ONLY: the blend backward ran its colour-only instance (compact accumulator rows): every plane / depth / normal moment is an
 // exact zero for every Gaussian, so the plane-fit backward and its eigen-decomposition are not even compiled in -- the general instance
 // needs 256 VGPRs + 86 spilled at 2 waves per SIMD for a block this one never executes (4 spilled here; 73.0 -> 70.6 us).
-template <bool FUSED, int NT, bool COLOUR_ONLY>
+// PARTIAL: masked refine step with frozen groups (RefineFuse::frozen_groups); false compiles exactly the unmasked kernel.
+template <bool FUSED, int NT, bool COLOUR_ONLY, bool PARTIAL = false>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(GEOM_WAVES_PER_EU)))
 geom_bwd_kernel(const GBArgs args)
 {
@@ -279,7 +313,9 @@ geom_bwd_kernel(const GBArgs args)
     float3 o_m2d = make_float3(0, 0, 0), o_color = make_float3(0, 0, 0), o_mean = make_float3(0, 0, 0), o_scale = make_float3(0, 0, 0);
     float o_opacity = 0.f, o_cov[6] = { 0, 0, 0, 0, 0, 0 };
     float4 o_rot = make_float4(0, 0, 0, 0);
-    float* dsh = a.M ? dsh_lds + threadIdx.x * FS : nullptr;
+    // (masked refine step with the SH group frozen: no SH gradient is formed, the launch gives this kernel no LDS rows for it)
+    const bool sh_frozen = PARTIAL && FUSED && (fz.frozen_groups & IGS_GROUP_SH) != 0u;
+    float* dsh = (a.M && !sh_frozen) ? dsh_lds + threadIdx.x * FS : nullptr;
     bool sh_written = false;
     bool found_nan = false;          // (!FUSED, a.nan_host: any NaN among the gradients the reference asserts on, __init__.py:156-162)
     __shared__ float small_lds[FUSED ? NT * 12 : 1];      // xyz 3 | rotation 4 | opacity 1 | scale 3 gradients of every thread
@@ -534,9 +570,13 @@ geom_bwd_kernel(const GBArgs args)
         GTL(2);
         if (a.shs) {
             const float3 dir_orig = mean - make_float3(a.campos[0], a.campos[1], a.campos[2]);
-            const float3 dm = sh_backward(a.D, a.M, a.shs + (size_t)idx * a.M * 3, dir_orig, clamped, o_color, dsh);
-            o_mean = o_mean + dm;
-            sh_written = true;
+            if (sh_frozen) {
+                o_mean = o_mean + sh_backward_dir_only(a.D, a.shs + (size_t)idx * a.M * 3, dir_orig, clamped, o_color);
+            } else {
+                const float3 dm = sh_backward(a.D, a.M, a.shs + (size_t)idx * a.M * 3, dir_orig, clamped, o_color, dsh);
+                o_mean = o_mean + dm;
+                sh_written = true;
+            }
             if constexpr (FUSED) {
                 if (fz.color_out) {
                     fz.color_out[3 * (size_t)idx] = (clamped & 1u) ? 0.f : o_color.x;
@@ -679,14 +719,16 @@ geom_bwd_kernel(const GBArgs args)
                 const int sk[4] = { 3, 4, 1, 3 }, sfirst[4] = { 0, 3, 7, 8 };
                 const float slr[4] = { fz.lr_xyz, fz.lr_rot, fz.lr_opacity, fz.lr_scale };
                 float4 SP[4], SM[4], SV[4];
+                // masked refine step: frozen groups (opacity q = 2, scale q = 3) are neither read nor written (kernel-uniform)
+                const bool qlive[4] = { true, true, !PARTIAL || (fz.frozen_groups & IGS_GROUP_OPACITY) == 0u, !PARTIAL || (fz.frozen_groups & IGS_GROUP_SCALE) == 0u };
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
-                    const bool ok = (int)threadIdx.x < (ng * sk[q]) / 4;
+                    const bool ok = qlive[q] && (int)threadIdx.x < (ng * sk[q]) / 4;
                     const size_t o = sb[q] / 4 + threadIdx.x;
                     if (ok) { SP[q] = ((const float4*)fz.param)[o]; SM[q] = ld_moment((const float4*)fz.exp_avg + o); SV[q] = ld_moment((const float4*)fz.exp_avg_sq + o); }
                 }
                 // -- first batch of the SH span goes out before the small groups are computed
-                const int total4 = (ng * F) >> 2;
+                const int total4 = sh_frozen ? 0 : (ng * F) >> 2;
                 constexpr int UB = 2;
                 float4 HP[UB], HM[UB], HV[UB];
                 auto sh_load = [&](int batch) {
@@ -719,7 +761,7 @@ geom_bwd_kernel(const GBArgs args)
                 if (nbatch > 0) sh_load(0);
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
-                    if ((int)threadIdx.x < (ng * sk[q]) / 4) {
+                    if (qlive[q] && (int)threadIdx.x < (ng * sk[q]) / 4) {
                         float g[4];
 #pragma unroll
                         for (int c = 0; c < 4; c++) { const int e = 4 * (int)threadIdx.x + c, gl = e / sk[q]; g[c] = small_lds[gl * 12 + sfirst[q] + (e - gl * sk[q])]; }
@@ -768,11 +810,12 @@ geom_bwd_kernel(const GBArgs args)
             };
             small_group(fz.off_xyz, 3, 0, fz.lr_xyz);
             small_group(fz.off_rot, 4, 3, fz.lr_rot);
-            small_group(fz.off_opacity, 1, 7, fz.lr_opacity);
-            small_group(fz.off_scale, 3, 8, fz.lr_scale);
+            if (!PARTIAL || !(fz.frozen_groups & IGS_GROUP_OPACITY)) small_group(fz.off_opacity, 1, 7, fz.lr_opacity);
+            if (!PARTIAL || !(fz.frozen_groups & IGS_GROUP_SCALE)) small_group(fz.off_scale, 3, 8, fz.lr_scale);
         }
-        // N > 1 colour exchange: the SH gradient of the step is rebuilt from the gathered colour gradients, this view's is not needed
-        const bool skip_sh = FUSED && fz.grad_out && (fz.color_out || fz.colors_extracted);
+        // N > 1 colour exchange: the SH gradient of the step is rebuilt from the gathered colour gradients, this view's is not needed;
+        // masked refine step with the SH group frozen: nothing to update
+        const bool skip_sh = sh_frozen || (FUSED && fz.grad_out && (fz.color_out || fz.colors_extracted));
         if (!skip_sh) {
         const int total = ng * F;
         float* dst = FUSED ? fz.param + fz.off_sh + (size_t)g0 * F : a.dL_dsh + (size_t)g0 * F;
@@ -857,13 +900,30 @@ hipError_t launch_geom_bwd(hipStream_t s, const GeomBwdArgs& a)
 hipError_t launch_geom_bwd_adam(hipStream_t s, const GeomBwdArgs& a, const RefineFuse& f)
 {
     GBArgs g; g.a = a; g.f = f;
+    if (f.first > 0) {
+        // masked refine step: the kernel sees the P - first trainable Gaussians as a problem of their own -- every per-Gaussian array
+        // and group offset starts at Gaussian `first`; the accumulator rows already do (row gid - first)
+        const size_t F0 = (size_t)f.first;
+        if (f.first > a.P || f.grad_out || f.color_out || a.dL_dmean2D) return hipErrorInvalidValue;
+        g.a.P = a.P - f.first;
+        g.a.radii = a.radii + F0; g.a.rec = a.rec + F0 * REC_F;
+        g.a.means3D = a.means3D + 3 * F0; g.a.scales = a.scales ? a.scales + 3 * F0 : nullptr;
+        g.a.rotations = a.rotations ? a.rotations + 4 * F0 : nullptr; g.a.shs = a.shs ? a.shs + F0 * 3 * a.M : nullptr;
+        if (a.plane_cache) g.a.plane_cache = a.plane_cache + F0 * PLANE_CACHE_F;
+        if (a.cov3D_precomp) g.a.cov3D_precomp = a.cov3D_precomp + 6 * F0;
+        g.f.off_xyz += 3 * F0; g.f.off_rot += 4 * F0; g.f.off_sh += F0 * 3 * a.M; g.f.off_opacity += F0; g.f.off_scale += 3 * F0;
+    }
     constexpr int NT = GEOM_ADAM_THREADS;
-    const size_t lds = a.M ? (size_t)NT * (3 * a.M + 1) * sizeof(float) : 0;
-    int blocks = (a.P + NT - 1) / NT;
+    const size_t lds = (a.M && !(f.frozen_groups & IGS_GROUP_SH)) ? (size_t)NT * (3 * a.M + 1) * sizeof(float) : 0;
+    int blocks = (g.a.P + NT - 1) / NT;
+    if (blocks < 1) blocks = 1;          // (everything frozen: workgroup 0 still posts the loss value)
     const int cap = GEOM_ADAM_BLOCKS;
     if (blocks > cap) blocks = cap;
-    if (a.gacc_compact) hipLaunchKernelGGL((geom_bwd_kernel<true, NT, true>), dim3(blocks), dim3(NT), lds, s, g);
-    else                hipLaunchKernelGGL((geom_bwd_kernel<true, NT, false>), dim3(blocks), dim3(NT), lds, s, g);
+    if (f.frozen_groups) {          // (masked refine step with frozen groups: the instances that test the group bits)
+        if (a.gacc_compact) hipLaunchKernelGGL((geom_bwd_kernel<true, NT, true, true>), dim3(blocks), dim3(NT), lds, s, g);
+        else                hipLaunchKernelGGL((geom_bwd_kernel<true, NT, false, true>), dim3(blocks), dim3(NT), lds, s, g);
+    } else if (a.gacc_compact) hipLaunchKernelGGL((geom_bwd_kernel<true, NT, true>), dim3(blocks), dim3(NT), lds, s, g);
+    else                       hipLaunchKernelGGL((geom_bwd_kernel<true, NT, false>), dim3(blocks), dim3(NT), lds, s, g);
     return hipGetLastError();
 }
 

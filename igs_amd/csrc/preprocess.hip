@@ -197,8 +197,8 @@ preprocess_body(const FwdParams& p, const uint32_t blk, float* __restrict__ rec,
         // refine step: this kernel is latency-bound and leaves the memory pipes idle -- zero-fill the backward's accumulator
         // line of this Gaussian (and the loss shards) here instead of in a 25 MB fill of its own.  AFTER the wave's loads: issued at
         // the top, the stores sat in front of them in the memory pipeline (position loads back after 4.8 us instead of 1.0)
-        if (idx < p.P) {
-            float4* Z4 = (float4*)(p.zero_gacc + (size_t)idx * p.zero_gacc_stride);
+        if (idx < p.P && idx >= p.zero_gacc_first) {          // (masked refine step: rows exist for the trainable Gaussians only)
+            float4* Z4 = (float4*)(p.zero_gacc + (size_t)(idx - p.zero_gacc_first) * p.zero_gacc_stride);
             const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
             for (int k = 0; k < GACC_F / 2; k++)            // (16 bytes = two doubles per store)

@@ -29,23 +29,127 @@ GROUPS = (("xyz", 3), ("rotation", 4), ("opacity", 1), ("scaling", 3), ("shs", 4
 DEFAULT_LRS = dict(xyz=0.0016, rotation=0.01, shs=0.0025, opacity=0.05, scaling=0.005)      # configs/demo.yaml:64-69
 
 
-class GaussianParams:
-    """Flat SoA parameter store + Adam state (replica held by every rank)."""
+# ---- masked refinement (`refine_item` of GaussianModel.load_fromstream, gaussian_model.py:265-348) ----------------------------------
+REFINE_ITEM_KEYS = ("no_shs", "no_opacity", "no_scaling", "use_mask", "use_new_shs", "tracking")
+# refine_item flag -> the group it freezes (xyz and rotation are always trained) and its bit in igs_refine_mask_args::frozen_groups
+FREEZING_FLAGS = (("no_shs", "shs", _cabi.GROUP_SH), ("no_opacity", "opacity", _cabi.GROUP_OPACITY), ("no_scaling", "scaling", _cabi.GROUP_SCALE))
 
-    def __init__(self, raw, device, lrs=None, betas=(0.9, 0.999), eps=1e-15):
+
+def parse_refine_item(refine_item):
+    """`refine_item` as a dict of booleans over REFINE_ITEM_KEYS.  Accepts a mapping or any object with attribute access (an OmegaConf
+    node); a missing key (or None) means False.  use_new_shs / tracking are not supported and raise NotImplementedError."""
+    out = dict.fromkeys(REFINE_ITEM_KEYS, False)
+    if refine_item is None:
+        return out
+    for k in REFINE_ITEM_KEYS:
+        if hasattr(refine_item, "keys") and hasattr(refine_item, "get"):
+            v = refine_item.get(k, False)
+        else:
+            try:
+                v = getattr(refine_item, k)
+            except (AttributeError, KeyError):
+                v = False
+        out[k] = bool(v) if v is not None else False
+    if out["use_new_shs"]:
+        raise NotImplementedError("refine_item.use_new_shs (fresh SH coefficients per frame) is not supported by this build")
+    if out["tracking"]:
+        raise NotImplementedError("refine_item.tracking is not supported by this build")
+    return out
+
+
+def normalize_mask(mask, P):
+    """The Gaussians a mask selects for training, as a bool tensor over P on the host: `mask` is an index tensor (what the
+    reference's select_points_bbox returns) or a bool tensor of length P."""
+    m = torch.as_tensor(mask).detach().cpu()
+    if m.dtype == torch.bool:
+        if m.shape != (P,):
+            raise ValueError("a bool mask must have shape (%d,), got %s" % (P, tuple(m.shape)))
+        return m.clone()
+    if m.is_floating_point() or m.dim() != 1:
+        raise ValueError("a mask is a 1-D index tensor or a bool tensor over the Gaussians")
+    m = m.long()
+    if m.numel() and (int(m.min()) < 0 or int(m.max()) >= P):
+        raise ValueError("mask indices must lie in [0, %d)" % P)
+    out = torch.zeros(P, dtype=torch.bool)
+    out[m] = True
+    return out
+
+
+def partition_order(trainable):
+    """Store order of a partitioned model: perm[i] = original index of the Gaussian at position i -- frozen Gaussians first, trainable
+    ones last, each part in its original order (the reference concatenates its outbox and dynamic tensors the same way)."""
+    t = torch.as_tensor(trainable, dtype=torch.bool)
+    return torch.cat([torch.nonzero(~t).flatten(), torch.nonzero(t).flatten()])
+
+
+def compose_order(order, perm):
+    """Order after reordering a store whose position i held original Gaussian order[i] by `perm` (new position i <- old perm[i])."""
+    return perm.long() if order is None else order[perm.long()]
+
+
+def inverse_order(order):
+    """inv with inv[order[i]] = i: indexing a store's rows with it gives them back in the original order."""
+    inv = torch.empty_like(order)
+    inv[order] = torch.arange(order.numel(), device=order.device, dtype=order.dtype)
+    return inv
+
+
+class GaussianParams:
+    """Flat SoA parameter store + Adam state (replica held by every rank).
+
+    `refine_item` / `mask` mirror load_fromstream: with `use_mask` only the Gaussians `mask` selects are trained, and the store is
+    partitioned -- frozen Gaussians in [0, trainable_from), trainable ones in [trainable_from, P); `no_shs` / `no_opacity` /
+    `no_scaling` freeze whole groups (`frozen_groups`).  `original_order()` undoes the partition with every later sort."""
+
+    def __init__(self, raw, device, lrs=None, betas=(0.9, 0.999), eps=1e-15, refine_item=None, mask=None):
         P = raw["xyz"].shape[0]
         self.device = device
         self.lrs = dict(DEFAULT_LRS if lrs is None else lrs)
         self.betas, self.eps, self.step_count = betas, eps, 0
+        if refine_item is None and mask is not None:
+            refine_item = dict(use_mask=True)          # (a mask on its own means "train what it selects")
+        self.refine_item = parse_refine_item(refine_item)
+        self.frozen_groups = tuple(g for flag, g, _ in FREEZING_FLAGS if self.refine_item[flag])
+        self.frozen_group_bits = sum(b for flag, _, b in FREEZING_FLAGS if self.refine_item[flag])
+        perm = None
+        self.trainable_from, self.mask_num = 0, P
+        if self.refine_item["use_mask"]:
+            if mask is None:
+                raise ValueError("refine_item.use_mask needs a mask (index tensor or bool tensor over the Gaussians)")
+            trainable = normalize_mask(mask, P)
+            self.mask_num = int(trainable.sum())
+            self.trainable_from = P - self.mask_num
+            perm = partition_order(trainable)
         total = sum(k for _, k in GROUPS) * P
         flat = torch.empty(total, dtype=torch.float32, device=device)
         o = 0
         for name, k in GROUPS:
             n = k * P
-            flat[o:o + n].copy_(raw[name].reshape(-1).to(device))
+            src = raw[name]
+            if perm is not None:
+                src = src.index_select(0, perm.to(src.device))
+            flat[o:o + n].copy_(src.reshape(-1).to(device))
             o += n
         self._bind(P, flat, torch.zeros(total, dtype=torch.float32, device=device),
                    torch.zeros(total, dtype=torch.float32, device=device))
+        if perm is not None:
+            self.order = perm.to(device)
+
+    @property
+    def partial(self):
+        """True when only part of the model is trained (a partition or frozen groups)."""
+        return self.trainable_from > 0 or self.frozen_group_bits != 0
+
+    def trainable_spans(self):
+        """[(group, float offset, float count)] of what Adam updates: the trainable sub-span of every group that is not frozen."""
+        F, P = self.trainable_from, self.P
+        out = []
+        for name, k in GROUPS:
+            if name in self.frozen_groups:
+                continue
+            o, _ = self.spans[name]
+            out.append((name, o + k * F, k * (P - F)))
+        return out
 
     def _bind(self, P, flat, exp_avg, exp_avg_sq):
         """(Re)binds the store to flat buffers of P Gaussians: spans, aliasing leaves and a fresh gradient buffer."""
@@ -74,18 +178,26 @@ class GaussianParams:
         had when the store was created -- `original_order()` undoes every sort so far."""
         import ctypes as C
         xyz = self.leaves["xyz"].detach().contiguous()
-        lohi = torch.cat([xyz.min(dim=0).values, xyz.max(dim=0).values]).contiguous()      # stays on the device: no host read-back
         Lb = _cabi.lib()
         perm = torch.empty(self.P, dtype=torch.int32, device=self.device)
         need = Lb.igs_morton_order_scratch_bytes(self.P)
         if getattr(self, "_morton_scratch", None) is None or self._morton_scratch.numel() < need:
             self._morton_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            # keys, identity and the stable radix sort are the library's own (sort.hip); same order as torch.argsort(code, stable=True)
-            rc = Lb.igs_morton_order(torch.cuda.current_stream(self.device).cuda_stream, self.P, xyz.data_ptr(), lohi.data_ptr(), bits,
-                                     self._morton_scratch.data_ptr(), perm.data_ptr())
-        if rc != 0:
-            raise RuntimeError("igs_morton_order failed: %d" % rc)
+        # a partitioned store is sorted part by part: frozen Gaussians stay in [0, trainable_from), trainable ones behind them
+        F = self.trainable_from
+        for lo, hi in ((0, F), (F, self.P)):
+            if hi <= lo:
+                continue
+            sub = xyz[lo:hi]
+            lohi = torch.cat([sub.min(dim=0).values, sub.max(dim=0).values]).contiguous()      # stays on the device: no host read-back
+            with torch.cuda.device(self.device):
+                # keys, identity and the stable radix sort are the library's own (sort.hip); same order as torch.argsort(code, stable=True)
+                rc = Lb.igs_morton_order(torch.cuda.current_stream(self.device).cuda_stream, hi - lo, sub.data_ptr(), lohi.data_ptr(), bits,
+                                         self._morton_scratch.data_ptr(), perm[lo:hi].data_ptr())
+            if rc != 0:
+                raise RuntimeError("igs_morton_order failed: %d" % rc)
+            if lo > 0:
+                perm[lo:hi] += lo
         P = self.P
         new = [torch.empty_like(self.flat) for _ in range(3)]
         off = (C.c_size_t * 5)(*[self.spans[n][0] for n in ("xyz", "rotation", "shs", "opacity", "scaling")])
@@ -97,16 +209,16 @@ class GaussianParams:
             raise RuntimeError("igs_densify_remap failed: %d" % rc)
         prev = getattr(self, "order", None)
         self._bind(P, *new)
-        self.order = perm.long() if prev is None or prev.numel() != P else prev[perm.long()]
+        self.order = compose_order(prev if prev is not None and prev.numel() == P else None, perm)
         return perm
 
     def original_order(self):
-        """Raw leaves permuted back to the order the store was created with (valid while no densification changed the set)."""
+        """Raw leaves permuted back to the order the store was created with -- the partition of a masked store and every sort undone
+        (convert2stream, gaussian_model.py:350-367; valid while no densification changed the set)."""
         out = {}
         inv = None
         if getattr(self, "order", None) is not None and self.order.numel() == self.P:
-            inv = torch.empty_like(self.order)
-            inv[self.order] = torch.arange(self.P, device=self.order.device)
+            inv = inverse_order(self.order)
         for k, v in self.leaves.items():
             out[k] = v.detach()[inv] if inv is not None else v.detach()
         return out
@@ -140,12 +252,14 @@ class GaussianParams:
         key = "_adam_groups_small" if skip_sh else "_adam_groups"
         if not hasattr(self, key):
             import ctypes as C
-            names = [n for n, _ in GROUPS if not (skip_sh and n == "shs")]
-            k = len(names)
-            setattr(self, key, ((C.c_size_t * k)(*[self.spans[n][0] for n in names]),
-                                (C.c_size_t * k)(*[self.spans[n][1] for n in names]),
-                                (C.c_float * k)(*[self.lrs[n] for n in names]), k))
+            # (a partially trained store: the trainable sub-span of every group that is not frozen)
+            spans = [(n, o, c) for n, o, c in self.trainable_spans() if not (skip_sh and n == "shs") and c > 0]
+            k = len(spans)
+            setattr(self, key, ((C.c_size_t * k)(*[o for _, o, _ in spans]), (C.c_size_t * k)(*[c for _, _, c in spans]),
+                                (C.c_float * k)(*[self.lrs[n] for n, _, _ in spans]), k))
         off, cnt, lrs, k = getattr(self, key)
+        if k == 0:
+            return                      # (everything frozen)
         rc = L.igs_adam_step_groups(stream, k, off, cnt, lrs, self.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
                                     self.exp_avg_sq.data_ptr(), b1, b2, self.eps, bc1, bc2s)
         if rc != 0:
@@ -310,6 +424,12 @@ class Refiner:
         self.densify_log = []
         # bench.py: HIP-event pairs around the collectives of the N > 1 step (None = not recorded)
         self.exchange_events = None
+        if getattr(params, "partial", False):
+            # masked refinement (refine_item / mask of GaussianParams) is built for one GPU and a fixed Gaussian set
+            if densify is not None:
+                raise NotImplementedError("densify-and-prune with a mask or frozen groups (refine_item) is not supported")
+            if world_size > 1:
+                raise NotImplementedError("multi-GPU refinement (world_size > 1) with a mask or frozen groups (refine_item) is not supported")
 
     class _Timed:
         """Brackets a group of collectives with events on the current stream (the collective's own stream is joined to it)."""
@@ -474,7 +594,11 @@ class Refiner:
             a.color_ready_event = None
         a.scratch_clean = 0 if os.environ.get("IGS_SCRATCH_CLEAN") == "0" else 1      # (RasterBuffers: zero-filled at allocation, touched by this library only)
         with torch.cuda.device(dev):
-            nr = L.igs_refine_step(C.byref(a))
+            if p.partial:      # frozen Gaussians [0, trainable_from) and / or frozen groups: the masked entry point
+                m = _cabi.RefineMaskArgs(p.trainable_from, p.frozen_group_bits)
+                nr = L.igs_refine_step_masked(C.byref(a), C.byref(m))
+            else:
+                nr = L.igs_refine_step(C.byref(a))
         _rast._check(nr, "igs_refine_step")
         if a.gt_stats:
             self.gt_stats.confirm(self._view)              # filled (or read) by a call that succeeded
@@ -621,7 +745,8 @@ class Refiner:
         picks = getattr(self, "last_picks", None) if explicit_view is None else None
         if 1 < self.world_size <= 64 and self.fused and self.exchange == "colors" and picks is not None:      # (the library takes at most 64 views)
             return self._colour_exchange_step(cam, gt, picks)
-        pkg = self._fused_step(cam, gt, grads_only=True) if self.fused else self._native_step(cam, gt)
+        # (a partially trained store: the native launches end in the full gradient, the optimiser steps the trainable spans only)
+        pkg = self._fused_step(cam, gt, grads_only=True) if self.fused and not p.partial else self._native_step(cam, gt)
         if self.world_size > 1:
             import torch.distributed as dist
             with self._Timed(self):
@@ -730,9 +855,12 @@ class Refiner:
             b1, b2 = p.betas
             bc1, bc2s = 1.0 - b1 ** p.step_count, math.sqrt(1.0 - b2 ** p.step_count)
             stream = torch.cuda.current_stream(p.device).cuda_stream
+            live = {n: (o, cnt) for n, o, cnt in p.trainable_spans()}          # (a masked store: trainable sub-spans of unfrozen groups)
             for n, g in zip(names, grads):
-                o, cnt = p.spans[n]
-                g = g.contiguous()
+                if n not in live or live[n][1] == 0:
+                    continue
+                o, cnt = live[n]
+                g = g.contiguous().view(-1)[o - p.spans[n][0]:]
                 rc = L.igs_adam_step(stream, cnt, p.flat.data_ptr() + 4 * o, g.data_ptr(), p.exp_avg.data_ptr() + 4 * o,
                                      p.exp_avg_sq.data_ptr() + 4 * o, p.lrs[n], b1, b2, p.eps, bc1, bc2s)
                 if rc != 0:

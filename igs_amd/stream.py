@@ -39,9 +39,13 @@ class SyntheticStream:
 
 
 def run_stream(raw, cams, bg, frames, refine_iterations=50, device="cuda", loss="l1_ssim", densify=None, source=None, lrs=None,
-               world_size=1, rank=0, spatial_sort=True, log=None, lambda_depth_normal=0.0):
-    """Refines `raw` through `frames` frames; returns a list of per-frame dicts {psnr_before, psnr_after, seconds, num_gaussians}.
-    `source.next_frame()` supplies each frame's ground-truth images (default: SyntheticStream)."""
+               world_size=1, rank=0, spatial_sort=True, log=None, lambda_depth_normal=0.0, refine_item=None, mask=None, states=None):
+    """Refines `raw` through `frames` frames; returns a list of per-frame dicts {psnr_before, psnr_after, seconds, num_gaussians,
+    mask_num}.  `source.next_frame()` supplies each frame's ground-truth images (default: SyntheticStream).
+    `refine_item` / `mask` as GaussianParams takes them (load_fromstream); mask="dynamic" takes each frame's mask from the source
+    (`source.dynamic`, over the Gaussians in their original order).  A partially trained frame hands its Gaussians on in their
+    original order (convert2stream), so a mask keeps indexing the same Gaussians from frame to frame.  `states`: a list that receives
+    the raw parameters each frame hands on."""
     dev = torch.device(device)
     cams = [c.to(dev) for c in cams]
     bg = bg.to(dev)
@@ -51,7 +55,10 @@ def run_stream(raw, cams, bg, frames, refine_iterations=50, device="cuda", loss=
     for f in range(frames):
         gts = source.next_frame()
         # load_fromstream (gaussian_model.py:265-348): new leaves and a NEW optimizer for every frame
-        params = GaussianParams(cur, dev, lrs=lrs)
+        m = source.dynamic if isinstance(mask, str) and mask == "dynamic" else mask
+        if isinstance(mask, str) and mask != "dynamic":
+            raise ValueError("mask: an index / bool tensor or \"dynamic\"")
+        params = GaussianParams(cur, dev, lrs=lrs, refine_item=refine_item, mask=m)
         if spatial_sort:
             params.spatial_sort()
         ref = Refiner(params, cams, gts, bg, loss=loss, world_size=world_size, rank=rank, seed=f, densify=densify,
@@ -67,10 +74,15 @@ def run_stream(raw, cams, bg, frames, refine_iterations=50, device="cuda", loss=
         dt = time.perf_counter() - t0
         with torch.no_grad():
             p1 = float(psnr(render(params.activated(), cams[0], bg)["images_pred"], gts[0]))
-        rec = dict(frame=f, psnr_before=p0, psnr_after=p1, seconds=dt, num_gaussians=params.P,
+        rec = dict(frame=f, psnr_before=p0, psnr_after=p1, seconds=dt, num_gaussians=params.P, mask_num=params.mask_num,
                    gaussians_per_s=params.P * refine_iterations * world_size / dt)
         out.append(rec)
         if log:
             log(rec)
-        cur = {k: v.detach().clone() for k, v in params.leaves.items()}          # convert2stream: next frame starts from here
+        if params.partial:          # convert2stream: partition and sort undone
+            cur = {k: v.clone() for k, v in params.original_order().items()}
+        else:
+            cur = {k: v.detach().clone() for k, v in params.leaves.items()}      # convert2stream: next frame starts from here
+        if states is not None:
+            states.append(cur)
     return out

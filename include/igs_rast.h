@@ -347,6 +347,26 @@ typedef struct igs_refine_step_args {
 int igs_refine_step(const igs_refine_step_args* args);
 size_t igs_refine_step_args_size(void);       /* sizeof(igs_refine_step_args) of the loaded library: bindings check it before the first call */
 
+/* Masked refinement (the `refine_item` of the reference's GaussianModel.load_fromstream): only part of the model is trained.
+ * The store is partitioned by the caller: Gaussians [0, first_trainable) are frozen, [first_trainable, P) are trained.  A frozen
+ * Gaussian still renders and still occludes the others; its parameters and Adam moments are not touched.  `frozen_groups` freezes
+ * whole parameter groups of the trained Gaussians as well (no_shs / no_opacity / no_scaling); xyz and rotation are always trained.
+ * The blend backward forms no moments for frozen splats, the per-Gaussian backward and Adam run over [first_trainable, P) only, and
+ * only those rows of the accumulator workspace are used.  m == NULL or {0, 0}: exactly igs_refine_step.
+ * IGS_RAST_E_INVALID (before any HIP call) for first_trainable outside [0, P], unknown group bits, a frozen xyz / rotation,
+ * and for grad_out / color_grad_out / dL_dmean2D combined with a mask that freezes anything. */
+#define IGS_GROUP_XYZ      1u
+#define IGS_GROUP_ROT      2u
+#define IGS_GROUP_SH       4u
+#define IGS_GROUP_OPACITY  8u
+#define IGS_GROUP_SCALE   16u
+typedef struct igs_refine_mask_args {
+    int first_trainable;                      /* Gaussians [0, first_trainable) are frozen; 0 = all trainable */
+    unsigned frozen_groups;                   /* IGS_GROUP_SH | IGS_GROUP_OPACITY | IGS_GROUP_SCALE (xyz / rotation cannot be frozen) */
+} igs_refine_mask_args;
+int igs_refine_step_masked(const igs_refine_step_args* args, const igs_refine_mask_args* m);
+size_t igs_refine_mask_args_size(void);       /* sizeof(igs_refine_mask_args) of the loaded library */
+
 /* Multi-GPU refine step (extension; views are sharded over the ranks): dL/dSH of the step = sum over its views of
  * basis(direction_v) x dL/dcolour_v (backward.cu:21-140, the W(k, b) rows of the SH backward).  Every rank all-gathers the
  * 3-float colour gradients of all views (`color_grad_out` of igs_refine_step: 12 bytes per Gaussian and view instead of a
