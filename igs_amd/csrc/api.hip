@@ -175,6 +175,9 @@ struct FwdExtra {
     BlendBwdArgs* fused_bwd = nullptr;
     bool* fused_ran = nullptr;
     int* fused_instance = nullptr;
+    // igs_rast_count_gaussians: vanilla preprocess (dilated conic, raw opacity) and the counting colour-only blend (blend_count.hip);
+    // the per-Gaussian pixel counts land here (zeroed by the preprocess of every attempt, so a redone frame counts once)
+    int* count = nullptr;
 };
 // where the last slab-binned forward left its device-side validity words (refine step guards)
 struct LastFwd { const uint32_t* overflow = nullptr; const uint32_t* prefilter = nullptr; };
@@ -204,7 +207,7 @@ static int forward_impl(
     if (!geometry_buffer || !binning_buffer || !image_buffer) return fail(IGS_RAST_E_INVALID, "igs_rast_forward: NULL scratch callback");
     if (!means3D || !opacities || !viewmatrix || !projmatrix || !cam_pos || !background || !radii)
         return fail(IGS_RAST_E_INVALID, "igs_rast_forward: NULL required input");
-    if (!out_color || !out_coord || !out_mcoord || !out_depth || !out_mdepth || !out_alpha || !out_normal)
+    if (!out_color || (!ex.count && (!out_coord || !out_mcoord || !out_depth || !out_mdepth || !out_alpha || !out_normal)))
         return fail(IGS_RAST_E_INVALID, "igs_rast_forward: NULL output");
     if (!colors_precomp && !shs) return fail(IGS_RAST_E_INVALID, "igs_rast_forward: neither shs nor colors_precomp");
     if (!cov3D_precomp && (!scales || !rotations)) return fail(IGS_RAST_E_INVALID, "igs_rast_forward: neither scales/rotations nor cov3D_precomp");
@@ -243,6 +246,7 @@ static int forward_impl(
     fp.zero_gacc = ex.zero_gacc; fp.zero_loss = ex.zero_loss; fp.zero_loss2 = ex.zero_loss2; fp.zero_gacc_first = ex.zero_gacc_first;
     if (ex.plane_tag) { fp.plane_cache = (float*)(gbase + GL.planes); fp.plane_tag = ex.plane_tag; }
     fp.zero_gacc_stride = ex.skip_bwd_state ? GACC_COMPACT_F : GACC_F;      // (colour-only loss <=> compact accumulator rows)
+    const bool vanilla = ex.count != nullptr;
     g_last_fwd = LastFwd();
 
     const size_t counter_bytes = (COUNTER_SHARDS + 1) * COUNTER_SHARD_STRIDE * 4;
@@ -285,7 +289,7 @@ static int forward_impl(
         else HIP_TRY(zero_fill_async(s, tile_count, IL.zero_end - IL.tile_count), "zero tile counters");   // tile_count + stats + counters
         g_counters_dirty = true;
         prof_mark(s, ST_GAP);
-        HIP_TRY(launch_preprocess_fwd(s, fp, rec, tiles, nullptr, nullptr, radii, counters, nullptr, 0, tile_count, pairs, slab_size),
+        HIP_TRY(launch_preprocess_fwd(s, fp, rec, tiles, nullptr, nullptr, radii, counters, nullptr, 0, tile_count, pairs, slab_size, ex.count),
                 "preprocess_fwd launch");
         DBG_SYNC("preprocess_fwd");
         prof_mark(s, ST_PREPROCESS);
@@ -310,7 +314,7 @@ static int forward_impl(
         sort_geometry((uint32_t)P, &dnb, &dper);
         HIP_TRY(hipMemsetAsync(ghist, 0, (size_t)256 * SORT_MAX_BLOCKS * 4, s), "memset depth-sort histogram 0");
         prof_mark(s, ST_GAP);
-        HIP_TRY(launch_preprocess_fwd(s, fp, rec, tiles, keys_a, vals_a, radii, counters, ghist, dper, nullptr, nullptr, 0), "preprocess_fwd launch");
+        HIP_TRY(launch_preprocess_fwd(s, fp, rec, tiles, keys_a, vals_a, radii, counters, ghist, dper, nullptr, nullptr, 0, ex.count), "preprocess_fwd launch");
         DBG_SYNC("preprocess_fwd");
         prof_mark(s, ST_PREPROCESS);
         // instance count: read back while the depth sort runs
@@ -389,7 +393,10 @@ static int forward_impl(
     g_status_stream = s;
     const bool fuse_tiles = ex.fused_bwd && ex.skip_bwd_state && slab_pending && !colors_precomp && (require_coord != 0) == (require_depth != 0);
     if (ex.fused_ran) *ex.fused_ran = fuse_tiles;
-    if (fuse_tiles) {
+    if (vanilla) {
+        ba.tile_order = nullptr;                 // (no backward follows a count pass)
+        HIP_TRY(launch_blend_count(s, ba, ex.count), "blend_count launch");
+    } else if (fuse_tiles) {
         BlendBwdArgs& bb = *ex.fused_bwd;
         bb.W = width; bb.H = height; bb.gx = gx; bb.gy = gy; bb.fx = fp.fx; bb.fy = fp.fy; bb.bg = background;
         bb.ranges = ranges; bb.point_list = point_list; bb.rec = rec; bb.colors_precomp = nullptr;
@@ -458,6 +465,41 @@ extern "C" int igs_rast_forward(
                         cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, kernel_size, prefiltered, out_color,
                         out_coord, out_mcoord, out_depth, out_mdepth, out_alpha, out_normal, radii, require_coord, require_depth,
                         debug, radix, 0, ex0);
+}
+
+// The count pass of the compress rasterizer (CudaRasterizer::Rasterizer::forwardCount, compress rasterizer_impl.cu:441-530): vanilla
+// preprocess, the same binning (slab, or the global sort), the counting colour-only blend, then score = count x opacity over P.
+// Returns num_rendered or a negative code; every argument is checked before the first HIP call.
+extern "C" int igs_rast_count_gaussians(
+    void* stream,
+    igs_rast_alloc_fn geometry_buffer, void* geometry_user, igs_rast_alloc_fn binning_buffer, void* binning_user,
+    igs_rast_alloc_fn image_buffer, void* image_user,
+    int P, int D, int M, const float* background, int width, int height,
+    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
+    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+    const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+    float tan_fovx, float tan_fovy, int prefiltered,
+    float* out_color, int* count, float* score, int* radii, int debug)
+{
+    hipStream_t s = (hipStream_t)stream;
+    const bool hint_clean = g_hint_clean; g_hint_clean = false;      // (consumed by this call, even a refused one)
+    if (P < 0 || width <= 0 || height <= 0) return fail(IGS_RAST_E_INVALID, "igs_rast_count_gaussians: bad sizes");
+    if (g_pending.active) return fail(IGS_RAST_E_INVALID, "igs_rast_count_gaussians: an asynchronous forward is pending on this thread; call igs_rast_forward_finish() first");
+    if (P == 0) return 0;                                       // rasterize_points.cu CountGaussiansCUDA: nothing is launched
+    if (!out_color || !count || !score || !radii) return fail(IGS_RAST_E_INVALID, "igs_rast_count_gaussians: NULL output");
+    prof_new_frame();
+    const char* e = getenv("IGS_BINNING");                    // "radix" forces the global-sort path (tests)
+    const bool radix = e && strcmp(e, "radix") == 0;
+    FwdExtra ex; ex.scratch_clean = hint_clean; ex.count = count;
+    const int R = forward_impl(stream, geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M,
+                               background, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+                               cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, 0.0f, prefiltered, out_color,
+                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, radii, 0, 0, debug, radix, 0, ex);
+    if (R < 0) return R;
+    // (after the frame is final: a slab overflow has redone it inside forward_impl)
+    HIP_TRY(launch_count_score(s, P, count, opacities, score), "count_score launch");
+    DBG_SYNC("count_score");
+    return R;
 }
 
 // Asynchronous variant for callers that keep enqueueing work (the native refine step): identical to igs_rast_forward but

@@ -130,7 +130,7 @@ struct FwdParams {
 // ---- launchers (each returns hipError_t of the launch) ----
 hipError_t launch_preprocess_fwd(hipStream_t s, const FwdParams& p, float* rec, uint32_t* tiles, uint32_t* depth_keys,
                                  uint32_t* ident, int* radii, uint32_t* counters, uint32_t* hist0, uint32_t per_block,
-                                 uint32_t* tile_count, uint64_t* pairs, uint32_t slab);
+                                 uint32_t* tile_count, uint64_t* pairs, uint32_t slab, int* count = nullptr);
 void sort_geometry(uint32_t n, uint32_t* nb, uint32_t* per);
 hipError_t launch_tile_sort(hipStream_t s, uint32_t T, uint32_t* tile_count, const uint64_t* pairs, uint32_t* point_list,
                             uint32_t* ranges, uint32_t slab, uint32_t* stats, uint32_t* counters, uint32_t P,
@@ -169,6 +169,9 @@ struct BlendFwdArgs {
     const uint32_t* step_order = nullptr; uint32_t* reset_cursors = nullptr;
 };
 hipError_t launch_blend_fwd(hipStream_t s, const BlendFwdArgs& a, bool coord, bool depth);
+// count_gaussians (blend_count.hip): colour-only blend that also counts, per Gaussian, the pixels it is blended into
+hipError_t launch_blend_count(hipStream_t s, const BlendFwdArgs& a, int* count);
+hipError_t launch_count_score(hipStream_t s, int P, const int* count, const float* opacities, float* score);
 
 struct BlendBwdArgs {
     int W, H, gx, gy;

@@ -2,6 +2,7 @@
 // Replaces FORWARD::preprocess / preprocessCUDA (DGR/cuda_rasterizer/forward.cu:307-423), checkFrustum
 // (rasterizer_impl.cu:54-66) and the tiles_touched reduction that the reference does with cub::DeviceScan.
 #include "geom_math.h"
+#include <type_traits>
 
 __constant__ float SH_C0 = 0.28209479177387814f;
 __constant__ float SH_C1 = 0.4886025119029199f;
@@ -37,6 +38,7 @@ __device__ __forceinline__ float3 sh_to_rgb(int deg, const float* __restrict__ s
 }
 
 struct PreArgs { FwdParams p; };
+struct PreArgsCount { FwdParams p; int* zero_count; };
 
 // The kernel is latency-bound: a view sees ~40 % of the Gaussians, in Morton order whole waves are culled, and the ~1250 waves that do
 // have work each walk one serial chain (loads -> EWA -> plane fit -> SH -> record -> binning round trips) on a SIMD they have nearly to
@@ -45,6 +47,10 @@ struct PreArgs { FwdParams p; };
 //   ROLE_RECORD : the same cull tests (same arithmetic, so the same verdict), then plane fit, SH -> RGB and the 128-byte record
 // The EWA projection is computed twice; the machine has the room (preprocess 43.5 -> see DESIGN.md section 5).  ROLE_BOTH is the unsplit
 // kernel (-DPRE_NO_SPLIT).
+// VANILLA: the preprocess of the compress rasterizer's count pass (vanilla 3DGS, compress-diff-gaussian-rasterization forward.cu:74-262):
+// the 2-D covariance dilated by 0.3 on its diagonal, the raw opacity (no RaDe-GS compensation), no plane fit; radius, rectangle, RGB and
+// depth key as in RaDe-GS.  The record keeps its layout (the plane / normal fields are zero) and the binning role zeroes the counts
+// (`zero_count`, which only the VANILLA kernel's arguments carry: PreArgs and with it every existing kernel stay as they were).
 enum { ROLE_BOTH = 0, ROLE_BIN = 1, ROLE_RECORD = 2 };
 
 #ifdef PRE_TIMELINE
@@ -62,12 +68,12 @@ extern "C" int igs_debug_preprocess_timeline(unsigned long long* host, int n)
 #define TL(k) do { } while (0)
 #endif
 
-template <int ROLE>
+template <int ROLE, bool VANILLA = false>
 __device__ __forceinline__ void
 preprocess_body(const FwdParams& p, const uint32_t blk, float* __restrict__ rec, uint32_t* __restrict__ tiles, uint32_t* __restrict__ depth_keys,
                 uint32_t* __restrict__ ident, int* __restrict__ radii, uint32_t* __restrict__ counters,
                 uint32_t* __restrict__ hist0, uint32_t per_block, uint32_t* __restrict__ tile_count,
-                uint64_t* __restrict__ pairs, uint32_t slab)
+                uint64_t* __restrict__ pairs, uint32_t slab, int* __restrict__ zero_count = nullptr)
 {
     constexpr bool BIN = ROLE != ROLE_RECORD, RECORD = ROLE != ROLE_BIN;
     const int idx = (int)blk * 256 + threadIdx.x;
@@ -106,7 +112,7 @@ preprocess_body(const FwdParams& p, const uint32_t blk, float* __restrict__ rec,
                 cov3d_from_scale_rot(s, p.scale_modifier, q, cov3D);
             }
             Cov2DCtx c;
-            cov2d_ctx(c, p_orig, cov3D, p.view, p.fx, p.fy, p.tan_fovx, p.tan_fovy, p.kernel_size, RECORD);      // (the binning role skips the eigen-solver)
+            cov2d_ctx(c, p_orig, cov3D, p.view, p.fx, p.fy, p.tan_fovx, p.tan_fovy, p.kernel_size, RECORD && !VANILLA);      // (the binning role skips the eigen-solver)
             if (RECORD && p.plane_cache) plane_cache_store(p.plane_cache + (size_t)idx * PLANE_CACHE_F, c, p.plane_tag);
             TL(2);
             float cp[6] = { 0, 0, 0, 0, 0, 0 }, rp[2] = { 0, 0 };
@@ -137,7 +143,8 @@ preprocess_body(const FwdParams& p, const uint32_t blk, float* __restrict__ rec,
             const float ts = sqrtf(p_view.x * p_view.x + p_view.y * p_view.y + p_view.z * p_view.z);
             const float coef = c.coef_zero ? 0.0f : c.coef;
             // geometry that the reference stores even for Gaussians it drops later is irrelevant: nothing reads it
-            const float cx = c.cov2[0], cy = c.cov2[1], cz = c.cov2[2];
+            float cx = c.cov2[0], cy = c.cov2[1], cz = c.cov2[2];
+            if constexpr (VANILLA) { cx = cx + 0.3f; cz = cz + 0.3f; }         // low-pass dilation (compress forward.cu:114-115)
             const float det = cx * cz - cy * cy;
             if (det == 0.0f) break;
             const float det_inv = 1.f / det;
@@ -173,7 +180,8 @@ preprocess_body(const FwdParams& p, const uint32_t blk, float* __restrict__ rec,
             if constexpr (RECORD) {
             R4[0] = make_float4(pix, piy, conic.x, conic.y);
             const float opacity = p.raw_activations ? act_sigmoid(p.opacities[idx]) : p.opacities[idx];
-            R4[1] = make_float4(conic.z, opacity * coef, rgb.x, rgb.y);
+            if constexpr (VANILLA) R4[1] = make_float4(conic.z, opacity, rgb.x, rgb.y);        // conic_opacity.w = opacities[idx]
+            else R4[1] = make_float4(conic.z, opacity * coef, rgb.x, rgb.y);
             R4[2] = make_float4(rgb.z, ts, rp[0], rp[1]);
             R4[3] = make_float4(p_view.x, p_view.y, p_view.z, nrm.x);
             R4[4] = make_float4(cp[0], cp[1], cp[2], cp[3]);
@@ -186,6 +194,7 @@ preprocess_body(const FwdParams& p, const uint32_t blk, float* __restrict__ rec,
         if constexpr (BIN) {
         radii[idx] = radius;
         tiles[idx] = my_tiles;
+        if constexpr (VANILLA) zero_count[idx] = 0;       // (every attempt of a frame counts from zero: slab overflow redoes the frame)
         }
         if (BIN && hist0) {                                          // radix binning: keys + first-pass histogram of the depth sort
             depth_keys[idx] = dkey;
@@ -344,35 +353,49 @@ preprocess_body(const FwdParams& p, const uint32_t blk, float* __restrict__ rec,
 }
 
 // (80 VGPRs = 6 workgroups per CU: 28 of the 1564 start late.  Forcing 7 per CU -- 72 VGPRs, 12 spilled -- changes nothing: 38.0 us)
-template <bool SPLIT>
+template <bool SPLIT, bool VANILLA = false>
 __global__ void __launch_bounds__(256)
-preprocess_fwd_kernel(const PreArgs a, float* __restrict__ rec, uint32_t* __restrict__ tiles, uint32_t* __restrict__ depth_keys,
+preprocess_fwd_kernel(const typename std::conditional<VANILLA, PreArgsCount, PreArgs>::type a, float* __restrict__ rec, uint32_t* __restrict__ tiles, uint32_t* __restrict__ depth_keys,
                       uint32_t* __restrict__ ident, int* __restrict__ radii, uint32_t* __restrict__ counters,
                       uint32_t* __restrict__ hist0, uint32_t per_block, uint32_t* __restrict__ tile_count,
                       uint64_t* __restrict__ pairs, uint32_t slab)
 {
+    int* zc = nullptr;
+    if constexpr (VANILLA) zc = a.zero_count;
     if constexpr (!SPLIT) {
-        preprocess_body<ROLE_BOTH>(a.p, blockIdx.x, rec, tiles, depth_keys, ident, radii, counters, hist0, per_block, tile_count, pairs, slab);
+        preprocess_body<ROLE_BOTH, VANILLA>(a.p, blockIdx.x, rec, tiles, depth_keys, ident, radii, counters, hist0, per_block, tile_count, pairs, slab, zc);
     } else {
         // neighbouring workgroups take the two roles of the same 256 Gaussians: their parameter lines are fetched once
         const uint32_t blk = blockIdx.x >> 1;
-        if (blockIdx.x & 1u) preprocess_body<ROLE_RECORD>(a.p, blk, rec, tiles, depth_keys, ident, radii, counters, hist0, per_block, tile_count, pairs, slab);
-        else                 preprocess_body<ROLE_BIN>(a.p, blk, rec, tiles, depth_keys, ident, radii, counters, hist0, per_block, tile_count, pairs, slab);
+        if (blockIdx.x & 1u) preprocess_body<ROLE_RECORD, VANILLA>(a.p, blk, rec, tiles, depth_keys, ident, radii, counters, hist0, per_block, tile_count, pairs, slab, zc);
+        else                 preprocess_body<ROLE_BIN, VANILLA>(a.p, blk, rec, tiles, depth_keys, ident, radii, counters, hist0, per_block, tile_count, pairs, slab, zc);
     }
 }
 
 hipError_t launch_preprocess_fwd(hipStream_t s, const FwdParams& p, float* rec, uint32_t* tiles, uint32_t* depth_keys,
                                  uint32_t* ident, int* radii, uint32_t* counters, uint32_t* hist0, uint32_t per_block,
-                                 uint32_t* tile_count, uint64_t* pairs, uint32_t slab)
+                                 uint32_t* tile_count, uint64_t* pairs, uint32_t slab, int* count)
 {
-    PreArgs a; a.p = p;
     // (staging the SH rows through LDS was tried here and lost: 50 KB/block costs more occupancy than the strided reads cost)
+    if (!count) {
+        PreArgs a; a.p = p;
 #ifdef PRE_NO_SPLIT
-    hipLaunchKernelGGL(preprocess_fwd_kernel<false>, dim3((p.P + 255) / 256), dim3(256), 0, s, a, rec, tiles, depth_keys, ident, radii, counters,
-                       hist0, per_block, tile_count, pairs, slab);
+        hipLaunchKernelGGL(preprocess_fwd_kernel<false>, dim3((p.P + 255) / 256), dim3(256), 0, s, a, rec, tiles, depth_keys, ident, radii, counters,
+                           hist0, per_block, tile_count, pairs, slab);
 #else
-    hipLaunchKernelGGL(preprocess_fwd_kernel<true>, dim3(2 * ((p.P + 255) / 256)), dim3(256), 0, s, a, rec, tiles, depth_keys, ident, radii, counters,
-                       hist0, per_block, tile_count, pairs, slab);
+        hipLaunchKernelGGL(preprocess_fwd_kernel<true>, dim3(2 * ((p.P + 255) / 256)), dim3(256), 0, s, a, rec, tiles, depth_keys, ident, radii, counters,
+                           hist0, per_block, tile_count, pairs, slab);
+#endif
+        return hipGetLastError();
+    }
+    // count_gaussians: the vanilla variant, which also zeroes the counts
+    PreArgsCount a; a.p = p; a.zero_count = count;
+#ifdef PRE_NO_SPLIT
+    hipLaunchKernelGGL((preprocess_fwd_kernel<false, true>), dim3((p.P + 255) / 256), dim3(256), 0, s, a, rec, tiles, depth_keys, ident, radii,
+                       counters, hist0, per_block, tile_count, pairs, slab);
+#else
+    hipLaunchKernelGGL((preprocess_fwd_kernel<true, true>), dim3(2 * ((p.P + 255) / 256)), dim3(256), 0, s, a, rec, tiles, depth_keys, ident,
+                       radii, counters, hist0, per_block, tile_count, pairs, slab);
 #endif
     return hipGetLastError();
 }

@@ -5,6 +5,7 @@
 //
 // Built by igs_amd/build_ext.py with the host compiler (no device code in this file); links libigs_rast.so.
 //
+// It also carries count_gaussians, the count pass of the compress package (compress-diff-gaussian-rasterization rasterize_points.cu:130-217).
 // Extensions over the reference's signatures are keyword-only extras with defaults (the positional lists are the reference's):
 //   rasterize_gaussians(..., scratch=None, out_images=None, out_radii=None, mode=0, scratch_clean=False)
 //   rasterize_gaussians_backward(..., workspace=None, out_*=None)         any upstream gradient may be None (= zeros)
@@ -138,6 +139,51 @@ FwdTuple rasterize_gaussians(
         check((int)rendered, "igs_rast_forward");
     }
     return FwdTuple(rendered, color, coord, mcoord, alpha, normal, depth, mdepth, radii, ss->geom, ss->binning, ss->img);
+}
+
+using CountTuple = std::tuple<Tensor, Tensor, int64_t, Tensor, Tensor, Tensor, Tensor, Tensor>;
+
+// _C.count_gaussians of the compress package (CountGaussiansCUDA, compress-diff-gaussian-rasterization rasterize_points.cu:130-217):
+// the reference's 20 positional arguments (no kernel_size: vanilla 3DGS; f_count is accepted and, as there, not read).
+// Returns (gaussians_count [P] int32, important_score [P] float32, num_rendered, color [3,H,W], radii [P] int32, geomBuffer,
+// binningBuffer, imgBuffer).  The count is exact and the score is count x opacity (include/igs_rast.h: igs_rast_count_gaussians).
+CountTuple count_gaussians(
+    const Tensor& background, const Tensor& means3D, const Tensor& colors, const Tensor& opacity, const Tensor& scales,
+    const Tensor& rotations, double scale_modifier, const Tensor& cov3D_precomp, const Tensor& viewmatrix, const Tensor& projmatrix,
+    double tan_fovx, double tan_fovy, int64_t image_height, int64_t image_width, const Tensor& sh, int64_t degree,
+    const Tensor& campos, bool prefiltered, bool debug, bool f_count, const std::shared_ptr<ScratchSet>& scratch)
+{
+    (void)f_count;
+    if (means3D.dim() != 2 || means3D.size(1) != 3) throw RasterizerError("means3D must have dimensions (num_points, 3)");
+    if (!means3D.is_cuda()) throw RasterizerError("igs_amd rasterizer: tensors must be on a GPU (no CPU fallback)");
+    const c10::Device dev = means3D.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const int64_t P = means3D.size(0), H = image_height, W = image_width;
+    if (H <= 0 || W <= 0) throw RasterizerError("image_height and image_width must be positive");
+    In m3(means3D, dev, "means3D"), col(colors, dev, "colors_precomp"), op(opacity, dev, "opacities"), sc(scales, dev, "scales"),
+       rot(rotations, dev, "rotations"), cov(cov3D_precomp, dev, "cov3D_precomp"), shs(sh, dev, "shs"), bg(background, dev, "bg"),
+       view(viewmatrix, dev, "viewmatrix"), proj(projmatrix, dev, "projmatrix"), cam(campos, dev, "campos");
+    const int64_t M = shs.p ? shs.keep.size(1) : 0;
+    auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
+    auto iopt = fopt.dtype(at::kInt);
+    // every element is written by the kernels when P > 0 (counts: zeroed by the preprocess; colour: every pixel)
+    Tensor color = P > 0 ? at::empty({3, H, W}, fopt) : at::zeros({3, H, W}, fopt);
+    Tensor radii = P > 0 ? at::empty({P}, iopt) : at::zeros({0}, iopt);
+    Tensor count = P > 0 ? at::empty({P}, iopt) : at::zeros({0}, iopt);
+    Tensor score = P > 0 ? at::empty({P}, fopt) : at::zeros({0}, fopt);
+    if (scratch && scratch->device != dev) throw RasterizerError("scratch set lives on " + scratch->device.str() + ", the tensors on " + dev.str());
+    std::shared_ptr<ScratchSet> ss = scratch ? scratch : std::make_shared<ScratchSet>(dev, false);
+    int64_t rendered = 0;
+    if (P != 0) {
+        hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+        rendered = igs_rast_count_gaussians(stream, grow_cb, &ss->g_geom, grow_cb, &ss->g_binning, grow_cb, &ss->g_img, (int)P, (int)degree,
+                                            (int)M, bg.p, (int)W, (int)H, m3.p, shs.p, col.p, op.p, sc.p, (float)scale_modifier, rot.p, cov.p,
+                                            view.p, proj.p, cam.p, (float)tan_fovx, (float)tan_fovy, prefiltered ? 1 : 0,
+                                            color.data_ptr<float>(), count.data_ptr<int>(), score.data_ptr<float>(), radii.data_ptr<int>(),
+                                            debug ? 1 : 0);
+        check((int)rendered, "igs_rast_count_gaussians");
+    }
+    return CountTuple(count, score, rendered, color, radii, ss->geom, ss->binning, ss->img);
 }
 
 using BwdTuple = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
@@ -414,6 +460,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
         check(v, "igs_rast_nan_report_wait_at");
         return v != 0;
     }, py::arg("word"), py::arg("seq"), py::call_guard<py::gil_scoped_release>());
+    m.def("count_gaussians", &count_gaussians, py::arg("background"), py::arg("means3D"), py::arg("colors"), py::arg("opacity"),
+          py::arg("scales"), py::arg("rotations"), py::arg("scale_modifier"), py::arg("cov3D_precomp"), py::arg("viewmatrix"),
+          py::arg("projmatrix"), py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("image_height"), py::arg("image_width"), py::arg("sh"),
+          py::arg("degree"), py::arg("campos"), py::arg("prefiltered"), py::arg("debug"), py::arg("f_count"), py::kw_only(),
+          py::arg("scratch") = std::shared_ptr<ScratchSet>(), py::call_guard<py::gil_scoped_release>());
     m.def("mark_visible", &mark_visible, py::arg("means3D"), py::arg("viewmatrix"), py::arg("projmatrix"), py::call_guard<py::gil_scoped_release>());
     m.def("integrate_gaussians_to_points", [](const py::args&, const py::kwargs&) -> py::object {
         // GOF tetrahedra integration (DGR/rasterize_points.cu:269-387): mesh extraction only, never reached from IGS

@@ -147,6 +147,41 @@ int igs_rast_last_posted_status(int* num_rendered, unsigned* overflow, unsigned*
  * the same promise for the fused step).  A broken promise costs a wrong or redone frame or an error code, never a fault. */
 void igs_rast_hint_scratch_clean(int on);
 
+/* Count pass of the compress rasterizer (diff_gaussian_rasterization_compress, CountGaussiansCUDA / forwardCount of
+ * compress-diff-gaussian-rasterization rasterize_points.cu:130-217, rasterizer_impl.cu:441-530): vanilla-3DGS preprocess (2-D covariance
+ * dilated by 0.3, raw opacity), the same binning as igs_rast_forward, a colour-only blend into out_color [3,H,W] (background included),
+ * and per Gaussian:
+ *   count[i] = the exact number of pixels into which Gaussian i is blended (the reference's non-atomic increments undercount),
+ *   score[i] = (float)count[i] * opacities[i], rounded once.
+ * radii [P] as the vanilla preprocess computes them.  Returns num_rendered or a negative IGS_RAST_E_* code (bad sizes / NULL outputs:
+ * IGS_RAST_E_INVALID before any HIP call; prefiltered with a culled point: IGS_RAST_E_PREFILTER).  P == 0 launches nothing. */
+int igs_rast_count_gaussians(
+    void* stream,
+    igs_rast_alloc_fn geometry_buffer, void* geometry_user,
+    igs_rast_alloc_fn binning_buffer, void* binning_user,
+    igs_rast_alloc_fn image_buffer, void* image_user,
+    int P, int D, int M,
+    const float* background,              /* [3] */
+    int width, int height,
+    const float* means3D,                 /* [P,3] */
+    const float* shs,                     /* [P,M,3] or NULL */
+    const float* colors_precomp,          /* [P,3] or NULL */
+    const float* opacities,               /* [P] */
+    const float* scales,                  /* [P,3] or NULL */
+    float scale_modifier,
+    const float* rotations,               /* [P,4] or NULL */
+    const float* cov3D_precomp,           /* [P,6] or NULL */
+    const float* viewmatrix,              /* [16] */
+    const float* projmatrix,              /* [16] */
+    const float* cam_pos,                 /* [3] */
+    float tan_fovx, float tan_fovy,
+    int prefiltered,
+    float* out_color,                     /* [3,H,W] */
+    int* count,                           /* [P] */
+    float* score,                         /* [P] */
+    int* radii,                           /* [P] */
+    int debug);
+
 /* Binning scratch tuning (no reference counterpart).  The default path gives every 16x16 tile a slab of `slots_per_tile`
  * instance slots (12 bytes each) in binningBuffer; a frame in which some tile needs more is redone automatically with larger
  * slabs (and, beyond 16384 per tile, with the global radix sort), and the size then sticks for the calling thread.  Setting the
