@@ -154,9 +154,40 @@ extern "C" size_t igs_rast_backward_workspace_bytes(int P) { return ws_gacc_byte
 struct BinHint { uint32_t slab = 0; };              // instance slots per tile used by the last frames (0 = default)
 #define SLAB_MAX_BYTES (8ull << 30)                 // beyond this much slab scratch the global-sort path is used
 static thread_local BinHint g_hint;
+// a frame's largest tile needed `overflow` instance slots, more than its slab had: the slab that fits it with a quarter to spare (at
+// most TILE_SORT_BIG: denser tiles take the global sort)
+static uint32_t slab_hint_for(uint32_t overflow)
+{
+    const uint64_t want = ((uint64_t)overflow + overflow / 4 + 255) / 256 * 256;
+    return (uint32_t)(want > TILE_SORT_BIG ? TILE_SORT_BIG : want);
+}
 // igs_rast_forward_async leaves its host-side check of R to igs_rast_forward_finish
 struct PendingFwd { bool active = false; uint32_t slab = 0; };
 static thread_local PendingFwd g_pending;
+
+// the reference's forward argument list (CudaRasterizer::Rasterizer::forward), in the order of igs_rast_forward's parameters
+struct FwdIn {
+    hipStream_t s; igs_rast_alloc_fn geometry_buffer; void* geometry_user; igs_rast_alloc_fn binning_buffer; void* binning_user;
+    igs_rast_alloc_fn image_buffer; void* image_user; int P, D, M; const float* background; int width, height;
+    const float *means3D, *shs, *colors_precomp, *opacities, *scales; float scale_modifier; const float *rotations, *cov3D_precomp;
+    const float *viewmatrix, *projmatrix, *cam_pos; float tan_fovx, tan_fovy, kernel_size; int prefiltered;
+    float *out_color, *out_coord, *out_mcoord, *out_depth, *out_mdepth, *out_alpha, *out_normal; int* radii; int require_coord, require_depth, debug;
+};
+// the parameter list of igs_rast_forward, _async and _nowait (include/igs_rast.h), and the FwdIn made from it
+#define FWD_PARAMS                                                                                                                        \
+    void* stream, igs_rast_alloc_fn geometry_buffer, void* geometry_user, igs_rast_alloc_fn binning_buffer, void* binning_user,           \
+    igs_rast_alloc_fn image_buffer, void* image_user, int P, int D, int M, const float* background, int width, int height,               \
+    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities, const float* scales,                     \
+    float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,          \
+    const float* cam_pos, float tan_fovx, float tan_fovy, float kernel_size, int prefiltered, float* out_color, float* out_coord,        \
+    float* out_mcoord, float* out_depth, float* out_mdepth, float* out_alpha, float* out_normal, int* radii, int require_coord,            \
+    int require_depth, int debug
+#define FWD_IN                                                                                                                            \
+    FwdIn{ (hipStream_t)stream, geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M,          \
+           background, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,           \
+           viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, kernel_size, prefiltered, out_color, out_coord, out_mcoord, out_depth,     \
+           out_mdepth, out_alpha, out_normal, radii, require_coord, require_depth, debug }
+
 // what the extended entry points ask of the forward on top of the reference's argument list
 struct FwdExtra {
     bool defer_status = false;          // igs_rast_forward_async / igs_refine_step: do not wait for {R, overflow}
@@ -170,8 +201,8 @@ struct FwdExtra {
     bool skip_bwd_state = false;        // ... the loss is colour-only: blend_fwd need not store the geometry branches' backward state
     uint32_t plane_tag = 0;             // ... nonzero: a plane / depth / normal gradient will come back: keep Sigma^-1 per Gaussian under this tag
     // igs_refine_step with the L1 loss: run the colour-only blend backward inside the forward's tile kernel (blend_step.hip).  The
-    // caller fills everything of the backward's arguments that forward_impl does not know (bg, gacc, l1_*, want_absgrad); the
-    // list / record / geometry fields are set here.  *fused_ran reports whether that kernel was used (slab binning only).
+    // caller fills everything of the backward's arguments that the forward does not know (bg, gacc, l1_*, want_absgrad); the
+    // list / record / geometry fields are set by launch_blend.  *fused_ran reports whether that kernel was used (slab binning only).
     BlendBwdArgs* fused_bwd = nullptr;
     bool* fused_ran = nullptr;
     int* fused_instance = nullptr;
@@ -188,284 +219,292 @@ static thread_local bool g_counters_dirty = false;
 static thread_local bool g_hint_clean = false;
 extern "C" void igs_rast_hint_scratch_clean(int on) { g_hint_clean = on != 0; }
 
-static int forward_impl(
-    void* stream,
-    igs_rast_alloc_fn geometry_buffer, void* geometry_user, igs_rast_alloc_fn binning_buffer, void* binning_user,
-    igs_rast_alloc_fn image_buffer, void* image_user,
-    int P, int D, int M, const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-    const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-    float tan_fovx, float tan_fovy, float kernel_size, int prefiltered,
-    float* out_color, float* out_coord, float* out_mcoord, float* out_depth, float* out_mdepth, float* out_alpha,
-    float* out_normal, int* radii, int require_coord, int require_depth, int debug,
-    bool force_radix, uint64_t min_capacity, const FwdExtra& ex)
+// one forward frame: its sizes, the caller's geometry and image scratch (requested anew by every attempt) and the preprocess parameters
+struct Frame {
+    const FwdIn& in; const FwdExtra& ex; int gx, gy; size_t Tn; GeomLayout GL; ImgLayout IL;
+    char* gbase = nullptr; char* ibase = nullptr; FwdParams fp;
+    Frame(const FwdIn& i, const FwdExtra& e)
+        : in(i), ex(e), gx((i.width + TILE - 1) / TILE), gy((i.height + TILE - 1) / TILE), Tn((size_t)gx * gy), GL(i.P),
+          IL((size_t)i.width * i.height, Tn) {}
+    uint32_t* gbuf(size_t off) const { return (uint32_t*)(gbase + off); }
+    uint32_t* ibuf(size_t off) const { return (uint32_t*)(ibase + off); }
+    float* rec() const { return (float*)(gbase + GL.rec); }
+};
+static int carve_frame(Frame& f)
 {
-    hipStream_t s = (hipStream_t)stream;
-    if (P < 0 || width <= 0 || height <= 0) return fail(IGS_RAST_E_INVALID, "igs_rast_forward: bad sizes");
-    if (P == 0) return 0;                                       // rasterize_points.cu:90: nothing is launched
-    if (!geometry_buffer || !binning_buffer || !image_buffer) return fail(IGS_RAST_E_INVALID, "igs_rast_forward: NULL scratch callback");
-    if (!means3D || !opacities || !viewmatrix || !projmatrix || !cam_pos || !background || !radii)
-        return fail(IGS_RAST_E_INVALID, "igs_rast_forward: NULL required input");
-    if (!out_color || (!ex.count && (!out_coord || !out_mcoord || !out_depth || !out_mdepth || !out_alpha || !out_normal)))
-        return fail(IGS_RAST_E_INVALID, "igs_rast_forward: NULL output");
-    if (!colors_precomp && !shs) return fail(IGS_RAST_E_INVALID, "igs_rast_forward: neither shs nor colors_precomp");
-    if (!cov3D_precomp && (!scales || !rotations)) return fail(IGS_RAST_E_INVALID, "igs_rast_forward: neither scales/rotations nor cov3D_precomp");
-    if (!colors_precomp && (M < (D + 1) * (D + 1) || D < 0 || D > 3)) return fail(IGS_RAST_E_INVALID, "igs_rast_forward: SH degree / coefficient count mismatch");
-    if (int rc = ensure_slot()) return rc;
-
-    const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
-    const size_t Tn = (size_t)gx * gy, HW = (size_t)width * height;
-
-    const GeomLayout GL(P);
-    char* gbase = geometry_buffer(geometry_user, GL.total);
+    const FwdIn& in = f.in; const FwdExtra& ex = f.ex;
+    char* gbase = in.geometry_buffer(in.geometry_user, f.GL.total);
     if (!gbase) return fail(IGS_RAST_E_ALLOC, "geometry buffer callback returned NULL");
-    gbase = align_ptr(gbase);
-    const ImgLayout IL(HW, Tn);
-    char* ibase = image_buffer(image_user, IL.total);
+    f.gbase = align_ptr(gbase);
+    char* ibase = in.image_buffer(in.image_user, f.IL.total);
     if (!ibase) return fail(IGS_RAST_E_ALLOC, "image buffer callback returned NULL");
-    ibase = align_ptr(ibase);
-
-    float* rec = (float*)(gbase + GL.rec);
-    uint32_t* tiles = (uint32_t*)(gbase + GL.tiles);
-    uint32_t* keys_a = (uint32_t*)(gbase + GL.keys_a); uint32_t* keys_b = (uint32_t*)(gbase + GL.keys_b);
-    uint32_t* vals_a = (uint32_t*)(gbase + GL.vals_a); uint32_t* vals_b = (uint32_t*)(gbase + GL.vals_b);
-    uint32_t* ghist = (uint32_t*)(gbase + GL.hist);
-    uint32_t* blocksum = (uint32_t*)(gbase + GL.blocksum);
-    uint32_t* counters = (uint32_t*)(gbase + GL.counters);
-
-    FwdParams fp;
-    fp.P = P; fp.D = D; fp.M = M; fp.W = width; fp.H = height; fp.gx = gx; fp.gy = gy;
-    fp.means3D = means3D; fp.shs = shs; fp.colors_precomp = colors_precomp; fp.opacities = opacities;
-    fp.scales = scales; fp.rotations = rotations; fp.cov3D_precomp = cov3D_precomp;
-    fp.scale_modifier = scale_modifier; fp.tan_fovx = tan_fovx; fp.tan_fovy = tan_fovy;
-    fp.fy = height / (2.0f * tan_fovy); fp.fx = width / (2.0f * tan_fovx);       // rasterizer_impl.cu:288-289
-    fp.kernel_size = kernel_size; fp.prefiltered = prefiltered;
-    fp.view = viewmatrix; fp.proj = projmatrix; fp.campos = cam_pos;
+    f.ibase = align_ptr(ibase);
+    FwdParams& fp = f.fp = FwdParams();
+    fp.P = in.P; fp.D = in.D; fp.M = in.M; fp.W = in.width; fp.H = in.height; fp.gx = f.gx; fp.gy = f.gy;
+    fp.means3D = in.means3D; fp.shs = in.shs; fp.colors_precomp = in.colors_precomp; fp.opacities = in.opacities; fp.scales = in.scales;
+    fp.rotations = in.rotations; fp.cov3D_precomp = in.cov3D_precomp; fp.scale_modifier = in.scale_modifier; fp.tan_fovx = in.tan_fovx;
+    fp.tan_fovy = in.tan_fovy; fp.fy = in.height / (2.0f * in.tan_fovy); fp.fx = in.width / (2.0f * in.tan_fovx);       // rasterizer_impl.cu:288-289
+    fp.kernel_size = in.kernel_size; fp.prefiltered = in.prefiltered; fp.view = in.viewmatrix; fp.proj = in.projmatrix; fp.campos = in.cam_pos;
     fp.raw_activations = ex.raw_activations ? 1 : 0;
     fp.zero_gacc = ex.zero_gacc; fp.zero_loss = ex.zero_loss; fp.zero_loss2 = ex.zero_loss2; fp.zero_gacc_first = ex.zero_gacc_first;
-    if (ex.plane_tag) { fp.plane_cache = (float*)(gbase + GL.planes); fp.plane_tag = ex.plane_tag; }
+    if (ex.plane_tag) { fp.plane_cache = (float*)(f.gbase + f.GL.planes); fp.plane_tag = ex.plane_tag; }
     fp.zero_gacc_stride = ex.skip_bwd_state ? GACC_COMPACT_F : GACC_F;      // (colour-only loss <=> compact accumulator rows)
-    const bool vanilla = ex.count != nullptr;
     g_last_fwd = LastFwd();
+    return 0;
+}
 
+// what a binning stage leaves for the blend
+struct Binned {
+    uint32_t* ranges = nullptr; uint32_t* point_list = nullptr; uint32_t R = 0;      // (R: global sort only)
+    const uint32_t* slab_stats = nullptr;    // slab binning: {R, overflow, prefilter flag} on the device, posted by the blend kernel
+    uint32_t slab_size = 0;
+    bool pending = false;                    // slab binning: the host has not looked at R yet
+    bool fuse_tiles = false, step_order = false;      // ... the fused refine step's tile kernel runs; the tile sort wrote its dispatch order
+};
+
+// slab binning (default): nothing here needs the host to know R
+static int bin_slab(Frame& f, uint32_t slab, Binned& b)
+{
+    const hipStream_t s = f.in.s; const int debug = f.in.debug;
+    uint32_t *tile_count = f.ibuf(f.IL.tile_count), *stats = f.ibuf(f.IL.stats), *counters = f.ibuf(f.IL.counters);
+    const SlabLayout KL(f.Tn, slab);
+    char* bbase = f.in.binning_buffer(f.in.binning_user, KL.total);
+    if (!bbase) return fail(IGS_RAST_E_ALLOC, "binning buffer callback returned NULL");
+    bbase = align_ptr(bbase);
+    b.ranges = f.ibuf(f.IL.ranges); b.point_list = (uint32_t*)(bbase + KL.point_list); b.slab_size = slab;
+    uint64_t* pairs = (uint64_t*)(bbase + KL.pairs);
+    // The tile sort leaves the fill cursors and the count shards zeroed behind it, so a buffer that was clean before a frame is clean
+    // after it: a caller that vouches for its buffer (igs_refine_step_args::scratch_clean) skips the zero-fill launch, unless
+    // something on this thread was cut short between a binning kernel and its tile sort (g_counters_dirty).
+    if (f.ex.scratch_clean && !g_counters_dirty) f.fp.zero_stats = stats;
+    else HIP_TRY(zero_fill_async(s, tile_count, f.IL.zero_end - f.IL.tile_count), "zero tile counters");   // tile_count + stats + counters
+    g_counters_dirty = true;
+    prof_mark(s, ST_GAP);
+    HIP_TRY(launch_preprocess_fwd(s, f.fp, f.rec(), f.gbuf(f.GL.tiles), nullptr, nullptr, f.in.radii, counters, nullptr, 0, tile_count,
+                                  pairs, slab, f.ex.count), "preprocess_fwd launch");
+    DBG_SYNC("preprocess_fwd");
+    prof_mark(s, ST_PREPROCESS);
+    // fused refine step: the tile sort also writes the blend kernel's dispatch order and leaves the fill cursors for that kernel to zero
+    static const bool no_step_order = getenv("IGS_NO_STEP_ORDER") != nullptr;      // (A/B switch for measurements)
+    b.fuse_tiles = f.ex.fused_bwd && f.ex.skip_bwd_state && !f.in.colors_precomp && (f.in.require_coord != 0) == (f.in.require_depth != 0);
+    b.step_order = b.fuse_tiles && !no_step_order && step_order_usable((uint32_t)f.gx, (uint32_t)f.gy, slab);
+    HIP_TRY(launch_tile_sort(s, (uint32_t)f.Tn, tile_count, pairs, b.point_list, b.ranges, slab, stats, counters, (uint32_t)f.in.P,
+                             b.step_order ? f.ibuf(f.IL.tile_order) : nullptr, (uint32_t)f.gx, (uint32_t)f.gy), "tile_sort launch");
+    g_counters_dirty = b.step_order;          // (then clean only once the blend kernel has been launched)
+    DBG_SYNC("tile_sort");
+    prof_mark(s, ST_TILE_SORT);
+    b.slab_stats = stats; b.pending = true;
+    g_last_fwd.overflow = stats + 1; g_last_fwd.prefilter = stats + 2;      // (the tile sort moved the flag there)
+    return 0;
+}
+
+// global radix binning (fallback for tiles denser than TILE_SORT_BIG): the host reads R back before it sizes the binning buffer
+static int bin_radix(Frame& f, Binned& b)
+{
+    const hipStream_t s = f.in.s; const int debug = f.in.debug; const int P = f.in.P;
     const size_t counter_bytes = (COUNTER_SHARDS + 1) * COUNTER_SHARD_STRIDE * 4;
-    uint32_t* ranges = (uint32_t*)(ibase + IL.ranges);
-    uint32_t* point_list = nullptr;
-    uint32_t R = 0;
-    bool slab_pending = false;            // slab path: the host has not looked at R yet
-    bool use_step_order = false; uint32_t* step_cursors = nullptr;      // fused refine step: see the tile sort below
-    uint32_t slab_size = 0;                // slab size of this call
-    const uint32_t* slab_stats = nullptr;
+    uint32_t *counters = f.gbuf(f.GL.counters), *tiles = f.gbuf(f.GL.tiles), *ghist = f.gbuf(f.GL.hist), *blocksum = f.gbuf(f.GL.blocksum);
+    uint32_t *keys_a = f.gbuf(f.GL.keys_a), *keys_b = f.gbuf(f.GL.keys_b), *vals_a = f.gbuf(f.GL.vals_a), *vals_b = f.gbuf(f.GL.vals_b);
+    HIP_TRY(hipMemsetAsync(counters, 0, counter_bytes, s), "memset counters");
 
-    if (!force_radix) {
-        // ---------------- slab binning (default): nothing below needs the host to know R ----------------
-        uint32_t* tile_count = (uint32_t*)(ibase + IL.tile_count);
-        uint32_t* stats = (uint32_t*)(ibase + IL.stats);
+    uint32_t dnb = 0, dper = 0;
+    sort_geometry((uint32_t)P, &dnb, &dper);
+    HIP_TRY(hipMemsetAsync(ghist, 0, (size_t)256 * SORT_MAX_BLOCKS * 4, s), "memset depth-sort histogram 0");
+    prof_mark(s, ST_GAP);
+    HIP_TRY(launch_preprocess_fwd(s, f.fp, f.rec(), tiles, keys_a, vals_a, f.in.radii, counters, ghist, dper, nullptr, nullptr, 0, f.ex.count),
+            "preprocess_fwd launch");
+    DBG_SYNC("preprocess_fwd");
+    prof_mark(s, ST_PREPROCESS);
+    // instance count: read back while the depth sort runs
+    HIP_TRY(hipMemcpyAsync(g_slot.pinned, counters, counter_bytes, hipMemcpyDeviceToHost, s), "memcpy count");
+    HIP_TRY(hipEventRecord(g_slot.ev, s), "event record");
+    prof_mark(s, ST_GAP);
+
+    uint32_t *dk = nullptr, *order = nullptr;
+    HIP_TRY(radix_sort_pairs(s, (uint32_t)P, keys_a, keys_b, vals_a, vals_b, ghist, 0, 32, &dk, &order), "depth sort launch");
+    DBG_SYNC("depth sort");
+    prof_mark(s, ST_DEPTH_SORT);
+    const int nblk = (P + 255) / 256;
+    HIP_TRY(launch_count_sorted(s, P, order, tiles, blocksum), "count_sorted launch");
+    HIP_TRY(launch_scan_blocksums(s, nblk, blocksum), "scan_blocksums launch");
+    DBG_SYNC("scan");
+    prof_mark(s, ST_SCAN);
+
+    HIP_TRY(hipEventSynchronize(g_slot.ev), "event sync");
+    uint64_t R64 = 0;
+    for (int sh = 0; sh < COUNTER_SHARDS; sh++) R64 += g_slot.pinned[COUNTER_SHARD_STRIDE * (1 + sh)];
+    if (R64 > 0x7FFFFFFFull) return fail(IGS_RAST_E_INVALID, "instance count overflows int");
+    const uint32_t R = b.R = (uint32_t)R64;
+    if (g_slot.pinned[1]) return fail(IGS_RAST_E_PREFILTER, "Point is filtered although prefiltered is set. This shouldn't happen!");
+
+    const BinLayout BL(R);
+    char* bbase = f.in.binning_buffer(f.in.binning_user, BL.total);
+    if (!bbase) return fail(IGS_RAST_E_ALLOC, "binning buffer callback returned NULL");
+    bbase = align_ptr(bbase);
+    uint32_t* point_list = b.point_list = (uint32_t*)(bbase + BL.point_list);
+    uint32_t *bkeys_a = (uint32_t*)(bbase + BL.keys_a), *bkeys_b = (uint32_t*)(bbase + BL.keys_b), *bvals_b = (uint32_t*)(bbase + BL.vals_b);
+    uint32_t* bhist = (uint32_t*)(bbase + BL.hist);
+    uint32_t* ranges = b.ranges = f.ibuf(f.IL.ranges);
+
+    HIP_TRY(hipMemsetAsync(ranges, 0, f.Tn * 8, s), "memset ranges");               // rasterizer_impl.cu:383
+    prof_mark(s, ST_GAP);
+    if (R == 0) return 0;
+    const int bits = ceil_log2((uint32_t)f.Tn);
+    const int passes = (bits + 7) / 8;
+    // arrange the ping-pong so that the sorted ids land in point_list
+    uint32_t *ka, *kb, *va, *vb;
+    if (passes % 2 == 0) { ka = bkeys_a; va = point_list; kb = bkeys_b; vb = bvals_b; }
+    else                 { ka = bkeys_b; va = bvals_b;   kb = bkeys_a; vb = point_list; }
+    uint32_t tnb = 0, tper = 0;
+    sort_geometry(R, &tnb, &tper);
+    HIP_TRY(hipMemsetAsync(bhist, 0, (size_t)256 * SORT_MAX_BLOCKS * 4, s), "memset tile-sort histogram 0");
+    const uint32_t mask0 = bits >= 8 ? 255u : ((1u << bits) - 1u);
+    HIP_TRY(launch_emit_instances(s, P, f.gx, f.gy, order, tiles, blocksum, f.rec(), f.in.radii, ka, va, passes ? bhist : nullptr, tper, mask0),
+            "emit launch");
+    DBG_SYNC("emit");
+    prof_mark(s, ST_EMIT);
+    uint32_t *sk = nullptr, *sv = nullptr;
+    HIP_TRY(radix_sort_pairs(s, R, ka, kb, va, vb, bhist, 0, bits, &sk, &sv), "tile sort launch");
+    DBG_SYNC("tile sort");
+    prof_mark(s, ST_TILE_SORT);
+    if (sv != point_list) return fail(IGS_RAST_E_INVALID, "internal: sort ping-pong mismatch");
+    HIP_TRY(launch_tile_ranges(s, R, sk, ranges), "tile_ranges launch");
+    DBG_SYNC("tile_ranges");
+    prof_mark(s, ST_RANGES);
+    return 0;
+}
+
+// the blend kernel of the frame: the count pass's, the fused refine step's (forward + colour-only backward of a tile) or the plain one
+static int launch_blend(const Frame& f, const Binned& b)
+{
+    const FwdIn& in = f.in; const FwdExtra& ex = f.ex; const hipStream_t s = in.s; const int debug = in.debug;
+    BlendFwdArgs ba;
+    ba.W = in.width; ba.H = in.height; ba.gx = f.gx; ba.gy = f.gy; ba.fx = f.fp.fx; ba.fy = f.fp.fy; ba.bg = in.background;
+    ba.ranges = b.ranges; ba.point_list = b.point_list; ba.rec = f.rec(); ba.colors_precomp = in.colors_precomp;
+    ba.out_color = in.out_color; ba.out_coord = in.out_coord; ba.out_mcoord = in.out_mcoord; ba.out_depth = in.out_depth;
+    ba.out_mdepth = in.out_mdepth; ba.out_alpha = in.out_alpha; ba.out_normal = in.out_normal;
+    ba.n_contrib = f.ibuf(f.IL.n_contrib);
+    ba.accum_coord = (float*)f.ibuf(f.IL.accum_coord); ba.accum_depth = (float*)f.ibuf(f.IL.accum_depth);
+    ba.normal_length = (float*)f.ibuf(f.IL.normal_length);
+    ba.stats_src = b.slab_stats; ba.flag_src = b.slab_stats ? b.slab_stats + 2 : f.gbuf(f.GL.counters) + 1;
+    ba.host_dst = b.pending ? g_slot.pinned_dev : nullptr;
+    ba.tile_order = f.ibuf(f.IL.tile_order);          // built on the side for the backward (both binning paths)
+    ba.skip_bwd_state = ex.skip_bwd_state ? 1 : 0;
+    if (b.pending) { g_host_seq = g_host_seq + 1 ? g_host_seq + 1 : 1; g_slot.pinned[3] = 0; }
+    ba.host_seq = g_host_seq;
+    if (b.pending && ex.no_latch) g_nowait_seq = g_host_seq;
+    g_status_stream = s;
+    if (ex.fused_ran) *ex.fused_ran = b.fuse_tiles;
+    if (ex.count) {
+        ba.tile_order = nullptr;                 // (no backward follows a count pass)
+        HIP_TRY(launch_blend_count(s, ba, ex.count), "blend_count launch");
+    } else if (b.fuse_tiles) {
+        BlendBwdArgs& bb = *ex.fused_bwd;
+        bb.W = in.width; bb.H = in.height; bb.gx = f.gx; bb.gy = f.gy; bb.fx = f.fp.fx; bb.fy = f.fp.fy; bb.bg = in.background;
+        bb.ranges = b.ranges; bb.point_list = b.point_list; bb.rec = f.rec(); bb.colors_precomp = nullptr;
+        bb.tile_order = nullptr;
+        ba.tile_order = nullptr;                 // (no separate backward kernel that could use a load order)
+        if (b.step_order) { ba.step_order = f.ibuf(f.IL.tile_order); ba.reset_cursors = f.ibuf(f.IL.tile_count); }
+        HIP_TRY(launch_blend_step(s, ba, bb, in.require_coord != 0, in.require_depth != 0, ex.fused_instance), "blend_step launch");
+        if (b.step_order) g_counters_dirty = false;
+    } else {
+        HIP_TRY(launch_blend_fwd(s, ba, in.require_coord != 0, in.require_depth != 0), "blend_fwd launch");
+    }
+    DBG_SYNC("blend_fwd");
+    prof_mark(s, ST_BLEND_FWD);
+    return 0;
+}
+
+// what the blend kernel of a slab-binned frame posts into pinned host memory: R, the largest tile that overflowed its slab (0 = none),
+// the prefilter flag -- and, stored last, the sequence number p[3]
+struct FrameStatus { uint32_t R, overflow, prefilter; };
+static FrameStatus read_status(const uint32_t* p) { return { __atomic_load_n(&p[0], __ATOMIC_ACQUIRE), __atomic_load_n(&p[1], __ATOMIC_ACQUIRE), p[2] }; }
+// waits for the status of the current slab-binned frame and checks it: returns R or an error; *overflow as posted
+static int collect_status(hipStream_t s, uint32_t* overflow)
+{
+    if (int rc = wait_status(s)) return rc;
+    const FrameStatus st = read_status(g_slot.pinned);
+    *overflow = st.overflow;
+    if (st.prefilter) return fail(IGS_RAST_E_PREFILTER, "Point is filtered although prefiltered is set. This shouldn't happen!");
+    if (st.R > 0x7FFFFFFFu) return fail(IGS_RAST_E_INVALID, "instance count overflows int");
+    return (int)st.R;
+}
+
+// Checks the arguments, then renders the frame: binning, blend and -- unless it is deferred -- the host's look at the status.  The
+// attempts, in order: slabs of the sticky size; the global sort at once if those slabs would exceed 32-bit list positions or
+// SLAB_MAX_BYTES; after a slab overflow, slabs of at least the overflowing tile's count, or the global sort above TILE_SORT_BIG.
+static int forward_impl(const FwdIn& in, const FwdExtra& ex, bool radix)
+{
+    if (in.P < 0 || in.width <= 0 || in.height <= 0) return fail(IGS_RAST_E_INVALID, "igs_rast_forward: bad sizes");
+    if (in.P == 0) return 0;                                       // rasterize_points.cu:90: nothing is launched
+    if (!in.geometry_buffer || !in.binning_buffer || !in.image_buffer) return fail(IGS_RAST_E_INVALID, "igs_rast_forward: NULL scratch callback");
+    if (!in.means3D || !in.opacities || !in.viewmatrix || !in.projmatrix || !in.cam_pos || !in.background || !in.radii)
+        return fail(IGS_RAST_E_INVALID, "igs_rast_forward: NULL required input");
+    if (!in.out_color || (!ex.count && (!in.out_coord || !in.out_mcoord || !in.out_depth || !in.out_mdepth || !in.out_alpha || !in.out_normal)))
+        return fail(IGS_RAST_E_INVALID, "igs_rast_forward: NULL output");
+    if (!in.colors_precomp && !in.shs) return fail(IGS_RAST_E_INVALID, "igs_rast_forward: neither shs nor colors_precomp");
+    if (!in.cov3D_precomp && (!in.scales || !in.rotations)) return fail(IGS_RAST_E_INVALID, "igs_rast_forward: neither scales/rotations nor cov3D_precomp");
+    if (!in.colors_precomp && (in.M < (in.D + 1) * (in.D + 1) || in.D < 0 || in.D > 3))
+        return fail(IGS_RAST_E_INVALID, "igs_rast_forward: SH degree / coefficient count mismatch");
+    if (int rc = ensure_slot()) return rc;
+
+    Frame f(in, ex);
+    uint64_t min_capacity = 0;
+    for (;;) {
         // slab size: sticky per thread, grown when a frame overflowed (the refine loop renders similar views over and over)
         uint64_t slab = g_hint.slab ? g_hint.slab : 1024;
         if (min_capacity > slab) slab = (min_capacity + 255) / 256 * 256;
         if (slab > TILE_SORT_BIG) slab = TILE_SORT_BIG;
-        if (Tn * slab > 0x7FFFFFFFull || Tn * slab * 12 > SLAB_MAX_BYTES) {
-            // slabs would not fit the 32-bit list positions / a sane scratch size: global sort instead
-            return forward_impl(stream, geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M,
-                                background, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                                cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, kernel_size, prefiltered, out_color,
-                                out_coord, out_mcoord, out_depth, out_mdepth, out_alpha, out_normal, radii, require_coord, require_depth,
-                                debug, true, 0, ex);
+        if (f.Tn * slab > 0x7FFFFFFFull || f.Tn * slab * 12 > SLAB_MAX_BYTES) radix = true;      // (32-bit list positions / a sane scratch size)
+        if (int rc = carve_frame(f)) return rc;
+        Binned b;
+        if (int rc = radix ? bin_radix(f, b) : bin_slab(f, (uint32_t)slab, b)) return rc;
+        if (int rc = launch_blend(f, b)) return rc;
+        if (b.pending && ex.defer_status) {
+            if (!ex.no_latch) { g_pending.active = true; g_pending.slab = b.slab_size; }
+            if (g_prof.on) g_prof.calls++;
+            return 0x7FFFFFFF;                   // "unknown yet": an upper bound that igs_rast_backward accepts as R
         }
-        slab_size = (uint32_t)slab;
-        const SlabLayout KL(Tn, slab);
-        char* bbase = binning_buffer(binning_user, KL.total);
-        if (!bbase) return fail(IGS_RAST_E_ALLOC, "binning buffer callback returned NULL");
-        bbase = align_ptr(bbase);
-        point_list = (uint32_t*)(bbase + KL.point_list);
-        uint64_t* pairs = (uint64_t*)(bbase + KL.pairs);
-        counters = (uint32_t*)(ibase + IL.counters);
-        // The tile sort leaves the fill cursors and the count shards zeroed behind it, so a buffer that was clean before a frame is clean
-        // after it: a caller that vouches for its buffer (igs_refine_step_args::scratch_clean) skips the zero-fill launch, unless
-        // something on this thread was cut short between a binning kernel and its tile sort (g_counters_dirty).
-        if (ex.scratch_clean && !g_counters_dirty) fp.zero_stats = stats;
-        else HIP_TRY(zero_fill_async(s, tile_count, IL.zero_end - IL.tile_count), "zero tile counters");   // tile_count + stats + counters
-        g_counters_dirty = true;
-        prof_mark(s, ST_GAP);
-        HIP_TRY(launch_preprocess_fwd(s, fp, rec, tiles, nullptr, nullptr, radii, counters, nullptr, 0, tile_count, pairs, slab_size, ex.count),
-                "preprocess_fwd launch");
-        DBG_SYNC("preprocess_fwd");
-        prof_mark(s, ST_PREPROCESS);
-        // fused refine step: the tile sort also writes the blend kernel's dispatch order and leaves the fill cursors for that kernel to zero
-        static const bool no_step_order = getenv("IGS_NO_STEP_ORDER") != nullptr;      // (A/B switch for measurements)
-        use_step_order = !no_step_order && ex.fused_bwd && ex.skip_bwd_state && !colors_precomp && (require_coord != 0) == (require_depth != 0)
-                         && step_order_usable((uint32_t)gx, (uint32_t)gy, slab_size);
-        step_cursors = tile_count;
-        HIP_TRY(launch_tile_sort(s, (uint32_t)Tn, tile_count, pairs, point_list, ranges, slab_size, stats, counters, (uint32_t)P,
-                                 use_step_order ? (uint32_t*)(ibase + IL.tile_order) : nullptr, (uint32_t)gx, (uint32_t)gy), "tile_sort launch");
-        g_counters_dirty = use_step_order;          // (then clean only once the blend kernel below has been launched)
-        DBG_SYNC("tile_sort");
-        prof_mark(s, ST_TILE_SORT);
-        slab_stats = stats;
-        g_last_fwd.overflow = stats + 1; g_last_fwd.prefilter = stats + 2;      // (the tile sort moved the flag there)
-        slab_pending = true;
-    } else {
-        // ---------------- global radix binning (fallback for tiles denser than TILE_SORT_BIG) ----------------
-        HIP_TRY(hipMemsetAsync(counters, 0, counter_bytes, s), "memset counters");
-
-        uint32_t dnb = 0, dper = 0;
-        sort_geometry((uint32_t)P, &dnb, &dper);
-        HIP_TRY(hipMemsetAsync(ghist, 0, (size_t)256 * SORT_MAX_BLOCKS * 4, s), "memset depth-sort histogram 0");
-        prof_mark(s, ST_GAP);
-        HIP_TRY(launch_preprocess_fwd(s, fp, rec, tiles, keys_a, vals_a, radii, counters, ghist, dper, nullptr, nullptr, 0, ex.count), "preprocess_fwd launch");
-        DBG_SYNC("preprocess_fwd");
-        prof_mark(s, ST_PREPROCESS);
-        // instance count: read back while the depth sort runs
-        HIP_TRY(hipMemcpyAsync(g_slot.pinned, counters, counter_bytes, hipMemcpyDeviceToHost, s), "memcpy count");
-        HIP_TRY(hipEventRecord(g_slot.ev, s), "event record");
-        prof_mark(s, ST_GAP);
-
-        uint32_t *dk = nullptr, *order = nullptr;
-        HIP_TRY(radix_sort_pairs(s, (uint32_t)P, keys_a, keys_b, vals_a, vals_b, ghist, 0, 32, &dk, &order), "depth sort launch");
-        DBG_SYNC("depth sort");
-        prof_mark(s, ST_DEPTH_SORT);
-        const int nblk = (P + 255) / 256;
-        HIP_TRY(launch_count_sorted(s, P, order, tiles, blocksum), "count_sorted launch");
-        HIP_TRY(launch_scan_blocksums(s, nblk, blocksum), "scan_blocksums launch");
-        DBG_SYNC("scan");
-        prof_mark(s, ST_SCAN);
-
-        HIP_TRY(hipEventSynchronize(g_slot.ev), "event sync");
-        uint64_t R64 = 0;
-        for (int sh = 0; sh < COUNTER_SHARDS; sh++) R64 += g_slot.pinned[COUNTER_SHARD_STRIDE * (1 + sh)];
-        if (R64 > 0x7FFFFFFFull) return fail(IGS_RAST_E_INVALID, "instance count overflows int");
-        R = (uint32_t)R64;
-        if (g_slot.pinned[1]) return fail(IGS_RAST_E_PREFILTER, "Point is filtered although prefiltered is set. This shouldn't happen!");
-
-        const BinLayout BL(R);
-        char* bbase = binning_buffer(binning_user, BL.total);
-        if (!bbase) return fail(IGS_RAST_E_ALLOC, "binning buffer callback returned NULL");
-        bbase = align_ptr(bbase);
-        point_list = (uint32_t*)(bbase + BL.point_list);
-        uint32_t* bkeys_a = (uint32_t*)(bbase + BL.keys_a); uint32_t* bkeys_b = (uint32_t*)(bbase + BL.keys_b);
-        uint32_t* bvals_b = (uint32_t*)(bbase + BL.vals_b);
-        uint32_t* bhist = (uint32_t*)(bbase + BL.hist);
-
-        HIP_TRY(hipMemsetAsync(ranges, 0, Tn * 8, s), "memset ranges");               // rasterizer_impl.cu:383
-        prof_mark(s, ST_GAP);
-        if (R > 0) {
-            const int bits = ceil_log2((uint32_t)Tn);
-            const int passes = (bits + 7) / 8;
-            // arrange the ping-pong so that the sorted ids land in point_list
-            uint32_t *ka, *kb, *va, *vb;
-            if (passes % 2 == 0) { ka = bkeys_a; va = point_list; kb = bkeys_b; vb = bvals_b; }
-            else                 { ka = bkeys_b; va = bvals_b;   kb = bkeys_a; vb = point_list; }
-            uint32_t tnb = 0, tper = 0;
-            sort_geometry(R, &tnb, &tper);
-            HIP_TRY(hipMemsetAsync(bhist, 0, (size_t)256 * SORT_MAX_BLOCKS * 4, s), "memset tile-sort histogram 0");
-            const uint32_t mask0 = bits >= 8 ? 255u : ((1u << bits) - 1u);
-            HIP_TRY(launch_emit_instances(s, P, gx, gy, order, tiles, blocksum, rec, radii, ka, va, passes ? bhist : nullptr, tper, mask0),
-                    "emit launch");
-            DBG_SYNC("emit");
-            prof_mark(s, ST_EMIT);
-            uint32_t *sk = nullptr, *sv = nullptr;
-            HIP_TRY(radix_sort_pairs(s, R, ka, kb, va, vb, bhist, 0, bits, &sk, &sv), "tile sort launch");
-            DBG_SYNC("tile sort");
-            prof_mark(s, ST_TILE_SORT);
-            if (sv != point_list) return fail(IGS_RAST_E_INVALID, "internal: sort ping-pong mismatch");
-            HIP_TRY(launch_tile_ranges(s, R, sk, ranges), "tile_ranges launch");
-            DBG_SYNC("tile_ranges");
-            prof_mark(s, ST_RANGES);
-        }
+        // slab binning: only now does the host look at R -- the whole pipeline above was enqueued without waiting for it
+        uint32_t overflow = 0;
+        const int R = b.pending ? collect_status(in.s, &overflow) : (int)b.R;
+        if (R < 0) return R;
+        if (!overflow) { if (g_prof.on) { g_prof.r_sum += (double)R; g_prof.calls++; } return R; }
+        // a tile holds more instances than its slab (overflow = the largest such tile): redo with what is now known
+        g_hint.slab = slab_hint_for(overflow);
+        radix = overflow > (uint32_t)TILE_SORT_BIG;
+        min_capacity = overflow;
     }
-
-    BlendFwdArgs ba;
-    ba.W = width; ba.H = height; ba.gx = gx; ba.gy = gy; ba.fx = fp.fx; ba.fy = fp.fy; ba.bg = background;
-    ba.ranges = ranges; ba.point_list = point_list; ba.rec = rec; ba.colors_precomp = colors_precomp;
-    ba.out_color = out_color; ba.out_coord = out_coord; ba.out_mcoord = out_mcoord; ba.out_depth = out_depth;
-    ba.out_mdepth = out_mdepth; ba.out_alpha = out_alpha; ba.out_normal = out_normal;
-    ba.n_contrib = (uint32_t*)(ibase + IL.n_contrib);
-    ba.accum_coord = (float*)(ibase + IL.accum_coord); ba.accum_depth = (float*)(ibase + IL.accum_depth);
-    ba.normal_length = (float*)(ibase + IL.normal_length);
-    ba.stats_src = slab_stats; ba.flag_src = slab_stats ? slab_stats + 2 : counters + 1; ba.host_dst = slab_pending ? g_slot.pinned_dev : nullptr;
-    ba.tile_order = (uint32_t*)(ibase + IL.tile_order);          // built on the side for the backward (both binning paths)
-    ba.skip_bwd_state = ex.skip_bwd_state ? 1 : 0;
-    if (slab_pending) { g_host_seq = g_host_seq + 1 ? g_host_seq + 1 : 1; g_slot.pinned[3] = 0; }
-    ba.host_seq = g_host_seq;
-    if (slab_pending && ex.no_latch) g_nowait_seq = g_host_seq;
-    g_status_stream = s;
-    const bool fuse_tiles = ex.fused_bwd && ex.skip_bwd_state && slab_pending && !colors_precomp && (require_coord != 0) == (require_depth != 0);
-    if (ex.fused_ran) *ex.fused_ran = fuse_tiles;
-    if (vanilla) {
-        ba.tile_order = nullptr;                 // (no backward follows a count pass)
-        HIP_TRY(launch_blend_count(s, ba, ex.count), "blend_count launch");
-    } else if (fuse_tiles) {
-        BlendBwdArgs& bb = *ex.fused_bwd;
-        bb.W = width; bb.H = height; bb.gx = gx; bb.gy = gy; bb.fx = fp.fx; bb.fy = fp.fy; bb.bg = background;
-        bb.ranges = ranges; bb.point_list = point_list; bb.rec = rec; bb.colors_precomp = nullptr;
-        bb.tile_order = nullptr;
-        ba.tile_order = nullptr;                 // (no separate backward kernel that could use a load order)
-        if (use_step_order) { ba.step_order = (const uint32_t*)(ibase + IL.tile_order); ba.reset_cursors = step_cursors; }
-        HIP_TRY(launch_blend_step(s, ba, bb, require_coord != 0, require_depth != 0, ex.fused_instance), "blend_step launch");
-        if (use_step_order) g_counters_dirty = false;
-    } else {
-        if (use_step_order) {                    // (cannot happen: the two conditions are the same terms -- but the cursors must not stay dirty)
-            HIP_TRY(zero_fill_async(s, step_cursors, (size_t)Tn * 4), "zero tile counters");
-            g_counters_dirty = false;
-        }
-        HIP_TRY(launch_blend_fwd(s, ba, require_coord != 0, require_depth != 0), "blend_fwd launch");
-    }
-    DBG_SYNC("blend_fwd");
-    prof_mark(s, ST_BLEND_FWD);
-    if (slab_pending && ex.defer_status) {
-        if (!ex.no_latch) { g_pending.active = true; g_pending.slab = slab_size; }
-        if (g_prof.on) g_prof.calls++;
-        return 0x7FFFFFFF;                       // "unknown yet": an upper bound that igs_rast_backward accepts as R
-    }
-    if (slab_pending) {
-        // only now does the host look at R: the whole pipeline above was enqueued without waiting for it
-        if (int rc = wait_status(s)) return rc;
-        const uint32_t R_dev = g_slot.pinned[0], overflow = g_slot.pinned[1];
-        if (g_slot.pinned[2]) return fail(IGS_RAST_E_PREFILTER, "Point is filtered although prefiltered is set. This shouldn't happen!");
-        if (R_dev > 0x7FFFFFFFu) return fail(IGS_RAST_E_INVALID, "instance count overflows int");
-        if (overflow) {
-            // a tile holds more instances than its slab (overflow = the largest such tile): redo with what is now known
-            const bool radix = overflow > (uint32_t)TILE_SORT_BIG;
-            const uint64_t want = ((uint64_t)overflow + overflow / 4 + 255) / 256 * 256;
-            g_hint.slab = (uint32_t)(want > TILE_SORT_BIG ? TILE_SORT_BIG : want);
-            return forward_impl(stream, geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M,
-                                background, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                                cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, kernel_size, prefiltered, out_color,
-                                out_coord, out_mcoord, out_depth, out_mdepth, out_alpha, out_normal, radii, require_coord, require_depth,
-                                debug, radix, overflow, ex);
-        }
-        R = R_dev;
-    }
-    if (g_prof.on) { g_prof.r_sum += (double)R; g_prof.calls++; }
-    return (int)R;
 }
 
-extern "C" int igs_rast_forward(
-    void* stream,
-    igs_rast_alloc_fn geometry_buffer, void* geometry_user, igs_rast_alloc_fn binning_buffer, void* binning_user,
-    igs_rast_alloc_fn image_buffer, void* image_user,
-    int P, int D, int M, const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-    const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-    float tan_fovx, float tan_fovy, float kernel_size, int prefiltered,
-    float* out_color, float* out_coord, float* out_mcoord, float* out_depth, float* out_mdepth, float* out_alpha,
-    float* out_normal, int* radii, int require_coord, int require_depth, int debug)
+// IGS_BINNING=radix forces the global-sort path (tests)
+static bool radix_forced() { const char* e = getenv("IGS_BINNING"); return e && strcmp(e, "radix") == 0; }
+
+// the common preamble of igs_rast_forward (Sync), igs_rast_forward_async (Deferred) and igs_rast_forward_nowait (Capture)
+enum class FwdMode { Sync, Deferred, Capture };
+static int forward_entry(FwdMode mode, const FwdIn& in)
 {
     const bool hint_clean = g_hint_clean; g_hint_clean = false;      // one-shot promise: consumed by THIS call, even a refused one
-    if (g_pending.active) return fail(IGS_RAST_E_INVALID, "igs_rast_forward: an asynchronous forward is pending on this thread; call igs_rast_forward_finish() first");
+    if (g_pending.active)          // (the status slot is single: a second frame must not start before the first one's count is collected)
+        return fail(IGS_RAST_E_INVALID,
+                    mode == FwdMode::Sync ? "igs_rast_forward: an asynchronous forward is pending on this thread; call igs_rast_forward_finish() first"
+                    : mode == FwdMode::Deferred ? "igs_rast_forward_async: the previous asynchronous forward has not been finished (igs_rast_forward_finish)"
+                    : "igs_rast_forward_nowait: an asynchronous forward is pending on this thread; call igs_rast_forward_finish() first");
+    if (mode == FwdMode::Capture) {
+        if (in.debug) return fail(IGS_RAST_E_INVALID, "igs_rast_forward_nowait: debug (a synchronisation after every launch) cannot be captured");
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= IGS_MAX_DEVICES || !g_slots.slot[dev].pinned)
+            return fail(IGS_RAST_E_INVALID, "igs_rast_forward_nowait: no status slot on this thread and device yet (run one igs_rast_forward first: pinned memory cannot be allocated during capture)");
+    }
     prof_new_frame();
-    const char* e = getenv("IGS_BINNING");                    // "radix" forces the global-sort path (tests)
-    const bool radix = e && strcmp(e, "radix") == 0;
-    FwdExtra ex0; ex0.scratch_clean = hint_clean;
-    return forward_impl(stream, geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M,
-                        background, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                        cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, kernel_size, prefiltered, out_color,
-                        out_coord, out_mcoord, out_depth, out_mdepth, out_alpha, out_normal, radii, require_coord, require_depth,
-                        debug, radix, 0, ex0);
+    FwdExtra ex;
+    ex.scratch_clean = hint_clean;
+    ex.defer_status = mode != FwdMode::Sync;
+    ex.no_latch = mode == FwdMode::Capture;
+    return forward_impl(in, ex, mode == FwdMode::Sync && radix_forced());
 }
+
+extern "C" int igs_rast_forward(FWD_PARAMS) { return forward_entry(FwdMode::Sync, FWD_IN); }
 
 // The count pass of the compress rasterizer (CudaRasterizer::Rasterizer::forwardCount, compress rasterizer_impl.cu:441-530): vanilla
 // preprocess, the same binning (slab, or the global sort), the counting colour-only blend, then score = count x opacity over P.
@@ -488,13 +527,15 @@ extern "C" int igs_rast_count_gaussians(
     if (P == 0) return 0;                                       // rasterize_points.cu CountGaussiansCUDA: nothing is launched
     if (!out_color || !count || !score || !radii) return fail(IGS_RAST_E_INVALID, "igs_rast_count_gaussians: NULL output");
     prof_new_frame();
-    const char* e = getenv("IGS_BINNING");                    // "radix" forces the global-sort path (tests)
-    const bool radix = e && strcmp(e, "radix") == 0;
+    FwdIn in{};                                                 // (no kernel_size, no geometry maps)
+    in.s = s; in.geometry_buffer = geometry_buffer; in.geometry_user = geometry_user; in.binning_buffer = binning_buffer;
+    in.binning_user = binning_user; in.image_buffer = image_buffer; in.image_user = image_user; in.P = P; in.D = D; in.M = M;
+    in.background = background; in.width = width; in.height = height; in.means3D = means3D; in.shs = shs; in.colors_precomp = colors_precomp;
+    in.opacities = opacities; in.scales = scales; in.scale_modifier = scale_modifier; in.rotations = rotations; in.cov3D_precomp = cov3D_precomp;
+    in.viewmatrix = viewmatrix; in.projmatrix = projmatrix; in.cam_pos = cam_pos; in.tan_fovx = tan_fovx; in.tan_fovy = tan_fovy;
+    in.prefiltered = prefiltered; in.out_color = out_color; in.radii = radii; in.debug = debug;
     FwdExtra ex; ex.scratch_clean = hint_clean; ex.count = count;
-    const int R = forward_impl(stream, geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M,
-                               background, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                               cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, 0.0f, prefiltered, out_color,
-                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, radii, 0, 0, debug, radix, 0, ex);
+    const int R = forward_impl(in, ex, radix_forced());
     if (R < 0) return R;
     // (after the frame is final: a slab overflow has redone it inside forward_impl)
     HIP_TRY(launch_count_score(s, P, count, opacities, score), "count_score launch");
@@ -508,77 +549,27 @@ extern "C" int igs_rast_count_gaussians(
 // read-back (which completed right after the tile scan, long before the blend) and returns the true num_rendered, or
 // IGS_RAST_E_RETRY if a tile overflowed its instance slab: everything enqueued since must then be discarded and
 // the frame redone with igs_rast_forward (the hints are updated, so it will fit).
-extern "C" int igs_rast_forward_async(
-    void* stream,
-    igs_rast_alloc_fn geometry_buffer, void* geometry_user, igs_rast_alloc_fn binning_buffer, void* binning_user,
-    igs_rast_alloc_fn image_buffer, void* image_user,
-    int P, int D, int M, const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-    const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-    float tan_fovx, float tan_fovy, float kernel_size, int prefiltered,
-    float* out_color, float* out_coord, float* out_mcoord, float* out_depth, float* out_mdepth, float* out_alpha,
-    float* out_normal, int* radii, int require_coord, int require_depth, int debug)
-{
-    // the status slot is single: a second frame must not be started before the first one's count has been collected
-    const bool hint_clean = g_hint_clean; g_hint_clean = false;      // (consumed by this call, even a refused one)
-    if (g_pending.active) return fail(IGS_RAST_E_INVALID, "igs_rast_forward_async: the previous asynchronous forward has not been finished (igs_rast_forward_finish)");
-    prof_new_frame();
-    FwdExtra ex; ex.defer_status = true; ex.scratch_clean = hint_clean;
-    const int rc = forward_impl(stream, geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M,
-                                background, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                                cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, kernel_size, prefiltered, out_color,
-                                out_coord, out_mcoord, out_depth, out_mdepth, out_alpha, out_normal, radii, require_coord, require_depth,
-                                debug, false, 0, ex);
-    return rc;
-}
+extern "C" int igs_rast_forward_async(FWD_PARAMS) { return forward_entry(FwdMode::Deferred, FWD_IN); }
 extern "C" int igs_rast_forward_finish(void)
 {
     if (!g_pending.active) return fail(IGS_RAST_E_INVALID, "igs_rast_forward_finish: no asynchronous forward pending");
     g_pending.active = false;
-    if (int rc = wait_status(g_status_stream)) return rc;
-    const uint32_t R_dev = g_slot.pinned[0], overflow = g_slot.pinned[1];
-    if (g_slot.pinned[2]) return fail(IGS_RAST_E_PREFILTER, "Point is filtered although prefiltered is set. This shouldn't happen!");
-    if (R_dev > 0x7FFFFFFFu) return fail(IGS_RAST_E_INVALID, "instance count overflows int");
+    uint32_t overflow = 0;
+    const int R = collect_status(g_status_stream, &overflow);
+    if (R < 0) return R;
     if (overflow) {
-        const uint64_t want = ((uint64_t)overflow + overflow / 4 + 255) / 256 * 256;
-        g_hint.slab = (uint32_t)(want > TILE_SORT_BIG ? TILE_SORT_BIG : want);       // igs_rast_forward falls back further if needed
+        g_hint.slab = slab_hint_for(overflow);       // igs_rast_forward falls back further if needed
         return fail(IGS_RAST_E_RETRY, "a tile overflowed its instance slab: redo the frame");
     }
-    if (g_prof.on) g_prof.r_sum += (double)R_dev;
-    return (int)R_dev;
+    if (g_prof.on) g_prof.r_sum += (double)R;
+    return R;
 }
 
 // Forward for stream capture (hipGraph): identical launches, NO host-side wait, no pending latch -- nothing in it is illegal
 // while the stream is capturing (the pinned status slot must exist already: run one ordinary forward on this thread and device
 // first).  Every replay of the captured launches posts its {R, overflow, prefilter flag} into the slot;
 // igs_rast_last_status() reads it back once the caller has synchronised the stream.
-extern "C" int igs_rast_forward_nowait(
-    void* stream,
-    igs_rast_alloc_fn geometry_buffer, void* geometry_user, igs_rast_alloc_fn binning_buffer, void* binning_user,
-    igs_rast_alloc_fn image_buffer, void* image_user,
-    int P, int D, int M, const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
-    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-    const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-    float tan_fovx, float tan_fovy, float kernel_size, int prefiltered,
-    float* out_color, float* out_coord, float* out_mcoord, float* out_depth, float* out_mdepth, float* out_alpha,
-    float* out_normal, int* radii, int require_coord, int require_depth, int debug)
-{
-    const bool hint_clean = g_hint_clean; g_hint_clean = false;      // (consumed by this call, even a refused one)
-    if (g_pending.active) return fail(IGS_RAST_E_INVALID, "igs_rast_forward_nowait: an asynchronous forward is pending on this thread; call igs_rast_forward_finish() first");
-    if (debug) return fail(IGS_RAST_E_INVALID, "igs_rast_forward_nowait: debug (a synchronisation after every launch) cannot be captured");
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= IGS_MAX_DEVICES || !g_slots.slot[dev].pinned)
-        return fail(IGS_RAST_E_INVALID, "igs_rast_forward_nowait: no status slot on this thread and device yet (run one igs_rast_forward first: pinned memory cannot be allocated during capture)");
-    prof_new_frame();
-    FwdExtra ex; ex.defer_status = true; ex.no_latch = true; ex.scratch_clean = hint_clean;
-    return forward_impl(stream, geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P, D, M,
-                        background, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                        cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, kernel_size, prefiltered, out_color,
-                        out_coord, out_mcoord, out_depth, out_mdepth, out_alpha, out_normal, radii, require_coord, require_depth,
-                        0, false, 0, ex);
-}
+extern "C" int igs_rast_forward_nowait(FWD_PARAMS) { return forward_entry(FwdMode::Capture, FWD_IN); }
 // What the last slab-binned forward of this thread and device posted.  *overflow != 0: a tile needed that many instance slots and
 // the per-tile slabs were smaller -- the frame (and everything computed from it) is invalid; the slab hint has been raised, so a
 // new capture / an ordinary igs_rast_forward will fit.  Only meaningful once the stream has been synchronised.
@@ -593,24 +584,15 @@ static int last_status(int* num_rendered, unsigned* overflow, unsigned* prefilte
     const uint32_t seq = __atomic_load_n(&p[3], __ATOMIC_ACQUIRE);
     if (check_seq && seq != (g_nowait_seq ? g_nowait_seq : g_host_seq))
         return fail(IGS_RAST_E_RETRY, "igs_rast_last_status: the captured forward has not posted its status yet (replay the graph and synchronise the stream first)");
-    const uint32_t R = __atomic_load_n(&p[0], __ATOMIC_ACQUIRE), ov = __atomic_load_n(&p[1], __ATOMIC_ACQUIRE);
-    if (num_rendered) *num_rendered = R > 0x7FFFFFFFu ? 0x7FFFFFFF : (int)R;
-    if (overflow) *overflow = ov;
-    if (prefilter_flag) *prefilter_flag = p[2];
-    if (ov) {
-        const uint64_t want = ((uint64_t)ov + ov / 4 + 255) / 256 * 256;
-        if (want > g_hint.slab) g_hint.slab = (uint32_t)(want > TILE_SORT_BIG ? TILE_SORT_BIG : want);
-    }
+    const FrameStatus st = read_status(p);
+    if (num_rendered) *num_rendered = st.R > 0x7FFFFFFFu ? 0x7FFFFFFF : (int)st.R;
+    if (overflow) *overflow = st.overflow;
+    if (prefilter_flag) *prefilter_flag = st.prefilter;
+    if (st.overflow && slab_hint_for(st.overflow) > g_hint.slab) g_hint.slab = slab_hint_for(st.overflow);      // (only ever grows it)
     return 0;
 }
-extern "C" int igs_rast_last_status(int* num_rendered, unsigned* overflow, unsigned* prefilter_flag)
-{
-    return last_status(num_rendered, overflow, prefilter_flag, true);
-}
-extern "C" int igs_rast_last_posted_status(int* num_rendered, unsigned* overflow, unsigned* prefilter_flag)
-{
-    return last_status(num_rendered, overflow, prefilter_flag, false);
-}
+extern "C" int igs_rast_last_status(int* num_rendered, unsigned* overflow, unsigned* prefilter) { return last_status(num_rendered, overflow, prefilter, true); }
+extern "C" int igs_rast_last_posted_status(int* num_rendered, unsigned* overflow, unsigned* prefilter) { return last_status(num_rendered, overflow, prefilter, false); }
 
 extern "C" void igs_rast_set_slab_hint(unsigned slots_per_tile) { g_hint.slab = slots_per_tile > TILE_SORT_BIG ? TILE_SORT_BIG : slots_per_tile; }
 extern "C" unsigned igs_rast_get_slab_hint(void) { return g_hint.slab; }
@@ -638,6 +620,31 @@ extern "C" void igs_rast_next_backward_options(int nan_report, float clamp_grads
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= IGS_MAX_DEVICES) return;
     g_nan[dev].requested = nan_report != 0;
+}
+// the NaN report asked for this backward, if any (one-shot: the request is consumed here, even if the call fails later)
+static int take_nan_request(NanSlot** slot)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= IGS_MAX_DEVICES || !g_nan[dev].requested) return 0;
+    NanSlot& n = g_nan[dev]; n.requested = false;
+    if (!n.pinned) {
+        HIP_TRY(hipHostMalloc((void**)&n.pinned, NAN_RING * 4, hipHostMallocDefault), "hipHostMalloc");
+        HIP_TRY(hipHostGetDevicePointer((void**)&n.pinned_dev, n.pinned, 0), "hipHostGetDevicePointer");
+        memset(n.pinned, 0, NAN_RING * 4);
+        n.tickets = new NanTicket[NAN_RING];
+    }
+    *slot = &n; g_nan_dev = dev;
+    return 0;
+}
+// the next ticket of `n` for the per-Gaussian kernel about to be launched with `ga`
+static int next_nan_ticket(NanSlot& n, GeomBwdArgs& ga, NanTicket** ticket)
+{
+    n.seq = n.seq + 1 ? n.seq + 1 : 1;
+    NanTicket* t = &n.tickets[n.seq % NAN_RING];
+    if (!t->ev) HIP_TRY(hipEventCreateWithFlags(&t->ev, hipEventDisableTiming), "hipEventCreate");
+    t->word = n.pinned + (n.seq % NAN_RING); t->seq = n.seq;
+    ga.nan_host = n.pinned_dev + (n.seq % NAN_RING); ga.nan_seq = n.seq;
+    *ticket = t; return 0;
 }
 static int nan_wait_ticket(const NanTicket* t, uint32_t seq)
 {
@@ -676,86 +683,73 @@ extern "C" int igs_rast_nan_report_wait_at(const void* ticket, unsigned seq)
     return nan_wait_ticket((const NanTicket*)ticket, seq);
 }
 
-// l1_gt != NULL: L1 loss fused into the blend backward (dL_dpix ignored); fuse != NULL: activation backward + Adam fused into
-// the per-Gaussian backward (no gradient outputs except the optional dL_dmean2D).
-static int backward_impl(
-    void* stream, int P, int D, int M, int R, const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* colors_precomp, const float* alphas,
-    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-    const float* viewmatrix, const float* projmatrix, const float* campos,
-    float tan_fovx, float tan_fovy, float kernel_size, const int* radii, const float* normalmap,
-    const char* geom_buffer, const char* binning_buffer, const char* image_buffer,
-    const float* dL_dpix, const float* dL_dpix_coord, const float* dL_dpix_mcoord, const float* dL_dpix_depth,
-    const float* dL_dpix_mdepth, const float* dL_dalphas, const float* dL_dpixel_normals,
-    void* workspace,
-    float* dL_dmean2D, float* dL_dcolor, float* dL_dopacity, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
-    float* dL_dscale, float* dL_drot, int require_coord, int require_depth, int debug,
-    const float* l1_gt, const float* l1_color, float l1_scale, const RefineFuse* fuse)
+// the reference's backward argument list (CudaRasterizer::Rasterizer::backward), in the order of igs_rast_backward's parameters
+struct BwdIn {
+    hipStream_t s; int P, D, M, R; const float* background; int width, height;
+    const float *means3D, *shs, *colors_precomp, *alphas, *scales; float scale_modifier; const float *rotations, *cov3D_precomp;
+    const float *viewmatrix, *projmatrix, *campos; float tan_fovx, tan_fovy, kernel_size; const int* radii; const float* normalmap;
+    const char *geom_buffer, *binning_buffer, *image_buffer;
+    const float *dL_dpix, *dL_dpix_coord, *dL_dpix_mcoord, *dL_dpix_depth, *dL_dpix_mdepth, *dL_dalphas, *dL_dpixel_normals; void* workspace;
+    float *dL_dmean2D, *dL_dcolor, *dL_dopacity, *dL_dmean3D, *dL_dcov3D, *dL_dsh, *dL_dscale, *dL_drot; int require_coord, require_depth, debug;
+};
+// what igs_refine_step fuses into the backward: the activation backward + Adam into the per-Gaussian kernel (no gradient outputs except
+// the optional dL_dmean2D), and with l1_gt != NULL the L1 loss into the blend backward (dL_dpix ignored)
+struct BwdFused { const RefineFuse& adam; const float* l1_gt; const float* l1_color; float l1_scale; };
+
+static int backward_impl(const BwdIn& in, const BwdFused* fz)
 {
-    hipStream_t s = (hipStream_t)stream;
-    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(IGS_RAST_E_INVALID, "igs_rast_backward: bad sizes");
+    const hipStream_t s = in.s; const int debug = in.debug; const int P = in.P;
+    const RefineFuse* fuse = fz ? &fz->adam : nullptr;
+    if (P < 0 || in.R < 0 || in.width <= 0 || in.height <= 0) return fail(IGS_RAST_E_INVALID, "igs_rast_backward: bad sizes");
     if (P == 0) return 0;                                       // rasterize_points.cu:195
-    if (!geom_buffer || !image_buffer || (!binning_buffer && R > 0) || !workspace)
+    if (!in.geom_buffer || !in.image_buffer || (!in.binning_buffer && in.R > 0) || !in.workspace)
         return fail(IGS_RAST_E_INVALID, "igs_rast_backward: NULL scratch buffer");
-    if (!means3D || !alphas || !viewmatrix || !projmatrix || !campos || !background || !radii || !normalmap)
+    if (!in.means3D || !in.alphas || !in.viewmatrix || !in.projmatrix || !in.campos || !in.background || !in.radii || !in.normalmap)
         return fail(IGS_RAST_E_INVALID, "igs_rast_backward: NULL required input");
     // any of the seven upstream gradients may be NULL = "all zeros" (an output that did not take part in the loss)
-    if (!fuse && (!dL_dmean2D || !dL_dcolor || !dL_dopacity || !dL_dmean3D || !dL_dcov3D || !dL_dscale || !dL_drot || (M > 0 && !dL_dsh)))
+    if (!fuse && (!in.dL_dmean2D || !in.dL_dcolor || !in.dL_dopacity || !in.dL_dmean3D || !in.dL_dcov3D || !in.dL_dscale || !in.dL_drot
+                  || (in.M > 0 && !in.dL_dsh)))
         return fail(IGS_RAST_E_INVALID, "igs_rast_backward: NULL output");
 
     if ((uint64_t)P * GACC_F * 8 >= (1ull << 32))      // (the blend backward addresses its accumulator rows with 32-bit byte offsets)
         return fail(IGS_RAST_E_INVALID, "igs_rast_backward: more than 16 million Gaussians are not supported");
-    const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
-    const size_t Tn = (size_t)gx * gy, HW = (size_t)width * height;
+    const int gx = (in.width + TILE - 1) / TILE, gy = (in.height + TILE - 1) / TILE;
+    const size_t Tn = (size_t)gx * gy, HW = (size_t)in.width * in.height;
     const GeomLayout GL(P);
     const ImgLayout IL(HW, Tn);
-    const BinLayout BL(R);
-    const char* gbase = align_ptr(geom_buffer);
-    const char* ibase = align_ptr(image_buffer);
-    const char* bbase = binning_buffer ? align_ptr(binning_buffer) : nullptr;
-    double* gacc = (double*)align_ptr((const char*)workspace);
-    const float fy = height / (2.0f * tan_fovy), fx = width / (2.0f * tan_fovx);
+    const BinLayout BL(in.R);
+    const char* gbase = align_ptr(in.geom_buffer);
+    const char* ibase = align_ptr(in.image_buffer);
+    const char* bbase = in.binning_buffer ? align_ptr(in.binning_buffer) : nullptr;
+    double* gacc = (double*)align_ptr((const char*)in.workspace);
+    const float fy = in.height / (2.0f * in.tan_fovy), fx = in.width / (2.0f * in.tan_fovx);
 
-    // NaN report asked for this backward (one-shot, consumed here even if the call fails later)
+    const float clamp_next = g_next_clamp; g_next_clamp = 0.f;       // (one-shot, consumed here even if the call fails later)
     NanSlot* nan = nullptr;
-    const float clamp_next = g_next_clamp; g_next_clamp = 0.f;
-    if (!fuse) {
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < IGS_MAX_DEVICES && g_nan[dev].requested) {
-            g_nan[dev].requested = false;
-            NanSlot& n = g_nan[dev];
-            if (!n.pinned) {
-                HIP_TRY(hipHostMalloc((void**)&n.pinned, NAN_RING * 4, hipHostMallocDefault), "hipHostMalloc");
-                HIP_TRY(hipHostGetDevicePointer((void**)&n.pinned_dev, n.pinned, 0), "hipHostGetDevicePointer");
-                memset(n.pinned, 0, NAN_RING * 4);
-                n.tickets = new NanTicket[NAN_RING];
-            }
-            nan = &n; g_nan_dev = dev;
-        }
-    }
+    if (!fuse) { if (int rc = take_nan_request(&nan)) return rc; }
     prof_mark(s, ST_GAP);
     float* loss_shards = (float*)((char*)gacc + ws_gacc_bytes(P));
     // which blend instance will run (launch_blend_bwd decides the same way): the colour-only one packs its moments into 64-byte rows
-    const bool will_compact = !(require_coord && (dL_dpix_coord || dL_dpix_mcoord)) && !(require_depth && (dL_dpix_depth || dL_dpix_mdepth))
-                              && !((require_coord || require_depth) && dL_dpixel_normals);
+    const bool will_compact = !(in.require_coord && (in.dL_dpix_coord || in.dL_dpix_mcoord)) && !(in.require_depth && (in.dL_dpix_depth || in.dL_dpix_mdepth))
+                              && !((in.require_coord || in.require_depth) && in.dL_dpixel_normals);
     if (!(fuse && fuse->prezeroed)) {              // (igs_refine_step: the forward's preprocess kernel zero-filled the accumulators)
         HIP_TRY(zero_fill_async(s, gacc, (size_t)P * (will_compact ? GACC_COMPACT_F : GACC_F) * 8), "zero gacc");
-        if (l1_gt) HIP_TRY(zero_fill_async(s, loss_shards, WS_LOSS_BYTES), "zero loss shards");
+        if (fz && fz->l1_gt) HIP_TRY(zero_fill_async(s, loss_shards, WS_LOSS_BYTES), "zero loss shards");
     }
     prof_mark(s, ST_MEMSET);
     BlendBwdArgs ba;
-    ba.W = width; ba.H = height; ba.gx = gx; ba.gy = gy; ba.fx = fx; ba.fy = fy; ba.bg = background;
+    ba.W = in.width; ba.H = in.height; ba.gx = gx; ba.gy = gy; ba.fx = fx; ba.fy = fy; ba.bg = in.background;
     ba.ranges = (const uint32_t*)(ibase + IL.ranges);
     ba.point_list = bbase ? (const uint32_t*)(bbase + BL.point_list) : nullptr;
-    ba.rec = (const float*)(gbase + GL.rec); ba.colors_precomp = colors_precomp;
-    ba.alphas = alphas; ba.normalmap = normalmap;
+    ba.rec = (const float*)(gbase + GL.rec); ba.colors_precomp = in.colors_precomp;
+    ba.alphas = in.alphas; ba.normalmap = in.normalmap;
     ba.accum_coord = (const float*)(ibase + IL.accum_coord); ba.accum_depth = (const float*)(ibase + IL.accum_depth);
     ba.normal_length = (const float*)(ibase + IL.normal_length); ba.n_contrib = (const uint32_t*)(ibase + IL.n_contrib);
-    ba.dL_dpix = dL_dpix; ba.dL_dcoord = dL_dpix_coord; ba.dL_dmcoord = dL_dpix_mcoord; ba.dL_ddepth = dL_dpix_depth;
-    ba.dL_dmdepth = dL_dpix_mdepth; ba.dL_dalpha = dL_dalphas; ba.dL_dnormal = dL_dpixel_normals;
+    ba.dL_dpix = in.dL_dpix; ba.dL_dcoord = in.dL_dpix_coord; ba.dL_dmcoord = in.dL_dpix_mcoord; ba.dL_ddepth = in.dL_dpix_depth;
+    ba.dL_dmdepth = in.dL_dpix_mdepth; ba.dL_dalpha = in.dL_dalphas; ba.dL_dnormal = in.dL_dpixel_normals;
     ba.gacc = gacc;
-    ba.l1_gt = l1_gt; ba.l1_color = l1_color; ba.l1_scale = l1_scale; ba.l1_loss = loss_shards;
-    ba.want_absgrad = (fuse && !dL_dmean2D) ? 0 : 1;
+    ba.l1_gt = fz ? fz->l1_gt : nullptr; ba.l1_color = fz ? fz->l1_color : nullptr; ba.l1_scale = fz ? fz->l1_scale : 0.f; ba.l1_loss = loss_shards;
+    ba.want_absgrad = (fuse && !in.dL_dmean2D) ? 0 : 1;
     ba.tile_order = (const uint32_t*)(ibase + IL.tile_order);    // the forward's blend kernel ordered the tiles heaviest-first
     ba.first_trainable = fuse ? fuse->first : 0;                 // (masked refine step: frozen splats form no moments)
     bool gacc_compact = will_compact;
@@ -764,29 +758,30 @@ static int backward_impl(
         // the blend backward ran inside the forward's tile kernel (blend_step.hip): colour-only moments in compact rows
         if (!will_compact) return fail(IGS_RAST_E_INVALID, "internal: fused tile kernel with a non-compact accumulator layout");
         prof_mark(s, ST_BLEND_BWD);
-    } else if (R > 0) {
-        HIP_TRY(launch_blend_bwd(s, ba, require_coord != 0, require_depth != 0, &gacc_compact, &inst_bits), "blend_bwd launch");
+    } else if (in.R > 0) {
+        HIP_TRY(launch_blend_bwd(s, ba, in.require_coord != 0, in.require_depth != 0, &gacc_compact, &inst_bits), "blend_bwd launch");
         if (gacc_compact != will_compact) return fail(IGS_RAST_E_INVALID, "internal: accumulator layout mismatch");
         __atomic_store_n(&g_last_bwd_instance, inst_bits, __ATOMIC_RELAXED);
         DBG_SYNC("blend_bwd");
         prof_mark(s, ST_BLEND_BWD);
     } else __atomic_store_n(&g_last_bwd_instance, -1, __ATOMIC_RELAXED);
     GeomBwdArgs ga;
-    ga.P = P; ga.D = D; ga.M = shs ? M : 0; ga.W = width; ga.H = height;
-    ga.means3D = means3D; ga.shs = shs; ga.scales = scales; ga.rotations = rotations; ga.cov3D_precomp = cov3D_precomp;
-    ga.radii = radii; ga.scale_modifier = scale_modifier; ga.tan_fovx = tan_fovx; ga.tan_fovy = tan_fovy;
-    ga.fx = fx; ga.fy = fy; ga.kernel_size = kernel_size;
-    ga.view = viewmatrix; ga.proj = projmatrix; ga.campos = campos;
+    ga.P = P; ga.D = in.D; ga.M = in.shs ? in.M : 0; ga.W = in.width; ga.H = in.height;
+    ga.means3D = in.means3D; ga.shs = in.shs; ga.scales = in.scales; ga.rotations = in.rotations; ga.cov3D_precomp = in.cov3D_precomp;
+    ga.radii = in.radii; ga.scale_modifier = in.scale_modifier; ga.tan_fovx = in.tan_fovx; ga.tan_fovy = in.tan_fovy;
+    ga.fx = fx; ga.fy = fy; ga.kernel_size = in.kernel_size;
+    ga.view = in.viewmatrix; ga.proj = in.projmatrix; ga.campos = in.campos;
     ga.rec = ba.rec; ga.gacc = gacc; ga.gacc_compact = gacc_compact ? 1 : 0;
     if (fuse && fuse->plane_tag) { ga.plane_cache = (const float*)(gbase + GL.planes); ga.plane_tag = fuse->plane_tag; }
-    ga.dL_dmean2D = dL_dmean2D; ga.dL_dcolor = dL_dcolor; ga.dL_dopacity = dL_dopacity; ga.dL_dmean3D = dL_dmean3D;
-    ga.dL_dcov3D = dL_dcov3D; ga.dL_dsh = dL_dsh; ga.dL_dscale = dL_dscale; ga.dL_drot = dL_drot;
+    ga.dL_dmean2D = in.dL_dmean2D; ga.dL_dcolor = in.dL_dcolor; ga.dL_dopacity = in.dL_dopacity; ga.dL_dmean3D = in.dL_dmean3D;
+    ga.dL_dcov3D = in.dL_dcov3D; ga.dL_dsh = in.dL_dsh; ga.dL_dscale = in.dL_dscale; ga.dL_drot = in.dL_drot;
     if (fuse) {
         RefineFuse f = *fuse;
         if (!f.loss_shards) f.loss_shards = loss_shards;
         if (f.color_event && f.color_out && f.grad_out) {
             // N > 1: this view's colour gradients leave one kernel early, the all-gather runs underneath the per-Gaussian kernel
-            HIP_TRY(launch_extract_view_colors(s, P, radii, ba.rec, gacc, gacc_compact ? 1 : 0, shs != nullptr && M > 0, f.color_out), "extract_view_colors launch");
+            HIP_TRY(launch_extract_view_colors(s, P, in.radii, ba.rec, gacc, gacc_compact ? 1 : 0, in.shs != nullptr && in.M > 0, f.color_out),
+                    "extract_view_colors launch");
             HIP_TRY(hipEventRecord((hipEvent_t)f.color_event, s), "record colour event");
             f.color_out = nullptr; f.colors_extracted = 1;
         }
@@ -794,13 +789,7 @@ static int backward_impl(
     } else {
         ga.clamp = clamp_next;
         NanTicket* ticket = nullptr;
-        if (nan) {
-            nan->seq = nan->seq + 1 ? nan->seq + 1 : 1;
-            ticket = &nan->tickets[nan->seq % NAN_RING];
-            if (!ticket->ev) HIP_TRY(hipEventCreateWithFlags(&ticket->ev, hipEventDisableTiming), "hipEventCreate");
-            ticket->word = nan->pinned + (nan->seq % NAN_RING); ticket->seq = nan->seq;
-            ga.nan_host = nan->pinned_dev + (nan->seq % NAN_RING); ga.nan_seq = nan->seq;
-        }
+        if (nan) { if (int rc = next_nan_ticket(*nan, ga, &ticket)) return rc; }
         HIP_TRY(launch_geom_bwd(s, ga), "geom_bwd launch");
         if (ticket) { HIP_TRY(hipEventRecord(ticket->ev, s), "record NaN-report event"); nan->pending = true; }
     }
@@ -822,11 +811,12 @@ extern "C" int igs_rast_backward(
     float* dL_dmean2D, float* dL_dcolor, float* dL_dopacity, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
     float* dL_dscale, float* dL_drot, int require_coord, int require_depth, int debug)
 {
-    return backward_impl(stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, alphas, scales, scale_modifier,
-                         rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, kernel_size, radii, normalmap,
-                         geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dpix_coord, dL_dpix_mcoord, dL_dpix_depth,
-                         dL_dpix_mdepth, dL_dalphas, dL_dpixel_normals, workspace, dL_dmean2D, dL_dcolor, dL_dopacity, dL_dmean3D,
-                         dL_dcov3D, dL_dsh, dL_dscale, dL_drot, require_coord, require_depth, debug, nullptr, nullptr, 0.f, nullptr);
+    const BwdIn in{ (hipStream_t)stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, alphas, scales, scale_modifier,
+                    rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, kernel_size, radii, normalmap, geom_buffer,
+                    binning_buffer, image_buffer, dL_dpix, dL_dpix_coord, dL_dpix_mcoord, dL_dpix_depth, dL_dpix_mdepth, dL_dalphas,
+                    dL_dpixel_normals, workspace, dL_dmean2D, dL_dcolor, dL_dopacity, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                    require_coord, require_depth, debug };
+    return backward_impl(in, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -836,12 +826,20 @@ extern "C" int igs_rast_backward(
 struct ScratchCapture { igs_rast_alloc_fn fn; void* user; char* last; };
 static char* capture_alloc(void* user, size_t n) { ScratchCapture* c = (ScratchCapture*)user; c->last = c->fn(c->user, n); return c->last; }
 
-extern "C" size_t igs_refine_loss_scratch_bytes(int width, int height)
-{
-    const size_t HW = (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0);
-    // { SSIM scratch | dL/dcolor 3 HW | depth-normal: dL/ddepth HW, dL/dmdepth HW, dL/dnormal 3 HW | 64 shards }
-    return ((igs_ssim_l1_scratch_bytes(width, height) + 255) & ~(size_t)255) + 3 * HW * 4 + 5 * HW * 4 + 4096 + 512;
-}
+// igs_refine_step_args::loss_scratch, byte offsets: { SSIM kernels' own scratch (nine maps, then 2 x 64 shards) | dL/dcolor [3][H][W] |
+// depth-normal regulariser: dL/ddepth [H][W], dL/dmdepth [H][W], dL/dnormal [3][H][W] | its 64 shards (at the next 256-byte address) }
+struct LossScratchLayout {
+    size_t ssim_shards, grad_img, dn_depth, dn_mdepth, dn_normal, dn_shards, total;
+    LossScratchLayout(int width, int height)
+    {
+        const size_t HW = (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0);
+        ssim_shards = align_up(9 * HW * 4, 256);
+        grad_img = align_up(igs_ssim_l1_scratch_bytes(width, height), 256);
+        dn_depth = grad_img + 3 * HW * 4; dn_mdepth = dn_depth + HW * 4; dn_normal = dn_mdepth + HW * 4; dn_shards = dn_normal + 3 * HW * 4;
+        total = dn_shards + 4096 + 512;
+    }
+};
+extern "C" size_t igs_refine_loss_scratch_bytes(int width, int height) { return LossScratchLayout(width, height).total; }
 
 extern "C" size_t igs_refine_step_args_size(void) { return sizeof(igs_refine_step_args); }
 
@@ -870,22 +868,10 @@ extern "C" int igs_refine_step_masked(const igs_refine_step_args* a, const igs_r
     return refine_step_impl(a, m->first_trainable, m->frozen_groups);
 }
 
-static int refine_step_impl(const igs_refine_step_args* a, int first, unsigned frozen)
+// what the refine step fuses into its per-Gaussian kernel: Adam with this step's bias corrections folded into the learning rates, and the
+// loss read back from its shards (ssim_shards / dn_shards: the SSIM and depth-normal losses' shards, NULL = that loss is off)
+static RefineFuse refine_fuse(const igs_refine_step_args* a, int first, unsigned frozen, const float* ssim_shards, const float* dn_shards)
 {
-    if (!a) return fail(IGS_RAST_E_INVALID, "igs_refine_step: NULL args");
-    if (g_pending.active) return fail(IGS_RAST_E_INVALID, "igs_refine_step: an asynchronous forward is pending on this thread; call igs_rast_forward_finish() first");
-    if (a->P <= 0 || a->M <= 0 || a->width <= 0 || a->height <= 0 || (a->step < 1 && !a->grad_out))
-        return fail(IGS_RAST_E_INVALID, "igs_refine_step: bad sizes");
-    if (!a->param || (!a->grad_out && (!a->exp_avg || !a->exp_avg_sq)) || !a->gt || !a->out_images || !a->radii || !a->workspace || !a->background)
-        return fail(IGS_RAST_E_INVALID, "igs_refine_step: NULL pointer");
-    const size_t HW = (size_t)a->width * a->height;
-    float* img = a->out_images;
-    float *color = img, *coord = img + 3 * HW, *mcoord = img + 6 * HW, *depth = img + 9 * HW, *mdepth = img + 10 * HW,
-          *alpha = img + 11 * HW, *normal = img + 12 * HW;
-    const float* xyz = a->param + a->off_xyz; const float* shs = a->param + a->off_sh;
-    const float* opac = a->param + a->off_opacity; const float* scal = a->param + a->off_scale; const float* rotn = a->param + a->off_rot;
-    ScratchCapture cg{ a->geometry_buffer, a->geometry_user, nullptr }, cb{ a->binning_buffer, a->binning_user, nullptr },
-                   ci{ a->image_buffer, a->image_user, nullptr };
     const int stepno = a->step < 1 ? 1 : a->step;
     const double bc1 = 1.0 - pow((double)a->beta1, (double)stepno), bc2 = 1.0 - pow((double)a->beta2, (double)stepno);
     RefineFuse f;
@@ -898,34 +884,65 @@ static int refine_step_impl(const igs_refine_step_args* a, int first, unsigned f
     f.color_out = a->color_grad_out;
     f.color_event = a->color_ready_event;
     f.b1 = a->beta1; f.b2 = a->beta2; f.eps = a->eps; f.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-    const float inv_n = 1.0f / (float)(3 * HW);
-    const bool dssim = a->lambda_dssim > 0.f;
-    const bool dn = a->lambda_depth_normal > 0.f;
-    if ((dssim || dn) && !a->loss_scratch) return fail(IGS_RAST_E_INVALID, "igs_refine_step: lambda_dssim / lambda_depth_normal > 0 need loss_scratch");
-    if (dn && !a->require_depth) return fail(IGS_RAST_E_INVALID, "igs_refine_step: the depth-normal regulariser needs require_depth");
-    // scratch of the SSIM mode: { loss kernels' own scratch (maps + 2 x 64 shards) | dL/dcolor [3][H][W] }
-    float* ssim_shards = nullptr; float* grad_img = nullptr;
-    float *dn_gd = nullptr, *dn_gm = nullptr, *dn_gn = nullptr, *dn_shards = nullptr;
-    if (dn) {
-        const size_t own = (igs_ssim_l1_scratch_bytes(a->width, a->height) + 255) & ~(size_t)255;
-        float* base = (float*)((char*)a->loss_scratch + own) + 3 * HW;
-        dn_gd = base; dn_gm = base + HW; dn_gn = base + 2 * HW; dn_shards = (float*)(((uintptr_t)(base + 5 * HW) + 255) & ~(uintptr_t)255);
-    }
-    if (dssim) {
-        const size_t own = (igs_ssim_l1_scratch_bytes(a->width, a->height) + 255) & ~(size_t)255;
-        ssim_shards = (float*)((char*)a->loss_scratch + (((size_t)9 * HW * 4 + 255) & ~(size_t)255));
-        grad_img = (float*)((char*)a->loss_scratch + own);
-    }
+    const float inv_n = 1.0f / (float)(3 * (size_t)a->width * a->height);
     f.loss_out = a->loss_out; f.loss_shards2 = nullptr; f.loss_bias = 0.f; f.loss_scale2 = 0.f;
     f.loss_shards3 = dn_shards; f.loss_scale3 = 1.0f;       // (the kernel's shards already carry weight * lambda / HW)
-    if (dssim) {          // loss = lambda w (1 - mean ssim) + (1 - lambda) w mean|d|
+    if (ssim_shards) {    // loss = lambda w (1 - mean ssim) + (1 - lambda) w mean|d|
         f.loss_shards = ssim_shards; f.loss_scale = -a->lambda_dssim * a->loss_weight * inv_n;
         f.loss_shards2 = ssim_shards + 1024; f.loss_scale2 = (1.f - a->lambda_dssim) * a->loss_weight * inv_n;
         f.loss_bias = a->lambda_dssim * a->loss_weight;
     } else {
         f.loss_shards = nullptr; f.loss_scale = a->loss_weight * inv_n;
     }
-    const float l1_scale = a->loss_weight * inv_n;
+    return f;
+}
+
+static int refine_step_impl(const igs_refine_step_args* a, int first, unsigned frozen)
+{
+    if (!a) return fail(IGS_RAST_E_INVALID, "igs_refine_step: NULL args");
+    if (g_pending.active) return fail(IGS_RAST_E_INVALID, "igs_refine_step: an asynchronous forward is pending on this thread; call igs_rast_forward_finish() first");
+    if (a->P <= 0 || a->M <= 0 || a->width <= 0 || a->height <= 0 || (a->step < 1 && !a->grad_out))
+        return fail(IGS_RAST_E_INVALID, "igs_refine_step: bad sizes");
+    if (!a->param || (!a->grad_out && (!a->exp_avg || !a->exp_avg_sq)) || !a->gt || !a->out_images || !a->radii || !a->workspace || !a->background)
+        return fail(IGS_RAST_E_INVALID, "igs_refine_step: NULL pointer");
+    const bool dssim = a->lambda_dssim > 0.f, dn = a->lambda_depth_normal > 0.f;
+    if ((dssim || dn) && !a->loss_scratch) return fail(IGS_RAST_E_INVALID, "igs_refine_step: lambda_dssim / lambda_depth_normal > 0 need loss_scratch");
+    if (dn && !a->require_depth) return fail(IGS_RAST_E_INVALID, "igs_refine_step: the depth-normal regulariser needs require_depth");
+    const hipStream_t s = (hipStream_t)a->stream;
+    const size_t HW = (size_t)a->width * a->height;
+    float* img = a->out_images;
+    float *color = img, *depth = img + 9 * HW, *mdepth = img + 10 * HW, *alpha = img + 11 * HW, *normal = img + 12 * HW;
+    ScratchCapture cg{ a->geometry_buffer, a->geometry_user, nullptr }, cb{ a->binning_buffer, a->binning_user, nullptr },
+                   ci{ a->image_buffer, a->image_user, nullptr };
+    const LossScratchLayout LS(a->width, a->height);
+    char* ls = (char*)a->loss_scratch;
+    float *ssim_shards = dssim ? (float*)(ls + LS.ssim_shards) : nullptr, *grad_img = dssim ? (float*)(ls + LS.grad_img) : nullptr;
+    float *dn_gd = dn ? (float*)(ls + LS.dn_depth) : nullptr, *dn_gm = dn ? (float*)(ls + LS.dn_mdepth) : nullptr;
+    float *dn_gn = dn ? (float*)(ls + LS.dn_normal) : nullptr, *dn_shards = dn ? (float*)align_ptr(ls + LS.dn_shards) : nullptr;
+    RefineFuse f = refine_fuse(a, first, frozen, ssim_shards, dn_shards);
+    const float l1_scale = a->loss_weight * (1.0f / (float)(3 * HW));
+    const BwdFused fused{ f, dssim ? nullptr : a->gt, color, l1_scale };
+    // depth-normal regulariser on the maps the forward renders: its three gradient maps switch the blend backward to the <depth, normal> instance
+    DepthNormalJob dnj;
+    dnj.fx = a->width / (2.0f * a->tan_fovx); dnj.fy = a->height / (2.0f * a->tan_fovy); dnj.depth = depth; dnj.mdepth = mdepth; dnj.normal = normal;
+    dnj.weight = a->loss_weight * a->lambda_depth_normal; dnj.depth_ratio = a->depth_ratio > 0.f ? a->depth_ratio : 0.6f;
+    dnj.g_depth = dn_gd; dnj.g_mdepth = dn_gm; dnj.g_normal = dn_gn; dnj.loss_shards = dn_shards;
+
+    FwdIn in{};          // (the parameters are the raw optimiser leaves inside `param`)
+    in.s = s; in.geometry_buffer = capture_alloc; in.geometry_user = &cg; in.binning_buffer = capture_alloc; in.binning_user = &cb;
+    in.image_buffer = capture_alloc; in.image_user = &ci; in.P = a->P; in.D = a->D; in.M = a->M; in.background = a->background;
+    in.width = a->width; in.height = a->height; in.means3D = a->param + a->off_xyz; in.shs = a->param + a->off_sh;
+    in.opacities = a->param + a->off_opacity; in.scales = a->param + a->off_scale; in.scale_modifier = 1.0f; in.rotations = a->param + a->off_rot;
+    in.viewmatrix = a->viewmatrix; in.projmatrix = a->projmatrix; in.cam_pos = a->cam_pos; in.tan_fovx = a->tan_fovx; in.tan_fovy = a->tan_fovy;
+    in.out_color = color; in.out_coord = img + 3 * HW; in.out_mcoord = img + 6 * HW; in.out_depth = depth; in.out_mdepth = mdepth;
+    in.out_alpha = alpha; in.out_normal = normal; in.radii = a->radii; in.require_coord = a->require_coord; in.require_depth = a->require_depth;
+    BwdIn bw{};
+    bw.s = s; bw.P = a->P; bw.D = a->D; bw.M = a->M; bw.background = a->background; bw.width = a->width; bw.height = a->height;
+    bw.means3D = in.means3D; bw.shs = in.shs; bw.alphas = alpha; bw.scales = in.scales; bw.scale_modifier = 1.0f; bw.rotations = in.rotations;
+    bw.viewmatrix = a->viewmatrix; bw.projmatrix = a->projmatrix; bw.campos = a->cam_pos; bw.tan_fovx = a->tan_fovx; bw.tan_fovy = a->tan_fovy;
+    bw.radii = a->radii; bw.normalmap = normal; bw.dL_dpix = grad_img; bw.dL_dpix_depth = dn_gd; bw.dL_dpix_mdepth = dn_gm;
+    bw.dL_dpixel_normals = dn_gn; bw.workspace = a->workspace; bw.dL_dmean2D = a->dL_dmean2D; bw.require_coord = a->require_coord;
+    bw.require_depth = a->require_depth;
 
     prof_new_frame();
     for (int attempt = 0; attempt < 2; attempt++) {
@@ -950,15 +967,11 @@ static int refine_step_impl(const igs_refine_step_args* a, int first, unsigned f
         } else f.plane_tag = 0;
         ex.scratch_clean = a->scratch_clean != 0;
         // L1 loss, colour-only backward: forward and backward blend of a tile in one kernel (blend_step.hip)
-        BlendBwdArgs fused_bwd;
+        BlendBwdArgs fused_bwd{};
         bool fused_ran = false;
         int fused_inst = -1;
         static const bool no_fuse = getenv("IGS_NO_TILE_FUSION") != nullptr;      // (A/B switch for measurements)
         if (!dssim && !dn && !no_fuse) {
-            fused_bwd.alphas = nullptr; fused_bwd.normalmap = nullptr; fused_bwd.accum_coord = nullptr; fused_bwd.accum_depth = nullptr;
-            fused_bwd.normal_length = nullptr; fused_bwd.n_contrib = nullptr;
-            fused_bwd.dL_dpix = nullptr; fused_bwd.dL_dcoord = nullptr; fused_bwd.dL_dmcoord = nullptr; fused_bwd.dL_ddepth = nullptr;
-            fused_bwd.dL_dmdepth = nullptr; fused_bwd.dL_dalpha = nullptr; fused_bwd.dL_dnormal = nullptr;
             fused_bwd.gacc = ex.zero_gacc;
             fused_bwd.l1_gt = a->gt; fused_bwd.l1_color = color; fused_bwd.l1_scale = l1_scale;
             fused_bwd.l1_loss = (float*)((char*)ex.zero_gacc + ws_gacc_bytes(a->P));
@@ -966,43 +979,27 @@ static int refine_step_impl(const igs_refine_step_args* a, int first, unsigned f
             fused_bwd.first_trainable = first;
             ex.fused_bwd = &fused_bwd; ex.fused_ran = &fused_ran; ex.fused_instance = &fused_inst;
         }
-        const int R = forward_impl(a->stream, capture_alloc, &cg, capture_alloc, &cb, capture_alloc, &ci, a->P, a->D, a->M, a->background,
-                                   a->width, a->height, xyz, shs, nullptr, opac, scal, 1.0f, rotn, nullptr, a->viewmatrix, a->projmatrix,
-                                   a->cam_pos, a->tan_fovx, a->tan_fovy, 0.0f, 0, color, coord, mcoord, depth, mdepth, alpha, normal,
-                                   a->radii, a->require_coord, a->require_depth, 0, false, 0, ex);
+        const int R = forward_impl(in, ex, false);
         if (R < 0) return R;
         f.guard_overflow = g_last_fwd.overflow; f.guard_prefilter = g_last_fwd.prefilter;
         f.blend_done = fused_ran ? 1 : 0;
         if (fused_ran) __atomic_store_n(&g_last_bwd_instance, fused_inst, __ATOMIC_RELAXED);
-        DepthNormalJob dnj;
-        if (dn) {
-            // depth-normal regulariser on the maps just rendered: its three gradient maps switch the blend backward to the
-            // <depth, normal> instance
-            dnj.fx = a->width / (2.0f * a->tan_fovx); dnj.fy = a->height / (2.0f * a->tan_fovy);
-            dnj.depth = depth; dnj.mdepth = mdepth; dnj.normal = normal; dnj.weight = a->loss_weight * a->lambda_depth_normal;
-            dnj.depth_ratio = a->depth_ratio > 0.f ? a->depth_ratio : 0.6f;
-            dnj.g_depth = dn_gd; dnj.g_mdepth = dn_gm; dnj.g_normal = dn_gn; dnj.loss_shards = dn_shards;
-        }
         static const bool no_mix = getenv("IGS_NO_LOSS_MIX") != nullptr;      // (A/B switch for measurements)
         const bool mix = dssim && dn && !no_mix;       // both image-space losses: the regulariser rides in the SSIM gradient's launch
         if (dssim) {
-            prof_mark((hipStream_t)a->stream, ST_GAP);
-            if (launch_ssim_l1((hipStream_t)a->stream, a->width, a->height, color, a->gt, a->lambda_dssim, a->loss_weight, a->loss_scratch,
+            prof_mark(s, ST_GAP);
+            if (launch_ssim_l1(s, a->width, a->height, color, a->gt, a->lambda_dssim, a->loss_weight, a->loss_scratch,
                                grad_img, false, a->gt_stats, a->gt_stats_valid != 0, mix ? &dnj : nullptr) != hipSuccess)
                 return fail(IGS_RAST_E_HIP, "ssim loss launch");
-            prof_mark((hipStream_t)a->stream, ST_MEMSET);          // (the stage slot the fused step does not otherwise use: "loss")
+            prof_mark(s, ST_MEMSET);          // (the stage slot the fused step does not otherwise use: "loss")
         }
         if (dn && !mix) {
-            hipStream_t ms = (hipStream_t)a->stream;
-            HIP_TRY(zero_fill_async(ms, dn_shards, 4096), "zero shards");
-            HIP_TRY(launch_depth_normal(ms, a->width, a->height, dnj.fx, dnj.fy, depth, mdepth, normal, dnj.weight, dnj.depth_ratio, dn_gd, dn_gm,
+            HIP_TRY(zero_fill_async(s, dn_shards, 4096), "zero shards");
+            HIP_TRY(launch_depth_normal(s, a->width, a->height, dnj.fx, dnj.fy, depth, mdepth, normal, dnj.weight, dnj.depth_ratio, dn_gd, dn_gm,
                                         dn_gn, dn_shards), "depth_normal launch");
         }
-        const int rc = backward_impl(a->stream, a->P, a->D, a->M, R, a->background, a->width, a->height, xyz, shs, nullptr, alpha, scal, 1.0f,
-                                     rotn, nullptr, a->viewmatrix, a->projmatrix, a->cam_pos, a->tan_fovx, a->tan_fovy, 0.0f, a->radii,
-                                     normal, cg.last, cb.last, ci.last, dssim ? grad_img : nullptr, nullptr, nullptr, dn_gd, dn_gm, nullptr,
-                                     dn_gn, a->workspace, a->dL_dmean2D, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                     a->require_coord, a->require_depth, 0, dssim ? nullptr : a->gt, color, l1_scale, &f);
+        bw.R = R; bw.geom_buffer = cg.last; bw.binning_buffer = cb.last; bw.image_buffer = ci.last;
+        const int rc = backward_impl(bw, &fused);
         if (rc < 0) return rc;
         if (!g_pending.active) return R;           // synchronous forward: R is already the true count
         const int Rt = igs_rast_forward_finish();
@@ -1011,6 +1008,7 @@ static int refine_step_impl(const igs_refine_step_args* a, int first, unsigned f
     }
     return fail(IGS_RAST_E_INVALID, "igs_refine_step: internal retry failure");
 }
+
 
 // Morton order of the Gaussians' positions (sort.hip): perm[i] = index of the Gaussian that comes i-th along the Z-order curve of
 // xyz quantised to `bits` bits per axis inside the box lohi = {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z} (device memory).

@@ -448,6 +448,5 @@ __device__ __forceinline__ void st_param(float4* p, const float4& x)
 // Zero-fill of a 4-byte-aligned span by a kernel of this library (refine_ops.hip) instead of hipMemsetAsync: the same cost on the
 // stream (the runtime's memset is a fill kernel too), and a plain kernel node when the stream is being captured into a hipGraph --
 // captured memset nodes misbehaved on this runtime (round 2: stale counters in the replay, a crash at hipStreamEndCapture).
-// `extra` / `extra_words`: a second range of at most 256 words zeroed by the same launch.
-hipError_t zero_fill_async(hipStream_t s, void* p, size_t bytes, void* extra = nullptr, int extra_words = 0);
+hipError_t zero_fill_async(hipStream_t s, void* p, size_t bytes);
 

@@ -482,9 +482,8 @@ extern "C" int igs_densify_remap(void* stream, int P_new, int M, const int* src,
     return hipGetLastError() == hipSuccess ? 0 : IGS_RAST_E_HIP;
 }
 
-__global__ void __launch_bounds__(256) zero_fill_kernel(uint32_t* __restrict__ p, size_t words, uint32_t* __restrict__ extra, int extra_words)
+__global__ void __launch_bounds__(256) zero_fill_kernel(uint32_t* __restrict__ p, size_t words)
 {
-    if (blockIdx.x == 0 && (int)threadIdx.x < extra_words) extra[threadIdx.x] = 0u;      // (a second, tiny range: at most 256 words)
     // 16-byte stores over the aligned middle, single words at the ragged ends
     const size_t head = min(words, (size_t)((16u - ((uintptr_t)p & 15u)) & 15u) / 4);
     const size_t n4 = (words - head) / 4;
@@ -497,16 +496,15 @@ __global__ void __launch_bounds__(256) zero_fill_kernel(uint32_t* __restrict__ p
         if (tail0 + threadIdx.x < words) p[tail0 + threadIdx.x] = 0u;
     }
 }
-hipError_t zero_fill_async(hipStream_t s, void* p, size_t bytes, void* extra, int extra_words)
+hipError_t zero_fill_async(hipStream_t s, void* p, size_t bytes)
 {
-    if (bytes == 0 && extra_words == 0) return hipSuccess;
-    if (extra_words < 0 || extra_words > 256) return hipErrorInvalidValue;
-    if (extra_words == 0 && ((((uintptr_t)p) | bytes) & 3u)) return hipMemsetAsync(p, 0, bytes, s);      // (not word-granular: never the case in this library)
+    if (bytes == 0) return hipSuccess;
+    if ((((uintptr_t)p) | bytes) & 3u) return hipMemsetAsync(p, 0, bytes, s);      // (not word-granular: never the case in this library)
     const size_t words = bytes / 4;
     size_t blocks = (words / 4 + 255) / 256;
     if (blocks < 1) blocks = 1;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (uint32_t*)p, words, (uint32_t*)extra, extra_words);
+    hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (uint32_t*)p, words);
     return hipGetLastError();
 }
 

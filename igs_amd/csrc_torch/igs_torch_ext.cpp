@@ -92,6 +92,30 @@ void check(int rc, const char* what)
     if (rc < 0) throw RasterizerError(std::string(what) + " failed (" + std::to_string(rc) + "): " + igs_rast_last_error());
 }
 
+// what rasterize_gaussians and count_gaussians share: checks, device guard, the eleven float inputs, M, scratch set, current stream
+struct FwdCall {
+    c10::Device dev; c10::hip::HIPGuardMasqueradingAsCUDA guard; int64_t P, H, W;
+    In m3, col, op, sc, rot, cov, shs, bg, view, proj, cam; int64_t M; std::shared_ptr<ScratchSet> ss; hipStream_t stream;
+    static const Tensor& points(const Tensor& means3D)
+    {
+        if (means3D.dim() != 2 || means3D.size(1) != 3) throw RasterizerError("means3D must have dimensions (num_points, 3)");
+        if (!means3D.is_cuda()) throw RasterizerError("igs_amd rasterizer: tensors must be on a GPU (no CPU fallback)");
+        return means3D;
+    }
+    FwdCall(const Tensor& background, const Tensor& means3D, const Tensor& colors, const Tensor& opacity, const Tensor& scales,
+            const Tensor& rotations, const Tensor& cov3D_precomp, const Tensor& viewmatrix, const Tensor& projmatrix, const Tensor& sh,
+            const Tensor& campos, int64_t image_height, int64_t image_width, const std::shared_ptr<ScratchSet>& scratch)
+        : dev(points(means3D).device()), guard(dev), P(means3D.size(0)), H(image_height), W(image_width),
+          m3(means3D, dev, "means3D"), col(colors, dev, "colors_precomp"), op(opacity, dev, "opacities"), sc(scales, dev, "scales"),
+          rot(rotations, dev, "rotations"), cov(cov3D_precomp, dev, "cov3D_precomp"), shs(sh, dev, "shs"), bg(background, dev, "bg"),
+          view(viewmatrix, dev, "viewmatrix"), proj(projmatrix, dev, "projmatrix"), cam(campos, dev, "campos"), M(shs.p ? shs.keep.size(1) : 0),
+          ss(scratch ? scratch : std::make_shared<ScratchSet>(dev, false)), stream(c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream())
+    {
+        if (H <= 0 || W <= 0) throw RasterizerError("image_height and image_width must be positive");
+        if (scratch && scratch->device != dev) throw RasterizerError("scratch set lives on " + scratch->device.str() + ", the tensors on " + dev.str());
+    }
+};
+
 using FwdTuple = std::tuple<int64_t, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
 
 // _C.rasterize_gaussians (RasterizeGaussiansCUDA, DGR/rasterize_points.cu:35-133).
@@ -105,40 +129,28 @@ FwdTuple rasterize_gaussians(
     const Tensor& campos, bool prefiltered, bool require_coord, bool require_depth, bool debug,
     const std::shared_ptr<ScratchSet>& scratch, const OptTensor& out_images, const OptTensor& out_radii, int64_t mode, bool scratch_clean)
 {
-    if (means3D.dim() != 2 || means3D.size(1) != 3) throw RasterizerError("means3D must have dimensions (num_points, 3)");
-    if (!means3D.is_cuda()) throw RasterizerError("igs_amd rasterizer: tensors must be on a GPU (no CPU fallback)");
-    const c10::Device dev = means3D.device();
-    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const int64_t P = means3D.size(0), H = image_height, W = image_width;
-    In m3(means3D, dev, "means3D"), col(colors, dev, "colors_precomp"), op(opacity, dev, "opacities"), sc(scales, dev, "scales"),
-       rot(rotations, dev, "rotations"), cov(cov3D_precomp, dev, "cov3D_precomp"), shs(sh, dev, "shs"), bg(background, dev, "bg"),
-       view(viewmatrix, dev, "viewmatrix"), proj(projmatrix, dev, "projmatrix"), cam(campos, dev, "campos");
-    const int64_t M = shs.p ? shs.keep.size(1) : 0;
-    auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
+    const FwdCall c(background, means3D, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh, campos, image_height, image_width, scratch);
+    const int64_t P = c.P, H = c.H, W = c.W;
+    auto fopt = at::TensorOptions().dtype(at::kFloat).device(c.dev);
     // one allocation for the seven images; every pixel is written by the kernels when P > 0
-    if (H <= 0 || W <= 0) throw RasterizerError("image_height and image_width must be positive");
-    if (out_images.has_value()) check_out(*out_images, 15 * H * W, at::kFloat, dev, "out_images");
-    if (out_radii.has_value()) check_out(*out_radii, P, at::kInt, dev, "out_radii");
+    if (out_images.has_value()) check_out(*out_images, 15 * H * W, at::kFloat, c.dev, "out_images");
+    if (out_radii.has_value()) check_out(*out_radii, P, at::kInt, c.dev, "out_radii");
     Tensor imgs = out_images.has_value() ? *out_images : (P > 0 ? at::empty({15, H, W}, fopt) : at::zeros({15, H, W}, fopt));
     Tensor radii = out_radii.has_value() ? *out_radii : (P > 0 ? at::empty({P}, fopt.dtype(at::kInt)) : at::zeros({0}, fopt.dtype(at::kInt)));
-    if (scratch && scratch->device != dev) throw RasterizerError("scratch set lives on " + scratch->device.str() + ", the tensors on " + dev.str());
-    std::shared_ptr<ScratchSet> ss = scratch ? scratch : std::make_shared<ScratchSet>(dev, false);
     Tensor color = imgs.narrow(0, 0, 3), coord = imgs.narrow(0, 3, 3), mcoord = imgs.narrow(0, 6, 3), depth = imgs.narrow(0, 9, 1),
            mdepth = imgs.narrow(0, 10, 1), alpha = imgs.narrow(0, 11, 1), normal = imgs.narrow(0, 12, 3);
     int64_t rendered = 0;
     if (P != 0) {
-        hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
         auto fwd = mode == 1 ? igs_rast_forward_async : (mode == 2 ? igs_rast_forward_nowait : igs_rast_forward);
         if (scratch_clean) igs_rast_hint_scratch_clean(1);
-        float* ib = imgs.data_ptr<float>();
-        const size_t HW = (size_t)H * W;
-        rendered = fwd(stream, grow_cb, &ss->g_geom, grow_cb, &ss->g_binning, grow_cb, &ss->g_img, (int)P, (int)degree, (int)M, bg.p, (int)W, (int)H, m3.p, shs.p, col.p,
-                       op.p, sc.p, (float)scale_modifier, rot.p, cov.p, view.p, proj.p, cam.p, (float)tan_fovx, (float)tan_fovy,
-                       (float)kernel_size, prefiltered ? 1 : 0, ib, ib + 3 * HW, ib + 6 * HW, ib + 9 * HW, ib + 10 * HW, ib + 11 * HW,
-                       ib + 12 * HW, radii.data_ptr<int>(), require_coord ? 1 : 0, require_depth ? 1 : 0, debug ? 1 : 0);
+        float* ib = imgs.data_ptr<float>(); const size_t HW = (size_t)H * W;
+        rendered = fwd(c.stream, grow_cb, &c.ss->g_geom, grow_cb, &c.ss->g_binning, grow_cb, &c.ss->g_img, (int)P, (int)degree, (int)c.M, c.bg.p,
+                       (int)W, (int)H, c.m3.p, c.shs.p, c.col.p, c.op.p, c.sc.p, (float)scale_modifier, c.rot.p, c.cov.p, c.view.p, c.proj.p,
+                       c.cam.p, (float)tan_fovx, (float)tan_fovy, (float)kernel_size, prefiltered ? 1 : 0, ib, ib + 3 * HW, ib + 6 * HW, ib + 9 * HW,
+                       ib + 10 * HW, ib + 11 * HW, ib + 12 * HW, radii.data_ptr<int>(), require_coord ? 1 : 0, require_depth ? 1 : 0, debug ? 1 : 0);
         check((int)rendered, "igs_rast_forward");
     }
-    return FwdTuple(rendered, color, coord, mcoord, alpha, normal, depth, mdepth, radii, ss->geom, ss->binning, ss->img);
+    return FwdTuple(rendered, color, coord, mcoord, alpha, normal, depth, mdepth, radii, c.ss->geom, c.ss->binning, c.ss->img);
 }
 
 using CountTuple = std::tuple<Tensor, Tensor, int64_t, Tensor, Tensor, Tensor, Tensor, Tensor>;
@@ -151,39 +163,26 @@ CountTuple count_gaussians(
     const Tensor& background, const Tensor& means3D, const Tensor& colors, const Tensor& opacity, const Tensor& scales,
     const Tensor& rotations, double scale_modifier, const Tensor& cov3D_precomp, const Tensor& viewmatrix, const Tensor& projmatrix,
     double tan_fovx, double tan_fovy, int64_t image_height, int64_t image_width, const Tensor& sh, int64_t degree,
-    const Tensor& campos, bool prefiltered, bool debug, bool f_count, const std::shared_ptr<ScratchSet>& scratch)
+    const Tensor& campos, bool prefiltered, bool debug, bool /*f_count*/, const std::shared_ptr<ScratchSet>& scratch)
 {
-    (void)f_count;
-    if (means3D.dim() != 2 || means3D.size(1) != 3) throw RasterizerError("means3D must have dimensions (num_points, 3)");
-    if (!means3D.is_cuda()) throw RasterizerError("igs_amd rasterizer: tensors must be on a GPU (no CPU fallback)");
-    const c10::Device dev = means3D.device();
-    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const int64_t P = means3D.size(0), H = image_height, W = image_width;
-    if (H <= 0 || W <= 0) throw RasterizerError("image_height and image_width must be positive");
-    In m3(means3D, dev, "means3D"), col(colors, dev, "colors_precomp"), op(opacity, dev, "opacities"), sc(scales, dev, "scales"),
-       rot(rotations, dev, "rotations"), cov(cov3D_precomp, dev, "cov3D_precomp"), shs(sh, dev, "shs"), bg(background, dev, "bg"),
-       view(viewmatrix, dev, "viewmatrix"), proj(projmatrix, dev, "projmatrix"), cam(campos, dev, "campos");
-    const int64_t M = shs.p ? shs.keep.size(1) : 0;
-    auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
-    auto iopt = fopt.dtype(at::kInt);
+    const FwdCall c(background, means3D, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh, campos, image_height, image_width, scratch);
+    const int64_t P = c.P, H = c.H, W = c.W;
+    auto fopt = at::TensorOptions().dtype(at::kFloat).device(c.dev), iopt = fopt.dtype(at::kInt);
     // every element is written by the kernels when P > 0 (counts: zeroed by the preprocess; colour: every pixel)
     Tensor color = P > 0 ? at::empty({3, H, W}, fopt) : at::zeros({3, H, W}, fopt);
     Tensor radii = P > 0 ? at::empty({P}, iopt) : at::zeros({0}, iopt);
     Tensor count = P > 0 ? at::empty({P}, iopt) : at::zeros({0}, iopt);
     Tensor score = P > 0 ? at::empty({P}, fopt) : at::zeros({0}, fopt);
-    if (scratch && scratch->device != dev) throw RasterizerError("scratch set lives on " + scratch->device.str() + ", the tensors on " + dev.str());
-    std::shared_ptr<ScratchSet> ss = scratch ? scratch : std::make_shared<ScratchSet>(dev, false);
     int64_t rendered = 0;
     if (P != 0) {
-        hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
-        rendered = igs_rast_count_gaussians(stream, grow_cb, &ss->g_geom, grow_cb, &ss->g_binning, grow_cb, &ss->g_img, (int)P, (int)degree,
-                                            (int)M, bg.p, (int)W, (int)H, m3.p, shs.p, col.p, op.p, sc.p, (float)scale_modifier, rot.p, cov.p,
-                                            view.p, proj.p, cam.p, (float)tan_fovx, (float)tan_fovy, prefiltered ? 1 : 0,
+        rendered = igs_rast_count_gaussians(c.stream, grow_cb, &c.ss->g_geom, grow_cb, &c.ss->g_binning, grow_cb, &c.ss->g_img, (int)P, (int)degree,
+                                            (int)c.M, c.bg.p, (int)W, (int)H, c.m3.p, c.shs.p, c.col.p, c.op.p, c.sc.p, (float)scale_modifier,
+                                            c.rot.p, c.cov.p, c.view.p, c.proj.p, c.cam.p, (float)tan_fovx, (float)tan_fovy, prefiltered ? 1 : 0,
                                             color.data_ptr<float>(), count.data_ptr<int>(), score.data_ptr<float>(), radii.data_ptr<int>(),
                                             debug ? 1 : 0);
         check((int)rendered, "igs_rast_count_gaussians");
     }
-    return CountTuple(count, score, rendered, color, radii, ss->geom, ss->binning, ss->img);
+    return CountTuple(count, score, rendered, color, radii, c.ss->geom, c.ss->binning, c.ss->img);
 }
 
 using BwdTuple = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;

@@ -124,6 +124,70 @@ def test_c_abi_validates_before_any_hip_call():
     assert call(P=0, color=None, count=None, score=None, radii=None) == 0      # nothing to do, nothing launched
 
 
+def test_c_abi_forward_and_backward_validate_before_any_hip_call():
+    from igs_amd import _cabi
+    L = _cabi.lib()
+
+    @_cabi.ALLOC_FN
+    def never(user, n):                 # a scratch request would mean the call went past its checks
+        raise AssertionError("scratch requested")
+
+    buf = (C.c_float * 64)()
+    p = C.cast(buf, C.c_void_p)
+    fwd_names = ["stream", "geom", "geom_user", "binning", "binning_user", "image", "image_user", "P", "D", "M", "background", "W", "H",
+                 "means3D", "shs", "colors_precomp", "opacities", "scales", "scale_modifier", "rotations", "cov3D_precomp",
+                 "viewmatrix", "projmatrix", "cam_pos", "tan_fovx", "tan_fovy", "kernel_size", "prefiltered",
+                 "color", "coord", "mcoord", "depth", "mdepth", "alpha", "normal", "radii", "require_coord", "require_depth", "debug"]
+    fwd_ok = dict(stream=None, geom=never, geom_user=None, binning=never, binning_user=None, image=never, image_user=None,
+                  P=4, D=0, M=1, background=p, W=16, H=16, means3D=p, shs=p, colors_precomp=None, opacities=p, scales=p,
+                  scale_modifier=1.0, rotations=p, cov3D_precomp=None, viewmatrix=p, projmatrix=p, cam_pos=p, tan_fovx=0.5,
+                  tan_fovy=0.5, kernel_size=0.0, prefiltered=0, color=p, coord=p, mcoord=p, depth=p, mdepth=p, alpha=p, normal=p,
+                  radii=p, require_coord=1, require_depth=1, debug=0)
+    null_fn = _cabi.ALLOC_FN()
+    fwd_bad = [dict(P=-1), dict(W=0), dict(H=-3), dict(geom=null_fn), dict(binning=null_fn), dict(image=null_fn), dict(D=1, M=1), dict(D=4, M=25)]
+    fwd_bad += [{k: None} for k in ("means3D", "opacities", "viewmatrix", "projmatrix", "cam_pos", "background", "radii",
+                                    "color", "coord", "mcoord", "depth", "mdepth", "alpha", "normal")]
+    fwd_bad += [dict(shs=None), dict(scales=None), dict(rotations=None)]
+
+    def fwd(fn, **kw):
+        a = dict(fwd_ok, **kw)
+        return fn(*[a[k] for k in fwd_names])
+
+    for fn in (L.igs_rast_forward, L.igs_rast_forward_async, L.igs_rast_forward_nowait):
+        for kw in fwd_bad:
+            assert fwd(fn, **kw) == -1, (fn.__name__, kw)                 # IGS_RAST_E_INVALID
+            assert L.igs_rast_last_error(), (fn.__name__, kw)
+    # (igs_rast_forward_nowait looks for its pinned status slot first: without a forward before it, even P == 0 is refused)
+    for fn in (L.igs_rast_forward, L.igs_rast_forward_async):
+        assert fwd(fn, P=0, geom=null_fn, means3D=None, color=None, radii=None) == 0, fn.__name__      # nothing to do, nothing launched
+    assert L.igs_rast_forward_finish() == -1                            # no refused call above latched a pending forward
+
+    bwd_names = ["stream", "P", "D", "M", "R", "background", "W", "H", "means3D", "shs", "colors_precomp", "alphas", "scales",
+                 "scale_modifier", "rotations", "cov3D_precomp", "viewmatrix", "projmatrix", "campos", "tan_fovx", "tan_fovy",
+                 "kernel_size", "radii", "normalmap", "geom_buffer", "binning_buffer", "image_buffer", "dL_dpix", "dL_dcoord",
+                 "dL_dmcoord", "dL_ddepth", "dL_dmdepth", "dL_dalpha", "dL_dnormal", "workspace", "dL_dmean2D", "dL_dcolor",
+                 "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot", "require_coord", "require_depth", "debug"]
+    bwd_ok = dict(stream=None, P=4, D=0, M=1, R=8, background=p, W=16, H=16, means3D=p, shs=p, colors_precomp=None, alphas=p, scales=p,
+                  scale_modifier=1.0, rotations=p, cov3D_precomp=None, viewmatrix=p, projmatrix=p, campos=p, tan_fovx=0.5, tan_fovy=0.5,
+                  kernel_size=0.0, radii=p, normalmap=p, geom_buffer=p, binning_buffer=p, image_buffer=p, dL_dpix=p, dL_dcoord=None,
+                  dL_dmcoord=None, dL_ddepth=None, dL_dmdepth=None, dL_dalpha=None, dL_dnormal=None, workspace=p, dL_dmean2D=p,
+                  dL_dcolor=p, dL_dopacity=p, dL_dmean3D=p, dL_dcov3D=p, dL_dsh=p, dL_dscale=p, dL_drot=p, require_coord=1,
+                  require_depth=1, debug=0)
+    bwd_bad = [dict(P=-1), dict(R=-1), dict(W=0), dict(H=-3), dict(P=1 << 24)]
+    bwd_bad += [{k: None} for k in ("geom_buffer", "binning_buffer", "image_buffer", "workspace", "means3D", "alphas", "viewmatrix",
+                                    "projmatrix", "campos", "background", "radii", "normalmap", "dL_dmean2D", "dL_dcolor", "dL_dopacity",
+                                    "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot")]
+
+    def bwd(**kw):
+        a = dict(bwd_ok, **kw)
+        return L.igs_rast_backward(*[a[k] for k in bwd_names])
+
+    for kw in bwd_bad:
+        assert bwd(**kw) == -1, kw
+        assert L.igs_rast_last_error(), kw
+    assert bwd(P=0, geom_buffer=None, workspace=None, means3D=None, dL_dcolor=None) == 0
+
+
 def test_package_does_not_import_oracle():
     for f in os.listdir(PKG):
         if not f.endswith(".py"):
