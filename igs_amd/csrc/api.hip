@@ -1022,6 +1022,21 @@ extern "C" int igs_morton_order(void* stream, int P, const float* xyz, const flo
     return 0;
 }
 
+// simple-knn's distCUDA2 (knn.hip; the contract is in include/igs_rast.h)
+extern "C" size_t igs_knn_scratch_bytes(int P)
+{
+    if (P < 0 || P > IGS_KNN_MAX_POINTS) return 0;
+    return knn_scratch_bytes(P) + 256;
+}
+extern "C" int igs_knn_mean_dist2(void* stream, int P, const float* xyz, void* scratch, float* out)
+{
+    if (P < 0 || P > IGS_KNN_MAX_POINTS) return fail(IGS_RAST_E_INVALID, "igs_knn_mean_dist2: P out of range (0..IGS_KNN_MAX_POINTS)");
+    if (P == 0) return 0;
+    if (!xyz || !scratch || !out) return fail(IGS_RAST_E_INVALID, "igs_knn_mean_dist2: NULL pointer");
+    HIP_TRY(launch_knn_mean_dist2((hipStream_t)stream, P, xyz, scratch, out), "knn launch");
+    return 0;
+}
+
 // Test support: the per-tile sort of the slab binning on caller-made slabs (sort.hip: launch_tile_sort).  tile_count[T] instances per
 // tile (reset to zero by the launch), pairs[T * slab] = depth bits << 32 | Gaussian id, out: point_list[T * slab] (ids, sorted by the
 // 64-bit key inside every tile's slab), ranges[2 T], stats[4] ([1] = largest tile that overflowed its slab).  Everything device memory.

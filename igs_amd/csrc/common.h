@@ -146,6 +146,8 @@ hipError_t radix_sort_pairs(hipStream_t s, uint32_t n, uint32_t* keys_a, uint32_
                             uint32_t* hist, int bit_lo, int bit_hi, uint32_t** out_keys, uint32_t** out_vals);
 size_t morton_scratch_bytes(int P);
 hipError_t launch_morton_order(hipStream_t s, int P, const float* xyz, const float* lohi, int bits, void* scratch, int* perm);
+size_t knn_scratch_bytes(int P);
+hipError_t launch_knn_mean_dist2(hipStream_t s, int P, const float* xyz, void* scratch, float* out);    // knn.hip
 hipError_t launch_count_sorted(hipStream_t s, int P, const uint32_t* order, const uint32_t* tiles, uint32_t* blocksum);
 hipError_t launch_scan_blocksums(hipStream_t s, int nblocks, uint32_t* blocksum);
 hipError_t launch_emit_instances(hipStream_t s, int P, int gx, int gy, const uint32_t* order, const uint32_t* tiles,

@@ -6,6 +6,7 @@
 // Built by igs_amd/build_ext.py with the host compiler (no device code in this file); links libigs_rast.so.
 //
 // It also carries count_gaussians, the count pass of the compress package (compress-diff-gaussian-rasterization rasterize_points.cu:130-217).
+// And distCUDA2, the one function of simple-knn (mean squared distance to the three nearest neighbours, create_from_pcd's initial scales).
 // Extensions over the reference's signatures are keyword-only extras with defaults (the positional lists are the reference's):
 //   rasterize_gaussians(..., scratch=None, out_images=None, out_radii=None, mode=0, scratch_clean=False)
 //   rasterize_gaussians_backward(..., workspace=None, out_*=None)         any upstream gradient may be None (= zeros)
@@ -275,6 +276,27 @@ Tensor mark_visible(const Tensor& means3D, const Tensor& viewmatrix, const Tenso
     return present;
 }
 
+// simple_knn._C.distCUDA2 (simple-knn ext.cpp / spatial.cu): mean squared distance of every point to its three nearest neighbours
+Tensor distCUDA2(const Tensor& points)
+{
+    if (points.scalar_type() != at::kFloat)
+        throw RasterizerError(std::string("distCUDA2: points must be float32 (got ") + c10::toString(points.scalar_type()) + ")");
+    if (points.dim() != 2 || points.size(1) != 3) throw RasterizerError("distCUDA2: points must have shape [N, 3] (got " + c10::str(points.sizes()) + ")");
+    const int64_t P = points.size(0);
+    if (P > IGS_KNN_MAX_POINTS)
+        throw RasterizerError("distCUDA2: " + std::to_string(P) + " points is more than the supported " + std::to_string(IGS_KNN_MAX_POINTS));
+    if (!points.is_cuda()) throw RasterizerError("distCUDA2: points must be on a GPU (no CPU fallback)");
+    const c10::Device dev = points.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    Tensor out = at::empty({P}, points.options());
+    if (P == 0) return out;
+    const Tensor xyz = points.contiguous();
+    Tensor scratch = at::empty({(int64_t)igs_knn_scratch_bytes((int)P)}, at::TensorOptions().dtype(at::kByte).device(dev));
+    check(igs_knn_mean_dist2(c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream(), (int)P, xyz.data_ptr<float>(),
+                             scratch.data_ptr(), out.data_ptr<float>()), "igs_knn_mean_dist2");
+    return out;
+}
+
 // igs_adam_step_multi over lists of tensors (igs_amd/optim.py): one launch for up to 8 parameters
 void adam_step_multi(const std::vector<Tensor>& params, const std::vector<Tensor>& grads, const std::vector<Tensor>& exp_avgs,
                      const std::vector<Tensor>& exp_avg_sqs, const std::vector<double>& lrs, const std::vector<double>& bc1,
@@ -465,6 +487,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("degree"), py::arg("campos"), py::arg("prefiltered"), py::arg("debug"), py::arg("f_count"), py::kw_only(),
           py::arg("scratch") = std::shared_ptr<ScratchSet>(), py::call_guard<py::gil_scoped_release>());
     m.def("mark_visible", &mark_visible, py::arg("means3D"), py::arg("viewmatrix"), py::arg("projmatrix"), py::call_guard<py::gil_scoped_release>());
+    m.def("distCUDA2", &distCUDA2, py::arg("points"), py::call_guard<py::gil_scoped_release>());
     m.def("integrate_gaussians_to_points", [](const py::args&, const py::kwargs&) -> py::object {
         // GOF tetrahedra integration (DGR/rasterize_points.cu:269-387): mesh extraction only, never reached from IGS
         PyErr_SetString(PyExc_NotImplementedError, "integrate_gaussians_to_points is outside the IGS hot path and is not implemented");

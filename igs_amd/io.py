@@ -129,6 +129,37 @@ def load_start_gaussians(path, max_sh_degree=3):
     return dict(xyz=t(xyz), rotation=t(rots), shs=shs, opacity=logit, scaling=log_scale)
 
 
+SH_C0 = 0.28209479177387814              # RGB2SH (utils/sh_utils.py): DC coefficient of the degree-0 band
+
+
+def load_point_cloud_ply(path):
+    """fetchPly (RaDe-GS scene/dataset_readers.py:156-162): the COLMAP-style points3D.ply as (xyz [P,3], rgb [P,3]) float32 CPU
+    tensors, rgb = red/green/blue (uint8) / 255.  The nx/ny/nz columns are optional and not returned."""
+    v = read_ply_vertices(path)
+    xyz = np.stack((v["x"], v["y"], v["z"]), axis=1)
+    rgb = np.stack((v["red"], v["green"], v["blue"]), axis=1) / 255.0
+    return torch.tensor(xyz).float(), torch.tensor(rgb).float()
+
+
+def gaussians_from_point_cloud(xyz, rgb, device, max_sh_degree=3):
+    """create_from_pcd (RaDe-GS scene/gaussian_model.py:316-340) as the raw dict load_start_gaussians returns, on `device`:
+    xyz, rotation (1,0,0,0), shs [P,(d+1)^2,3] with DC (rgb - 0.5) / SH_C0 and zeros after it, opacity = logit(0.1) [P,1],
+    scaling = log(sqrt(clamp_min(distCUDA2(xyz), 1e-7))) repeated to [P,3].  distCUDA2 is the native kNN (no CPU fallback)."""
+    from ._cabi import ext
+    xyz = torch.as_tensor(xyz).to(device=device, dtype=torch.float32)
+    rgb = torch.as_tensor(rgb).to(device=device, dtype=torch.float32)
+    P, K = xyz.shape[0], (max_sh_degree + 1) ** 2
+    shs = torch.zeros((P, K, 3), dtype=torch.float32, device=device)
+    shs[:, 0] = (rgb - 0.5) / SH_C0
+    dist2 = torch.clamp_min(ext().distCUDA2(xyz), 0.0000001)
+    scaling = torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3)
+    rotation = torch.zeros((P, 4), dtype=torch.float32, device=device)
+    rotation[:, 0] = 1
+    o = 0.1 * torch.ones((P, 1), dtype=torch.float32, device=device)
+    opacity = torch.log(o / (1 - o))                              # inverse_sigmoid
+    return dict(xyz=xyz, rotation=rotation, shs=shs, opacity=opacity, scaling=scaling)
+
+
 def _ply_columns(names, K):
     """Column indices, in the order igs_ply_to_params wants them (include/igs_rast.h)."""
     idx = {n: i for i, n in enumerate(names)}

@@ -495,6 +495,24 @@ int igs_debug_tile_sort(void* stream, int T, unsigned int* tile_count, const uns
                         unsigned int* ranges, int slab, unsigned int* stats, int P);
 int igs_morton_order(void* stream, int P, const float* xyz, const float* lohi, int bits, void* scratch, int* perm);
 
+/* Mean squared distance to the three nearest neighbours: simple-knn's distCUDA2 (the "simple-knn" package of 3DGS, spatial.cu), which
+ * RaDe-GS's create_from_pcd uses for the initial scales: out[i] = (b0 + b1 + b2) / 3.0f in float32, left to right, where b0 <= b1 <= b2
+ * are the three smallest SQUARED distances |p_i - p_j|^2 over j != i (a different index: duplicates count, at distance 0).
+ *   - N <= 3: the slots without a neighbour hold FLT_MAX (simple-knn's best[3] = {FLT_MAX, ...}): N = 1 and N = 2 give +inf, N = 3
+ *     gives (b0 + b1 + FLT_MAX) / 3.0f = FLT_MAX / 3.
+ *   - non-finite input (a NaN or +-inf coordinate): such a point is never a neighbour of a finite point, so a finite point with at
+ *     least three finite neighbours gets the value it would get without the non-finite points; the non-finite points' own outputs are
+ *     unspecified.  No fault, no hang.
+ *   - exact search (boxes only skip candidates that provably cannot enter the three smallest), bit-identical from run to run and
+ *     under any permutation of the points.
+ * xyz: P x 3 float32, out: P float32, scratch: igs_knn_scratch_bytes(P) bytes, all DEVICE memory; everything is enqueued on `stream`,
+ * no host synchronisation, no device allocation.  0 <= P <= IGS_KNN_MAX_POINTS; P == 0 returns 0 and launches nothing (NULL pointers
+ * allowed); otherwise a NULL pointer or a P out of range returns IGS_RAST_E_INVALID before any HIP call.  igs_knn_scratch_bytes
+ * returns 0 for a P out of range. */
+#define IGS_KNN_MAX_POINTS (1 << 25)
+size_t igs_knn_scratch_bytes(int P);
+int igs_knn_mean_dist2(void* stream, int P, const float* xyz, void* scratch, float* out);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).
