@@ -50,7 +50,8 @@ EXPORTS = ["igs_rast_version", "igs_rast_last_error", "igs_rast_forward", "igs_r
            "igs_rast_profile_enable", "igs_rast_profile_read", "igs_adam_step", "igs_adam_step_groups", "igs_adam_step_multi", "igs_adam_step_multi_dev", "igs_adam_step_multi_dev_scratch_words", "igs_densify_stats", "igs_densify_remap", "igs_refine_step", "igs_refine_loss_scratch_bytes", "igs_ssim_l1_scratch_bytes", "igs_ssim_l1_loss_fwd_bwd", "igs_ssim_l1_loss_fwd_bwd_cached", "igs_ssim_mean_fwd_bwd", "igs_ssim_gt_stats_bytes", "igs_depth_normal_loss_fwd_bwd", "igs_l1_loss_fwd_bwd", "igs_l1_mean_fwd_bwd", "igs_activate_fwd", "igs_activate_bwd",
            "igs_sh_grad_from_view_colors", "igs_adam_sh_from_view_colors", "igs_rast_last_backward_instance", "igs_rast_next_backward_options", "igs_rast_nan_report_wait", "igs_rast_nan_report_handle", "igs_rast_nan_report_wait_at", "igs_refine_step_args_size", "igs_rast_debug_poison_lds", "igs_adam_exchange_step", "igs_morton_order", "igs_morton_order_scratch_bytes", "igs_ply_to_params", "igs_params_to_ply", "igs_debug_tile_sort",
            "igs_refine_step_masked", "igs_refine_mask_args_size", "igs_rast_count_gaussians",
-           "igs_knn_scratch_bytes", "igs_knn_mean_dist2"]
+           "igs_knn_scratch_bytes", "igs_knn_mean_dist2", "igs_bbox_select_scratch_bytes", "igs_bbox_select", "igs_fps_scratch_bytes",
+           "igs_fps", "igs_knn_query"]
 
 VERSION = 4       # IGS_RAST_VERSION this binding was written against (include/igs_rast.h)
 
@@ -174,6 +175,16 @@ def lib():
         L.igs_knn_scratch_bytes.argtypes = [_i]
         L.igs_knn_mean_dist2.restype = _i
         L.igs_knn_mean_dist2.argtypes = [_vp, _i, _vp, _vp, _vp]
+        L.igs_bbox_select_scratch_bytes.restype = C.c_size_t
+        L.igs_bbox_select_scratch_bytes.argtypes = [_i]
+        L.igs_bbox_select.restype = _i
+        L.igs_bbox_select.argtypes = [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.igs_fps_scratch_bytes.restype = C.c_size_t
+        L.igs_fps_scratch_bytes.argtypes = [_i, _i, _i]
+        L.igs_fps.restype = _i
+        L.igs_fps.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp]
+        L.igs_knn_query.restype = _i
+        L.igs_knn_query.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp]
         L.igs_depth_normal_loss_fwd_bwd.restype = _i
         L.igs_depth_normal_loss_fwd_bwd.argtypes = [_vp, _i, _i, _f, _f, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp]
         L.igs_l1_loss_fwd_bwd.restype = _i

@@ -1037,6 +1037,51 @@ extern "C" int igs_knn_mean_dist2(void* stream, int P, const float* xyz, void* s
     return 0;
 }
 
+// the anchor graph: bbox select, FPS, kNN (anchors.hip; the contracts are in include/igs_rast.h)
+extern "C" size_t igs_bbox_select_scratch_bytes(int N)
+{
+    if (N < 0 || N > IGS_ANCHOR_MAX_POINTS) return 0;
+    return select_scratch_bytes(N) + 256;
+}
+extern "C" int igs_bbox_select(void* stream, int B, int N, const float* xyz, const int* ptr, const float* box, void* scratch,
+                               float* out_xyz, int64_t* out_idx, int* out_count)
+{
+    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES || N < 0 || N > IGS_ANCHOR_MAX_POINTS)
+        return fail(IGS_RAST_E_INVALID, "igs_bbox_select: B or N out of range");
+    if (!ptr || !box || !out_count || (N > 0 && (!xyz || !scratch || !out_xyz || !out_idx)))
+        return fail(IGS_RAST_E_INVALID, "igs_bbox_select: NULL pointer");
+    HIP_TRY(launch_bbox_select((hipStream_t)stream, B, N, xyz, ptr, box, scratch, out_xyz, out_idx, out_count), "bbox select launch");
+    return 0;
+}
+extern "C" size_t igs_fps_scratch_bytes(int B, int N, int max_n)
+{
+    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES || N < 0 || N > IGS_ANCHOR_MAX_POINTS || max_n < 0 || max_n > IGS_FPS_MAX_EXAMPLE_POINTS) return 0;
+    return fps_scratch_bytes(B, N, max_n) + 256;
+}
+extern "C" int igs_fps(void* stream, int B, int N, int max_n, const float* xyz, const int* ptr, const int* start, const int* out_ptr,
+                       int total, float init_d2, void* scratch, int64_t* out)
+{
+    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES || N < 0 || N > IGS_ANCHOR_MAX_POINTS || max_n < 0 || max_n > IGS_FPS_MAX_EXAMPLE_POINTS)
+        return fail(IGS_RAST_E_INVALID, "igs_fps: B, N or max_n out of range");
+    if (total < 0 || total > IGS_ANCHOR_MAX_POINTS) return fail(IGS_RAST_E_INVALID, "igs_fps: total out of range");
+    if (total == 0) return 0;
+    if (!(init_d2 >= 0.f)) return fail(IGS_RAST_E_INVALID, "igs_fps: init_d2 must be >= 0");
+    if (!ptr || !start || !out_ptr || !scratch || !out || (N > 0 && !xyz)) return fail(IGS_RAST_E_INVALID, "igs_fps: NULL pointer");
+    HIP_TRY(launch_fps((hipStream_t)stream, B, N, max_n, xyz, ptr, start, out_ptr, total, init_d2, scratch, out), "fps launch");
+    return 0;
+}
+extern "C" int igs_knn_query(void* stream, int B, int Nx, int Ny, const float* x, const float* y, const int* ptr_x, const int* ptr_y,
+                             int k, float weight_scale, int64_t* out_idx, float* out_d2, float* out_w)
+{
+    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES || Nx < 0 || Nx > IGS_ANCHOR_MAX_POINTS || Ny < 0 || Ny > IGS_ANCHOR_MAX_POINTS)
+        return fail(IGS_RAST_E_INVALID, "igs_knn_query: B, Nx or Ny out of range");
+    if (k < 1 || k > IGS_KNN_QUERY_MAX_K) return fail(IGS_RAST_E_INVALID, "igs_knn_query: k out of range (1..IGS_KNN_QUERY_MAX_K)");
+    if (Ny == 0) return 0;
+    if (!y || !ptr_x || !ptr_y || !out_idx || (Nx > 0 && !x)) return fail(IGS_RAST_E_INVALID, "igs_knn_query: NULL pointer");
+    HIP_TRY(launch_knn_query((hipStream_t)stream, Nx, Ny, B, x, y, ptr_x, ptr_y, k, weight_scale, out_idx, out_d2, out_w), "knn query launch");
+    return 0;
+}
+
 // Test support: the per-tile sort of the slab binning on caller-made slabs (sort.hip: launch_tile_sort).  tile_count[T] instances per
 // tile (reset to zero by the launch), pairs[T * slab] = depth bits << 32 | Gaussian id, out: point_list[T * slab] (ids, sorted by the
 // 64-bit key inside every tile's slab), ranges[2 T], stats[4] ([1] = largest tile that overflowed its slab).  Everything device memory.

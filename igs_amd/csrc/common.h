@@ -148,6 +148,15 @@ size_t morton_scratch_bytes(int P);
 hipError_t launch_morton_order(hipStream_t s, int P, const float* xyz, const float* lohi, int bits, void* scratch, int* perm);
 size_t knn_scratch_bytes(int P);
 hipError_t launch_knn_mean_dist2(hipStream_t s, int P, const float* xyz, void* scratch, float* out);    // knn.hip
+hipError_t launch_knn_bbox(hipStream_t s, int P, const float* xyz, float* part, float* lohi);          // knn.hip (phase 1 alone)
+size_t select_scratch_bytes(int N);                                                                      // anchors.hip
+hipError_t launch_bbox_select(hipStream_t s, int B, int N, const float* xyz, const int* ptr, const float* box, void* scratch,
+                              float* out_xyz, int64_t* out_idx, int* count);
+size_t fps_scratch_bytes(int B, int N, int max_n);
+hipError_t launch_fps(hipStream_t s, int B, int N, int max_n, const float* xyz, const int* ptr, const int* start, const int* out_ptr,
+                      int total, float init_d2, void* scratch, int64_t* out);
+hipError_t launch_knn_query(hipStream_t s, int Nx, int Ny, int B, const float* x, const float* y, const int* ptr_x, const int* ptr_y,
+                            int k, float scale, int64_t* out_idx, float* out_d2, float* out_w);
 hipError_t launch_count_sorted(hipStream_t s, int P, const uint32_t* order, const uint32_t* tiles, uint32_t* blocksum);
 hipError_t launch_scan_blocksums(hipStream_t s, int nblocks, uint32_t* blocksum);
 hipError_t launch_emit_instances(hipStream_t s, int P, int gx, int gy, const uint32_t* order, const uint32_t* tiles,

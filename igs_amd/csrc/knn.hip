@@ -22,11 +22,10 @@
 // smallest values.  The result is the same multiset of three values whatever the visiting order, hence bit-identical from run to run
 // and under any permutation of the input.
 #include "common.h"
+#include "knn_common.h"
 #include <float.h>
 
 #define KNN_K 3                    // neighbours averaged (simple-knn: best[3]); the insertion below is written for 3
-#define KNN_BITS 21                // Morton bits per axis
-#define KNN_BBOX_PARTS 1024        // phase-1 partial boxes (one wave each)
 static_assert(KNN_K == 3, "knn_insert keeps exactly three values");
 
 // scratch layout (offsets from a 256-byte aligned base)
@@ -53,22 +52,6 @@ struct KnnLayout {
     }
 };
 
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
-// THE distance: every candidate of every phase goes through this expression
-__device__ __forceinline__ float dist2(float qx, float qy, float qz, float cx, float cy, float cz)
-{
-    const float dx = qx - cx, dy = qy - cy, dz = qz - cz;
-    return __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, __fmul_rn(dx, dx)));
-}
-// lower bound of dist2(q, c) over the box {lo, hi}: per-axis gaps (0 inside), same expression; +inf for an empty box (lo = +inf)
-__device__ __forceinline__ float box_dist2(float qx, float qy, float qz, const float4& lo, const float4& hi)
-{
-    const float gx = fmaxf(fmaxf(lo.x - qx, qx - hi.x), 0.f);
-    const float gy = fmaxf(fmaxf(lo.y - qy, qy - hi.y), 0.f);
-    const float gz = fmaxf(fmaxf(lo.z - qz, qz - hi.z), 0.f);
-    return __fmaf_rn(gz, gz, __fmaf_rn(gy, gy, __fmul_rn(gx, gx)));
-}
 // lower bound of dist2(q, c) over q in box a, c in box b
 __device__ __forceinline__ float boxbox_dist2(const float4& alo, const float4& ahi, const float4& blo, const float4& bhi)
 {
@@ -83,19 +66,6 @@ __device__ __forceinline__ void knn_insert(float d, float& b0, float& b1, float&
     b2 = __builtin_amdgcn_fmed3f(b1, d, b2);
     b1 = __builtin_amdgcn_fmed3f(b0, d, b1);
     b0 = fminf(b0, d);
-}
-
-__device__ __forceinline__ float wave_min(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
 }
 
 // ---- phase 1: bounding box of the finite points (empty: lo = +inf, hi = -inf) ----
@@ -126,28 +96,6 @@ knn_bbox_final_kernel(int nparts, const float* __restrict__ part, float* __restr
 }
 
 // ---- phase 2: 63-bit Morton keys ----
-__device__ __forceinline__ uint64_t spread21(uint32_t v)
-{
-    uint64_t x = v & 0x1FFFFFull;
-    x = (x | (x << 32)) & 0x1F00000000FFFFull;
-    x = (x | (x << 16)) & 0x1F0000FF0000FFull;
-    x = (x | (x << 8)) & 0x100F00F00F00F00Full;
-    x = (x | (x << 4)) & 0x10C30C30C30C30C3ull;
-    return (x | (x << 2)) & 0x1249249249249249ull;
-}
-// position quantised to KNN_BITS bits per axis inside lohi; a degenerate extent gives cell 0, non-finite input some cell in range
-__device__ __forceinline__ uint64_t knn_key(const float* __restrict__ xyz, uint32_t i, const float* __restrict__ lohi)
-{
-    const float top = (float)((1u << KNN_BITS) - 1u);
-    uint64_t key = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float lo = lohi[k], ext = fmaxf(lohi[3 + k] - lo, 1e-30f);
-        const float t = fminf(fmaxf((xyz[3 * (size_t)i + k] - lo) / ext * top, 0.f), top);     // (fmaxf drops a NaN to 0)
-        key |= spread21((uint32_t)t) << k;
-    }
-    return key;
-}
 // round 1: key bits [0, 32) with the identity as values; fills the first radix pass's per-block histogram
 __global__ void __launch_bounds__(256)
 knn_keys_lo_kernel(int P, const float* __restrict__ xyz, const float* __restrict__ lohi, uint32_t* __restrict__ keys,
@@ -351,5 +299,16 @@ hipError_t launch_knn_mean_dist2(hipStream_t s, int P, const float* xyz, void* s
     hipLaunchKernelGGL(knn_node_kernel, gn, dim3(256), 0, s, K.L, K.Nn, (const float4*)leafbox, nodebox);
     hipLaunchKernelGGL(knn_query_kernel, gl, dim3(256), 0, s, P, K.L, K.Nn, (const float4*)pts, (const float4*)leafbox,
                        (const float4*)nodebox, (const uint32_t*)sv, out);
+    return hipGetLastError();
+}
+
+// phase 1 alone, for anchors.hip: lohi[6] = box of the finite points of xyz[P], part: KNN_BBOX_PARTS * 8 floats of scratch
+hipError_t launch_knn_bbox(hipStream_t s, int P, const float* xyz, float* part, float* lohi)
+{
+    int parts = (P + 63) / 64;
+    if (parts > KNN_BBOX_PARTS) parts = KNN_BBOX_PARTS;
+    if (parts < 1) parts = 1;
+    hipLaunchKernelGGL(knn_bbox_partial_kernel, dim3(parts), dim3(64), 0, s, P, xyz, part);
+    hipLaunchKernelGGL(knn_bbox_final_kernel, dim3(1), dim3(64), 0, s, parts, (const float*)part, lohi);
     return hipGetLastError();
 }

@@ -7,6 +7,8 @@
 //
 // It also carries count_gaussians, the count pass of the compress package (compress-diff-gaussian-rasterization rasterize_points.cu:130-217).
 // And distCUDA2, the one function of simple-knn (mean squared distance to the three nearest neighbours, create_from_pcd's initial scales).
+// And the anchor graph natives under the torch_cluster / fpsample drop-ins and igs_amd.anchors: anchors_bbox_select, anchors_fps,
+// anchors_knn (fixed output shapes, no host synchronisation).
 // Extensions over the reference's signatures are keyword-only extras with defaults (the positional lists are the reference's):
 //   rasterize_gaussians(..., scratch=None, out_images=None, out_radii=None, mode=0, scratch_clean=False)
 //   rasterize_gaussians_backward(..., workspace=None, out_*=None)         any upstream gradient may be None (= zeros)
@@ -297,6 +299,104 @@ Tensor distCUDA2(const Tensor& points)
     return out;
 }
 
+// ---- the anchor graph (anchors.hip; contracts in include/igs_rast.h) ----
+static void check_points(const Tensor& t, const char* fn, const char* name)
+{
+    if (t.scalar_type() != at::kFloat)
+        throw RasterizerError(std::string(fn) + ": " + name + " must be float32 (got " + c10::toString(t.scalar_type()) + ")");
+    if (t.dim() != 2 || t.size(1) != 3)
+        throw RasterizerError(std::string(fn) + ": " + name + " must have shape [N, 3] (got " + c10::str(t.sizes()) + ")");
+    if (t.size(0) > IGS_ANCHOR_MAX_POINTS)
+        throw RasterizerError(std::string(fn) + ": " + std::to_string(t.size(0)) + " points is more than the supported " + std::to_string(IGS_ANCHOR_MAX_POINTS));
+}
+static void require_gpu(const Tensor& t, const char* fn, const char* name)      // after the argument checks
+{
+    if (!t.is_cuda()) throw RasterizerError(std::string(fn) + ": " + name + " must be on a GPU (no CPU fallback)");
+}
+static Tensor offsets_i32(const Tensor& t, const char* fn, const char* name, const Tensor& like, int64_t n)
+{
+    if (t.dim() != 1 || t.size(0) != n)
+        throw RasterizerError(std::string(fn) + ": " + name + " must have shape [" + std::to_string(n) + "] (got " + c10::str(t.sizes()) + ")");
+    if (t.device() != like.device()) throw RasterizerError(std::string(fn) + ": " + name + " must be on the points' device");
+    return t.to(at::kInt).contiguous();
+}
+static hipStream_t cur_stream(const c10::Device& dev) { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream(); }
+
+// select_points_bbox for B examples at once: (xyz_in_box [N, 3], index inside the example [N] int64, count [B] int32); the first
+// sum(count) rows are example 0's in-box points in index order, then example 1's, ...
+std::tuple<Tensor, Tensor, Tensor> anchors_bbox_select(const Tensor& xyz, const Tensor& ptr, const Tensor& box)
+{
+    check_points(xyz, "anchors_bbox_select", "xyz");
+    const int64_t B = ptr.dim() == 1 ? ptr.size(0) - 1 : -1;
+    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES) throw RasterizerError("anchors_bbox_select: ptr must have shape [B + 1], 1 <= B <= IGS_ANCHOR_MAX_EXAMPLES");
+    if (box.scalar_type() != at::kFloat || box.numel() != B * 6 || box.device() != xyz.device())
+        throw RasterizerError("anchors_bbox_select: box must be float32 [B, 2, 3] on the points' device");
+    require_gpu(xyz, "anchors_bbox_select", "xyz");
+    const c10::Device dev = xyz.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const int64_t N = xyz.size(0);
+    const Tensor p = offsets_i32(ptr, "anchors_bbox_select", "ptr", xyz, B + 1), bx = box.contiguous(), x = xyz.contiguous();
+    Tensor out_xyz = at::empty({N, 3}, xyz.options()), out_idx = at::empty({N}, xyz.options().dtype(at::kLong));
+    Tensor count = at::empty({B}, xyz.options().dtype(at::kInt));
+    Tensor scratch = at::empty({(int64_t)igs_bbox_select_scratch_bytes((int)N)}, xyz.options().dtype(at::kByte));
+    check(igs_bbox_select(cur_stream(dev), (int)B, (int)N, x.data_ptr<float>(), p.data_ptr<int>(), bx.data_ptr<float>(), scratch.data_ptr(),
+                          out_xyz.data_ptr<float>(), out_idx.data_ptr<int64_t>(), count.data_ptr<int>()), "igs_bbox_select");
+    return {out_xyz, out_idx, count};
+}
+
+// farthest-point sampling: `total` samples, example b's at [out_ptr[b], out_ptr[b + 1]) (indices into xyz, selection order); max_n
+// bounds every example's size
+Tensor anchors_fps(const Tensor& xyz, const Tensor& ptr, const Tensor& start, const Tensor& out_ptr, int64_t total, int64_t max_n, double init_d2)
+{
+    check_points(xyz, "anchors_fps", "xyz");
+    const int64_t B = ptr.dim() == 1 ? ptr.size(0) - 1 : -1;
+    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES) throw RasterizerError("anchors_fps: ptr must have shape [B + 1], 1 <= B <= IGS_ANCHOR_MAX_EXAMPLES");
+    if (max_n < 0 || max_n > IGS_FPS_MAX_EXAMPLE_POINTS)
+        throw RasterizerError("anchors_fps: an example of " + std::to_string(max_n) + " points is more than the supported " + std::to_string(IGS_FPS_MAX_EXAMPLE_POINTS));
+    if (total < 0 || total > IGS_ANCHOR_MAX_POINTS) throw RasterizerError("anchors_fps: total out of range");
+    if (!(init_d2 >= 0.0)) throw RasterizerError("anchors_fps: init_d2 must be >= 0");
+    require_gpu(xyz, "anchors_fps", "xyz");
+    const c10::Device dev = xyz.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const Tensor p = offsets_i32(ptr, "anchors_fps", "ptr", xyz, B + 1), st = offsets_i32(start, "anchors_fps", "start", xyz, B);
+    const Tensor op = offsets_i32(out_ptr, "anchors_fps", "out_ptr", xyz, B + 1), x = xyz.contiguous();
+    Tensor out = at::empty({total}, xyz.options().dtype(at::kLong));
+    if (total == 0) return out;
+    const int N = (int)xyz.size(0);
+    Tensor scratch = at::empty({(int64_t)igs_fps_scratch_bytes((int)B, N, (int)max_n)}, xyz.options().dtype(at::kByte));
+    check(igs_fps(cur_stream(dev), (int)B, N, (int)max_n, x.data_ptr<float>(), p.data_ptr<int>(), st.data_ptr<int>(), op.data_ptr<int>(),
+                  (int)total, (float)init_d2, scratch.data_ptr(), out.data_ptr<int64_t>()), "igs_fps");
+    return out;
+}
+
+// torch_cluster knn as fixed shapes: (index into x [Ny, k] int64 with -1 padding, d2 [Ny, k] or None, weights [Ny, k] or None)
+std::tuple<Tensor, c10::optional<Tensor>, c10::optional<Tensor>> anchors_knn(const Tensor& x, const Tensor& y, const Tensor& ptr_x,
+                                                                              const Tensor& ptr_y, int64_t k, bool with_d2,
+                                                                              c10::optional<double> weight_scale)
+{
+    check_points(x, "anchors_knn", "x");
+    check_points(y, "anchors_knn", "y");
+    if (x.device() != y.device()) throw RasterizerError("anchors_knn: x and y must be on one device");
+    if (k < 1 || k > IGS_KNN_QUERY_MAX_K) throw RasterizerError("anchors_knn: k must be in [1, " + std::to_string(IGS_KNN_QUERY_MAX_K) + "] (got " + std::to_string(k) + ")");
+    const int64_t B = ptr_x.dim() == 1 ? ptr_x.size(0) - 1 : -1;
+    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES) throw RasterizerError("anchors_knn: ptr_x must have shape [B + 1], 1 <= B <= IGS_ANCHOR_MAX_EXAMPLES");
+    require_gpu(x, "anchors_knn", "x");
+    const c10::Device dev = x.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const Tensor px = offsets_i32(ptr_x, "anchors_knn", "ptr_x", x, B + 1), py = offsets_i32(ptr_y, "anchors_knn", "ptr_y", x, B + 1);
+    const Tensor xc = x.contiguous(), yc = y.contiguous();
+    const int64_t Ny = y.size(0);
+    Tensor idx = at::empty({Ny, k}, x.options().dtype(at::kLong));
+    c10::optional<Tensor> d2, w;
+    if (with_d2) d2 = at::empty({Ny, k}, x.options());
+    if (weight_scale) w = at::empty({Ny, k}, x.options());
+    if (Ny == 0) return {idx, d2, w};
+    check(igs_knn_query(cur_stream(dev), (int)B, (int)x.size(0), (int)Ny, xc.data_ptr<float>(), yc.data_ptr<float>(), px.data_ptr<int>(),
+                        py.data_ptr<int>(), (int)k, weight_scale ? (float)*weight_scale : 0.f, idx.data_ptr<int64_t>(),
+                        d2 ? d2->data_ptr<float>() : nullptr, w ? w->data_ptr<float>() : nullptr), "igs_knn_query");
+    return {idx, d2, w};
+}
+
 // igs_adam_step_multi over lists of tensors (igs_amd/optim.py): one launch for up to 8 parameters
 void adam_step_multi(const std::vector<Tensor>& params, const std::vector<Tensor>& grads, const std::vector<Tensor>& exp_avgs,
                      const std::vector<Tensor>& exp_avg_sqs, const std::vector<double>& lrs, const std::vector<double>& bc1,
@@ -488,6 +588,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("scratch") = std::shared_ptr<ScratchSet>(), py::call_guard<py::gil_scoped_release>());
     m.def("mark_visible", &mark_visible, py::arg("means3D"), py::arg("viewmatrix"), py::arg("projmatrix"), py::call_guard<py::gil_scoped_release>());
     m.def("distCUDA2", &distCUDA2, py::arg("points"), py::call_guard<py::gil_scoped_release>());
+    m.def("anchors_bbox_select", &anchors_bbox_select, py::arg("xyz"), py::arg("ptr"), py::arg("box"), py::call_guard<py::gil_scoped_release>());
+    m.def("anchors_fps", &anchors_fps, py::arg("xyz"), py::arg("ptr"), py::arg("start"), py::arg("out_ptr"), py::arg("total"), py::arg("max_n"),
+          py::arg("init_d2"), py::call_guard<py::gil_scoped_release>());
+    m.def("anchors_knn", &anchors_knn, py::arg("x"), py::arg("y"), py::arg("ptr_x"), py::arg("ptr_y"), py::arg("k"), py::arg("with_d2") = false,
+          py::arg("weight_scale") = py::none(), py::call_guard<py::gil_scoped_release>());
     m.def("integrate_gaussians_to_points", [](const py::args&, const py::kwargs&) -> py::object {
         // GOF tetrahedra integration (DGR/rasterize_points.cu:269-387): mesh extraction only, never reached from IGS
         PyErr_SetString(PyExc_NotImplementedError, "integrate_gaussians_to_points is outside the IGS hot path and is not implemented");

@@ -513,6 +513,48 @@ int igs_morton_order(void* stream, int P, const float* xyz, const float* lohi, i
 size_t igs_knn_scratch_bytes(int P);
 int igs_knn_mean_dist2(void* stream, int P, const float* xyz, void* scratch, float* out);
 
+/* The anchor graph of IGS's AGM-Net (igs/models/gs.py get_mask_fpsample; the torch_cluster and fpsample drop-ins): in-box selection,
+ * exact farthest-point sampling and batched k nearest neighbours (anchors.hip).  Common rules of the three entry points:
+ *   - points are float32 xyz triples (D = 3 only); examples are contiguous runs given by ptr[B + 1] (int32, ptr[0] = 0, ascending,
+ *     ptr[B] = the number of points), read on the device only;
+ *   - every pointer is DEVICE memory, everything is enqueued on `stream`, no host synchronisation, no device allocation;
+ *   - sizes out of range or a NULL required pointer return IGS_RAST_E_INVALID before any HIP call; a call with nothing to compute
+ *     returns 0 and launches nothing.  The *_scratch_bytes functions return 0 for sizes out of range.
+ *   - distances: d2 = fma(dz, dz, fma(dy, dy, dx * dx)) in float32 for every candidate (knn.hip's expression).
+ *
+ * igs_bbox_select: for every example b keeps the points with box[6b + a] <= p[a] <= box[6b + 3 + a] on all three axes (a NaN
+ *   coordinate is outside), in ascending index order (torch.where): out_xyz [N x 3] and out_idx [N] (int64, the index inside the
+ *   example) hold example 0's points, then example 1's, ...; out_count[B] (int32) the counts.  Entries past the total are unwritten.
+ *   scratch: igs_bbox_select_scratch_bytes(N).  1 <= B <= IGS_ANCHOR_MAX_EXAMPLES, 0 <= N <= IGS_ANCHOR_MAX_POINTS.
+ *
+ * igs_fps: vanilla farthest-point sampling per example: sel[0] = start[b] (an index inside the example; out of range: 0); cur[i] =
+ *   init_d2 for every finite point (-inf for a point with a non-finite coordinate: never selected while a finite point is left, never
+ *   lowers another); step s: cur[i] = min(cur[i], d2(i, sel[s-1])), sel[s] = argmax cur, ties to the lowest index.  Example b takes
+ *   out_ptr[b + 1] - out_ptr[b] samples into out[out_ptr[b] ...] (int64, indices into the whole xyz array, selection order); out
+ *   holds `total` entries (normally out_ptr[B]) and nothing past them is written; total == 0 launches nothing.  Exact: the
+ *   same sequence as the restatement whatever the spatial order.  max_n must bound every example's size (the
+ *   launch is shaped by it); an example larger than max_n, or an empty one, gets -1 samples.  init_d2 >= 0 (+inf allowed).
+ *   scratch: igs_fps_scratch_bytes(B, N, max_n).  1 <= B <= IGS_ANCHOR_MAX_EXAMPLES, 0 <= N <= IGS_ANCHOR_MAX_POINTS,
+ *   0 <= max_n <= IGS_FPS_MAX_EXAMPLE_POINTS.
+ *
+ * igs_knn_query: torch_cluster's knn: for every query y[j] of example b the k nearest x[i] of the same example (ptr_x / ptr_y give the
+ *   examples of x and y), ordered by (d2, i) ascending; a candidate counts only if d2 < 1e10 (NaN never).  out_idx [Ny x k] int64:
+ *   indices into x, -1 in the slots without a neighbour; out_d2 [Ny x k] (or NULL): d2, +inf in empty slots; out_w [Ny x k] (or
+ *   NULL): softmax(-weight_scale * sqrt(d2)) over the filled slots, 0 in empty ones.  No scratch.  1 <= k <= IGS_KNN_QUERY_MAX_K,
+ *   1 <= B <= IGS_ANCHOR_MAX_EXAMPLES, 0 <= Nx, Ny <= IGS_ANCHOR_MAX_POINTS. */
+#define IGS_ANCHOR_MAX_POINTS (1 << 26)
+#define IGS_ANCHOR_MAX_EXAMPLES (1 << 16)
+#define IGS_FPS_MAX_EXAMPLE_POINTS (1 << 22)
+#define IGS_KNN_QUERY_MAX_K 100
+size_t igs_bbox_select_scratch_bytes(int N);
+int igs_bbox_select(void* stream, int B, int N, const float* xyz, const int* ptr, const float* box, void* scratch, float* out_xyz,
+                    int64_t* out_idx, int* out_count);
+size_t igs_fps_scratch_bytes(int B, int N, int max_n);
+int igs_fps(void* stream, int B, int N, int max_n, const float* xyz, const int* ptr, const int* start, const int* out_ptr, int total,
+            float init_d2, void* scratch, int64_t* out);
+int igs_knn_query(void* stream, int B, int Nx, int Ny, const float* x, const float* y, const int* ptr_x, const int* ptr_y, int k,
+                  float weight_scale, int64_t* out_idx, float* out_d2, float* out_w);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).
