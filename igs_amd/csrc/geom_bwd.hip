@@ -675,12 +675,16 @@ geom_bwd_kernel(const GBArgs args)
                 for (int k = 0; k < 3; k++) g_ls[k] = go[k] * act_exp(ls[k]);
                 const float* rq = fz.param + fz.off_rot + 4 * (size_t)idx;
                 const float q0 = rq[0], q1 = rq[1], q2 = rq[2], q3 = rq[3];
-                const float nrm = fmaxf(sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3), 1e-12f);
+                const float len = sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+                const float nrm = fmaxf(len, 1e-12f);
                 const float inv = 1.0f / nrm;
                 const float n0 = q0 * inv, n1 = q1 * inv, n2 = q2 * inv, n3 = q3 * inv;
                 const float dt = n0 * o_rot.x + n1 * o_rot.y + n2 * o_rot.z + n3 * o_rot.w;
                 g_rot[0] = (o_rot.x - n0 * dt) * inv; g_rot[1] = (o_rot.y - n1 * dt) * inv;
                 g_rot[2] = (o_rot.z - n2 * dt) * inv; g_rot[3] = (o_rot.w - n3 * dt) * inv;
+                if (len < 1e-12f) {           // F.normalize below eps: q / eps, and clamp_min passes no gradient -- g / eps, no projection
+                    g_rot[0] = o_rot.x * inv; g_rot[1] = o_rot.y * inv; g_rot[2] = o_rot.z * inv; g_rot[3] = o_rot.w * inv;
+                }
             }
             // staged in LDS: the update below walks each parameter group's contiguous span of this workgroup with coalesced
             // accesses (per-thread 4-byte updates at strides of 12 / 16 bytes cost 30 us for 11 of the 59 parameters)

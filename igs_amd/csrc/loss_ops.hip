@@ -440,11 +440,12 @@ __device__ __forceinline__ void depth_normal_body(float* __restrict__ lds, const
                 const float n0 = c0 * inv, n1 = c1 * inv, n2 = c2 * inv;
                 dotn = q0 * n0 + q1 * n1 + q2 * n2;
                 if (mine) { gn0 -= s * n0; gn1 -= s * n1; gn2 -= s * n2; }
-                // backward of normalize (for len > eps) and of the cross product; dL/dn = -s * rendered_normal
+                // backward of normalize and of the cross product; dL/dn = -s * rendered_normal.  Below eps F.normalize divides by the
+                // clamped norm, whose clamp passes no gradient: e = h / eps, no projection term (c = 0 wherever both row or both column
+                // neighbours have depth 0, e.g. thin structures on an empty background)
                 const float h0 = -s * q0, h1 = -s * q1, h2 = -s * q2;
-                const float hn = h0 * n0 + h1 * n1 + h2 * n2;
-                const float k = tiny ? 0.f : inv;
-                const float e0 = (h0 - n0 * hn) * k, e1 = (h1 - n1 * hn) * k, e2 = (h2 - n2 * hn) * k;
+                const float hn = tiny ? 0.f : h0 * n0 + h1 * n1 + h2 * n2;
+                const float e0 = (h0 - n0 * hn) * inv, e1 = (h1 - n1 * hn) * inv, e2 = (h2 - n2 * hn) * inv;
                 ga0 = by_ * e2 - bz_ * e1; ga1 = bz_ * e0 - bx_ * e2; ga2 = bx_ * e1 - by_ * e0;        // b x e
                 gb0 = e1 * az - e2 * ay; gb1 = e2 * ax - e0 * az; gb2 = e0 * ay - e1 * ax;              // e x a
             }

@@ -381,12 +381,14 @@ activate_bwd_kernel(int P, const float* __restrict__ opacity, const float* __res
     for (int k = 0; k < 3; k++) g_log_scale[3 * i + k] = d_scale[3 * i + k] * scale[3 * i + k];
     const float q0 = rot[4 * i], q1 = rot[4 * i + 1], q2 = rot[4 * i + 2], q3 = rot[4 * i + 3];
     const float g0 = d_rot[4 * i], g1 = d_rot[4 * i + 1], g2 = d_rot[4 * i + 2], g3 = d_rot[4 * i + 3];
-    const float nrm = fmaxf(sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3), 1e-12f);
+    const float len = sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+    const float nrm = fmaxf(len, 1e-12f);
     const float inv = 1.0f / nrm;
     const float n0 = q0 * inv, n1 = q1 * inv, n2 = q2 * inv, n3 = q3 * inv;
     const float dt = n0 * g0 + n1 * g1 + n2 * g2 + n3 * g3;
-    g_rot[4 * i] = (g0 - n0 * dt) * inv; g_rot[4 * i + 1] = (g1 - n1 * dt) * inv;
-    g_rot[4 * i + 2] = (g2 - n2 * dt) * inv; g_rot[4 * i + 3] = (g3 - n3 * dt) * inv;
+    float o0 = (g0 - n0 * dt) * inv, o1 = (g1 - n1 * dt) * inv, o2 = (g2 - n2 * dt) * inv, o3 = (g3 - n3 * dt) * inv;
+    if (len < 1e-12f) { o0 = g0 * inv; o1 = g1 * inv; o2 = g2 * inv; o3 = g3 * inv; }      // F.normalize below eps: g / eps (clamp_min)
+    g_rot[4 * i] = o0; g_rot[4 * i + 1] = o1; g_rot[4 * i + 2] = o2; g_rot[4 * i + 3] = o3;
 }
 extern "C" int igs_activate_fwd(void* stream, int P, const float* logit, const float* log_scale, const float* rot, float* opacity,
                                 float* scale, float* rot_n)

@@ -68,9 +68,10 @@ def backproject(cam, depth):
     fx = W / (2 * math.tan(cam.FoVx / 2.0))
     fy = H / (2 * math.tan(cam.FoVy / 2.0))
     dev = depth.device
-    ys = (torch.arange(H, device=dev, dtype=torch.float32) + 0.5 - H / 2.0) / fy
-    xs = (torch.arange(W, device=dev, dtype=torch.float32) + 0.5 - W / 2.0) / fx
-    rays = torch.stack([xs.view(1, W).expand(H, W), ys.view(H, 1).expand(H, W), torch.ones(H, W, device=dev)], dim=0)
+    dt = depth.dtype if depth.dtype == torch.float64 else torch.float32      # (float64 depth: the rays in float64 too)
+    ys = (torch.arange(H, device=dev, dtype=dt) + 0.5 - H / 2.0) / fy
+    xs = (torch.arange(W, device=dev, dtype=dt) + 0.5 - W / 2.0) / fx
+    rays = torch.stack([xs.view(1, W).expand(H, W), ys.view(H, 1).expand(H, W), torch.ones(H, W, device=dev, dtype=dt)], dim=0)
     return rays * depth.reshape(1, H, W)
 
 
