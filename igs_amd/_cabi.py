@@ -51,7 +51,8 @@ EXPORTS = ["igs_rast_version", "igs_rast_last_error", "igs_rast_forward", "igs_r
            "igs_sh_grad_from_view_colors", "igs_adam_sh_from_view_colors", "igs_rast_last_backward_instance", "igs_rast_next_backward_options", "igs_rast_nan_report_wait", "igs_rast_nan_report_handle", "igs_rast_nan_report_wait_at", "igs_refine_step_args_size", "igs_rast_debug_poison_lds", "igs_adam_exchange_step", "igs_morton_order", "igs_morton_order_scratch_bytes", "igs_ply_to_params", "igs_params_to_ply", "igs_debug_tile_sort",
            "igs_refine_step_masked", "igs_refine_mask_args_size", "igs_rast_count_gaussians",
            "igs_knn_scratch_bytes", "igs_knn_mean_dist2", "igs_bbox_select_scratch_bytes", "igs_bbox_select", "igs_fps_scratch_bytes",
-           "igs_fps", "igs_knn_query"]
+           "igs_fps", "igs_knn_query", "igs_anchor_interp_fwd", "igs_anchor_interp_index_bytes", "igs_anchor_interp_index",
+           "igs_anchor_interp_bwd", "igs_gaussian_deform_fwd", "igs_gaussian_deform_bwd"]
 
 VERSION = 4       # IGS_RAST_VERSION this binding was written against (include/igs_rast.h)
 
@@ -185,6 +186,18 @@ def lib():
         L.igs_fps.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp]
         L.igs_knn_query.restype = _i
         L.igs_knn_query.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp]
+        L.igs_anchor_interp_fwd.restype = _i
+        L.igs_anchor_interp_fwd.argtypes = [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]
+        L.igs_anchor_interp_index_bytes.restype = C.c_size_t
+        L.igs_anchor_interp_index_bytes.argtypes = [_i, _i, _i, _i]
+        L.igs_anchor_interp_index.restype = _i
+        L.igs_anchor_interp_index.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp]
+        L.igs_anchor_interp_bwd.restype = _i
+        L.igs_anchor_interp_bwd.argtypes = [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.igs_gaussian_deform_fwd.restype = _i
+        L.igs_gaussian_deform_fwd.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.igs_gaussian_deform_bwd.restype = _i
+        L.igs_gaussian_deform_bwd.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
         L.igs_depth_normal_loss_fwd_bwd.restype = _i
         L.igs_depth_normal_loss_fwd_bwd.argtypes = [_vp, _i, _i, _f, _f, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp]
         L.igs_l1_loss_fwd_bwd.restype = _i

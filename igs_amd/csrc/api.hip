@@ -1082,6 +1082,87 @@ extern "C" int igs_knn_query(void* stream, int B, int Nx, int Ny, const float* x
     return 0;
 }
 
+// anchor feature interpolation and the Gaussian deform (motion.hip; the contracts are in include/igs_rast.h)
+static bool interp_sizes_ok(int N, int K, int D, int A)
+{
+    return N >= 0 && N <= IGS_INTERP_MAX_ROWS && K >= 1 && K <= IGS_INTERP_MAX_K && D >= 1 && D <= IGS_INTERP_MAX_D && A >= 1 &&
+           A <= IGS_INTERP_MAX_ANCHORS && (long long)N * K <= IGS_INTERP_MAX_EDGES;
+}
+static int interp_size_fail(const char* fn, int N, int K, int D, int A)
+{
+    char what[160];
+    if (N < 0 || N > IGS_INTERP_MAX_ROWS) snprintf(what, sizeof what, "%s: N out of range (0..IGS_INTERP_MAX_ROWS)", fn);
+    else if (K < 1 || K > IGS_INTERP_MAX_K) snprintf(what, sizeof what, "%s: K out of range (1..IGS_INTERP_MAX_K)", fn);
+    else if (D < 1 || D > IGS_INTERP_MAX_D) snprintf(what, sizeof what, "%s: D out of range (1..IGS_INTERP_MAX_D)", fn);
+    else if (A < 1 || A > IGS_INTERP_MAX_ANCHORS) snprintf(what, sizeof what, "%s: A_total out of range (1..IGS_INTERP_MAX_ANCHORS)", fn);
+    else snprintf(what, sizeof what, "%s: N * K out of range (IGS_INTERP_MAX_EDGES)", fn);
+    return fail(IGS_RAST_E_INVALID, what);
+}
+static bool dtype_ok(int dtype) { return dtype == IGS_DTYPE_F32 || dtype == IGS_DTYPE_F16; }
+
+extern "C" int igs_anchor_interp_fwd(void* stream, int N, int K, int D, int A_total, int dtype, const void* F, const int64_t* col,
+                                     const float* w, float* out)
+{
+    if (!interp_sizes_ok(N, K, D, A_total)) return interp_size_fail("igs_anchor_interp_fwd", N, K, D, A_total);
+    if (!dtype_ok(dtype)) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_fwd: unknown dtype code");
+    if (N == 0) return 0;
+    if (!F || !col || !w || !out) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_fwd: NULL pointer");
+    HIP_TRY(launch_interp_fwd((hipStream_t)stream, N, K, D, A_total, dtype, F, col, w, out), "anchor interp fwd launch");
+    return 0;
+}
+extern "C" size_t igs_anchor_interp_index_bytes(int N, int K, int A_total, int D)
+{
+    if (!interp_sizes_ok(N, K, D, A_total)) return 0;
+    return interp_scratch_bytes(N, K, A_total, D) + 256;
+}
+extern "C" int igs_anchor_interp_index(void* stream, int N, int K, int A_total, int D, const int64_t* col, void* scratch)
+{
+    if (!interp_sizes_ok(N, K, D, A_total)) return interp_size_fail("igs_anchor_interp_index", N, K, D, A_total);
+    if (N == 0) return 0;
+    if (!col || !scratch) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_index: NULL pointer");
+    HIP_TRY(launch_interp_index((hipStream_t)stream, N, K, A_total, D, col, scratch), "anchor interp index launch");
+    return 0;
+}
+extern "C" int igs_anchor_interp_bwd(void* stream, int N, int K, int D, int A_total, int dtype, const void* F, const float* w,
+                                     const float* dout, void* scratch, void* dF, float* dw)
+{
+    if (!interp_sizes_ok(N, K, D, A_total)) return interp_size_fail("igs_anchor_interp_bwd", N, K, D, A_total);
+    if (!dtype_ok(dtype)) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_bwd: unknown dtype code");
+    if (!dF && !dw) return 0;
+    if (N == 0) {       // no edges: every anchor's gradient is zero
+        if (dF) HIP_TRY(zero_fill_async((hipStream_t)stream, dF, (size_t)A_total * D * (dtype == IGS_DTYPE_F16 ? 2 : 4)), "zero dF");
+        return 0;
+    }
+    if (!w || !dout || !scratch || (dw && !F)) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_bwd: NULL pointer");
+    HIP_TRY(launch_interp_bwd((hipStream_t)stream, N, K, D, A_total, dtype, F, w, dout, scratch, dF, dw), "anchor interp bwd launch");
+    return 0;
+}
+extern "C" int igs_gaussian_deform_fwd(void* stream, int P, int M, int dtype, const float* xyz, const float* rot, const int64_t* mask,
+                                       const void* dxyz, const void* drot, float* xyz_out, float* rot_out)
+{
+    if (P < 0 || P > IGS_DEFORM_MAX_POINTS) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_fwd: P out of range (0..IGS_DEFORM_MAX_POINTS)");
+    if (M < 0 || M > P) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_fwd: M out of range (0..P)");
+    if (!dtype_ok(dtype)) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_fwd: unknown dtype code");
+    if (P == 0) return 0;
+    if (!xyz || !rot || !xyz_out || !rot_out || (M > 0 && (!mask || !dxyz || !drot)))
+        return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_fwd: NULL pointer");
+    HIP_TRY(launch_deform_fwd((hipStream_t)stream, P, M, dtype, xyz, rot, mask, dxyz, drot, xyz_out, rot_out), "gaussian deform fwd launch");
+    return 0;
+}
+extern "C" int igs_gaussian_deform_bwd(void* stream, int P, int M, int dtype, const float* rot, const int64_t* mask, const void* drot,
+                                       const float* g_xyz, const float* g_rot, float* d_xyz, float* d_rot, void* d_dxyz, void* d_drot)
+{
+    if (P < 0 || P > IGS_DEFORM_MAX_POINTS) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_bwd: P out of range (0..IGS_DEFORM_MAX_POINTS)");
+    if (M < 0 || M > P) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_bwd: M out of range (0..P)");
+    if (!dtype_ok(dtype)) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_bwd: unknown dtype code");
+    if (P == 0 || (!d_xyz && !d_rot && !d_dxyz && !d_drot)) return 0;
+    if (M > 0 && (!mask || ((d_rot || d_drot) && (!rot || !drot))))
+        return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_bwd: NULL pointer");
+    HIP_TRY(launch_deform_bwd((hipStream_t)stream, P, M, dtype, rot, mask, drot, g_xyz, g_rot, d_xyz, d_rot, d_dxyz, d_drot),
+            "gaussian deform bwd launch");
+    return 0;
+}
+
 // Test support: the per-tile sort of the slab binning on caller-made slabs (sort.hip: launch_tile_sort).  tile_count[T] instances per
 // tile (reset to zero by the launch), pairs[T * slab] = depth bits << 32 | Gaussian id, out: point_list[T * slab] (ids, sorted by the
 // 64-bit key inside every tile's slab), ranges[2 T], stats[4] ([1] = largest tile that overflowed its slab).  Everything device memory.

@@ -157,6 +157,16 @@ hipError_t launch_fps(hipStream_t s, int B, int N, int max_n, const float* xyz, 
                       int total, float init_d2, void* scratch, int64_t* out);
 hipError_t launch_knn_query(hipStream_t s, int Nx, int Ny, int B, const float* x, const float* y, const int* ptr_x, const int* ptr_y,
                             int k, float scale, int64_t* out_idx, float* out_d2, float* out_w);
+hipError_t launch_interp_fwd(hipStream_t s, int N, int K, int D, int A, int dtype, const void* F, const int64_t* col, const float* w,
+                             float* out);                                                                // motion.hip
+size_t interp_scratch_bytes(int N, int K, int A, int D);
+hipError_t launch_interp_index(hipStream_t s, int N, int K, int A, int D, const int64_t* col, void* scratch);
+hipError_t launch_interp_bwd(hipStream_t s, int N, int K, int D, int A, int dtype, const void* F, const float* w, const float* dout,
+                             void* scratch, void* dF, float* dw);
+hipError_t launch_deform_fwd(hipStream_t s, int P, int M, int dtype, const float* xyz, const float* rot, const int64_t* mask,
+                             const void* dxyz, const void* drot, float* xyz_out, float* rot_out);
+hipError_t launch_deform_bwd(hipStream_t s, int P, int M, int dtype, const float* rot, const int64_t* mask, const void* drot,
+                             const float* g_xyz, const float* g_rot, float* d_xyz, float* d_rot, void* d_dxyz, void* d_drot);
 hipError_t launch_count_sorted(hipStream_t s, int P, const uint32_t* order, const uint32_t* tiles, uint32_t* blocksum);
 hipError_t launch_scan_blocksums(hipStream_t s, int nblocks, uint32_t* blocksum);
 hipError_t launch_emit_instances(hipStream_t s, int P, int gx, int gy, const uint32_t* order, const uint32_t* tiles,

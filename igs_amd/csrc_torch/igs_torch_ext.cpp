@@ -9,6 +9,8 @@
 // And distCUDA2, the one function of simple-knn (mean squared distance to the three nearest neighbours, create_from_pcd's initial scales).
 // And the anchor graph natives under the torch_cluster / fpsample drop-ins and igs_amd.anchors: anchors_bbox_select, anchors_fps,
 // anchors_knn (fixed output shapes, no host synchronisation).
+// And the two consumers of the anchor graph under igs_amd.motion: motion_interp_fwd / _index / _bwd (anchor feature interpolation) and
+// motion_deform_fwd / _bwd (GaussianModel.deform); unsupported dtypes raise NotImplementedError.
 // Extensions over the reference's signatures are keyword-only extras with defaults (the positional lists are the reference's):
 //   rasterize_gaussians(..., scratch=None, out_images=None, out_radii=None, mode=0, scratch_clean=False)
 //   rasterize_gaussians_backward(..., workspace=None, out_*=None)         any upstream gradient may be None (= zeros)
@@ -397,6 +399,166 @@ std::tuple<Tensor, c10::optional<Tensor>, c10::optional<Tensor>> anchors_knn(con
     return {idx, d2, w};
 }
 
+// ---- anchor feature interpolation and the Gaussian deform (motion.hip; contracts in include/igs_rast.h) ----
+struct NotImplemented : public std::runtime_error { using std::runtime_error::runtime_error; };
+
+static int motion_dtype(const Tensor& t, const char* fn, const char* name)
+{
+    if (t.scalar_type() == at::kFloat) return IGS_DTYPE_F32;
+    if (t.scalar_type() == at::kHalf) return IGS_DTYPE_F16;
+    throw NotImplemented(std::string(fn) + ": " + name + " must be float32 or float16 (got " + c10::toString(t.scalar_type()) + ")");
+}
+static void motion_expect(const Tensor& t, const char* fn, const char* name, at::ScalarType dt, std::initializer_list<int64_t> shape)
+{
+    if (t.scalar_type() != dt)
+        throw NotImplemented(std::string(fn) + ": " + name + " must be " + c10::toString(dt) + " (got " + c10::toString(t.scalar_type()) + ")");
+    bool ok = t.dim() == (int64_t)shape.size();
+    int i = 0;
+    for (int64_t n : shape) { if (ok && n >= 0 && t.size(i) != n) ok = false; i++; }
+    if (!ok) throw RasterizerError(std::string(fn) + ": " + name + " has shape " + c10::str(t.sizes()) + ", expected " + c10::str(at::IntArrayRef(shape)) + " (-1: any)");
+}
+static void same_device(const Tensor& t, const Tensor& like, const char* fn, const char* name)
+{
+    if (t.device() != like.device()) throw RasterizerError(std::string(fn) + ": " + name + " must be on " + c10::str(like.device()));
+}
+
+// out [N, D] float32 = sum_k w[n, k] * F[col[n, k]]: F [A_total, D] float32 / float16, col [N, K] int64, w [N, K] float32
+Tensor motion_interp_fwd(const Tensor& F, const Tensor& col, const Tensor& w)
+{
+    const char* fn = "motion_interp_fwd";
+    const int dt = motion_dtype(F, fn, "features");
+    if (F.dim() != 2) throw RasterizerError(std::string(fn) + ": features must have shape [A_total, D] (got " + c10::str(F.sizes()) + ")");
+    motion_expect(col, fn, "col", at::kLong, {-1, -1});
+    motion_expect(w, fn, "weights", at::kFloat, {col.size(0), col.size(1)});
+    const int64_t N = col.size(0), K = col.size(1), A = F.size(0), D = F.size(1);
+    if (K < 1 || K > IGS_INTERP_MAX_K || D < 1 || D > IGS_INTERP_MAX_D || A < 1 || A > IGS_INTERP_MAX_ANCHORS || N > IGS_INTERP_MAX_ROWS ||
+        N * K > IGS_INTERP_MAX_EDGES)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (1 <= K <= 100, 1 <= D <= 1024, 1 <= A_total <= 2^24, N <= 2^24, N * K <= 2^30)");
+    require_gpu(F, fn, "features");
+    same_device(col, F, fn, "col");
+    same_device(w, F, fn, "weights");
+    const c10::Device dev = F.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    Tensor out = at::empty({N, D}, F.options().dtype(at::kFloat));
+    if (N == 0) return out;
+    const Tensor Fc = F.contiguous(), cc = col.contiguous(), wc = w.contiguous();
+    check(igs_anchor_interp_fwd(cur_stream(dev), (int)N, (int)K, (int)D, (int)A, dt, Fc.data_ptr(), cc.data_ptr<int64_t>(), wc.data_ptr<float>(),
+                                out.data_ptr<float>()), "igs_anchor_interp_fwd");
+    return out;
+}
+
+// the inverse index of col (and room for the backward's partials at width D): a uint8 tensor to hand to motion_interp_bwd
+Tensor motion_interp_index(const Tensor& col, int64_t A, int64_t D)
+{
+    const char* fn = "motion_interp_index";
+    motion_expect(col, fn, "col", at::kLong, {-1, -1});
+    const int64_t N = col.size(0), K = col.size(1);
+    const size_t bytes = (N <= INT_MAX && K <= INT_MAX && A <= INT_MAX && D <= INT_MAX) ? igs_anchor_interp_index_bytes((int)N, (int)K, (int)A, (int)D) : 0;
+    if (bytes == 0) throw RasterizerError(std::string(fn) + ": sizes out of range");
+    require_gpu(col, fn, "col");
+    const c10::Device dev = col.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    Tensor scratch = at::empty({(int64_t)bytes}, col.options().dtype(at::kByte));
+    const Tensor cc = col.contiguous();
+    check(igs_anchor_interp_index(cur_stream(dev), (int)N, (int)K, (int)A, (int)D, cc.data_ptr<int64_t>(), scratch.data_ptr()), "igs_anchor_interp_index");
+    return scratch;
+}
+
+// (dF [A_total, D] in F's dtype or None, dw [N, K] float32 or None) from the index of motion_interp_index
+std::tuple<OptTensor, OptTensor> motion_interp_bwd(const Tensor& F, const Tensor& w, const Tensor& dout, const Tensor& index, bool want_dF,
+                                                   bool want_dw)
+{
+    const char* fn = "motion_interp_bwd";
+    const int dt = motion_dtype(F, fn, "features");
+    if (F.dim() != 2) throw RasterizerError(std::string(fn) + ": features must have shape [A_total, D] (got " + c10::str(F.sizes()) + ")");
+    motion_expect(w, fn, "weights", at::kFloat, {-1, -1});
+    const int64_t N = w.size(0), K = w.size(1), A = F.size(0), D = F.size(1);
+    motion_expect(dout, fn, "grad_out", at::kFloat, {N, D});
+    motion_expect(index, fn, "index", at::kByte, {-1});
+    require_gpu(F, fn, "features");
+    same_device(w, F, fn, "weights");
+    same_device(dout, F, fn, "grad_out");
+    same_device(index, F, fn, "index");
+    const size_t need = igs_anchor_interp_index_bytes((int)N, (int)K, (int)A, (int)D);
+    if (need == 0 || (size_t)index.numel() < need) throw RasterizerError(std::string(fn) + ": index too small for these sizes (or sizes out of range)");
+    const c10::Device dev = F.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    OptTensor dF, dw;
+    if (want_dF) dF = at::empty({A, D}, F.options());
+    if (want_dw) dw = at::empty({N, K}, w.options());
+    const Tensor Fc = F.contiguous(), wc = w.contiguous(), gc = dout.contiguous();
+    check(igs_anchor_interp_bwd(cur_stream(dev), (int)N, (int)K, (int)D, (int)A, dt, Fc.data_ptr(), wc.data_ptr<float>(), gc.data_ptr<float>(),
+                                index.data_ptr(), dF ? dF->data_ptr() : nullptr, dw ? dw->data_ptr<float>() : nullptr), "igs_anchor_interp_bwd");
+    return {dF, dw};
+}
+
+static void deform_checks(const char* fn, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot, int* dt)
+{
+    motion_expect(rot, fn, "rotation", at::kFloat, {-1, 4});
+    motion_expect(mask, fn, "mask", at::kLong, {-1});
+    *dt = motion_dtype(drot, fn, "res_rotation");
+    if (dxyz.scalar_type() != drot.scalar_type()) throw NotImplemented(std::string(fn) + ": res_xyz and res_rotation must share a dtype");
+    motion_expect(dxyz, fn, "res_xyz", dxyz.scalar_type(), {mask.size(0), 3});
+    motion_expect(drot, fn, "res_rotation", drot.scalar_type(), {mask.size(0), 4});
+    if (rot.size(0) > IGS_DEFORM_MAX_POINTS || mask.size(0) > rot.size(0))
+        throw RasterizerError(std::string(fn) + ": sizes out of range (M <= P <= 2^26)");
+}
+
+// (xyz_out, rotation_out): xyz[mask] += res_xyz, rotation[mask] = qmul(nrm(rotation[mask]), nrm(res_rotation))
+std::tuple<Tensor, Tensor> motion_deform_fwd(const Tensor& xyz, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot)
+{
+    const char* fn = "motion_deform_fwd";
+    int dt;
+    motion_expect(xyz, fn, "xyz", at::kFloat, {-1, 3});
+    deform_checks(fn, rot, mask, dxyz, drot, &dt);
+    if (rot.size(0) != xyz.size(0)) throw RasterizerError(std::string(fn) + ": xyz and rotation must have the same number of rows");
+    require_gpu(xyz, fn, "xyz");
+    for (const Tensor* t : { &rot, &mask, &dxyz, &drot }) same_device(*t, xyz, fn, "every input");
+    const c10::Device dev = xyz.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const int64_t P = xyz.size(0), M = mask.size(0);
+    Tensor xo = at::empty({P, 3}, xyz.options()), ro = at::empty({P, 4}, xyz.options());
+    if (P == 0) return {xo, ro};
+    const Tensor xc = xyz.contiguous(), rc = rot.contiguous(), mc = mask.contiguous(), dxc = dxyz.contiguous(), drc = drot.contiguous();
+    check(igs_gaussian_deform_fwd(cur_stream(dev), (int)P, (int)M, dt, xc.data_ptr<float>(), rc.data_ptr<float>(), mc.data_ptr<int64_t>(),
+                                  dxc.data_ptr(), drc.data_ptr(), xo.data_ptr<float>(), ro.data_ptr<float>()), "igs_gaussian_deform_fwd");
+    return {xo, ro};
+}
+
+// (d_xyz, d_rotation, d_res_xyz, d_res_rotation), each None unless asked for; g_xyz / g_rot may be None (zero)
+std::tuple<OptTensor, OptTensor, OptTensor, OptTensor> motion_deform_bwd(const Tensor& rot, const Tensor& mask, const Tensor& dxyz,
+                                                                         const Tensor& drot, const OptTensor& g_xyz, const OptTensor& g_rot,
+                                                                         bool want_xyz, bool want_rot, bool want_dxyz, bool want_drot)
+{
+    const char* fn = "motion_deform_bwd";
+    int dt;
+    deform_checks(fn, rot, mask, dxyz, drot, &dt);
+    const int64_t P = rot.size(0), M = mask.size(0);
+    if (g_xyz) motion_expect(*g_xyz, fn, "grad_xyz", at::kFloat, {P, 3});
+    if (g_rot) motion_expect(*g_rot, fn, "grad_rotation", at::kFloat, {P, 4});
+    require_gpu(rot, fn, "rotation");
+    for (const Tensor* t : { &mask, &dxyz, &drot }) same_device(*t, rot, fn, "every input");
+    if (g_xyz) same_device(*g_xyz, rot, fn, "grad_xyz");
+    if (g_rot) same_device(*g_rot, rot, fn, "grad_rotation");
+    const c10::Device dev = rot.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    OptTensor dx, dr, ddx, ddr;
+    if (want_xyz) dx = at::empty({P, 3}, rot.options());
+    if (want_rot) dr = at::empty({P, 4}, rot.options());
+    if (want_dxyz) ddx = at::empty({M, 3}, drot.options());
+    if (want_drot) ddr = at::empty({M, 4}, drot.options());
+    if (P == 0) return {dx, dr, ddx, ddr};
+    const Tensor rc = rot.contiguous(), mc = mask.contiguous(), drc = drot.contiguous();
+    Tensor gx, gr;
+    if (g_xyz) gx = g_xyz->contiguous();
+    if (g_rot) gr = g_rot->contiguous();
+    check(igs_gaussian_deform_bwd(cur_stream(dev), (int)P, (int)M, dt, rc.data_ptr<float>(), mc.data_ptr<int64_t>(), drc.data_ptr(),
+                                  g_xyz ? gx.data_ptr<float>() : nullptr, g_rot ? gr.data_ptr<float>() : nullptr, dx ? dx->data_ptr<float>() : nullptr,
+                                  dr ? dr->data_ptr<float>() : nullptr, ddx ? ddx->data_ptr() : nullptr, ddr ? ddr->data_ptr() : nullptr),
+          "igs_gaussian_deform_bwd");
+    return {dx, dr, ddx, ddr};
+}
+
 // igs_adam_step_multi over lists of tensors (igs_amd/optim.py): one launch for up to 8 parameters
 void adam_step_multi(const std::vector<Tensor>& params, const std::vector<Tensor>& grads, const std::vector<Tensor>& exp_avgs,
                      const std::vector<Tensor>& exp_avg_sqs, const std::vector<double>& lrs, const std::vector<double>& bc1,
@@ -522,6 +684,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
     namespace py = pybind11;
     py::register_exception<RasterizerError>(m, "RasterizerError", PyExc_RuntimeError);
+    py::register_exception<NotImplemented>(m, "NotImplementedDtype", PyExc_NotImplementedError);
     py::class_<ScratchSet, std::shared_ptr<ScratchSet>>(m, "ScratchSet")
         .def(py::init([](const py::object& device, bool persistent) {
                  return std::make_shared<ScratchSet>(torch::python::detail::py_object_to_device(device), persistent);
@@ -593,6 +756,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("init_d2"), py::call_guard<py::gil_scoped_release>());
     m.def("anchors_knn", &anchors_knn, py::arg("x"), py::arg("y"), py::arg("ptr_x"), py::arg("ptr_y"), py::arg("k"), py::arg("with_d2") = false,
           py::arg("weight_scale") = py::none(), py::call_guard<py::gil_scoped_release>());
+    m.def("motion_interp_fwd", &motion_interp_fwd, py::arg("features"), py::arg("col"), py::arg("weights"), py::call_guard<py::gil_scoped_release>());
+    m.def("motion_interp_index", &motion_interp_index, py::arg("col"), py::arg("A"), py::arg("D"), py::call_guard<py::gil_scoped_release>());
+    m.def("motion_interp_bwd", &motion_interp_bwd, py::arg("features"), py::arg("weights"), py::arg("grad_out"), py::arg("index"),
+          py::arg("want_features") = true, py::arg("want_weights") = true, py::call_guard<py::gil_scoped_release>());
+    m.def("motion_deform_fwd", &motion_deform_fwd, py::arg("xyz"), py::arg("rotation"), py::arg("mask"), py::arg("res_xyz"),
+          py::arg("res_rotation"), py::call_guard<py::gil_scoped_release>());
+    m.def("motion_deform_bwd", &motion_deform_bwd, py::arg("rotation"), py::arg("mask"), py::arg("res_xyz"), py::arg("res_rotation"),
+          py::arg("grad_xyz"), py::arg("grad_rotation"), py::arg("want_xyz") = true, py::arg("want_rotation") = true,
+          py::arg("want_res_xyz") = true, py::arg("want_res_rotation") = true, py::call_guard<py::gil_scoped_release>());
     m.def("integrate_gaussians_to_points", [](const py::args&, const py::kwargs&) -> py::object {
         // GOF tetrahedra integration (DGR/rasterize_points.cu:269-387): mesh extraction only, never reached from IGS
         PyErr_SetString(PyExc_NotImplementedError, "integrate_gaussians_to_points is outside the IGS hot path and is not implemented");

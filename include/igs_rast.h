@@ -555,6 +555,60 @@ int igs_fps(void* stream, int B, int N, int max_n, const float* xyz, const int* 
 int igs_knn_query(void* stream, int B, int Nx, int Ny, const float* x, const float* y, const int* ptr_x, const int* ptr_y, int k,
                   float weight_scale, int64_t* out_idx, float* out_d2, float* out_w);
 
+/* The two consumers of the anchor graph (motion.hip): anchor feature interpolation (the tail of
+ * GS3DRenderer.query_ir_grid, igs/models/gs.py:812-822) and the Gaussian deform (GaussianModel.deform, gs.py:347-375, with
+ * quaternion_multiply, igs/utils/general_utils.py:177-200).  Common rules of the six entry points:
+ *   - every pointer is DEVICE memory, everything is enqueued on `stream`, no host synchronisation, no device allocation;
+ *   - sizes out of range, an unknown dtype code or a NULL required pointer return IGS_RAST_E_INVALID before any HIP call; a call with
+ *     nothing to compute (N == 0, M == 0 and P == 0, ...) returns 0 and launches nothing.  igs_anchor_interp_index_bytes returns 0 for
+ *     sizes out of range;
+ *   - dtype codes: IGS_DTYPE_F32 (float) or IGS_DTYPE_F16 (IEEE half); arithmetic is float32 throughout, half inputs are widened on
+ *     load and half outputs rounded once, to nearest even.
+ *
+ * igs_anchor_interp_fwd: out[n, d] = sum over k = 0 .. K-1 of w[n, k] * F[col[n, k], d], accumulated in float32 in slot order
+ *   (fmaf).  F [A_total x D] in `dtype` (the flattened [B, A, D] anchor features; col indexes the flattened rows, so example i's
+ *   columns are offset by i * A as in IGS.forward), col [N x K] int64, w [N x K] float32, out [N x D] float32.  A slot whose col is -1
+ *   or outside [0, A_total) contributes nothing (its weight is not read).  No scratch.
+ *   0 <= N <= IGS_INTERP_MAX_ROWS, 1 <= K <= IGS_INTERP_MAX_K, 1 <= D <= IGS_INTERP_MAX_D, 1 <= A_total <= IGS_INTERP_MAX_ANCHORS,
+ *   N * K <= IGS_INTERP_MAX_EDGES.
+ * igs_anchor_interp_index: builds the inverse index of col (per anchor, its incoming edges e = n * K + k in ascending e order: a stable
+ *   radix sort by anchor, per-anchor starts and chunk offsets) into `scratch` of igs_anchor_interp_index_bytes(N, K, A_total, D) bytes;
+ *   the same scratch also holds the backward's chunk partials for that D.  Limits as for the forward.
+ * igs_anchor_interp_bwd: dF[a, d] = sum over the edges (n, k) with col[n, k] = a, in ascending (n, k) order, of w[n, k] * dout[n, d]
+ *   (lists of more than one chunk are summed per chunk, then the chunk sums in chunk order), written in `dtype` (NULL: skipped; an
+ *   anchor without edges gets 0); dw[n, k] = <dout[n, :], F[col[n, k], :]> in float32 (NULL: skipped; 0 for a -1 or out-of-range
+ *   slot).  No float atomics: bitwise reproducible.  `scratch` must hold the index igs_anchor_interp_index built for the same col,
+ *   N, K, A_total and D (the index is read, not changed: several backward calls may share it).
+ *
+ * igs_gaussian_deform_fwd: xyz [P x 3] and rot [P x 4] float32; mask [M] int64, distinct indices in [0, P) (an index outside is
+ *   skipped); dxyz [M x 3] and drot [M x 4] in `dtype`.  Row i = mask[j] of xyz_out gets xyz[i] + dxyz[j], of rot_out
+ *   qmul(nrm(rot[i]), nrm(drot[j])) with nrm(q) = q / max(|q|, 1e-12) (F.normalize) and qmul the Hamilton product in
+ *   quaternion_multiply's order; every other row is copied bit for bit (nothing is copied when xyz_out == xyz, rot_out == rot: in place).
+ *   Two launches: the pass-through copy of both tensors, then the masked rows.  0 <= M <= P <= IGS_DEFORM_MAX_POINTS.
+ * igs_gaussian_deform_bwd: the gradients of that map for the upstream g_xyz [P x 3] and g_rot [P x 4] (float32; NULL = zero):
+ *   d_xyz [P x 3] = g_xyz; d_rot [P x 4] = g_rot outside the mask and the gradient through qmul and nrm(rot[i]) on it; d_dxyz [M x 3]
+ *   = g_xyz[mask[j]] and d_drot [M x 4] through qmul and nrm(drot[j]), both in `dtype`.  Through nrm: (g - n <n, g>) / |q| where
+ *   |q| >= 1e-12, g / 1e-12 below (F.normalize's clamp: division by the constant eps).  Any output may be NULL.  Two launches: the
+ *   pass-through copy, then the masked rows.  Same limits as the forward. */
+#define IGS_DTYPE_F32 0
+#define IGS_DTYPE_F16 1
+#define IGS_INTERP_MAX_ROWS (1 << 24)
+#define IGS_INTERP_MAX_K 100
+#define IGS_INTERP_MAX_D 1024
+#define IGS_INTERP_MAX_ANCHORS (1 << 24)
+#define IGS_INTERP_MAX_EDGES (1 << 30)
+#define IGS_DEFORM_MAX_POINTS (1 << 26)
+int igs_anchor_interp_fwd(void* stream, int N, int K, int D, int A_total, int dtype, const void* F, const int64_t* col, const float* w,
+                          float* out);
+size_t igs_anchor_interp_index_bytes(int N, int K, int A_total, int D);
+int igs_anchor_interp_index(void* stream, int N, int K, int A_total, int D, const int64_t* col, void* scratch);
+int igs_anchor_interp_bwd(void* stream, int N, int K, int D, int A_total, int dtype, const void* F, const float* w, const float* dout,
+                          void* scratch, void* dF, float* dw);
+int igs_gaussian_deform_fwd(void* stream, int P, int M, int dtype, const float* xyz, const float* rot, const int64_t* mask,
+                            const void* dxyz, const void* drot, float* xyz_out, float* rot_out);
+int igs_gaussian_deform_bwd(void* stream, int P, int M, int dtype, const float* rot, const int64_t* mask, const void* drot,
+                            const float* g_xyz, const float* g_rot, float* d_xyz, float* d_rot, void* d_dxyz, void* d_drot);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).
