@@ -30,16 +30,19 @@ __device__ __forceinline__ float3 dnormvdv(float3 v, float3 dv) {   // auxiliary
     return r;
 }
 
-// SH backward (backward.cu:21-140): writes dL_dsh[M][3] (all M rows; rows beyond the active degree are zero) and
-// returns the contribution to dL_dmean through the view direction.
+// SH backward (backward.cu:21-140): returns the contribution to dL_dmean through the view direction and stages the factors of
+// dL_dsh[M][3] in `bas` (a row of M + 4 floats): bas[k] = basis value b_k for the rows of the active degree, bas[M + c] = the
+// clamp-masked dL/dcolour g_c.  dL_dsh[k][c] = b_k * g_c, +0 for rows beyond the active degree: sh_grad4 / sh_grad1 below form
+// it where it is consumed (the reference's W(k, b) product, the same single rounding).
 __device__ __forceinline__ float3 sh_backward(int deg, int M, const float* __restrict__ sh, float3 dir_orig, uint32_t clamped,
-                                              float3 dL_dcolor, float* __restrict__ dsh)
+                                              float3 dL_dcolor, float* __restrict__ bas)
 {
     const float len = sqrtf(dot3(dir_orig, dir_orig));
     const float x = dir_orig.x / len, y = dir_orig.y / len, z = dir_orig.z / len;
     const float3 g = make_float3((clamped & 1u) ? 0.f : dL_dcolor.x, (clamped & 2u) ? 0.f : dL_dcolor.y, (clamped & 4u) ? 0.f : dL_dcolor.z);
     auto L = [&](int k) { return make_float3(sh[3 * k], sh[3 * k + 1], sh[3 * k + 2]); };
-    auto W = [&](int k, float b) { dsh[3 * k] = b * g.x; dsh[3 * k + 1] = b * g.y; dsh[3 * k + 2] = b * g.z; };
+    auto W = [&](int k, float b) { bas[k] = b; };
+    bas[M] = g.x; bas[M + 1] = g.y; bas[M + 2] = g.z;
     float3 dx = make_float3(0, 0, 0), dy = make_float3(0, 0, 0), dz = make_float3(0, 0, 0);
     W(0, BSH_C0);
     if (deg > 0) {
@@ -67,11 +70,52 @@ __device__ __forceinline__ float3 sh_backward(int deg, int M, const float* __res
             }
         }
     }
-    const int used = (deg + 1) * (deg + 1);
-    for (int k = used; k < M; k++) { dsh[3 * k] = 0.f; dsh[3 * k + 1] = 0.f; dsh[3 * k + 2] = 0.f; }
     const float3 dL_ddir = make_float3(dot3(dx, g), dot3(dy, g), dot3(dz, g));
     return dnormvdv(dir_orig, dL_ddir);
 }
+
+// dL_dsh of one Gaussian from its staged row (sh_backward): elements (row kr, channel kc) onwards in span order, clamped to +-clamp
+// when clamp > 0 (clamp variant).  Rows at or beyond `used` = (deg + 1)^2 are an explicit +0 (0 * a negative g_c would be -0).
+__device__ __forceinline__ float sh_grad1(const float* bas, int M, int used, int kr, int kc, float clamp)
+{
+    float x = kr < used ? bas[kr] * bas[M + kc] : 0.f;
+    if (clamp > 0.f) x = x < -clamp ? -clamp : (x > clamp ? clamp : x);      // (a NaN stays a NaN, as through torch.clamp)
+    return x;
+}
+__device__ __forceinline__ float4 sh_grad4(const float* bas, int M, int used, int kr, int kc, float clamp)
+{
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        v[j] = sh_grad1(bas, M, used, kr, kc, clamp);
+        if (++kc == 3) { kc = 0; kr++; }
+    }
+    return make_float4(v[0], v[1], v[2], v[3]);
+}
+// Adam (common.h: adam_update) on one SH coefficient with its contractions spelled out: m = fma(b1, m, (1 - b1) g),
+// v = fma(b2, v, ((1 - b2) g) g), p -= lr m / fma(sqrt(v), inv_sqrt_bc2, eps).  That is what the compiler made of adam_update in this
+// sweep while the gradient came from LDS; once the sweep formed b_k * g_c itself the contraction heuristics picked fma(1 - b1, g, b1 m)
+// instead -- the same at step 1 (zero moments), one rounding apart from step 2 on.
+__device__ __forceinline__ void adam_update_sh(float& p, float& m, float& v, float g, float lr, float b1, float b2, float eps, float inv_sqrt_bc2)
+{
+#pragma clang fp contract(off)
+    m = __builtin_fmaf(b1, m, (1.f - b1) * g);
+    v = __builtin_fmaf(b2, v, (1.f - b2) * g * g);
+    p -= lr * m / __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps);
+}
+// Walks a workgroup's SH span [ng][M][3] by a fixed stride of elements: element e is Gaussian gl, row kr, channel kc (no division per step).
+struct ShCursor {
+    int gl, kr, kc, dg, dkr, dkc;
+    __device__ __forceinline__ ShCursor(int e0, int step, int M) {
+        const int F = 3 * M;
+        gl = e0 / F; const int k = e0 - gl * F; kr = k / 3; kc = k - 3 * kr;
+        dg = step / F; const int dk = step - dg * F; dkr = dk / 3; dkc = dk - 3 * dkr;
+    }
+    __device__ __forceinline__ void next(int M) {
+        kc += dkc; if (kc >= 3) { kc -= 3; kr++; }
+        kr += dkr; gl += dg; if (kr >= M) { kr -= M; gl++; }
+    }
+};
 
 // The SH backward's contribution to dL_dmean alone (masked refine step with the SH group frozen: xyz is still trained, so dL/dcolour
 // still reaches the mean through the view direction, but no SH gradient is formed).  Same expressions and order as sh_backward.
@@ -262,8 +306,14 @@ hipError_t launch_sh_adam_views(hipStream_t s, int P, int D, int M, int V, const
 
 struct GBArgs { GeomBwdArgs a; RefineFuse f; };
 
+// Launch bounds (waves per SIMD).  The colour-only instances (the bench's refine step) fit 128 VGPRs: 4 waves per SIMD and 5 KiB of SH
+// rows + 3 KiB of small-group rows per 64-Gaussian workgroup hold 4,096 workgroups on the chip at once, so a 200k-Gaussian grid
+// (3,125 workgroups) runs in one round.  The general instances need the plane-fit backward's registers and stay at 2.
 #ifndef GEOM_WAVES_PER_EU
 #define GEOM_WAVES_PER_EU 2
+#endif
+#ifndef GEOM_WAVES_PER_EU_COLOUR
+#define GEOM_WAVES_PER_EU_COLOUR 4
 #endif
 #ifdef GEOM_TIMELINE
 // debug build only (tools/debug/geom_timeline.py): per workgroup, the 100 MHz clock at the marks of its life
@@ -283,7 +333,7 @@ extern "C" int igs_debug_geom_timeline(unsigned long long* host, int n)
 // needs 256 VGPRs + 86 spilled at 2 waves per SIMD for a block this one never executes (4 spilled here; 73.0 -> 70.6 us).
 // PARTIAL: masked refine step with frozen groups (RefineFuse::frozen_groups); false compiles exactly the unmasked kernel.
 template <bool FUSED, int NT, bool COLOUR_ONLY, bool PARTIAL = false>
-__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(GEOM_WAVES_PER_EU)))
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(COLOUR_ONLY ? GEOM_WAVES_PER_EU_COLOUR : GEOM_WAVES_PER_EU)))
 geom_bwd_kernel(const GBArgs args)
 {
     const GeomBwdArgs& a = args.a;
@@ -299,15 +349,17 @@ geom_bwd_kernel(const GBArgs args)
             if (threadIdx.x == 0) fz.loss_out[0] = fz.loss_bias + v;
         }
     }
-    // a workgroup walks groups of NT Gaussians (grid-stride): with fewer workgroups than groups, the workgroups of a CU drift
-    // apart after their first group, so the latency-bound per-Gaussian phase of one overlaps the streaming Adam phase of another
+    // one workgroup per group of NT Gaussians.  (No grid-stride loop: the compiler hoisted the loop-invariant work out of one and kept
+    // it live across the whole body -- 236 VGPRs and 171 spilled SGPRs for the colour-only instance instead of 90 and none.)
     GTL(0);
-    const int ngroups = (a.P + NT - 1) / NT;
-    for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const int grp = blockIdx.x;
     const int idx = grp * NT + threadIdx.x;
-    // dL_dsh rows are staged in LDS ((3M+1)-float padded rows) and written out with coalesced stores at the end
-    extern __shared__ __attribute__((aligned(16))) float dsh_lds[];
-    const int F = 3 * a.M, FS = F + 1;
+    // the factors of dL_dsh are staged in LDS (sh_backward: M basis values + 3 masked colour gradients + 1 pad per Gaussian) and the
+    // sweep at the end forms the products as it walks the span with coalesced accesses
+    extern __shared__ __attribute__((aligned(16))) float sh_lds[];
+    const int F = 3 * a.M, SS = a.M + 4;
+    const int sh_used = min((a.D + 1) * (a.D + 1), a.M);
+    const float sh_clamp = FUSED ? fz.clamp : a.clamp;
     const bool active = idx < a.P;
 
     float3 o_m2d = make_float3(0, 0, 0), o_color = make_float3(0, 0, 0), o_mean = make_float3(0, 0, 0), o_scale = make_float3(0, 0, 0);
@@ -315,7 +367,7 @@ geom_bwd_kernel(const GBArgs args)
     float4 o_rot = make_float4(0, 0, 0, 0);
     // (masked refine step with the SH group frozen: no SH gradient is formed, the launch gives this kernel no LDS rows for it)
     const bool sh_frozen = PARTIAL && FUSED && (fz.frozen_groups & IGS_GROUP_SH) != 0u;
-    float* dsh = (a.M && !sh_frozen) ? dsh_lds + threadIdx.x * FS : nullptr;
+    float* dsh = (a.M && !sh_frozen) ? sh_lds + threadIdx.x * SS : nullptr;
     bool sh_written = false;
     bool found_nan = false;          // (!FUSED, a.nan_host: any NaN among the gradients the reference asserts on, __init__.py:156-162)
     __shared__ float small_lds[FUSED ? NT * 12 : 1];      // xyz 3 | rotation 4 | opacity 1 | scale 3 gradients of every thread
@@ -637,7 +689,6 @@ geom_bwd_kernel(const GBArgs args)
                 o_opacity = cl(o_opacity);
                 o_scale = make_float3(cl(o_scale.x), cl(o_scale.y), cl(o_scale.z));
                 o_rot = make_float4(cl(o_rot.x), cl(o_rot.y), cl(o_rot.z), cl(o_rot.w));
-                if (dsh && sh_written) for (int k = 0; k < F; k++) dsh[k] = cl(dsh[k]);
             }
             a.dL_dcolor[3 * idx] = o_color.x; a.dL_dcolor[3 * idx + 1] = o_color.y; a.dL_dcolor[3 * idx + 2] = o_color.z;
             a.dL_dopacity[idx] = o_opacity;
@@ -661,7 +712,6 @@ geom_bwd_kernel(const GBArgs args)
                 o_opacity = cl(o_opacity);
                 o_scale = make_float3(cl(o_scale.x), cl(o_scale.y), cl(o_scale.z));
                 o_rot = make_float4(cl(o_rot.x), cl(o_rot.y), cl(o_rot.z), cl(o_rot.w));
-                if (dsh && sh_written) for (int k = 0; k < F; k++) dsh[k] = cl(dsh[k]);
             }
             // ---- activation backward (gaussian_model.py:90-127) for this Gaussian's 11 small parameters ----
             const float g_xyz[3] = { o_mean.x, o_mean.y, o_mean.z };
@@ -693,7 +743,7 @@ geom_bwd_kernel(const GBArgs args)
             sg[3] = g_rot[0]; sg[4] = g_rot[1]; sg[5] = g_rot[2]; sg[6] = g_rot[3];
             sg[7] = g_logit; sg[8] = g_ls[0]; sg[9] = g_ls[1]; sg[10] = g_ls[2];
         }
-        if (dsh && !sh_written) for (int k = 0; k < F; k++) dsh[k] = 0.f;
+        if (dsh && !sh_written) for (int k = 0; k < a.M + 3; k++) dsh[k] = 0.f;         // (0 * 0: every product +0)
     }
     GTL(3);
     if (a.M) {
@@ -702,9 +752,10 @@ geom_bwd_kernel(const GBArgs args)
         const int ng = min(NT, a.P - g0);
         bool fast_done = false;
         if constexpr (FUSED) {
-            // ---- fast path of the in-place update (every span 16-byte aligned, no gradient output): all loads of a batch are
-            //      issued before the first result is needed.  With one load-compute-store round trip per item the kernel ran at
-            //      the latency of ~16 dependent HBM round trips per wave instead of at bandwidth.
+            // ---- fast path of the in-place update (every span 16-byte aligned, no gradient output): float4 items, the loads of two
+            //      of them in flight per thread before the first is needed.  Only LDS carries state from the per-Gaussian phase into
+            //      this sweep, and one set of item registers is live at a time: that is what fits the colour-only instances in 128
+            //      VGPRs (4 waves per SIMD), and the other waves of the SIMD cover the rest of the HBM latency.
             const size_t bx = fz.off_xyz + (size_t)g0 * 3, br = fz.off_rot + (size_t)g0 * 4, bo = fz.off_opacity + (size_t)g0,
                          bs = fz.off_scale + (size_t)g0 * 3, bh = fz.off_sh + (size_t)g0 * F;
             const uintptr_t pa = (uintptr_t)fz.param, ma = (uintptr_t)fz.exp_avg, va = (uintptr_t)fz.exp_avg_sq;
@@ -712,72 +763,60 @@ geom_bwd_kernel(const GBArgs args)
                             && ((ng & 3) == 0);
             if (al) {
                 fast_done = true;
-                auto adam4 = [&](float4& P4, float4& M4, float4& V4, float g0_, float g1_, float g2_, float g3_, float lr) {
-                    adam_update(P4.x, M4.x, V4.x, g0_, lr, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
-                    adam_update(P4.y, M4.y, V4.y, g1_, lr, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
-                    adam_update(P4.z, M4.z, V4.z, g2_, lr, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
-                    adam_update(P4.w, M4.w, V4.w, g3_, lr, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
+                constexpr int UB = 2;
+                float4 HP[UB], HM[UB], HV[UB];
+                auto load = [&](int u, size_t o) {
+                    HP[u] = ((const float4*)fz.param)[o]; HM[u] = ld_moment((const float4*)fz.exp_avg + o); HV[u] = ld_moment((const float4*)fz.exp_avg_sq + o);
                 };
-                // -- the four small groups: one float4 item per thread and group at most (NT threads, <= 4 NT floats per group)
+                auto store = [&](int u, size_t o) {
+                    st_param((float4*)fz.param + o, HP[u]); st_moment((float4*)fz.exp_avg + o, HM[u]); st_moment((float4*)fz.exp_avg_sq + o, HV[u]);
+                };
+                // -- the four small groups, two at a time: one float4 item per thread and group at most (NT threads, <= 4 NT floats per group)
                 const size_t sb[4] = { bx, br, bo, bs };
                 const int sk[4] = { 3, 4, 1, 3 }, sfirst[4] = { 0, 3, 7, 8 };
                 const float slr[4] = { fz.lr_xyz, fz.lr_rot, fz.lr_opacity, fz.lr_scale };
-                float4 SP[4], SM[4], SV[4];
                 // masked refine step: frozen groups (opacity q = 2, scale q = 3) are neither read nor written (kernel-uniform)
                 const bool qlive[4] = { true, true, !PARTIAL || (fz.frozen_groups & IGS_GROUP_OPACITY) == 0u, !PARTIAL || (fz.frozen_groups & IGS_GROUP_SCALE) == 0u };
 #pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const bool ok = qlive[q] && (int)threadIdx.x < (ng * sk[q]) / 4;
-                    const size_t o = sb[q] / 4 + threadIdx.x;
-                    if (ok) { SP[q] = ((const float4*)fz.param)[o]; SM[q] = ld_moment((const float4*)fz.exp_avg + o); SV[q] = ld_moment((const float4*)fz.exp_avg_sq + o); }
-                }
-                // -- first batch of the SH span goes out before the small groups are computed
-                const int total4 = sh_frozen ? 0 : (ng * F) >> 2;
-                constexpr int UB = 2;
-                float4 HP[UB], HM[UB], HV[UB];
-                auto sh_load = [&](int batch) {
+                for (int q0 = 0; q0 < 4; q0 += UB) {
+#pragma unroll
+                    for (int u = 0; u < UB; u++)
+                        if (qlive[q0 + u] && (int)threadIdx.x < (ng * sk[q0 + u]) / 4) load(u, sb[q0 + u] / 4 + threadIdx.x);
 #pragma unroll
                     for (int u = 0; u < UB; u++) {
-                        const int i = (int)threadIdx.x + (batch * UB + u) * NT;
-                        if (i < total4) {
-                            const size_t o = bh / 4 + i;
-                            HP[u] = ((const float4*)fz.param)[o]; HM[u] = ld_moment((const float4*)fz.exp_avg + o); HV[u] = ld_moment((const float4*)fz.exp_avg_sq + o);
+                        const int q = q0 + u;
+                        if (qlive[q] && (int)threadIdx.x < (ng * sk[q]) / 4) {
+                            float g[4];
+#pragma unroll
+                            for (int c = 0; c < 4; c++) { const int e = 4 * (int)threadIdx.x + c, gl = e / sk[q]; g[c] = small_lds[gl * 12 + sfirst[q] + (e - gl * sk[q])]; }
+                            adam_update(HP[u].x, HM[u].x, HV[u].x, g[0], slr[q], fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
+                            adam_update(HP[u].y, HM[u].y, HV[u].y, g[1], slr[q], fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
+                            adam_update(HP[u].z, HM[u].z, HV[u].z, g[2], slr[q], fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
+                            adam_update(HP[u].w, HM[u].w, HV[u].w, g[3], slr[q], fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
+                            store(u, sb[q] / 4 + threadIdx.x);
                         }
-                    }
-                };
-                int row_g = (4 * (int)threadIdx.x) / F, row_k = 4 * (int)threadIdx.x - row_g * F;
-                const int row_dg = (4 * NT) / F, row_dk = 4 * NT - row_dg * F;
-                auto sh_finish = [&](int batch) {
-#pragma unroll
-                    for (int u = 0; u < UB; u++) {
-                        const int i = (int)threadIdx.x + (batch * UB + u) * NT;
-                        if (i < total4) {
-                            const float* sp = dsh_lds + row_g * FS + row_k;       // float 4 i of the span = Gaussian row_g, coefficient row_k
-                            adam4(HP[u], HM[u], HV[u], sp[0], sp[1], sp[2], sp[3], fz.lr_sh);
-                            const size_t o = bh / 4 + i;
-                            st_param((float4*)fz.param + o, HP[u]); st_moment((float4*)fz.exp_avg + o, HM[u]); st_moment((float4*)fz.exp_avg_sq + o, HV[u]);
-                        }
-                        row_g += row_dg; row_k += row_dk;                         // (items are visited in increasing i: no division per item)
-                        if (row_k >= F) { row_k -= F; row_g++; }
-                    }
-                };
-                const int nbatch = (total4 + UB * NT - 1) / (UB * NT);
-                if (nbatch > 0) sh_load(0);
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    if (qlive[q] && (int)threadIdx.x < (ng * sk[q]) / 4) {
-                        float g[4];
-#pragma unroll
-                        for (int c = 0; c < 4; c++) { const int e = 4 * (int)threadIdx.x + c, gl = e / sk[q]; g[c] = small_lds[gl * 12 + sfirst[q] + (e - gl * sk[q])]; }
-                        adam4(SP[q], SM[q], SV[q], g[0], g[1], g[2], g[3], slr[q]);
-                        const size_t o = sb[q] / 4 + threadIdx.x;
-                        st_param((float4*)fz.param + o, SP[q]); st_moment((float4*)fz.exp_avg + o, SM[q]); st_moment((float4*)fz.exp_avg_sq + o, SV[q]);
                     }
                 }
                 GTL(4);
-                for (int b = 0; b < nbatch; b++) {
-                    sh_finish(b);
-                    if (b + 1 < nbatch) sh_load(b + 1);
+                // -- the SH span: float4 item i = Gaussian cur.gl, elements from (row cur.kr, channel cur.kc) on
+                const int total4 = sh_frozen ? 0 : (ng * F) >> 2;
+                ShCursor cur(4 * (int)threadIdx.x, 4 * NT, a.M);
+                for (int i0 = threadIdx.x; i0 < total4; i0 += UB * NT) {
+#pragma unroll
+                    for (int u = 0; u < UB; u++)
+                        if (i0 + u * NT < total4) load(u, bh / 4 + i0 + u * NT);
+#pragma unroll
+                    for (int u = 0; u < UB; u++) {
+                        if (i0 + u * NT < total4) {
+                            const float4 g = sh_grad4(sh_lds + cur.gl * SS, a.M, sh_used, cur.kr, cur.kc, sh_clamp);
+                            adam_update_sh(HP[u].x, HM[u].x, HV[u].x, g.x, fz.lr_sh, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
+                            adam_update_sh(HP[u].y, HM[u].y, HV[u].y, g.y, fz.lr_sh, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
+                            adam_update_sh(HP[u].z, HM[u].z, HV[u].z, g.z, fz.lr_sh, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
+                            adam_update_sh(HP[u].w, HM[u].w, HV[u].w, g.w, fz.lr_sh, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
+                            store(u, bh / 4 + i0 + u * NT);
+                        }
+                        cur.next(a.M);
+                    }
                 }
             }
         }
@@ -830,45 +869,38 @@ geom_bwd_kernel(const GBArgs args)
                                        && (!fz.grad_out || (((uintptr_t)(fz.grad_out + fz.off_sh + (size_t)g0 * F)) & 15) == 0);
         if (aligned) {
             const int total4 = total >> 2;
-            int f = (int)threadIdx.x * 4;
-            int g = f / F, k = f - g * F;
-            const int dg = (4 * NT) / F, dk = (4 * NT) - dg * F;
-            for (int i = threadIdx.x; i < total4; i += NT) {
-                const float* sp = dsh_lds + g * FS + k;
+            ShCursor cur(4 * (int)threadIdx.x, 4 * NT, a.M);
+            for (int i = threadIdx.x; i < total4; i += NT, cur.next(a.M)) {
+                const float4 sp = sh_grad4(sh_lds + cur.gl * SS, a.M, sh_used, cur.kr, cur.kc, sh_clamp);
                 if (FUSED && fz.grad_out) {
-                    ((float4*)(fz.grad_out + fz.off_sh + (size_t)g0 * F))[i] = make_float4(sp[0], sp[1], sp[2], sp[3]);
+                    ((float4*)(fz.grad_out + fz.off_sh + (size_t)g0 * F))[i] = sp;
                 } else if constexpr (FUSED) {
                     // Adam on the SH coefficients of the workgroup's NT Gaussians: one contiguous, coalesced span of each buffer
                     float4 P4 = ((float4*)dst)[i], M4 = ((float4*)dst_m)[i], V4 = ((float4*)dst_v)[i];
-                    adam_update(P4.x, M4.x, V4.x, sp[0], fz.lr_sh, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
-                    adam_update(P4.y, M4.y, V4.y, sp[1], fz.lr_sh, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
-                    adam_update(P4.z, M4.z, V4.z, sp[2], fz.lr_sh, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
-                    adam_update(P4.w, M4.w, V4.w, sp[3], fz.lr_sh, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
+                    adam_update_sh(P4.x, M4.x, V4.x, sp.x, fz.lr_sh, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
+                    adam_update_sh(P4.y, M4.y, V4.y, sp.y, fz.lr_sh, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
+                    adam_update_sh(P4.z, M4.z, V4.z, sp.z, fz.lr_sh, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
+                    adam_update_sh(P4.w, M4.w, V4.w, sp.w, fz.lr_sh, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
                     ((float4*)dst)[i] = P4; ((float4*)dst_m)[i] = M4; ((float4*)dst_v)[i] = V4;
                 } else {
-                    ((float4*)dst)[i] = make_float4(sp[0], sp[1], sp[2], sp[3]);
-                    if (a.nan_host) found_nan |= (sp[0] != sp[0]) | (sp[1] != sp[1]) | (sp[2] != sp[2]) | (sp[3] != sp[3]);
+                    ((float4*)dst)[i] = sp;
+                    if (a.nan_host) found_nan |= (sp.x != sp.x) | (sp.y != sp.y) | (sp.z != sp.z) | (sp.w != sp.w);
                 }
-                g += dg; k += dk;
-                if (k >= F) { k -= F; g++; }
             }
         } else {
-            int f = (int)threadIdx.x;
-            int g = f / F, k = f - g * F;
-            const int dg = NT / F, dk = NT - dg * F;
-            for (int i = threadIdx.x; i < total; i += NT) {
+            ShCursor cur((int)threadIdx.x, NT, a.M);
+            for (int i = threadIdx.x; i < total; i += NT, cur.next(a.M)) {
+                const float gv = sh_grad1(sh_lds + cur.gl * SS, a.M, sh_used, cur.kr, cur.kc, sh_clamp);
                 if (FUSED && fz.grad_out) {
-                    fz.grad_out[fz.off_sh + (size_t)g0 * F + i] = dsh_lds[g * FS + k];
+                    fz.grad_out[fz.off_sh + (size_t)g0 * F + i] = gv;
                 } else if constexpr (FUSED) {
                     float p = dst[i], m = dst_m[i], v = dst_v[i];
-                    adam_update(p, m, v, dsh_lds[g * FS + k], fz.lr_sh, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
+                    adam_update_sh(p, m, v, gv, fz.lr_sh, fz.b1, fz.b2, fz.eps, fz.inv_sqrt_bc2);
                     dst[i] = p; dst_m[i] = m; dst_v[i] = v;
                 } else {
-                    dst[i] = dsh_lds[g * FS + k];
-                    if (a.nan_host) found_nan |= dst[i] != dst[i];
+                    dst[i] = gv;
+                    if (a.nan_host) found_nan |= gv != gv;
                 }
-                g += dg; k += dk;
-                if (k >= F) { k -= F; g++; }
             }
         }
         }      // !skip_sh
@@ -882,25 +914,23 @@ geom_bwd_kernel(const GBArgs args)
         // this GPU, and the kernel has just stored 70 MB through that L2 (refine_ops.hip: l1_mean_kernel).
         if (a.nan_host && found_nan) __atomic_store_n(a.nan_host, a.nan_seq, __ATOMIC_RELAXED);
     }
-    if (grp + (int)gridDim.x < ngroups) __syncthreads();          // the LDS rows are reused by the next group
-    }
 }
 
 hipError_t launch_geom_bwd(hipStream_t s, const GeomBwdArgs& a)
 {
     GBArgs g; g.a = a; g.f = RefineFuse();
-    const size_t lds = a.M ? (size_t)256 * (3 * a.M + 1) * sizeof(float) : 0;
+    const size_t lds = a.M ? (size_t)256 * (a.M + 4) * sizeof(float) : 0;
     hipLaunchKernelGGL((geom_bwd_kernel<false, 256, false>), dim3((a.P + 255) / 256), dim3(256), lds, s, g);
     return hipGetLastError();
 }
 // The fused kernel alternates a latency-bound phase (per-Gaussian math) with a bandwidth-bound one (Adam over the SH span):
-// small workgroups put more of them on a CU (LDS: 49 floats per thread), so the two phases of different workgroups overlap.
+// small workgroups put more of them on a CU, so the two phases of different workgroups overlap.  Per 64-Gaussian workgroup (M = 16):
+// 5 KiB of SH rows + 3 KiB of small-group rows = 20 workgroups per CU by LDS (160 KiB), 16 by the colour-only instances' 4 waves per SIMD.
 #ifndef GEOM_ADAM_THREADS
 #define GEOM_ADAM_THREADS 64
 #endif
-#ifndef GEOM_ADAM_BLOCKS
-#define GEOM_ADAM_BLOCKS (1 << 30)     // (capping the grid was measured: at 12 waves per CU by LDS every group is resident at once anyway, fewer workgroups only lose occupancy)
-#endif
+// dynamic LDS of the fused launch: the staged SH rows (sh_backward), M + 4 floats per Gaussian (tests/test_geom_bwd_resources.py reads it)
+extern "C" size_t igs_geom_bwd_adam_dyn_lds(int M) { return (size_t)GEOM_ADAM_THREADS * (M + 4) * sizeof(float); }
 hipError_t launch_geom_bwd_adam(hipStream_t s, const GeomBwdArgs& a, const RefineFuse& f)
 {
     GBArgs g; g.a = a; g.f = f;
@@ -918,11 +948,9 @@ hipError_t launch_geom_bwd_adam(hipStream_t s, const GeomBwdArgs& a, const Refin
         g.f.off_xyz += 3 * F0; g.f.off_rot += 4 * F0; g.f.off_sh += F0 * 3 * a.M; g.f.off_opacity += F0; g.f.off_scale += 3 * F0;
     }
     constexpr int NT = GEOM_ADAM_THREADS;
-    const size_t lds = (a.M && !(f.frozen_groups & IGS_GROUP_SH)) ? (size_t)NT * (3 * a.M + 1) * sizeof(float) : 0;
+    const size_t lds = (a.M && !(f.frozen_groups & IGS_GROUP_SH)) ? igs_geom_bwd_adam_dyn_lds(a.M) : 0;
     int blocks = (g.a.P + NT - 1) / NT;
     if (blocks < 1) blocks = 1;          // (everything frozen: workgroup 0 still posts the loss value)
-    const int cap = GEOM_ADAM_BLOCKS;
-    if (blocks > cap) blocks = cap;
     if (f.frozen_groups) {          // (masked refine step with frozen groups: the instances that test the group bits)
         if (a.gacc_compact) hipLaunchKernelGGL((geom_bwd_kernel<true, NT, true, true>), dim3(blocks), dim3(NT), lds, s, g);
         else                hipLaunchKernelGGL((geom_bwd_kernel<true, NT, false, true>), dim3(blocks), dim3(NT), lds, s, g);
