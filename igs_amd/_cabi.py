@@ -52,7 +52,8 @@ EXPORTS = ["igs_rast_version", "igs_rast_last_error", "igs_rast_forward", "igs_r
            "igs_refine_step_masked", "igs_refine_mask_args_size", "igs_rast_count_gaussians",
            "igs_knn_scratch_bytes", "igs_knn_mean_dist2", "igs_bbox_select_scratch_bytes", "igs_bbox_select", "igs_fps_scratch_bytes",
            "igs_fps", "igs_knn_query", "igs_anchor_interp_fwd", "igs_anchor_interp_index_bytes", "igs_anchor_interp_index",
-           "igs_anchor_interp_bwd", "igs_gaussian_deform_fwd", "igs_gaussian_deform_bwd"]
+           "igs_anchor_interp_bwd", "igs_gaussian_deform_fwd", "igs_gaussian_deform_bwd",
+           "igs_anchor_lift_scratch_bytes", "igs_anchor_lift_bwd_scratch_bytes", "igs_anchor_lift_fwd", "igs_anchor_lift_bwd"]
 
 VERSION = 4       # IGS_RAST_VERSION this binding was written against (include/igs_rast.h)
 
@@ -198,6 +199,15 @@ def lib():
         L.igs_gaussian_deform_fwd.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
         L.igs_gaussian_deform_bwd.restype = _i
         L.igs_gaussian_deform_bwd.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        _ll = C.c_longlong
+        L.igs_anchor_lift_scratch_bytes.restype = C.c_size_t
+        L.igs_anchor_lift_scratch_bytes.argtypes = [_i] * 7
+        L.igs_anchor_lift_bwd_scratch_bytes.restype = C.c_size_t
+        L.igs_anchor_lift_bwd_scratch_bytes.argtypes = [_i] * 7
+        L.igs_anchor_lift_fwd.restype = _i
+        L.igs_anchor_lift_fwd.argtypes = [_vp] + [_i] * 7 + [_vp] + [_ll] * 4 + [_vp] * 4 + [_ll] * 2 + [_vp]
+        L.igs_anchor_lift_bwd.restype = _i
+        L.igs_anchor_lift_bwd.argtypes = [_vp] + [_i] * 7 + [_vp] * 4 + [_ll] * 2 + [_vp] + [_ll] * 4 + [_vp]
         L.igs_depth_normal_loss_fwd_bwd.restype = _i
         L.igs_depth_normal_loss_fwd_bwd.argtypes = [_vp, _i, _i, _f, _f, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp]
         L.igs_l1_loss_fwd_bwd.restype = _i

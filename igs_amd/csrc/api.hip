@@ -1163,6 +1163,88 @@ extern "C" int igs_gaussian_deform_bwd(void* stream, int P, int M, int dtype, co
     return 0;
 }
 
+// multi-view anchor feature lifting (lift.hip; the contract is in include/igs_rast.h)
+static const char* lift_size_error(int B, int V, int A, int C, int H, int W)
+{
+    if (B < 0 || B > IGS_LIFT_MAX_SAMPLES) return "B out of range";
+    if (V < 1 || V > IGS_LIFT_MAX_V) return "V out of range (1..IGS_LIFT_MAX_V)";
+    if (A < 0 || A > IGS_LIFT_MAX_SAMPLES) return "A out of range";
+    if (C < 1 || C > IGS_LIFT_MAX_C) return "C out of range (1..IGS_LIFT_MAX_C)";
+    if (H < 1 || H > IGS_LIFT_MAX_HW) return "H out of range (1..IGS_LIFT_MAX_HW)";
+    if (W < 1 || W > IGS_LIFT_MAX_HW) return "W out of range (1..IGS_LIFT_MAX_HW)";
+    if ((long long)B * A > IGS_LIFT_MAX_SAMPLES) return "B * A out of range (IGS_LIFT_MAX_SAMPLES)";
+    if ((long long)B * V * H * W > IGS_LIFT_MAX_PIXELS) return "B * V * H * W out of range (IGS_LIFT_MAX_PIXELS)";
+    return nullptr;
+}
+static int lift_fail(const char* fn, const char* what)
+{
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: %s", fn, what);
+    return fail(IGS_RAST_E_INVALID, msg);
+}
+// the feature layouts read in place: every H x W plane contiguous (NCHW and any slicing of n or c); channels-last has no kernels here
+static const char* lift_stride_error(int C, int H, int W, long long fs_n, long long fs_c, long long fs_h, long long fs_w)
+{
+    if (fs_n < 0 || fs_c < 0) return "negative feature stride";
+    if ((W > 1 && fs_w != 1) || (H > 1 && fs_h != W)) {
+        if (fs_c == 1 && C > 1) return "channels-last features (fs_c == 1) are not read in place: pass plane-contiguous NCHW";
+        return "feature strides not supported: every H x W plane must be contiguous (fs_w == 1, fs_h == W)";
+    }
+    return nullptr;
+}
+extern "C" size_t igs_anchor_lift_scratch_bytes(int B, int V, int A, int C, int H, int W, int dtype)
+{
+    if (lift_size_error(B, V, A, C, H, W) || !dtype_ok(dtype)) return 0;
+    return lift_scratch_bytes(B, V, A, H, W, false) + 256;
+}
+extern "C" size_t igs_anchor_lift_bwd_scratch_bytes(int B, int V, int A, int C, int H, int W, int dtype)
+{
+    if (lift_size_error(B, V, A, C, H, W) || !dtype_ok(dtype)) return 0;
+    return lift_scratch_bytes(B, V, A, H, W, true) + 256;
+}
+extern "C" int igs_anchor_lift_fwd(void* stream, int B, int V, int A, int C, int H, int W, int dtype, const void* feat, long long fs_n,
+                                   long long fs_c, long long fs_h, long long fs_w, const float* points, const float* w2c, const float* intr,
+                                   float* out, long long os_a, long long os_c, void* scratch)
+{
+    const char* fn = "igs_anchor_lift_fwd";
+    if (const char* w = lift_size_error(B, V, A, C, H, W)) return lift_fail(fn, w);
+    if (!dtype_ok(dtype)) return lift_fail(fn, "unknown dtype code");
+    if (const char* w = lift_stride_error(C, H, W, fs_n, fs_c, fs_h, fs_w)) return lift_fail(fn, w);
+    if (!((os_a == 1 && os_c == A) || (os_c == 1 && os_a == C))) return lift_fail(fn, "output strides must be (os_a, os_c) = (1, A) or (C, 1)");
+    if (A == 0 || B == 0) return 0;
+    if (!feat || !points || !w2c || !intr || !out || !scratch) return lift_fail(fn, "NULL pointer");
+    HIP_TRY(launch_lift_fwd((hipStream_t)stream, B, V, A, C, H, W, dtype, feat, (size_t)fs_n, (size_t)fs_c, points, w2c, intr, out, (size_t)os_a,
+                            (size_t)os_c, scratch), "anchor lift fwd launch");
+    return 0;
+}
+extern "C" int igs_anchor_lift_bwd(void* stream, int B, int V, int A, int C, int H, int W, int dtype, const float* points, const float* w2c,
+                                   const float* intr, const float* dout, long long gs_a, long long gs_c, void* dfeat, long long fs_n,
+                                   long long fs_c, long long fs_h, long long fs_w, void* scratch)
+{
+    const char* fn = "igs_anchor_lift_bwd";
+    if (const char* w = lift_size_error(B, V, A, C, H, W)) return lift_fail(fn, w);
+    if (!dtype_ok(dtype)) return lift_fail(fn, "unknown dtype code");
+    if (const char* w = lift_stride_error(C, H, W, fs_n, fs_c, fs_h, fs_w)) return lift_fail(fn, w);
+    if (fs_c < (long long)H * W || fs_n < fs_c * C) return lift_fail(fn, "d feat planes overlap (fs_c >= H * W and fs_n >= C * fs_c required)");
+    if (!((gs_a == 1 && gs_c == A) || (gs_c == 1 && gs_a == C))) return lift_fail(fn, "d out strides must be (gs_a, gs_c) = (1, A) or (C, 1)");
+    if (B == 0) return 0;
+    if (!dfeat) return lift_fail(fn, "NULL pointer");
+    if (A == 0) {       // no samples: every element of d feat is zero (one fill per plane-contiguous tensor, else per image)
+        const size_t es = dtype == IGS_DTYPE_F16 ? 2 : 4;
+        if (fs_c == (long long)H * W && fs_n == fs_c * C)
+            HIP_TRY(zero_fill_async((hipStream_t)stream, dfeat, (size_t)B * V * C * H * W * es), "zero d feat");
+        else
+            for (long long n = 0; n < (long long)B * V; n++)
+                for (int c = 0; c < C; c++)
+                    HIP_TRY(zero_fill_async((hipStream_t)stream, (char*)dfeat + ((size_t)n * fs_n + (size_t)c * fs_c) * es, (size_t)H * W * es), "zero d feat");
+        return 0;
+    }
+    if (!points || !w2c || !intr || !dout || !scratch) return lift_fail(fn, "NULL pointer");
+    HIP_TRY(launch_lift_bwd((hipStream_t)stream, B, V, A, C, H, W, dtype, points, w2c, intr, dout, (size_t)gs_a, (size_t)gs_c, dfeat, (size_t)fs_n,
+                            (size_t)fs_c, scratch), "anchor lift bwd launch");
+    return 0;
+}
+
 // Test support: the per-tile sort of the slab binning on caller-made slabs (sort.hip: launch_tile_sort).  tile_count[T] instances per
 // tile (reset to zero by the launch), pairs[T * slab] = depth bits << 32 | Gaussian id, out: point_list[T * slab] (ids, sorted by the
 // 64-bit key inside every tile's slab), ranges[2 T], stats[4] ([1] = largest tile that overflowed its slab).  Everything device memory.

@@ -163,6 +163,12 @@ size_t interp_scratch_bytes(int N, int K, int A, int D);
 hipError_t launch_interp_index(hipStream_t s, int N, int K, int A, int D, const int64_t* col, void* scratch);
 hipError_t launch_interp_bwd(hipStream_t s, int N, int K, int D, int A, int dtype, const void* F, const float* w, const float* dout,
                              void* scratch, void* dF, float* dw);
+size_t lift_scratch_bytes(int B, int V, int A, int H, int W, bool backward);                             // lift.hip
+hipError_t launch_lift_fwd(hipStream_t s, int B, int V, int A, int C, int H, int W, int dtype, const void* feat, size_t fs_n, size_t fs_c,
+                           const float* points, const float* w2c, const float* intr, float* out, size_t os_a, size_t os_c, void* scratch);
+hipError_t launch_lift_bwd(hipStream_t s, int B, int V, int A, int C, int H, int W, int dtype, const float* points, const float* w2c,
+                           const float* intr, const float* dout, size_t gs_a, size_t gs_c, void* dfeat, size_t fs_n, size_t fs_c,
+                           void* scratch);
 hipError_t launch_deform_fwd(hipStream_t s, int P, int M, int dtype, const float* xyz, const float* rot, const int64_t* mask,
                              const void* dxyz, const void* drot, float* xyz_out, float* rot_out);
 hipError_t launch_deform_bwd(hipStream_t s, int P, int M, int dtype, const float* rot, const int64_t* mask, const void* drot,

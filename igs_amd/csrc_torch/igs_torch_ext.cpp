@@ -492,6 +492,78 @@ std::tuple<OptTensor, OptTensor> motion_interp_bwd(const Tensor& F, const Tensor
     return {dF, dw};
 }
 
+// ---- multi-view anchor feature lifting (lift.hip) ----
+struct LiftSizes { int64_t B, V, A, C, H, W; };
+static LiftSizes lift_check(const char* fn, const Tensor& points, const Tensor& w2c, const Tensor& intr, int64_t C, int64_t H, int64_t W, int dt)
+{
+    motion_expect(points, fn, "anchor_points", at::kFloat, {-1, -1, 3});
+    motion_expect(w2c, fn, "w2c", at::kFloat, {-1, 4, 4});
+    motion_expect(intr, fn, "intrinsics", at::kFloat, {w2c.size(0), 4});
+    const int64_t B = points.size(0), A = points.size(1), BV = w2c.size(0);
+    if (B < 1 || BV % B != 0 || BV / B < 1)
+        throw RasterizerError(std::string(fn) + ": " + std::to_string(BV) + " views do not divide into " + std::to_string(B) + " examples");
+    const int64_t V = BV / B;
+    if (B > INT_MAX || A > INT_MAX || C > INT_MAX || H > INT_MAX || W > INT_MAX || V > INT_MAX ||
+        igs_anchor_lift_scratch_bytes((int)B, (int)V, (int)A, (int)C, (int)H, (int)W, dt) == 0)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (C <= 1024, V <= 16, H, W <= 2048, B * V * H * W <= 2^24, B * A <= 2^24)");
+    return {B, V, A, C, H, W};
+}
+
+// out [B, C, A] float32 (the caller views it as [B, A, C]): feat [B*V, C, H, W] float32 / float16 with contiguous H x W planes,
+// points [B, A, 3], w2c [B*V, 4, 4], intr [B*V, 4] = fx, fy, cx, cy (float32)
+Tensor motion_lift_fwd(const Tensor& feat, const Tensor& points, const Tensor& w2c, const Tensor& intr)
+{
+    const char* fn = "motion_lift_fwd";
+    const int dt = motion_dtype(feat, fn, "motion_feature");
+    if (feat.dim() != 4) throw RasterizerError(std::string(fn) + ": motion_feature must have shape [B*V, C, H, W] (got " + c10::str(feat.sizes()) + ")");
+    if (feat.size(0) != w2c.size(0))
+        throw RasterizerError(std::string(fn) + ": motion_feature has shape " + c10::str(feat.sizes()) + " for " + std::to_string(w2c.size(0)) + " views");
+    const LiftSizes z = lift_check(fn, points, w2c, intr, feat.size(1), feat.size(2), feat.size(3), dt);
+    require_gpu(feat, fn, "motion_feature");
+    same_device(points, feat, fn, "anchor_points");
+    same_device(w2c, feat, fn, "w2c");
+    same_device(intr, feat, fn, "intrinsics");
+    const c10::Device dev = feat.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    Tensor out = at::empty({z.B, z.C, z.A}, feat.options().dtype(at::kFloat));
+    if (z.A == 0) return out;
+    Tensor scratch = at::empty({(int64_t)igs_anchor_lift_scratch_bytes((int)z.B, (int)z.V, (int)z.A, (int)z.C, (int)z.H, (int)z.W, dt)},
+                               feat.options().dtype(at::kByte));
+    const Tensor pc = points.contiguous(), wc = w2c.contiguous(), ic = intr.contiguous();
+    check(igs_anchor_lift_fwd(cur_stream(dev), (int)z.B, (int)z.V, (int)z.A, (int)z.C, (int)z.H, (int)z.W, dt, feat.data_ptr(), feat.stride(0),
+                              feat.stride(1), feat.stride(2), feat.stride(3), pc.data_ptr<float>(), wc.data_ptr<float>(), ic.data_ptr<float>(),
+                              out.data_ptr<float>(), 1, z.A, scratch.data_ptr()), "igs_anchor_lift_fwd");
+    return out;
+}
+
+// d motion_feature [B*V, C, H, W] contiguous, float16 when `half`, from grad_bca = d out viewed [B, C, A] (any strides; read in place when
+// it is [B, C, A]- or [B, A, C]-contiguous).  Every element is written.
+Tensor motion_lift_bwd(const Tensor& grad_bca, const Tensor& points, const Tensor& w2c, const Tensor& intr, int64_t H, int64_t W, bool half)
+{
+    const char* fn = "motion_lift_bwd";
+    const int dt = half ? IGS_DTYPE_F16 : IGS_DTYPE_F32;
+    motion_expect(grad_bca, fn, "grad_out", at::kFloat, {-1, -1, -1});
+    const LiftSizes z = lift_check(fn, points, w2c, intr, grad_bca.size(1), H, W, dt);
+    if (grad_bca.size(0) != z.B || grad_bca.size(2) != z.A)
+        throw RasterizerError(std::string(fn) + ": grad_out has shape " + c10::str(grad_bca.sizes()) + ", expected [B, C, A]");
+    require_gpu(grad_bca, fn, "grad_out");
+    same_device(points, grad_bca, fn, "anchor_points");
+    same_device(w2c, grad_bca, fn, "w2c");
+    same_device(intr, grad_bca, fn, "intrinsics");
+    const c10::Device dev = grad_bca.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    Tensor dfeat = at::empty({z.B * z.V, z.C, z.H, z.W}, grad_bca.options().dtype(half ? at::kHalf : at::kFloat));
+    const bool bac = grad_bca.stride(0) == z.A * z.C && grad_bca.stride(1) == 1 && grad_bca.stride(2) == z.C;      // [B, A, C]-contiguous
+    const Tensor g = (bac || z.A == 0) ? grad_bca : grad_bca.contiguous();
+    const size_t bytes = igs_anchor_lift_bwd_scratch_bytes((int)z.B, (int)z.V, (int)z.A, (int)z.C, (int)z.H, (int)z.W, dt);
+    Tensor scratch = at::empty({z.A == 0 ? 0 : (int64_t)bytes}, grad_bca.options().dtype(at::kByte));
+    const Tensor pc = points.contiguous(), wc = w2c.contiguous(), ic = intr.contiguous();
+    check(igs_anchor_lift_bwd(cur_stream(dev), (int)z.B, (int)z.V, (int)z.A, (int)z.C, (int)z.H, (int)z.W, dt, pc.data_ptr<float>(),
+                              wc.data_ptr<float>(), ic.data_ptr<float>(), g.data_ptr<float>(), bac ? z.C : 1, bac ? 1 : z.A, dfeat.data_ptr(),
+                              z.C * z.H * z.W, z.H * z.W, z.W, 1, scratch.data_ptr()), "igs_anchor_lift_bwd");
+    return dfeat;
+}
+
 static void deform_checks(const char* fn, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot, int* dt)
 {
     motion_expect(rot, fn, "rotation", at::kFloat, {-1, 4});
@@ -760,6 +832,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("motion_interp_index", &motion_interp_index, py::arg("col"), py::arg("A"), py::arg("D"), py::call_guard<py::gil_scoped_release>());
     m.def("motion_interp_bwd", &motion_interp_bwd, py::arg("features"), py::arg("weights"), py::arg("grad_out"), py::arg("index"),
           py::arg("want_features") = true, py::arg("want_weights") = true, py::call_guard<py::gil_scoped_release>());
+    m.def("motion_lift_fwd", &motion_lift_fwd, py::arg("motion_feature"), py::arg("anchor_points"), py::arg("w2c"), py::arg("intrinsics"),
+          py::call_guard<py::gil_scoped_release>());
+    m.def("motion_lift_bwd", &motion_lift_bwd, py::arg("grad_out"), py::arg("anchor_points"), py::arg("w2c"), py::arg("intrinsics"), py::arg("H"),
+          py::arg("W"), py::arg("half") = false, py::call_guard<py::gil_scoped_release>());
     m.def("motion_deform_fwd", &motion_deform_fwd, py::arg("xyz"), py::arg("rotation"), py::arg("mask"), py::arg("res_xyz"),
           py::arg("res_rotation"), py::call_guard<py::gil_scoped_release>());
     m.def("motion_deform_bwd", &motion_deform_bwd, py::arg("rotation"), py::arg("mask"), py::arg("res_xyz"), py::arg("res_rotation"),

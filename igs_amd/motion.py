@@ -4,7 +4,11 @@ Per streamed frame and per training step, igs/models/gs.py runs: GS3DRenderer.qu
 the features of every in-box Gaussian's K nearest anchors, then the decoder MLP, then GaussianModel.deform (gs.py:347-375), which moves
 the masked Gaussians by the decoded residuals.  `query_ir_grid` and `deform` here are those two steps, with autograd.
 
+`grid_encoder_lift` / `lift_anchor_features` are the step in front of them: GridEncoder.forward's lift of the 2-D motion features onto the
+anchors (igs/models/grid_encoder.py:66-88 over igs/utils/ops.py:444-477; igs_amd/csrc/lift.hip), with autograd to the features.
+
 Deviations from the reference lines (INTEGRATION.md lists them):
+  - a lifted sample whose pixel coordinate is not finite adds zero; channels-last features are copied to NCHW first;
   - a neighbour slot whose column is -1 (knn_native's padding) or out of range contributes nothing (the reference would index with it);
   - the interpolation backward is deterministic (an inverse index instead of index_put_'s atomics);
   - float16 residuals are widened to float32 before normalisation (the reference normalises them in float16).
@@ -79,6 +83,109 @@ def query_ir_grid(anchor_feats, weights, neighbor, counts=None):
         _, c = torch.unique(batch_y, return_counts=True)
         counts = c.tolist()
     return torch.split(out, [int(c) for c in counts])
+
+
+class _Lift(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, points, w2c, intr):
+        out = _ext().motion_lift_fwd(feat, points, w2c, intr)                # [B, C, A]
+        ctx.save_for_backward(points, w2c, intr)                             # the backward needs no features
+        ctx.hw, ctx.half = feat.shape[-2:], feat.dtype == torch.float16
+        return out.permute(0, 2, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        points, w2c, intr = ctx.saved_tensors
+        d = _ext().motion_lift_bwd(g.float().permute(0, 2, 1), points, w2c, intr, ctx.hw[0], ctx.hw[1], ctx.half)
+        return d, None, None, None
+
+
+def _lift(motion_feature, anchor_points, w2c, intr, fn):
+    for t, name in ((anchor_points, "anchor_points"), (w2c, "c2ws"), (intr, "intrinsics")):
+        if t.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError(f"{fn}: gradients to {name} are not provided (only to motion_feature)")
+    f = motion_feature
+    if not (f.dim() == 4 and (f.shape[3] == 1 or f.stride(3) == 1) and (f.shape[2] == 1 or f.stride(2) == f.shape[3])):
+        f = f.contiguous()                   # channels-last and other strided patterns: made plane-contiguous NCHW first
+    if torch.is_grad_enabled() and f.requires_grad:
+        return _Lift.apply(f, anchor_points, w2c, intr)
+    return _ext().motion_lift_fwd(f, anchor_points, w2c, intr).permute(0, 2, 1)      # under no_grad nothing is saved
+
+
+def _lift_shapes(motion_feature, anchor_points, c2ws, fn):
+    if motion_feature.dim() != 4:
+        raise ValueError(f"{fn}: motion_feature must be [B*V, C, H, W] (got {list(motion_feature.shape)})")
+    if anchor_points.dim() != 3 or anchor_points.shape[-1] != 3:
+        raise ValueError(f"{fn}: anchor_points must be [B, A, 3] (got {list(anchor_points.shape)})")
+    if c2ws.dim() == 4:
+        if c2ws.shape[0] != anchor_points.shape[0]:
+            raise ValueError(f"{fn}: c2ws {list(c2ws.shape)} does not match {anchor_points.shape[0]} examples")
+        c2ws = c2ws.reshape(-1, *c2ws.shape[2:])
+    B, BV = anchor_points.shape[0], motion_feature.shape[0]
+    if c2ws.dim() != 3 or tuple(c2ws.shape[1:]) != (4, 4) or c2ws.shape[0] != BV or B < 1 or BV % B:
+        raise ValueError(f"{fn}: c2ws must be [B*V, 4, 4] or [B, V, 4, 4] with B*V = {BV} views for {B} examples (got {list(c2ws.shape)})")
+    if motion_feature.dtype not in FEATURE_DTYPES:
+        raise NotImplementedError(f"{fn}: motion_feature must be float32 or float16 (got {motion_feature.dtype})")
+    if anchor_points.dtype != torch.float32 or c2ws.dtype != torch.float32:
+        raise NotImplementedError(f"{fn}: anchor_points and c2ws must be float32 (got {anchor_points.dtype}, {c2ws.dtype})")
+    if not (motion_feature.is_cuda and anchor_points.is_cuda and c2ws.is_cuda):
+        raise RuntimeError(f"{fn}: tensors must be on a GPU (no CPU fallback)")
+    return c2ws
+
+
+def lift_anchor_features(motion_feature, anchor_points, c2ws, intrinsics):
+    """perspective_projection (igs/utils/ops.py:444-477) for all views plus the mean over the views (grid_encoder.py:84-88): [B, A, C]
+    float32, a permuted view of a [B, C, A] buffer (what GridEncoder's conv reads after its own permute).
+
+    motion_feature [B*V, C, H, W] float32 / float16, any strides (plane-contiguous NCHW, slices of n and c included, is read in place;
+    channels-last and everything else is copied to NCHW first); anchor_points [B, A, 3]; c2ws [B*V, 4, 4] or [B, V, 4, 4], inverted with
+    torch.linalg.inv as the reference does; intrinsics [B*V, 3, 3] of the form [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] (checked with one
+    host read; anything else raises NotImplementedError) or [B*V, 4] = fx, fy, cx, cy (no read).  Gradients reach motion_feature only,
+    in its dtype, summed in a fixed order (bitwise reproducible); the backward keeps the points and cameras, not the features."""
+    fn = "lift_anchor_features"
+    c2ws = _lift_shapes(motion_feature, anchor_points, c2ws, fn)
+    BV = c2ws.shape[0]
+    if intrinsics.dim() == 3 and tuple(intrinsics.shape) == (BV, 3, 3):
+        K = intrinsics.detach().float().cpu()
+        form = torch.zeros(3, 3, dtype=torch.bool)
+        form[0, 1] = form[1, 0] = form[2, 0] = form[2, 1] = True
+        if not ((K[:, form] == 0).all() and (K[:, 2, 2] == 1).all()):
+            raise NotImplementedError(f"{fn}: intrinsics must be [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]")
+        intr = torch.stack([intrinsics[:, 0, 0], intrinsics[:, 1, 1], intrinsics[:, 0, 2], intrinsics[:, 1, 2]], 1)
+    elif intrinsics.dim() == 2 and tuple(intrinsics.shape) == (BV, 4):
+        intr = intrinsics
+    else:
+        raise ValueError(f"{fn}: intrinsics must be [B*V, 3, 3] or [B*V, 4] with B*V = {BV} (got {list(intrinsics.shape)})")
+    if intr.dtype != torch.float32:
+        raise NotImplementedError(f"{fn}: intrinsics must be float32 (got {intr.dtype})")
+    return _lift(motion_feature, anchor_points, torch.linalg.inv(c2ws), intr.to(c2ws.device), fn)
+
+
+def grid_encoder_lift(motion_feature, anchor_points, FOV, c2w_input, fov=None):
+    """GridEncoder.forward's perspective_projection branch (grid_encoder.py:66-88): motion_grids [B, A, C] float32.
+
+    Reproduces the reference's intrinsics as written: `W, H = motion_feature.shape[-2:]` (the names are swapped), fx =
+    fov2focal(FOV[0, 0], shape[-2]), cx = shape[-2] / 2, fy = fov2focal(FOV[0, 1], shape[-1]), cy = shape[-1] / 2, and FOV[0] serves
+    every example and view; the sampling itself normalises with the true width and height.  FOV [B, 2] on any device: the focal
+    lengths are computed where it lies, in float32, without a host read.  fov=(fovx, fovy) as host floats replaces FOV[0] (FOV may then
+    be None)."""
+    fn = "grid_encoder_lift"
+    if c2w_input.dim() != 4:
+        raise ValueError(f"{fn}: c2w_input must be [B, V, 4, 4] (got {list(c2w_input.shape)})")
+    c2ws = _lift_shapes(motion_feature, anchor_points, c2w_input, fn)
+    Wn, Hn = motion_feature.shape[-2:]                                   # the reference's names
+    if fov is not None:                      # host floats: fov2focal in double, rounded once into the float32 matrix
+        import math
+        intr = torch.tensor([Wn / (2 * math.tan(float(fov[0]) / 2)), Hn / (2 * math.tan(float(fov[1]) / 2)), Wn / 2.0, Hn / 2.0],
+                            dtype=torch.float32)
+    else:                                    # fov2focal's tensor branch (graphics_utils.py:73-75) where FOV lies, in its dtype: no host read
+        if FOV.dim() != 2 or FOV.shape[-1] != 2:
+            raise ValueError(f"{fn}: FOV must be [B, 2] (got {list(FOV.shape)})")
+        f0 = FOV[0].detach()
+        focal = torch.tensor([float(Wn), float(Hn)], dtype=f0.dtype, device=f0.device) / (2 * torch.tan(f0 / 2))
+        intr = torch.cat([focal.float(), torch.tensor([Wn / 2.0, Hn / 2.0], dtype=torch.float32, device=f0.device)])
+    intr = intr.to(c2ws.device).expand(c2ws.shape[0], 4)
+    return _lift(motion_feature, anchor_points, torch.linalg.inv(c2ws), intr, fn)
 
 
 class _Deform(torch.autograd.Function):

@@ -609,6 +609,59 @@ int igs_gaussian_deform_fwd(void* stream, int P, int M, int dtype, const float* 
 int igs_gaussian_deform_bwd(void* stream, int P, int M, int dtype, const float* rot, const int64_t* mask, const void* drot,
                             const float* g_xyz, const float* g_rot, float* d_xyz, float* d_rot, void* d_dxyz, void* d_drot);
 
+/* Multi-view anchor feature lifting (lift.hip): GridEncoder.forward's "perspective_projection" branch
+ * (igs/models/grid_encoder.py:66-88) through perspective_projection (igs/utils/ops.py:444-477) and the mean over the views.
+ * For example b, anchor a, channel c, with (R_v, T_v) the top three rows of w2c[b * V + v] and (fx, fy, cx, cy) = intr[b * V + v]:
+ *
+ *   out[b, a, c] = (1 / V) * sum over v = 0 .. V-1 of bilinear_zero_pad(feat[b * V + v, c, :, :], ix, iy)
+ *   p_cam = R_v * p[b, a] + T_v
+ *   u = (fx * p_cam.x + cx * p_cam.z) / p_cam.z,  v = (fy * p_cam.y + cy * p_cam.z) / p_cam.z      (K * p_cam first, then / z)
+ *   ix = ((2 u / W - 1 + 1) * W - 1) / 2,  iy likewise with H      (grid_sample: bilinear, align_corners=False, padding_mode="zeros")
+ *
+ *   - no culling: a point with negative p_cam.z is divided by it like any other and its mirrored projection is sampled;
+ *   - the mean is over all V views, including those whose sample fell outside the map (they add zero);
+ *   - a corner outside the map contributes zero, the other corners of the sample still count;
+ *   - deviation: a sample whose ix or iy is not finite (z = 0, overflow) contributes zero (the reference hands NaN / inf to grid_sample);
+ *     the coordinates are range-tested in float (-1 < ix < W, -1 < iy < H) before any conversion to integer;
+ *   - float32 arithmetic throughout; per anchor the views are added in view order and the corners in the order (x0, y0), (x0 + 1, y0),
+ *     (x0, y0 + 1), (x0 + 1, y0 + 1) with fmaf (maps larger than one LDS band: band by band in row order), then one division by V.
+ * Common rules: every pointer is DEVICE memory, everything is enqueued on `stream`, no host synchronisation, no device allocation;
+ * sizes out of range, an unknown dtype code, a stride pattern that is not supported or a NULL required pointer return
+ * IGS_RAST_E_INVALID with a message (igs_rast_last_error) before any HIP call; a call with nothing to do (A == 0 or B == 0) returns 0
+ * without a launch (the backward with A == 0 and B > 0 zero-fills d feat).  The two *_scratch_bytes return 0 for sizes out of range.
+ * Limits: 0 <= B, 0 <= A, B * A <= IGS_LIFT_MAX_SAMPLES, 1 <= V <= IGS_LIFT_MAX_V, 1 <= C <= IGS_LIFT_MAX_C,
+ * 1 <= H, W <= IGS_LIFT_MAX_HW, B * V * H * W <= IGS_LIFT_MAX_PIXELS.
+ *
+ * igs_anchor_lift_fwd: feat [B*V, C, H, W] in `dtype` (IGS_DTYPE_F32 / IGS_DTYPE_F16, widened on load) with element strides fs_*: every
+ *   H x W plane must be contiguous (fs_w == 1, fs_h == W; fs_n and fs_c are free, so slices of n and c are read in place).
+ *   Channels-last (fs_c == 1) and every other pattern are refused with a message: there are no kernels for them in this version, the
+ *   caller makes the tensor plane-contiguous.  points [B, A, 3] float32; w2c [B*V, 4, 4] float32 row-major (the inverse of the
+ *   camera-to-world matrices); intr [B*V, 4] float32 = fx, fy, cx, cy.  out float32 at out[b * A * C + a * os_a + c * os_c] with
+ *   (os_a, os_c) = (1, A) (a [B, C, A] buffer, what GridEncoder's conv reads) or (C, 1) ([B, A, C]).  `scratch` of
+ *   igs_anchor_lift_scratch_bytes(...) bytes receives the sample table.  Two launches.
+ * igs_anchor_lift_bwd: d feat[n, c, y, x] = (1 / V) * sum of w * d out[b, a, c] over the (anchor, corner) pairs of view n = b * V + v
+ *   that touch pixel (y, x), in ascending (a, corner) order with fmaf, then one division by V, rounded once to `dtype`.  No float
+ *   atomics: bitwise reproducible.  EVERY element of d feat is written (zero where no sample landed), so the caller need not clear it.
+ *   d out float32 at dout[b * A * C + a * gs_a + c * gs_c], (gs_a, gs_c) = (1, A) or (C, 1); d feat in `dtype` with strides as the
+ *   forward's, planes not overlapping (fs_c >= H * W, fs_n >= C * fs_c).  The sample table is recomputed from points / w2c / intr (the
+ *   features themselves are not needed), so nothing has to be kept from the forward; `scratch` of
+ *   igs_anchor_lift_bwd_scratch_bytes(...) bytes holds the table and the inverse index (edges sorted by pixel with the library's
+ *   stable radix sort).  A workgroup keeps two channels of d out[b] in 64 KB of LDS while 2 * A floats fit (A <= 8192); for larger A it
+ *   reads d out from global memory per edge instead (same result, slower).  Gradients to points, poses and intrinsics are not provided. */
+#define IGS_LIFT_MAX_C 1024
+#define IGS_LIFT_MAX_V 16
+#define IGS_LIFT_MAX_HW 2048
+#define IGS_LIFT_MAX_PIXELS (1 << 24)
+#define IGS_LIFT_MAX_SAMPLES (1 << 24)
+size_t igs_anchor_lift_scratch_bytes(int B, int V, int A, int C, int H, int W, int dtype);
+size_t igs_anchor_lift_bwd_scratch_bytes(int B, int V, int A, int C, int H, int W, int dtype);
+int igs_anchor_lift_fwd(void* stream, int B, int V, int A, int C, int H, int W, int dtype, const void* feat, long long fs_n, long long fs_c,
+                        long long fs_h, long long fs_w, const float* points, const float* w2c, const float* intr, float* out,
+                        long long os_a, long long os_c, void* scratch);
+int igs_anchor_lift_bwd(void* stream, int B, int V, int A, int C, int H, int W, int dtype, const float* points, const float* w2c,
+                        const float* intr, const float* dout, long long gs_a, long long gs_c, void* dfeat, long long fs_n, long long fs_c,
+                        long long fs_h, long long fs_w, void* scratch);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).
