@@ -53,7 +53,8 @@ EXPORTS = ["igs_rast_version", "igs_rast_last_error", "igs_rast_forward", "igs_r
            "igs_knn_scratch_bytes", "igs_knn_mean_dist2", "igs_bbox_select_scratch_bytes", "igs_bbox_select", "igs_fps_scratch_bytes",
            "igs_fps", "igs_knn_query", "igs_anchor_interp_fwd", "igs_anchor_interp_index_bytes", "igs_anchor_interp_index",
            "igs_anchor_interp_bwd", "igs_gaussian_deform_fwd", "igs_gaussian_deform_bwd",
-           "igs_anchor_lift_scratch_bytes", "igs_anchor_lift_bwd_scratch_bytes", "igs_anchor_lift_fwd", "igs_anchor_lift_bwd"]
+           "igs_anchor_lift_scratch_bytes", "igs_anchor_lift_bwd_scratch_bytes", "igs_anchor_lift_fwd", "igs_anchor_lift_bwd",
+           "igs_ray_condition_fwd", "igs_modln_fwd", "igs_modln_bwd", "igs_modln_bwd_scratch_bytes"]
 
 VERSION = 4       # IGS_RAST_VERSION this binding was written against (include/igs_rast.h)
 
@@ -208,6 +209,14 @@ def lib():
         L.igs_anchor_lift_fwd.argtypes = [_vp] + [_i] * 7 + [_vp] + [_ll] * 4 + [_vp] * 4 + [_ll] * 2 + [_vp]
         L.igs_anchor_lift_bwd.restype = _i
         L.igs_anchor_lift_bwd.argtypes = [_vp] + [_i] * 7 + [_vp] * 4 + [_ll] * 2 + [_vp] + [_ll] * 4 + [_vp]
+        L.igs_ray_condition_fwd.restype = _i
+        L.igs_ray_condition_fwd.argtypes = [_vp] + [_i] * 5 + [_vp] * 3
+        L.igs_modln_bwd_scratch_bytes.restype = C.c_size_t
+        L.igs_modln_bwd_scratch_bytes.argtypes = [_i] * 4
+        L.igs_modln_fwd.restype = _i
+        L.igs_modln_fwd.argtypes = [_vp] + [_i] * 5 + [_vp] + [_ll] * 4 + [_i] + [_vp] * 3 + [_f] + [_vp] * 3
+        L.igs_modln_bwd.restype = _i
+        L.igs_modln_bwd.argtypes = [_vp] + [_i] * 5 + [_vp] + [_ll] * 4 + [_i] + [_vp] * 11
         L.igs_depth_normal_loss_fwd_bwd.restype = _i
         L.igs_depth_normal_loss_fwd_bwd.argtypes = [_vp, _i, _i, _f, _f, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp]
         L.igs_l1_loss_fwd_bwd.restype = _i

@@ -1245,6 +1245,67 @@ extern "C" int igs_anchor_lift_bwd(void* stream, int B, int V, int A, int C, int
     return 0;
 }
 
+// ray conditioning and fused LayerNorm + modulation (cond.hip; the contract is in include/igs_rast.h)
+extern "C" int igs_ray_condition_fwd(void* stream, int N, int H, int W, int Hd, int Wd, const float* rays, const float* depth, float* cond)
+{
+    const char* fn = "igs_ray_condition_fwd";
+    if (N < 0 || N > IGS_COND_MAX_PIXELS) return lift_fail(fn, "N out of range");
+    if (H < 1 || H > IGS_COND_MAX_HW) return lift_fail(fn, "H out of range (1..IGS_COND_MAX_HW)");
+    if (W < 1 || W > IGS_COND_MAX_HW) return lift_fail(fn, "W out of range (1..IGS_COND_MAX_HW)");
+    if (Hd < 1 || Hd > IGS_COND_MAX_HW) return lift_fail(fn, "Hd out of range (1..IGS_COND_MAX_HW)");
+    if (Wd < 1 || Wd > IGS_COND_MAX_HW) return lift_fail(fn, "Wd out of range (1..IGS_COND_MAX_HW)");
+    if ((long long)N * H * W > IGS_COND_MAX_PIXELS) return lift_fail(fn, "N * H * W out of range (IGS_COND_MAX_PIXELS)");
+    if (N == 0) return 0;
+    if (!rays || !depth || !cond) return lift_fail(fn, "NULL pointer");
+    HIP_TRY(launch_ray_condition((hipStream_t)stream, N, H, W, Hd, Wd, rays, depth, cond), "ray condition launch");
+    return 0;
+}
+static const char* modln_size_error(int N, int C, int H, int W)
+{
+    if (N < 0 || N > IGS_COND_MAX_PIXELS) return "N out of range";
+    if (C < 1 || C > IGS_MODLN_MAX_C) return "C out of range (1..IGS_MODLN_MAX_C)";
+    if (H < 1 || H > IGS_COND_MAX_HW) return "H out of range (1..IGS_COND_MAX_HW)";
+    if (W < 1 || W > IGS_COND_MAX_HW) return "W out of range (1..IGS_COND_MAX_HW)";
+    if ((long long)N * H * W > IGS_COND_MAX_PIXELS) return "N * H * W out of range (IGS_COND_MAX_PIXELS)";
+    return nullptr;
+}
+extern "C" size_t igs_modln_bwd_scratch_bytes(int N, int C, int H, int W)
+{
+    if (modln_size_error(N, C, H, W)) return 0;
+    return modln_bwd_scratch_bytes(N, C, H * W) + 256;
+}
+extern "C" int igs_modln_fwd(void* stream, int N, int C, int H, int W, int x_dtype, const void* x, long long xs_n, long long xs_c, long long xs_h,
+                             long long xs_w, int mod_dtype, const void* mod, const float* weight, const float* bias, float eps, float* out,
+                             float* mean, float* rstd)
+{
+    const char* fn = "igs_modln_fwd";
+    if (const char* w = modln_size_error(N, C, H, W)) return lift_fail(fn, w);
+    if (!dtype_ok(x_dtype) || !dtype_ok(mod_dtype)) return lift_fail(fn, "unknown dtype code");
+    if (const char* w = lift_stride_error(C, H, W, xs_n, xs_c, xs_h, xs_w)) return lift_fail(fn, w);
+    if (!(eps >= 0.f)) return lift_fail(fn, "eps must be >= 0");
+    if ((mean == nullptr) != (rstd == nullptr)) return lift_fail(fn, "mean and rstd go together (both or neither)");
+    if (N == 0) return 0;
+    if (!x || !mod || !weight || !bias || !out) return lift_fail(fn, "NULL pointer");
+    HIP_TRY(launch_modln_fwd((hipStream_t)stream, N, C, H * W, x_dtype, x, (size_t)xs_n, (size_t)xs_c, mod_dtype, mod, weight, bias, eps, out, mean,
+                             rstd), "modln fwd launch");
+    return 0;
+}
+extern "C" int igs_modln_bwd(void* stream, int N, int C, int H, int W, int x_dtype, const void* x, long long xs_n, long long xs_c, long long xs_h,
+                             long long xs_w, int mod_dtype, const void* mod, const float* weight, const float* bias, const float* mean,
+                             const float* rstd, const float* gout, void* dx, void* dmod, float* dweight, float* dbias, void* scratch)
+{
+    const char* fn = "igs_modln_bwd";
+    if (const char* w = modln_size_error(N, C, H, W)) return lift_fail(fn, w);
+    if (!dtype_ok(x_dtype) || !dtype_ok(mod_dtype)) return lift_fail(fn, "unknown dtype code");
+    if (const char* w = lift_stride_error(C, H, W, xs_n, xs_c, xs_h, xs_w)) return lift_fail(fn, w);
+    if (N == 0 || (!dx && !dmod && !dweight && !dbias)) return 0;
+    if (!x || !mod || !weight || !bias || !mean || !rstd || !gout) return lift_fail(fn, "NULL pointer");
+    if ((dweight || dbias) && !scratch) return lift_fail(fn, "NULL pointer (scratch is required for d weight / d bias)");
+    HIP_TRY(launch_modln_bwd((hipStream_t)stream, N, C, H * W, x_dtype, x, (size_t)xs_n, (size_t)xs_c, mod_dtype, mod, weight, bias, mean, rstd, gout,
+                             dx, dmod, dweight, dbias, scratch), "modln bwd launch");
+    return 0;
+}
+
 // Test support: the per-tile sort of the slab binning on caller-made slabs (sort.hip: launch_tile_sort).  tile_count[T] instances per
 // tile (reset to zero by the launch), pairs[T * slab] = depth bits << 32 | Gaussian id, out: point_list[T * slab] (ids, sorted by the
 // 64-bit key inside every tile's slab), ranges[2 T], stats[4] ([1] = largest tile that overflowed its slab).  Everything device memory.

@@ -169,6 +169,14 @@ hipError_t launch_lift_fwd(hipStream_t s, int B, int V, int A, int C, int H, int
 hipError_t launch_lift_bwd(hipStream_t s, int B, int V, int A, int C, int H, int W, int dtype, const float* points, const float* w2c,
                            const float* intr, const float* dout, size_t gs_a, size_t gs_c, void* dfeat, size_t fs_n, size_t fs_c,
                            void* scratch);
+hipError_t launch_ray_condition(hipStream_t s, int N, int H, int W, int Hd, int Wd, const float* rays, const float* depth,
+                                float* cond);                                                            // cond.hip
+hipError_t launch_modln_fwd(hipStream_t s, int N, int C, int HW, int x_dtype, const void* x, size_t xs_n, size_t xs_c, int mod_dtype,
+                            const void* mod, const float* w, const float* b, float eps, float* out, float* mean, float* rstd);
+size_t modln_bwd_scratch_bytes(int N, int C, int HW);
+hipError_t launch_modln_bwd(hipStream_t s, int N, int C, int HW, int x_dtype, const void* x, size_t xs_n, size_t xs_c, int mod_dtype,
+                            const void* mod, const float* w, const float* b, const float* mean, const float* rstd, const float* gout, void* dx,
+                            void* dmod, float* dw, float* db, void* scratch);
 hipError_t launch_deform_fwd(hipStream_t s, int P, int M, int dtype, const float* xyz, const float* rot, const int64_t* mask,
                              const void* dxyz, const void* drot, float* xyz_out, float* rot_out);
 hipError_t launch_deform_bwd(hipStream_t s, int P, int M, int dtype, const float* rot, const int64_t* mask, const void* drot,

@@ -11,6 +11,7 @@
 // anchors_knn (fixed output shapes, no host synchronisation).
 // And the two consumers of the anchor graph under igs_amd.motion: motion_interp_fwd / _index / _bwd (anchor feature interpolation) and
 // motion_deform_fwd / _bwd (GaussianModel.deform); unsupported dtypes raise NotImplementedError.
+// And IGS.condition3D's native parts: cond_ray_fwd (the ray / depth condition) and modln_fwd / modln_bwd (LayerNorm + adaLN modulation).
 // Extensions over the reference's signatures are keyword-only extras with defaults (the positional lists are the reference's):
 //   rasterize_gaussians(..., scratch=None, out_images=None, out_radii=None, mode=0, scratch_clean=False)
 //   rasterize_gaussians_backward(..., workspace=None, out_*=None)         any upstream gradient may be None (= zeros)
@@ -564,6 +565,110 @@ Tensor motion_lift_bwd(const Tensor& grad_bca, const Tensor& points, const Tenso
     return dfeat;
 }
 
+// ---- ray conditioning and fused LayerNorm + modulation (cond.hip) ----
+// cond [N, H, W, 33] float32 from rays [N, H, W, 6] and depth [N, Hd, Wd] (float32; N = B * V views)
+Tensor cond_ray_fwd(const Tensor& rays, const Tensor& depth)
+{
+    const char* fn = "cond_ray_fwd";
+    motion_expect(rays, fn, "rays", at::kFloat, {-1, -1, -1, 6});
+    motion_expect(depth, fn, "depth", at::kFloat, {rays.size(0), -1, -1});
+    const int64_t N = rays.size(0), H = rays.size(1), W = rays.size(2), Hd = depth.size(1), Wd = depth.size(2);
+    if (H < 1 || W < 1 || Hd < 1 || Wd < 1 || H > IGS_COND_MAX_HW || W > IGS_COND_MAX_HW || Hd > IGS_COND_MAX_HW || Wd > IGS_COND_MAX_HW ||
+        N * H * W > IGS_COND_MAX_PIXELS)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (1 <= H, W, Hd, Wd <= 8192, N * H * W <= 2^24)");
+    require_gpu(rays, fn, "rays");
+    same_device(depth, rays, fn, "depth");
+    const c10::Device dev = rays.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    Tensor cond = at::empty({N, H, W, 33}, rays.options());
+    const Tensor rc = rays.contiguous(), dc = depth.contiguous();
+    check(igs_ray_condition_fwd(cur_stream(dev), (int)N, (int)H, (int)W, (int)Hd, (int)Wd, rc.data_ptr<float>(), dc.data_ptr<float>(),
+                                cond.data_ptr<float>()), "igs_ray_condition_fwd");
+    return cond;
+}
+
+struct ModlnSizes { int64_t N, C, H, W; int xdt, mdt; };
+static ModlnSizes modln_check(const char* fn, const Tensor& x, const Tensor& mod, const Tensor& weight, const Tensor& bias)
+{
+    ModlnSizes z;
+    z.xdt = motion_dtype(x, fn, "x");
+    z.mdt = motion_dtype(mod, fn, "mod");
+    if (x.dim() != 4) throw RasterizerError(std::string(fn) + ": x must have shape [N, C, H, W] (got " + c10::str(x.sizes()) + ")");
+    z.N = x.size(0); z.C = x.size(1); z.H = x.size(2); z.W = x.size(3);
+    motion_expect(mod, fn, "mod", mod.scalar_type(), {z.N, z.H, z.W, 2 * z.C});
+    motion_expect(weight, fn, "weight", at::kFloat, {z.C});
+    motion_expect(bias, fn, "bias", at::kFloat, {z.C});
+    if (z.C < 1 || z.C > IGS_MODLN_MAX_C || z.H < 1 || z.W < 1 || z.H > IGS_COND_MAX_HW || z.W > IGS_COND_MAX_HW ||
+        z.N * z.H * z.W > IGS_COND_MAX_PIXELS)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (1 <= C <= 1024, 1 <= H, W <= 8192, N * H * W <= 2^24)");
+    return z;
+}
+static void modln_devices(const char* fn, const Tensor& x, const Tensor& mod, const Tensor& weight, const Tensor& bias)      // after the shape checks
+{
+    require_gpu(x, fn, "x");
+    same_device(mod, x, fn, "mod");
+    same_device(weight, x, fn, "weight");
+    same_device(bias, x, fn, "bias");
+}
+
+// (out [N, C, H, W] float32 contiguous, mean, rstd [N, H, W] float32 or None): x [N, C, H, W] float32 / float16 with contiguous H x W
+// planes, mod [N, H, W, 2 C] float32 / float16, weight, bias [C] float32
+std::tuple<Tensor, OptTensor, OptTensor> modln_fwd(const Tensor& x, const Tensor& mod, const Tensor& weight, const Tensor& bias, double eps,
+                                                    bool save_stats)
+{
+    const char* fn = "modln_fwd";
+    const ModlnSizes z = modln_check(fn, x, mod, weight, bias);
+    modln_devices(fn, x, mod, weight, bias);
+    const c10::Device dev = x.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const auto fo = x.options().dtype(at::kFloat);
+    Tensor out = at::empty({z.N, z.C, z.H, z.W}, fo);
+    OptTensor mean, rstd;
+    if (save_stats) { mean = at::empty({z.N, z.H, z.W}, fo); rstd = at::empty({z.N, z.H, z.W}, fo); }
+    if (z.N == 0) return {out, mean, rstd};
+    const Tensor mc = mod.contiguous(), wc = weight.contiguous(), bc = bias.contiguous();
+    check(igs_modln_fwd(cur_stream(dev), (int)z.N, (int)z.C, (int)z.H, (int)z.W, z.xdt, x.data_ptr(), x.stride(0), x.stride(1), x.stride(2),
+                        x.stride(3), z.mdt, mc.data_ptr(), wc.data_ptr<float>(), bc.data_ptr<float>(), (float)eps, out.data_ptr<float>(),
+                        mean ? mean->data_ptr<float>() : nullptr, rstd ? rstd->data_ptr<float>() : nullptr), "igs_modln_fwd");
+    return {out, mean, rstd};
+}
+
+// (d x in x's dtype, d mod in mod's dtype, d weight, d bias), each None unless wanted
+std::tuple<OptTensor, OptTensor, OptTensor, OptTensor> modln_bwd(const Tensor& x, const Tensor& mod, const Tensor& weight, const Tensor& bias,
+                                                                  const Tensor& mean, const Tensor& rstd, const Tensor& grad_out, bool want_x,
+                                                                  bool want_mod, bool want_weight, bool want_bias)
+{
+    const char* fn = "modln_bwd";
+    const ModlnSizes z = modln_check(fn, x, mod, weight, bias);
+    motion_expect(mean, fn, "mean", at::kFloat, {z.N, z.H, z.W});
+    motion_expect(rstd, fn, "rstd", at::kFloat, {z.N, z.H, z.W});
+    motion_expect(grad_out, fn, "grad_out", at::kFloat, {z.N, z.C, z.H, z.W});
+    modln_devices(fn, x, mod, weight, bias);
+    same_device(mean, x, fn, "mean");
+    same_device(rstd, x, fn, "rstd");
+    same_device(grad_out, x, fn, "grad_out");
+    const c10::Device dev = x.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    OptTensor dx, dmod, dw, db;
+    const auto fo = x.options().dtype(at::kFloat);
+    if (want_x) dx = at::empty({z.N, z.C, z.H, z.W}, x.options());
+    if (want_mod) dmod = at::empty({z.N, z.H, z.W, 2 * z.C}, mod.options());
+    if (want_weight) dw = z.N == 0 ? at::zeros({z.C}, fo) : at::empty({z.C}, fo);
+    if (want_bias) db = z.N == 0 ? at::zeros({z.C}, fo) : at::empty({z.C}, fo);
+    if (z.N == 0 || !(want_x || want_mod || want_weight || want_bias)) return {dx, dmod, dw, db};
+    Tensor scratch;
+    if (want_weight || want_bias)
+        scratch = at::empty({(int64_t)igs_modln_bwd_scratch_bytes((int)z.N, (int)z.C, (int)z.H, (int)z.W)}, x.options().dtype(at::kByte));
+    const Tensor mc = mod.contiguous(), wc = weight.contiguous(), bc = bias.contiguous(), mu = mean.contiguous(), rs = rstd.contiguous(),
+                 gc = grad_out.contiguous();
+    check(igs_modln_bwd(cur_stream(dev), (int)z.N, (int)z.C, (int)z.H, (int)z.W, z.xdt, x.data_ptr(), x.stride(0), x.stride(1), x.stride(2),
+                        x.stride(3), z.mdt, mc.data_ptr(), wc.data_ptr<float>(), bc.data_ptr<float>(), mu.data_ptr<float>(), rs.data_ptr<float>(),
+                        gc.data_ptr<float>(), dx ? dx->data_ptr() : nullptr, dmod ? dmod->data_ptr() : nullptr,
+                        dw ? dw->data_ptr<float>() : nullptr, db ? db->data_ptr<float>() : nullptr,
+                        scratch.defined() ? scratch.data_ptr() : nullptr), "igs_modln_bwd");
+    return {dx, dmod, dw, db};
+}
+
 static void deform_checks(const char* fn, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot, int* dt)
 {
     motion_expect(rot, fn, "rotation", at::kFloat, {-1, 4});
@@ -836,6 +941,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::call_guard<py::gil_scoped_release>());
     m.def("motion_lift_bwd", &motion_lift_bwd, py::arg("grad_out"), py::arg("anchor_points"), py::arg("w2c"), py::arg("intrinsics"), py::arg("H"),
           py::arg("W"), py::arg("half") = false, py::call_guard<py::gil_scoped_release>());
+    m.def("cond_ray_fwd", &cond_ray_fwd, py::arg("rays"), py::arg("depth"), py::call_guard<py::gil_scoped_release>());
+    m.def("modln_fwd", &modln_fwd, py::arg("x"), py::arg("mod"), py::arg("weight"), py::arg("bias"), py::arg("eps") = 1e-6,
+          py::arg("save_stats") = false, py::call_guard<py::gil_scoped_release>());
+    m.def("modln_bwd", &modln_bwd, py::arg("x"), py::arg("mod"), py::arg("weight"), py::arg("bias"), py::arg("mean"), py::arg("rstd"),
+          py::arg("grad_out"), py::arg("want_x") = true, py::arg("want_mod") = true, py::arg("want_weight") = true, py::arg("want_bias") = true,
+          py::call_guard<py::gil_scoped_release>());
     m.def("motion_deform_fwd", &motion_deform_fwd, py::arg("xyz"), py::arg("rotation"), py::arg("mask"), py::arg("res_xyz"),
           py::arg("res_rotation"), py::call_guard<py::gil_scoped_release>());
     m.def("motion_deform_bwd", &motion_deform_bwd, py::arg("rotation"), py::arg("mask"), py::arg("res_xyz"), py::arg("res_rotation"),

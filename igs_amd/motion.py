@@ -7,7 +7,15 @@ the masked Gaussians by the decoded residuals.  `query_ir_grid` and `deform` her
 `grid_encoder_lift` / `lift_anchor_features` are the step in front of them: GridEncoder.forward's lift of the 2-D motion features onto the
 anchors (igs/models/grid_encoder.py:66-88 over igs/utils/ops.py:444-477; igs_amd/csrc/lift.hip), with autograd to the features.
 
+`ray_condition` / `modln` / `condition3d` are the step in front of the lift: IGS.condition3D (igs/IGS.py:185-210 with ray_to_plucker,
+rsh_cart_3 and ModLN; igs_amd/csrc/cond.hip).  The ray embedding and the fused LayerNorm + adaLN modulation are native, ModLN's small MLP
+between them stays PyTorch.
+
 Deviations from the reference lines (INTEGRATION.md lists them):
+  - condition3d returns the reference's shape, dtype and values NCHW-contiguous, where the reference returns a channels-last-strided
+    view of a [N, H, W, C] tensor: its only consumer, grid_encoder_lift, then reads it in place instead of copying it;
+  - float16 features are normalised in float32 and the result is float32; a float16 modulation is widened before `1 + scale` is formed
+    (the reference forms it in half);
   - a lifted sample whose pixel coordinate is not finite adds zero; channels-last features are copied to NCHW first;
   - a neighbour slot whose column is -1 (knn_native's padding) or out of range contributes nothing (the reference would index with it);
   - the interpolation backward is deterministic (an inverse index instead of index_put_'s atomics);
@@ -186,6 +194,93 @@ def grid_encoder_lift(motion_feature, anchor_points, FOV, c2w_input, fov=None):
         intr = torch.cat([focal.float(), torch.tensor([Wn / 2.0, Hn / 2.0], dtype=torch.float32, device=f0.device)])
     intr = intr.to(c2ws.device).expand(c2ws.shape[0], 4)
     return _lift(motion_feature, anchor_points, torch.linalg.inv(c2ws), intr, fn)
+
+
+class _ModLN(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mod, weight, bias, eps):
+        out, mean, rstd = _ext().modln_fwd(x, mod, weight, bias, eps, True)
+        ctx.save_for_backward(x, mod, weight, bias, mean, rstd)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, mod, weight, bias, mean, rstd = ctx.saved_tensors
+        nx, nm, nw, nb = ctx.needs_input_grad[:4]
+        dx, dmod, dw, db = _ext().modln_bwd(x, mod, weight, bias, mean, rstd, g.float(), nx, nm, nw, nb)
+        return dx, dmod, dw, db, None
+
+
+def _plane_contiguous(f):
+    return (f.shape[3] == 1 or f.stride(3) == 1) and (f.shape[2] == 1 or f.stride(2) == f.shape[3])
+
+
+def ray_condition(rays, depth, size):
+    """cond [B*V, H, W, 33] float32, contiguous: what IGS.condition3D hands ModLN's MLP (IGS.py:197-203, local_ray False).  rays
+    [B, V, H, W, 6] float32 = (origin, direction) at the feature resolution size = (H, W); depth [B, V, Hd, Wd] float32 at any resolution.
+    Channels 0-15: the degree <= 3 real spherical harmonics of the normalised direction, 16-31: of the raw moment origin x direction,
+    32: depth resized bilinearly (align_corners=False).  One launch; no backward (rays / depth that require grad raise)."""
+    fn = "ray_condition"
+    if rays.dim() != 5 or rays.shape[-1] != 6:
+        raise ValueError(f"{fn}: rays must be [B, V, H, W, 6] (got {list(rays.shape)})")
+    if depth.dim() != 4 or tuple(depth.shape[:2]) != tuple(rays.shape[:2]):
+        raise ValueError(f"{fn}: depth must be [B, V, Hd, Wd] with B, V = {list(rays.shape[:2])} (got {list(depth.shape)})")
+    if tuple(size) != tuple(rays.shape[2:4]):
+        raise ValueError(f"{fn}: rays are at {list(rays.shape[2:4])}, the feature resolution is {list(size)}")
+    if rays.dtype != torch.float32 or depth.dtype != torch.float32:
+        raise NotImplementedError(f"{fn}: rays and depth must be float32 (got {rays.dtype}, {depth.dtype})")
+    if torch.is_grad_enabled() and (rays.requires_grad or depth.requires_grad):
+        raise NotImplementedError(f"{fn}: gradients to rays and depth are not provided")
+    if not (rays.is_cuda and depth.is_cuda):
+        raise RuntimeError(f"{fn}: tensors must be on a GPU (no CPU fallback)")
+    return _ext().cond_ray_fwd(rays.reshape(-1, *rays.shape[2:]), depth.reshape(-1, *depth.shape[2:]))
+
+
+def modln(x, mod, weight, bias, eps=1e-6):
+    """out [N, C, H, W] float32, NCHW-contiguous = LayerNorm_C(x) * (1 + scale) + shift (ModLN.forward, IGS.py:282-284, on NCHW features).
+    x [N, C, H, W] float32 / float16 (plane-contiguous NCHW, slices of n and c included, is read in place; anything else is copied);
+    mod [N, H, W, 2C] float32 / float16, the MLP's output unchunked (shift = mod[..., :C], scale = mod[..., C:]); weight, bias [C] float32.
+    Mean and biased variance over the C channels of a pixel, in float32 from centred values.  Gradients reach x and mod in their dtypes
+    and weight / bias, the latter two summed in a fixed order (bitwise reproducible)."""
+    fn = "modln"
+    if x.dim() != 4:
+        raise ValueError(f"{fn}: x must be [N, C, H, W] (got {list(x.shape)})")
+    N, C, H, W = x.shape
+    if tuple(mod.shape) != (N, H, W, 2 * C):
+        raise ValueError(f"{fn}: mod must be [N, H, W, 2C] = {[N, H, W, 2 * C]} (got {list(mod.shape)})")
+    if tuple(weight.shape) != (C,) or tuple(bias.shape) != (C,):
+        raise ValueError(f"{fn}: weight and bias must be [C] = [{C}] (got {list(weight.shape)}, {list(bias.shape)})")
+    if x.dtype not in FEATURE_DTYPES or mod.dtype not in FEATURE_DTYPES:
+        raise NotImplementedError(f"{fn}: x and mod must be float32 or float16 (got {x.dtype}, {mod.dtype})")
+    if weight.dtype != torch.float32 or bias.dtype != torch.float32:
+        raise NotImplementedError(f"{fn}: weight and bias must be float32 (got {weight.dtype}, {bias.dtype})")
+    if not (x.is_cuda and mod.is_cuda and weight.is_cuda and bias.is_cuda):
+        raise RuntimeError(f"{fn}: tensors must be on a GPU (no CPU fallback)")
+    if not _plane_contiguous(x):
+        x = x.contiguous()
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, mod, weight, bias)):
+        return _ModLN.apply(x, mod, weight, bias, float(eps))
+    return _ext().modln_fwd(x, mod, weight, bias, float(eps), False)[0]          # under no_grad: one launch, nothing saved
+
+
+def condition3d(motion_feature, rays, depth, modln_module):
+    """IGS.condition3D (IGS.py:185-210, local_ray False): motion_feature [B*V, C, H, W] modulated by the ray / depth condition, float32,
+    NCHW-contiguous (the reference returns the same values as a channels-last-strided view).  modln_module: any object with .norm
+    (weight, bias, eps, normalized_shape == (C,)) and .mlp (a callable on [..., 33] returning [..., 2C]); the MLP runs in PyTorch."""
+    fn = "condition3d"
+    if motion_feature.dim() != 4:
+        raise ValueError(f"{fn}: motion_feature must be [B*V, C, H, W] (got {list(motion_feature.shape)})")
+    norm = modln_module.norm
+    C = motion_feature.shape[1]
+    if tuple(norm.normalized_shape) != (C,):
+        raise ValueError(f"{fn}: the module normalises {tuple(norm.normalized_shape)}, motion_feature has C = {C}")
+    if norm.weight is None or norm.bias is None:
+        raise NotImplementedError(f"{fn}: LayerNorm without affine parameters is not supported")
+    if rays.dim() == 5 and rays.shape[0] * rays.shape[1] != motion_feature.shape[0]:
+        raise ValueError(f"{fn}: rays {list(rays.shape)} do not match {motion_feature.shape[0]} views")
+    cond = ray_condition(rays, depth, motion_feature.shape[-2:])
+    mod = modln_module.mlp(cond)
+    return modln(motion_feature, mod, norm.weight, norm.bias, norm.eps)
 
 
 class _Deform(torch.autograd.Function):

@@ -662,6 +662,40 @@ int igs_anchor_lift_bwd(void* stream, int B, int V, int A, int C, int H, int W, 
                         const float* intr, const float* dout, long long gs_a, long long gs_c, void* dfeat, long long fs_n, long long fs_c,
                         long long fs_h, long long fs_w, void* scratch);
 
+/* Ray conditioning and fused LayerNorm + modulation (cond.hip): the non-GEMM parts of IGS.condition3D
+ * (igs/IGS.py:185-210 with ray_to_plucker :286-295, rsh_cart_3 :297-344, ModLN :259-284; local_ray False).  Everything runs on `stream`,
+ * reads nothing back and allocates nothing.  Sizes out of range, an unknown dtype code, a stride pattern that is not supported or a NULL
+ * required pointer return IGS_RAST_E_INVALID with a message before any HIP call; N == 0 returns 0 without a launch.
+ * Limits: 0 <= N, N * H * W <= IGS_COND_MAX_PIXELS, 1 <= H, W, Hd, Wd <= IGS_COND_MAX_HW, 1 <= C <= IGS_MODLN_MAX_C.
+ *
+ * igs_ray_condition_fwd: rays [N, H, W, 6] float32 = (origin, direction) per pixel of the N = B * V views, depth [N, Hd, Wd] float32, both
+ *   contiguous; cond [N, H, W, 33] float32.  d = direction / max(|direction|, 1e-12), m = origin x d (not normalised).  Channels 0-15: the
+ *   real spherical harmonics of degree <= 3 of d, index n (n + 1) + m, odd orders negated; 16-31: the same polynomials of m; 32: depth
+ *   resized bilinearly to H x W with half-pixel centres (source coordinate max((i + 0.5) Hd / H - 0.5, 0), upper neighbour clamped to the
+ *   last row / column, no antialiasing).  One launch; every 132-byte row leaves through LDS as part of one contiguous run per workgroup.
+ * igs_modln_fwd: x [N, C, H, W] in x_dtype (IGS_DTYPE_F32 / IGS_DTYPE_F16, widened on load) with element strides xs_* under
+ *   igs_anchor_lift_fwd's rule (every H x W plane contiguous; xs_n, xs_c free); mod [N, H, W, 2 C] contiguous in mod_dtype, shift =
+ *   mod[..., :C], scale = mod[..., C:]; weight, bias [C] float32; out [N, C, H, W] float32 contiguous:
+ *     out = ((x - mu) * r * weight + bias) * (1 + scale) + shift,  mu = mean_c x,  r = 1 / sqrt(mean_c (x - mu)^2 + eps)
+ *   (the biased variance, from centred values), all in float32.  mean, rstd [N, H, W] float32 receive mu and r for the backward when both
+ *   are given (both or neither).  One launch; a workgroup takes 64 consecutive pixels and all channels while C <= 244, fewer pixels above.
+ * igs_modln_bwd: from x, mod, weight, bias, the saved mean / rstd and gout = d out [N, C, H, W] float32 contiguous, each output optional
+ *   (NULL = not wanted): dx [N, C, H, W] contiguous in x_dtype; dmod [N, H, W, 2 C] in mod_dtype (d shift = gout, d scale = gout * y, y the
+ *   normalised value with the affine applied); dweight, dbias [C] float32, summed without float atomics: every workgroup leaves a row of
+ *   partial sums in `scratch` (igs_modln_bwd_scratch_bytes(...) bytes, needed only for these two), a second launch adds the rows in
+ *   workgroup order, so two runs agree bit for bit. */
+#define IGS_COND_MAX_PIXELS (1 << 24)
+#define IGS_COND_MAX_HW 8192
+#define IGS_MODLN_MAX_C 1024
+int igs_ray_condition_fwd(void* stream, int N, int H, int W, int Hd, int Wd, const float* rays, const float* depth, float* cond);
+size_t igs_modln_bwd_scratch_bytes(int N, int C, int H, int W);
+int igs_modln_fwd(void* stream, int N, int C, int H, int W, int x_dtype, const void* x, long long xs_n, long long xs_c, long long xs_h,
+                  long long xs_w, int mod_dtype, const void* mod, const float* weight, const float* bias, float eps, float* out, float* mean,
+                  float* rstd);
+int igs_modln_bwd(void* stream, int N, int C, int H, int W, int x_dtype, const void* x, long long xs_n, long long xs_c, long long xs_h,
+                  long long xs_w, int mod_dtype, const void* mod, const float* weight, const float* bias, const float* mean, const float* rstd,
+                  const float* gout, void* dx, void* dmod, float* dweight, float* dbias, void* scratch);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).
