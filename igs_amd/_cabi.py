@@ -45,16 +45,101 @@ class RefineMaskArgs(C.Structure):
 
 GROUP_XYZ, GROUP_ROT, GROUP_SH, GROUP_OPACITY, GROUP_SCALE = 1, 2, 4, 8, 16      # IGS_GROUP_*
 
-EXPORTS = ["igs_rast_version", "igs_rast_last_error", "igs_rast_forward", "igs_rast_backward_workspace_bytes",
-           "igs_rast_forward_async", "igs_rast_forward_finish", "igs_rast_forward_nowait", "igs_rast_last_status", "igs_rast_last_posted_status", "igs_rast_hint_scratch_clean", "igs_rast_set_slab_hint", "igs_rast_get_slab_hint", "igs_rast_backward", "igs_rast_mark_visible", "igs_rast_debug_dump",
-           "igs_rast_profile_enable", "igs_rast_profile_read", "igs_adam_step", "igs_adam_step_groups", "igs_adam_step_multi", "igs_adam_step_multi_dev", "igs_adam_step_multi_dev_scratch_words", "igs_densify_stats", "igs_densify_remap", "igs_refine_step", "igs_refine_loss_scratch_bytes", "igs_ssim_l1_scratch_bytes", "igs_ssim_l1_loss_fwd_bwd", "igs_ssim_l1_loss_fwd_bwd_cached", "igs_ssim_mean_fwd_bwd", "igs_ssim_gt_stats_bytes", "igs_depth_normal_loss_fwd_bwd", "igs_l1_loss_fwd_bwd", "igs_l1_mean_fwd_bwd", "igs_activate_fwd", "igs_activate_bwd",
-           "igs_sh_grad_from_view_colors", "igs_adam_sh_from_view_colors", "igs_rast_last_backward_instance", "igs_rast_next_backward_options", "igs_rast_nan_report_wait", "igs_rast_nan_report_handle", "igs_rast_nan_report_wait_at", "igs_refine_step_args_size", "igs_rast_debug_poison_lds", "igs_adam_exchange_step", "igs_morton_order", "igs_morton_order_scratch_bytes", "igs_ply_to_params", "igs_params_to_ply", "igs_debug_tile_sort",
-           "igs_refine_step_masked", "igs_refine_mask_args_size", "igs_rast_count_gaussians",
-           "igs_knn_scratch_bytes", "igs_knn_mean_dist2", "igs_bbox_select_scratch_bytes", "igs_bbox_select", "igs_fps_scratch_bytes",
-           "igs_fps", "igs_knn_query", "igs_anchor_interp_fwd", "igs_anchor_interp_index_bytes", "igs_anchor_interp_index",
-           "igs_anchor_interp_bwd", "igs_gaussian_deform_fwd", "igs_gaussian_deform_bwd",
-           "igs_anchor_lift_scratch_bytes", "igs_anchor_lift_bwd_scratch_bytes", "igs_anchor_lift_fwd", "igs_anchor_lift_bwd",
-           "igs_ray_condition_fwd", "igs_modln_fwd", "igs_modln_bwd", "igs_modln_bwd_scratch_bytes"]
+_sz, _ll, _u = C.c_size_t, C.c_longlong, C.c_uint
+_FORWARD = ([_vp, ALLOC_FN, _vp, ALLOC_FN, _vp, ALLOC_FN, _vp, _i, _i, _i, _vp, _i, _i]
+            + [_vp] * 5 + [_f, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i] + [_vp] * 8 + [_i, _i, _i])
+_STATUS = [C.POINTER(C.c_int), C.POINTER(_u), C.POINTER(_u)]
+
+# name: (restype, argtypes) of every function of include/igs_rast.h this binding declares, applied by lib().  One entry per function: a
+# wrong count here corrupts memory instead of failing, so tests/test_host_logic.py checks every length against the header.
+SIGNATURES = {
+    # the rasterizer (api.hip)
+    "igs_rast_version": (_i, []),
+    "igs_rast_last_error": (C.c_char_p, []),
+    "igs_rast_forward": (_i, _FORWARD),
+    "igs_rast_forward_async": (_i, _FORWARD),
+    "igs_rast_forward_finish": (_i, []),
+    "igs_rast_forward_nowait": (_i, _FORWARD),
+    "igs_rast_last_status": (_i, _STATUS),
+    "igs_rast_last_posted_status": (_i, _STATUS),
+    "igs_rast_hint_scratch_clean": (None, [_i]),
+    "igs_rast_count_gaussians": (_i, ([_vp, ALLOC_FN, _vp, ALLOC_FN, _vp, ALLOC_FN, _vp, _i, _i, _i, _vp, _i, _i]
+                                      + [_vp] * 5 + [_f, _vp, _vp, _vp, _vp, _vp, _f, _f, _i] + [_vp] * 4 + [_i])),
+    "igs_rast_set_slab_hint": (None, [_u]),
+    "igs_rast_get_slab_hint": (_u, []),
+    "igs_rast_backward_workspace_bytes": (_sz, [_i]),
+    "igs_rast_backward": (_i, ([_vp, _i, _i, _i, _i, _vp, _i, _i] + [_vp] * 5 + [_f, _vp, _vp, _vp, _vp, _vp, _f, _f, _f]
+                               + [_vp] * 5 + [_vp] * 7 + [_vp] + [_vp] * 8 + [_i, _i, _i])),
+    "igs_rast_mark_visible": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "igs_rast_debug_dump": (_i, [_vp, _i, _i, _i, _i] + [_vp] * 8),
+    "igs_rast_next_backward_options": (None, [_i, _f]),
+    "igs_rast_nan_report_wait": (_i, []),
+    "igs_rast_nan_report_handle": (_i, [_vp, _vp]),
+    "igs_rast_nan_report_wait_at": (_i, [_vp, _u]),
+    "igs_rast_last_backward_instance": (_i, []),
+    "igs_rast_debug_poison_lds": (_i, [_vp]),
+    "igs_rast_profile_enable": (_i, [_i]),
+    "igs_rast_profile_read": (_i, [_vp, _vp, _vp, _vp, _i]),
+    # optimiser, densification, activations, losses, PLY tables (refine_ops.hip, loss_ops.hip, io_ops.hip)
+    "igs_adam_step": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f]),
+    "igs_adam_step_groups": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f]),
+    "igs_adam_step_multi": (_i, [_vp, _i] + [_vp] * 8 + [_f, _f, _f]),
+    "igs_adam_step_multi_dev": (_i, [_vp, _i] + [_vp] * 8 + [_f, _f, _f]),
+    "igs_adam_step_multi_dev_scratch_words": (_sz, []),
+    "igs_densify_stats": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "igs_densify_remap": (_i, [_vp, _i, _i] + [_vp] * 13),
+    "igs_activate_fwd": (_i, [_vp, _i] + [_vp] * 6),
+    "igs_activate_bwd": (_i, [_vp, _i] + [_vp] * 9),
+    "igs_ssim_l1_scratch_bytes": (_sz, [_i, _i]),
+    "igs_ssim_l1_loss_fwd_bwd": (_i, [_vp, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp]),
+    "igs_ssim_gt_stats_bytes": (_sz, [_i, _i]),
+    "igs_ssim_l1_loss_fwd_bwd_cached": (_i, [_vp, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _i]),
+    "igs_ssim_mean_fwd_bwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "igs_depth_normal_loss_fwd_bwd": (_i, [_vp, _i, _i, _f, _f, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp]),
+    "igs_l1_loss_fwd_bwd": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _f]),
+    "igs_l1_mean_fwd_bwd": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "igs_ply_to_params": (_i, [_vp, _i, _vp, _i, _vp, _i, _i] + [_vp] * 5),
+    "igs_params_to_ply": (_i, [_vp, _i, _i] + [_vp] * 6),
+    # the fused refine step (api.hip) and the N > 1 exchange (geom_bwd.hip)
+    "igs_refine_step": (_i, [C.POINTER(RefineStepArgs)]),
+    "igs_refine_step_args_size": (_sz, []),
+    "igs_refine_step_masked": (_i, [C.POINTER(RefineStepArgs), C.POINTER(RefineMaskArgs)]),
+    "igs_refine_mask_args_size": (_sz, []),
+    "igs_refine_loss_scratch_bytes": (_sz, [_i, _i]),
+    "igs_sh_grad_from_view_colors": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp]),
+    "igs_adam_sh_from_view_colors": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f]),
+    "igs_adam_exchange_step": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp] + [_sz] * 5 + [_f] * 10),
+    # sort.hip
+    "igs_morton_order_scratch_bytes": (_sz, [_i]),
+    "igs_morton_order": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "igs_debug_tile_sort": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i]),
+    # knn.hip, anchors.hip
+    "igs_knn_scratch_bytes": (_sz, [_i]),
+    "igs_knn_mean_dist2": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "igs_bbox_select_scratch_bytes": (_sz, [_i]),
+    "igs_bbox_select": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "igs_fps_scratch_bytes": (_sz, [_i, _i, _i]),
+    "igs_fps": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp]),
+    "igs_knn_query": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp]),
+    # motion.hip
+    "igs_anchor_interp_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "igs_anchor_interp_index_bytes": (_sz, [_i, _i, _i, _i]),
+    "igs_anchor_interp_index": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "igs_anchor_interp_bwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "igs_gaussian_deform_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "igs_gaussian_deform_bwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # lift.hip
+    "igs_anchor_lift_scratch_bytes": (_sz, [_i] * 7),
+    "igs_anchor_lift_bwd_scratch_bytes": (_sz, [_i] * 7),
+    "igs_anchor_lift_fwd": (_i, [_vp] + [_i] * 7 + [_vp] + [_ll] * 4 + [_vp] * 4 + [_ll] * 2 + [_vp]),
+    "igs_anchor_lift_bwd": (_i, [_vp] + [_i] * 7 + [_vp] * 4 + [_ll] * 2 + [_vp] + [_ll] * 4 + [_vp]),
+    # cond.hip
+    "igs_ray_condition_fwd": (_i, [_vp] + [_i] * 5 + [_vp] * 3),
+    "igs_modln_bwd_scratch_bytes": (_sz, [_i] * 4),
+    "igs_modln_fwd": (_i, [_vp] + [_i] * 5 + [_vp] + [_ll] * 4 + [_i] + [_vp] * 3 + [_f] + [_vp] * 3),
+    "igs_modln_bwd": (_i, [_vp] + [_i] * 5 + [_vp] + [_ll] * 4 + [_i] + [_vp] * 11),
+}
+EXPORTS = list(SIGNATURES)
 
 VERSION = 4       # IGS_RAST_VERSION this binding was written against (include/igs_rast.h)
 
@@ -83,160 +168,17 @@ def lib():
     # on this path, so torch's runtime goes first.
     import torch  # noqa: F401
     L = C.CDLL(path)
-    L.igs_rast_version.restype = _i
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.igs_rast_version() != VERSION:
         raise RuntimeError("igs_amd: libigs_rast.so reports C-ABI version %d, this binding needs %d" % (L.igs_rast_version(), VERSION))
-    L.igs_refine_step_args_size.restype = C.c_size_t
     if L.igs_refine_step_args_size() != C.sizeof(RefineStepArgs):
         raise RuntimeError("igs_amd: igs_refine_step_args is %d bytes in the library, %d in the binding"
                            % (L.igs_refine_step_args_size(), C.sizeof(RefineStepArgs)))
-    L.igs_refine_mask_args_size.restype = C.c_size_t
-    L.igs_refine_mask_args_size.argtypes = []
     if L.igs_refine_mask_args_size() != C.sizeof(RefineMaskArgs):
         raise RuntimeError("igs_amd: igs_refine_mask_args is %d bytes in the library, %d in the binding"
                            % (L.igs_refine_mask_args_size(), C.sizeof(RefineMaskArgs)))
-    L.igs_rast_last_backward_instance.restype = _i
-    L.igs_rast_last_backward_instance.argtypes = []
-    L.igs_rast_next_backward_options.restype = None
-    L.igs_rast_next_backward_options.argtypes = [_i, _f]
-    L.igs_rast_nan_report_wait.restype = _i
-    L.igs_rast_nan_report_wait.argtypes = []
-    L.igs_rast_debug_poison_lds.restype = _i
-    L.igs_rast_debug_poison_lds.argtypes = [_vp]
-    L.igs_rast_last_error.restype = C.c_char_p
-    L.igs_rast_forward.restype = _i
-    L.igs_rast_forward.argtypes = ([_vp, ALLOC_FN, _vp, ALLOC_FN, _vp, ALLOC_FN, _vp, _i, _i, _i, _vp, _i, _i]
-                                   + [_vp] * 5 + [_f, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i] + [_vp] * 8 + [_i, _i, _i])
-    L.igs_rast_count_gaussians.restype = _i
-    L.igs_rast_count_gaussians.argtypes = ([_vp, ALLOC_FN, _vp, ALLOC_FN, _vp, ALLOC_FN, _vp, _i, _i, _i, _vp, _i, _i]
-                                           + [_vp] * 5 + [_f, _vp, _vp, _vp, _vp, _vp, _f, _f, _i] + [_vp] * 4 + [_i])
-    L.igs_rast_forward_async.restype = _i
-    L.igs_rast_forward_async.argtypes = L.igs_rast_forward.argtypes
-    L.igs_rast_forward_nowait.restype = _i
-    L.igs_rast_forward_nowait.argtypes = L.igs_rast_forward.argtypes
-    L.igs_rast_hint_scratch_clean.restype = None
-    L.igs_rast_hint_scratch_clean.argtypes = [_i]
-    L.igs_rast_last_status.restype = _i
-    L.igs_rast_last_status.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
-    L.igs_rast_last_posted_status.restype = _i
-    L.igs_rast_last_posted_status.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
-    L.igs_rast_forward_finish.restype = _i
-    L.igs_rast_forward_finish.argtypes = []
-    L.igs_rast_set_slab_hint.restype = None
-    L.igs_rast_set_slab_hint.argtypes = [C.c_uint]
-    L.igs_rast_get_slab_hint.restype = C.c_uint
-    L.igs_rast_get_slab_hint.argtypes = []
-    L.igs_rast_backward_workspace_bytes.restype = C.c_size_t
-    L.igs_rast_backward_workspace_bytes.argtypes = [_i]
-    L.igs_rast_backward.restype = _i
-    L.igs_rast_backward.argtypes = ([_vp, _i, _i, _i, _i, _vp, _i, _i] + [_vp] * 5 + [_f, _vp, _vp, _vp, _vp, _vp, _f, _f, _f]
-                                    + [_vp] * 5 + [_vp] * 7 + [_vp] + [_vp] * 8 + [_i, _i, _i])
-    L.igs_rast_mark_visible.restype = _i
-    L.igs_rast_mark_visible.argtypes = [_vp, _i, _vp, _vp, _vp, _vp]
-    L.igs_rast_debug_dump.restype = _i
-    L.igs_rast_debug_dump.argtypes = [_vp, _i, _i, _i, _i] + [_vp] * 8
-    L.igs_rast_profile_enable.restype = _i
-    L.igs_rast_profile_enable.argtypes = [_i]
-    L.igs_rast_profile_read.restype = _i
-    L.igs_rast_profile_read.argtypes = [_vp, _vp, _vp, _vp, _i]
-    if hasattr(L, "igs_adam_step"):
-        L.igs_adam_step.restype = _i
-        L.igs_adam_step.argtypes = [_vp, C.c_size_t, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f]
-        L.igs_adam_step_groups.restype = _i
-        L.igs_adam_step_groups.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f]
-        L.igs_adam_step_multi.restype = _i
-        L.igs_adam_step_multi.argtypes = [_vp, _i] + [_vp] * 8 + [_f, _f, _f]
-        L.igs_adam_step_multi_dev.restype = _i
-        L.igs_adam_step_multi_dev.argtypes = [_vp, _i] + [_vp] * 8 + [_f, _f, _f]
-        L.igs_adam_step_multi_dev_scratch_words.restype = C.c_size_t
-        L.igs_adam_step_multi_dev_scratch_words.argtypes = []
-        L.igs_densify_stats.restype = _i
-        L.igs_densify_stats.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _vp]
-        L.igs_densify_remap.restype = _i
-        L.igs_densify_remap.argtypes = [_vp, _i, _i] + [_vp] * 13
-        L.igs_refine_step.restype = _i
-        L.igs_refine_step.argtypes = [C.POINTER(RefineStepArgs)]
-        L.igs_refine_step_masked.restype = _i
-        L.igs_refine_step_masked.argtypes = [C.POINTER(RefineStepArgs), C.POINTER(RefineMaskArgs)]
-        L.igs_refine_loss_scratch_bytes.restype = C.c_size_t
-        L.igs_refine_loss_scratch_bytes.argtypes = [_i, _i]
-        L.igs_ssim_l1_scratch_bytes.restype = C.c_size_t
-        L.igs_ssim_l1_scratch_bytes.argtypes = [_i, _i]
-        L.igs_ssim_l1_loss_fwd_bwd.restype = _i
-        L.igs_ssim_l1_loss_fwd_bwd.argtypes = [_vp, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp]
-        L.igs_ssim_l1_loss_fwd_bwd_cached.restype = _i
-        L.igs_ssim_l1_loss_fwd_bwd_cached.argtypes = [_vp, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _i]
-        L.igs_ssim_gt_stats_bytes.restype = C.c_size_t
-        L.igs_ssim_gt_stats_bytes.argtypes = [_i, _i]
-        L.igs_morton_order_scratch_bytes.restype = C.c_size_t
-        L.igs_debug_tile_sort.restype = _i
-        L.igs_debug_tile_sort.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i]
-        L.igs_morton_order_scratch_bytes.argtypes = [_i]
-        L.igs_morton_order.restype = _i
-        L.igs_morton_order.argtypes = [_vp, _i, _vp, _vp, _i, _vp, _vp]
-        L.igs_knn_scratch_bytes.restype = C.c_size_t
-        L.igs_knn_scratch_bytes.argtypes = [_i]
-        L.igs_knn_mean_dist2.restype = _i
-        L.igs_knn_mean_dist2.argtypes = [_vp, _i, _vp, _vp, _vp]
-        L.igs_bbox_select_scratch_bytes.restype = C.c_size_t
-        L.igs_bbox_select_scratch_bytes.argtypes = [_i]
-        L.igs_bbox_select.restype = _i
-        L.igs_bbox_select.argtypes = [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-        L.igs_fps_scratch_bytes.restype = C.c_size_t
-        L.igs_fps_scratch_bytes.argtypes = [_i, _i, _i]
-        L.igs_fps.restype = _i
-        L.igs_fps.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp]
-        L.igs_knn_query.restype = _i
-        L.igs_knn_query.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp]
-        L.igs_anchor_interp_fwd.restype = _i
-        L.igs_anchor_interp_fwd.argtypes = [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]
-        L.igs_anchor_interp_index_bytes.restype = C.c_size_t
-        L.igs_anchor_interp_index_bytes.argtypes = [_i, _i, _i, _i]
-        L.igs_anchor_interp_index.restype = _i
-        L.igs_anchor_interp_index.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp]
-        L.igs_anchor_interp_bwd.restype = _i
-        L.igs_anchor_interp_bwd.argtypes = [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]
-        L.igs_gaussian_deform_fwd.restype = _i
-        L.igs_gaussian_deform_fwd.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-        L.igs_gaussian_deform_bwd.restype = _i
-        L.igs_gaussian_deform_bwd.argtypes = [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-        _ll = C.c_longlong
-        L.igs_anchor_lift_scratch_bytes.restype = C.c_size_t
-        L.igs_anchor_lift_scratch_bytes.argtypes = [_i] * 7
-        L.igs_anchor_lift_bwd_scratch_bytes.restype = C.c_size_t
-        L.igs_anchor_lift_bwd_scratch_bytes.argtypes = [_i] * 7
-        L.igs_anchor_lift_fwd.restype = _i
-        L.igs_anchor_lift_fwd.argtypes = [_vp] + [_i] * 7 + [_vp] + [_ll] * 4 + [_vp] * 4 + [_ll] * 2 + [_vp]
-        L.igs_anchor_lift_bwd.restype = _i
-        L.igs_anchor_lift_bwd.argtypes = [_vp] + [_i] * 7 + [_vp] * 4 + [_ll] * 2 + [_vp] + [_ll] * 4 + [_vp]
-        L.igs_ray_condition_fwd.restype = _i
-        L.igs_ray_condition_fwd.argtypes = [_vp] + [_i] * 5 + [_vp] * 3
-        L.igs_modln_bwd_scratch_bytes.restype = C.c_size_t
-        L.igs_modln_bwd_scratch_bytes.argtypes = [_i] * 4
-        L.igs_modln_fwd.restype = _i
-        L.igs_modln_fwd.argtypes = [_vp] + [_i] * 5 + [_vp] + [_ll] * 4 + [_i] + [_vp] * 3 + [_f] + [_vp] * 3
-        L.igs_modln_bwd.restype = _i
-        L.igs_modln_bwd.argtypes = [_vp] + [_i] * 5 + [_vp] + [_ll] * 4 + [_i] + [_vp] * 11
-        L.igs_depth_normal_loss_fwd_bwd.restype = _i
-        L.igs_depth_normal_loss_fwd_bwd.argtypes = [_vp, _i, _i, _f, _f, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp]
-        L.igs_l1_loss_fwd_bwd.restype = _i
-        L.igs_l1_loss_fwd_bwd.argtypes = [_vp, C.c_size_t, _vp, _vp, _vp, _vp, _f]
-        L.igs_l1_mean_fwd_bwd.restype = _i
-        L.igs_l1_mean_fwd_bwd.argtypes = [_vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp]
-        L.igs_ply_to_params.restype = _i
-        L.igs_ply_to_params.argtypes = [_vp, _i, _vp, _i, _vp, _i, _i] + [_vp] * 5
-        L.igs_params_to_ply.restype = _i
-        L.igs_params_to_ply.argtypes = [_vp, _i, _i] + [_vp] * 6
-        L.igs_activate_fwd.restype = _i
-        L.igs_activate_fwd.argtypes = [_vp, _i] + [_vp] * 6
-        L.igs_activate_bwd.restype = _i
-        L.igs_activate_bwd.argtypes = [_vp, _i] + [_vp] * 9
-        L.igs_sh_grad_from_view_colors.restype = _i
-        L.igs_sh_grad_from_view_colors.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp]
-        L.igs_adam_sh_from_view_colors.restype = _i
-        L.igs_adam_sh_from_view_colors.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f]
-        L.igs_adam_exchange_step.restype = _i
-        L.igs_adam_exchange_step.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp] + [C.c_size_t] * 5 + [_f] * 10
     _LIB = L
     return L
 

@@ -14,6 +14,7 @@
 // (c) knn: brute force in index order, one query per lane, k sorted slots in registers, x staged in LDS tiles.
 #include "common.h"
 #include "knn_common.h"
+#include "host_api.h"
 #include <float.h>
 
 #define FPS_WAVES 16                 // waves of the FPS workgroup
@@ -127,10 +128,10 @@ select_scatter_kernel(int N, int B, const float* __restrict__ xyz, const int* __
     }
 }
 
-size_t select_scratch_bytes(int N) { return align_up(((size_t)N / 256 + 2) * 4, 256) + 256; }
+static size_t select_scratch_bytes(int N) { return align_up(((size_t)N / 256 + 2) * 4, 256) + 256; }
 
-hipError_t launch_bbox_select(hipStream_t s, int B, int N, const float* xyz, const int* ptr, const float* box, void* scratch,
-                              float* out_xyz, int64_t* out_idx, int* count)
+static hipError_t launch_bbox_select(hipStream_t s, int B, int N, const float* xyz, const int* ptr, const float* box, void* scratch,
+                                     float* out_xyz, int64_t* out_idx, int* count)
 {
     hipError_t e = zero_fill_async(s, count, (size_t)B * 4);
     if (e != hipSuccess || N == 0) return e;
@@ -383,10 +384,10 @@ fps_kernel(int N, int nrows, int total, int LS, const int* __restrict__ ptr, con
     }
 }
 
-size_t fps_scratch_bytes(int B, int N, int max_n) { return FpsLayout(B, N, max_n).total; }
+static size_t fps_scratch_bytes(int B, int N, int max_n) { return FpsLayout(B, N, max_n).total; }
 
-hipError_t launch_fps(hipStream_t s, int B, int N, int max_n, const float* xyz, const int* ptr, const int* start, const int* out_ptr,
-                      int total, float init_d2, void* scratch, int64_t* out)
+static hipError_t launch_fps(hipStream_t s, int B, int N, int max_n, const float* xyz, const int* ptr, const int* start, const int* out_ptr,
+                             int total, float init_d2, void* scratch, int64_t* out)
 {
     if (B <= 0) return hipSuccess;
     const FpsLayout F(B, N, max_n);
@@ -518,8 +519,8 @@ static void knnq_launch(hipStream_t s, int Nx, int Ny, int B, int k, const float
         hipLaunchKernelGGL((knnq_kernel<K, true>), g, dim3(KNNQ_THREADS), 0, s, Nx, Ny, B, k, x, y, ptr_x, ptr_y, scale, out_idx, out_d2, out_w);
 }
 
-hipError_t launch_knn_query(hipStream_t s, int Nx, int Ny, int B, const float* x, const float* y, const int* ptr_x, const int* ptr_y,
-                            int k, float scale, int64_t* out_idx, float* out_d2, float* out_w)
+static hipError_t launch_knn_query(hipStream_t s, int Nx, int Ny, int B, const float* x, const float* y, const int* ptr_x, const int* ptr_y,
+                                   int k, float scale, int64_t* out_idx, float* out_d2, float* out_w)
 {
     if (Ny <= 0) return hipSuccess;
     if (k <= 8) knnq_launch<8>(s, Nx, Ny, B, k, x, y, ptr_x, ptr_y, scale, out_idx, out_d2, out_w);
@@ -527,4 +528,49 @@ hipError_t launch_knn_query(hipStream_t s, int Nx, int Ny, int B, const float* x
     else if (k <= 32) knnq_launch<32>(s, Nx, Ny, B, k, x, y, ptr_x, ptr_y, scale, out_idx, out_d2, out_w);
     else knnq_launch<100>(s, Nx, Ny, B, k, x, y, ptr_x, ptr_y, scale, out_idx, out_d2, out_w);
     return hipGetLastError();
+}
+
+// the entry points (the contracts are in include/igs_rast.h)
+extern "C" size_t igs_bbox_select_scratch_bytes(int N)
+{
+    if (N < 0 || N > IGS_ANCHOR_MAX_POINTS) return 0;
+    return select_scratch_bytes(N) + 256;
+}
+extern "C" int igs_bbox_select(void* stream, int B, int N, const float* xyz, const int* ptr, const float* box, void* scratch,
+                               float* out_xyz, int64_t* out_idx, int* out_count)
+{
+    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES || N < 0 || N > IGS_ANCHOR_MAX_POINTS)
+        return fail(IGS_RAST_E_INVALID, "igs_bbox_select: B or N out of range");
+    if (!ptr || !box || !out_count || (N > 0 && (!xyz || !scratch || !out_xyz || !out_idx)))
+        return fail(IGS_RAST_E_INVALID, "igs_bbox_select: NULL pointer");
+    HIP_TRY(launch_bbox_select((hipStream_t)stream, B, N, xyz, ptr, box, scratch, out_xyz, out_idx, out_count), "bbox select launch");
+    return 0;
+}
+extern "C" size_t igs_fps_scratch_bytes(int B, int N, int max_n)
+{
+    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES || N < 0 || N > IGS_ANCHOR_MAX_POINTS || max_n < 0 || max_n > IGS_FPS_MAX_EXAMPLE_POINTS) return 0;
+    return fps_scratch_bytes(B, N, max_n) + 256;
+}
+extern "C" int igs_fps(void* stream, int B, int N, int max_n, const float* xyz, const int* ptr, const int* start, const int* out_ptr,
+                       int total, float init_d2, void* scratch, int64_t* out)
+{
+    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES || N < 0 || N > IGS_ANCHOR_MAX_POINTS || max_n < 0 || max_n > IGS_FPS_MAX_EXAMPLE_POINTS)
+        return fail(IGS_RAST_E_INVALID, "igs_fps: B, N or max_n out of range");
+    if (total < 0 || total > IGS_ANCHOR_MAX_POINTS) return fail(IGS_RAST_E_INVALID, "igs_fps: total out of range");
+    if (total == 0) return 0;
+    if (!(init_d2 >= 0.f)) return fail(IGS_RAST_E_INVALID, "igs_fps: init_d2 must be >= 0");
+    if (!ptr || !start || !out_ptr || !scratch || !out || (N > 0 && !xyz)) return fail(IGS_RAST_E_INVALID, "igs_fps: NULL pointer");
+    HIP_TRY(launch_fps((hipStream_t)stream, B, N, max_n, xyz, ptr, start, out_ptr, total, init_d2, scratch, out), "fps launch");
+    return 0;
+}
+extern "C" int igs_knn_query(void* stream, int B, int Nx, int Ny, const float* x, const float* y, const int* ptr_x, const int* ptr_y,
+                             int k, float weight_scale, int64_t* out_idx, float* out_d2, float* out_w)
+{
+    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES || Nx < 0 || Nx > IGS_ANCHOR_MAX_POINTS || Ny < 0 || Ny > IGS_ANCHOR_MAX_POINTS)
+        return fail(IGS_RAST_E_INVALID, "igs_knn_query: B, Nx or Ny out of range");
+    if (k < 1 || k > IGS_KNN_QUERY_MAX_K) return fail(IGS_RAST_E_INVALID, "igs_knn_query: k out of range (1..IGS_KNN_QUERY_MAX_K)");
+    if (Ny == 0) return 0;
+    if (!y || !ptr_x || !ptr_y || !out_idx || (Nx > 0 && !x)) return fail(IGS_RAST_E_INVALID, "igs_knn_query: NULL pointer");
+    HIP_TRY(launch_knn_query((hipStream_t)stream, Nx, Ny, B, x, y, ptr_x, ptr_y, k, weight_scale, out_idx, out_d2, out_w), "knn query launch");
+    return 0;
 }

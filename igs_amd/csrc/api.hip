@@ -1,23 +1,29 @@
-// api.hip -- C-ABI entry points (include/igs_rast.h) and host-side orchestration on a HIP stream.
+// api.hip -- the rasterizer and the refine step: their C-ABI entry points (include/igs_rast.h) and host-side orchestration on a HIP
+// stream (status slots, binning, forward, backward, fused refine step), plus the error message behind igs_rast_last_error().
+// Every other subsystem's entry points are defined next to its kernels (host_api.h: the error plumbing they share).
 // Counterpart of CudaRasterizer::Rasterizer::{forward,backward,markVisible}
 // (DGR/cuda_rasterizer/rasterizer_impl.cu:176-188, 254-425, 429-571).
 #include <atomic>
 #include "common.h"
+#include "host_api.h"
 #include <math.h>
-#include "../../include/igs_rast.h"
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
 #include <time.h>
 
 static thread_local char g_err[512] = "";
-static int fail(int code, const char* what, hipError_t e = hipSuccess)
+int fail(int code, const char* what, hipError_t e)
 {
     if (e != hipSuccess) snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
     else snprintf(g_err, sizeof g_err, "%s", what);
     return code;
 }
-#define HIP_TRY(expr, what) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(IGS_RAST_E_HIP, what, e_); } while (0)
+int fail_in(const char* fn, const char* what)
+{
+    snprintf(g_err, sizeof g_err, "%s: %s", fn, what);
+    return IGS_RAST_E_INVALID;
+}
 // IGS_TRACE_LAUNCHES=1 (debugging aid): synchronise after every launch like debug mode and name it on stderr once it has completed --
 // after a GPU memory fault (which aborts the process) the launch that follows the last name printed is the one that faulted
 static const bool g_trace_launches = getenv("IGS_TRACE_LAUNCHES") != nullptr;
@@ -1010,315 +1016,6 @@ static int refine_step_impl(const igs_refine_step_args* a, int first, unsigned f
 }
 
 
-// Morton order of the Gaussians' positions (sort.hip): perm[i] = index of the Gaussian that comes i-th along the Z-order curve of
-// xyz quantised to `bits` bits per axis inside the box lohi = {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z} (device memory).
-extern "C" size_t igs_morton_order_scratch_bytes(int P) { return morton_scratch_bytes(P) + 256; }
-extern "C" int igs_morton_order(void* stream, int P, const float* xyz, const float* lohi, int bits, void* scratch, int* perm)
-{
-    if (P < 0 || bits < 1 || bits > 10) return fail(IGS_RAST_E_INVALID, "igs_morton_order: bad sizes (1..10 bits per axis)");
-    if (P == 0) return 0;
-    if (!xyz || !lohi || !scratch || !perm) return fail(IGS_RAST_E_INVALID, "igs_morton_order: NULL pointer");
-    HIP_TRY(launch_morton_order((hipStream_t)stream, P, xyz, lohi, bits, scratch, perm), "morton order launch");
-    return 0;
-}
-
-// simple-knn's distCUDA2 (knn.hip; the contract is in include/igs_rast.h)
-extern "C" size_t igs_knn_scratch_bytes(int P)
-{
-    if (P < 0 || P > IGS_KNN_MAX_POINTS) return 0;
-    return knn_scratch_bytes(P) + 256;
-}
-extern "C" int igs_knn_mean_dist2(void* stream, int P, const float* xyz, void* scratch, float* out)
-{
-    if (P < 0 || P > IGS_KNN_MAX_POINTS) return fail(IGS_RAST_E_INVALID, "igs_knn_mean_dist2: P out of range (0..IGS_KNN_MAX_POINTS)");
-    if (P == 0) return 0;
-    if (!xyz || !scratch || !out) return fail(IGS_RAST_E_INVALID, "igs_knn_mean_dist2: NULL pointer");
-    HIP_TRY(launch_knn_mean_dist2((hipStream_t)stream, P, xyz, scratch, out), "knn launch");
-    return 0;
-}
-
-// the anchor graph: bbox select, FPS, kNN (anchors.hip; the contracts are in include/igs_rast.h)
-extern "C" size_t igs_bbox_select_scratch_bytes(int N)
-{
-    if (N < 0 || N > IGS_ANCHOR_MAX_POINTS) return 0;
-    return select_scratch_bytes(N) + 256;
-}
-extern "C" int igs_bbox_select(void* stream, int B, int N, const float* xyz, const int* ptr, const float* box, void* scratch,
-                               float* out_xyz, int64_t* out_idx, int* out_count)
-{
-    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES || N < 0 || N > IGS_ANCHOR_MAX_POINTS)
-        return fail(IGS_RAST_E_INVALID, "igs_bbox_select: B or N out of range");
-    if (!ptr || !box || !out_count || (N > 0 && (!xyz || !scratch || !out_xyz || !out_idx)))
-        return fail(IGS_RAST_E_INVALID, "igs_bbox_select: NULL pointer");
-    HIP_TRY(launch_bbox_select((hipStream_t)stream, B, N, xyz, ptr, box, scratch, out_xyz, out_idx, out_count), "bbox select launch");
-    return 0;
-}
-extern "C" size_t igs_fps_scratch_bytes(int B, int N, int max_n)
-{
-    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES || N < 0 || N > IGS_ANCHOR_MAX_POINTS || max_n < 0 || max_n > IGS_FPS_MAX_EXAMPLE_POINTS) return 0;
-    return fps_scratch_bytes(B, N, max_n) + 256;
-}
-extern "C" int igs_fps(void* stream, int B, int N, int max_n, const float* xyz, const int* ptr, const int* start, const int* out_ptr,
-                       int total, float init_d2, void* scratch, int64_t* out)
-{
-    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES || N < 0 || N > IGS_ANCHOR_MAX_POINTS || max_n < 0 || max_n > IGS_FPS_MAX_EXAMPLE_POINTS)
-        return fail(IGS_RAST_E_INVALID, "igs_fps: B, N or max_n out of range");
-    if (total < 0 || total > IGS_ANCHOR_MAX_POINTS) return fail(IGS_RAST_E_INVALID, "igs_fps: total out of range");
-    if (total == 0) return 0;
-    if (!(init_d2 >= 0.f)) return fail(IGS_RAST_E_INVALID, "igs_fps: init_d2 must be >= 0");
-    if (!ptr || !start || !out_ptr || !scratch || !out || (N > 0 && !xyz)) return fail(IGS_RAST_E_INVALID, "igs_fps: NULL pointer");
-    HIP_TRY(launch_fps((hipStream_t)stream, B, N, max_n, xyz, ptr, start, out_ptr, total, init_d2, scratch, out), "fps launch");
-    return 0;
-}
-extern "C" int igs_knn_query(void* stream, int B, int Nx, int Ny, const float* x, const float* y, const int* ptr_x, const int* ptr_y,
-                             int k, float weight_scale, int64_t* out_idx, float* out_d2, float* out_w)
-{
-    if (B < 1 || B > IGS_ANCHOR_MAX_EXAMPLES || Nx < 0 || Nx > IGS_ANCHOR_MAX_POINTS || Ny < 0 || Ny > IGS_ANCHOR_MAX_POINTS)
-        return fail(IGS_RAST_E_INVALID, "igs_knn_query: B, Nx or Ny out of range");
-    if (k < 1 || k > IGS_KNN_QUERY_MAX_K) return fail(IGS_RAST_E_INVALID, "igs_knn_query: k out of range (1..IGS_KNN_QUERY_MAX_K)");
-    if (Ny == 0) return 0;
-    if (!y || !ptr_x || !ptr_y || !out_idx || (Nx > 0 && !x)) return fail(IGS_RAST_E_INVALID, "igs_knn_query: NULL pointer");
-    HIP_TRY(launch_knn_query((hipStream_t)stream, Nx, Ny, B, x, y, ptr_x, ptr_y, k, weight_scale, out_idx, out_d2, out_w), "knn query launch");
-    return 0;
-}
-
-// anchor feature interpolation and the Gaussian deform (motion.hip; the contracts are in include/igs_rast.h)
-static bool interp_sizes_ok(int N, int K, int D, int A)
-{
-    return N >= 0 && N <= IGS_INTERP_MAX_ROWS && K >= 1 && K <= IGS_INTERP_MAX_K && D >= 1 && D <= IGS_INTERP_MAX_D && A >= 1 &&
-           A <= IGS_INTERP_MAX_ANCHORS && (long long)N * K <= IGS_INTERP_MAX_EDGES;
-}
-static int interp_size_fail(const char* fn, int N, int K, int D, int A)
-{
-    char what[160];
-    if (N < 0 || N > IGS_INTERP_MAX_ROWS) snprintf(what, sizeof what, "%s: N out of range (0..IGS_INTERP_MAX_ROWS)", fn);
-    else if (K < 1 || K > IGS_INTERP_MAX_K) snprintf(what, sizeof what, "%s: K out of range (1..IGS_INTERP_MAX_K)", fn);
-    else if (D < 1 || D > IGS_INTERP_MAX_D) snprintf(what, sizeof what, "%s: D out of range (1..IGS_INTERP_MAX_D)", fn);
-    else if (A < 1 || A > IGS_INTERP_MAX_ANCHORS) snprintf(what, sizeof what, "%s: A_total out of range (1..IGS_INTERP_MAX_ANCHORS)", fn);
-    else snprintf(what, sizeof what, "%s: N * K out of range (IGS_INTERP_MAX_EDGES)", fn);
-    return fail(IGS_RAST_E_INVALID, what);
-}
-static bool dtype_ok(int dtype) { return dtype == IGS_DTYPE_F32 || dtype == IGS_DTYPE_F16; }
-
-extern "C" int igs_anchor_interp_fwd(void* stream, int N, int K, int D, int A_total, int dtype, const void* F, const int64_t* col,
-                                     const float* w, float* out)
-{
-    if (!interp_sizes_ok(N, K, D, A_total)) return interp_size_fail("igs_anchor_interp_fwd", N, K, D, A_total);
-    if (!dtype_ok(dtype)) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_fwd: unknown dtype code");
-    if (N == 0) return 0;
-    if (!F || !col || !w || !out) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_fwd: NULL pointer");
-    HIP_TRY(launch_interp_fwd((hipStream_t)stream, N, K, D, A_total, dtype, F, col, w, out), "anchor interp fwd launch");
-    return 0;
-}
-extern "C" size_t igs_anchor_interp_index_bytes(int N, int K, int A_total, int D)
-{
-    if (!interp_sizes_ok(N, K, D, A_total)) return 0;
-    return interp_scratch_bytes(N, K, A_total, D) + 256;
-}
-extern "C" int igs_anchor_interp_index(void* stream, int N, int K, int A_total, int D, const int64_t* col, void* scratch)
-{
-    if (!interp_sizes_ok(N, K, D, A_total)) return interp_size_fail("igs_anchor_interp_index", N, K, D, A_total);
-    if (N == 0) return 0;
-    if (!col || !scratch) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_index: NULL pointer");
-    HIP_TRY(launch_interp_index((hipStream_t)stream, N, K, A_total, D, col, scratch), "anchor interp index launch");
-    return 0;
-}
-extern "C" int igs_anchor_interp_bwd(void* stream, int N, int K, int D, int A_total, int dtype, const void* F, const float* w,
-                                     const float* dout, void* scratch, void* dF, float* dw)
-{
-    if (!interp_sizes_ok(N, K, D, A_total)) return interp_size_fail("igs_anchor_interp_bwd", N, K, D, A_total);
-    if (!dtype_ok(dtype)) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_bwd: unknown dtype code");
-    if (!dF && !dw) return 0;
-    if (N == 0) {       // no edges: every anchor's gradient is zero
-        if (dF) HIP_TRY(zero_fill_async((hipStream_t)stream, dF, (size_t)A_total * D * (dtype == IGS_DTYPE_F16 ? 2 : 4)), "zero dF");
-        return 0;
-    }
-    if (!w || !dout || !scratch || (dw && !F)) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_bwd: NULL pointer");
-    HIP_TRY(launch_interp_bwd((hipStream_t)stream, N, K, D, A_total, dtype, F, w, dout, scratch, dF, dw), "anchor interp bwd launch");
-    return 0;
-}
-extern "C" int igs_gaussian_deform_fwd(void* stream, int P, int M, int dtype, const float* xyz, const float* rot, const int64_t* mask,
-                                       const void* dxyz, const void* drot, float* xyz_out, float* rot_out)
-{
-    if (P < 0 || P > IGS_DEFORM_MAX_POINTS) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_fwd: P out of range (0..IGS_DEFORM_MAX_POINTS)");
-    if (M < 0 || M > P) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_fwd: M out of range (0..P)");
-    if (!dtype_ok(dtype)) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_fwd: unknown dtype code");
-    if (P == 0) return 0;
-    if (!xyz || !rot || !xyz_out || !rot_out || (M > 0 && (!mask || !dxyz || !drot)))
-        return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_fwd: NULL pointer");
-    HIP_TRY(launch_deform_fwd((hipStream_t)stream, P, M, dtype, xyz, rot, mask, dxyz, drot, xyz_out, rot_out), "gaussian deform fwd launch");
-    return 0;
-}
-extern "C" int igs_gaussian_deform_bwd(void* stream, int P, int M, int dtype, const float* rot, const int64_t* mask, const void* drot,
-                                       const float* g_xyz, const float* g_rot, float* d_xyz, float* d_rot, void* d_dxyz, void* d_drot)
-{
-    if (P < 0 || P > IGS_DEFORM_MAX_POINTS) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_bwd: P out of range (0..IGS_DEFORM_MAX_POINTS)");
-    if (M < 0 || M > P) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_bwd: M out of range (0..P)");
-    if (!dtype_ok(dtype)) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_bwd: unknown dtype code");
-    if (P == 0 || (!d_xyz && !d_rot && !d_dxyz && !d_drot)) return 0;
-    if (M > 0 && (!mask || ((d_rot || d_drot) && (!rot || !drot))))
-        return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_bwd: NULL pointer");
-    HIP_TRY(launch_deform_bwd((hipStream_t)stream, P, M, dtype, rot, mask, drot, g_xyz, g_rot, d_xyz, d_rot, d_dxyz, d_drot),
-            "gaussian deform bwd launch");
-    return 0;
-}
-
-// multi-view anchor feature lifting (lift.hip; the contract is in include/igs_rast.h)
-static const char* lift_size_error(int B, int V, int A, int C, int H, int W)
-{
-    if (B < 0 || B > IGS_LIFT_MAX_SAMPLES) return "B out of range";
-    if (V < 1 || V > IGS_LIFT_MAX_V) return "V out of range (1..IGS_LIFT_MAX_V)";
-    if (A < 0 || A > IGS_LIFT_MAX_SAMPLES) return "A out of range";
-    if (C < 1 || C > IGS_LIFT_MAX_C) return "C out of range (1..IGS_LIFT_MAX_C)";
-    if (H < 1 || H > IGS_LIFT_MAX_HW) return "H out of range (1..IGS_LIFT_MAX_HW)";
-    if (W < 1 || W > IGS_LIFT_MAX_HW) return "W out of range (1..IGS_LIFT_MAX_HW)";
-    if ((long long)B * A > IGS_LIFT_MAX_SAMPLES) return "B * A out of range (IGS_LIFT_MAX_SAMPLES)";
-    if ((long long)B * V * H * W > IGS_LIFT_MAX_PIXELS) return "B * V * H * W out of range (IGS_LIFT_MAX_PIXELS)";
-    return nullptr;
-}
-static int lift_fail(const char* fn, const char* what)
-{
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: %s", fn, what);
-    return fail(IGS_RAST_E_INVALID, msg);
-}
-// the feature layouts read in place: every H x W plane contiguous (NCHW and any slicing of n or c); channels-last has no kernels here
-static const char* lift_stride_error(int C, int H, int W, long long fs_n, long long fs_c, long long fs_h, long long fs_w)
-{
-    if (fs_n < 0 || fs_c < 0) return "negative feature stride";
-    if ((W > 1 && fs_w != 1) || (H > 1 && fs_h != W)) {
-        if (fs_c == 1 && C > 1) return "channels-last features (fs_c == 1) are not read in place: pass plane-contiguous NCHW";
-        return "feature strides not supported: every H x W plane must be contiguous (fs_w == 1, fs_h == W)";
-    }
-    return nullptr;
-}
-extern "C" size_t igs_anchor_lift_scratch_bytes(int B, int V, int A, int C, int H, int W, int dtype)
-{
-    if (lift_size_error(B, V, A, C, H, W) || !dtype_ok(dtype)) return 0;
-    return lift_scratch_bytes(B, V, A, H, W, false) + 256;
-}
-extern "C" size_t igs_anchor_lift_bwd_scratch_bytes(int B, int V, int A, int C, int H, int W, int dtype)
-{
-    if (lift_size_error(B, V, A, C, H, W) || !dtype_ok(dtype)) return 0;
-    return lift_scratch_bytes(B, V, A, H, W, true) + 256;
-}
-extern "C" int igs_anchor_lift_fwd(void* stream, int B, int V, int A, int C, int H, int W, int dtype, const void* feat, long long fs_n,
-                                   long long fs_c, long long fs_h, long long fs_w, const float* points, const float* w2c, const float* intr,
-                                   float* out, long long os_a, long long os_c, void* scratch)
-{
-    const char* fn = "igs_anchor_lift_fwd";
-    if (const char* w = lift_size_error(B, V, A, C, H, W)) return lift_fail(fn, w);
-    if (!dtype_ok(dtype)) return lift_fail(fn, "unknown dtype code");
-    if (const char* w = lift_stride_error(C, H, W, fs_n, fs_c, fs_h, fs_w)) return lift_fail(fn, w);
-    if (!((os_a == 1 && os_c == A) || (os_c == 1 && os_a == C))) return lift_fail(fn, "output strides must be (os_a, os_c) = (1, A) or (C, 1)");
-    if (A == 0 || B == 0) return 0;
-    if (!feat || !points || !w2c || !intr || !out || !scratch) return lift_fail(fn, "NULL pointer");
-    HIP_TRY(launch_lift_fwd((hipStream_t)stream, B, V, A, C, H, W, dtype, feat, (size_t)fs_n, (size_t)fs_c, points, w2c, intr, out, (size_t)os_a,
-                            (size_t)os_c, scratch), "anchor lift fwd launch");
-    return 0;
-}
-extern "C" int igs_anchor_lift_bwd(void* stream, int B, int V, int A, int C, int H, int W, int dtype, const float* points, const float* w2c,
-                                   const float* intr, const float* dout, long long gs_a, long long gs_c, void* dfeat, long long fs_n,
-                                   long long fs_c, long long fs_h, long long fs_w, void* scratch)
-{
-    const char* fn = "igs_anchor_lift_bwd";
-    if (const char* w = lift_size_error(B, V, A, C, H, W)) return lift_fail(fn, w);
-    if (!dtype_ok(dtype)) return lift_fail(fn, "unknown dtype code");
-    if (const char* w = lift_stride_error(C, H, W, fs_n, fs_c, fs_h, fs_w)) return lift_fail(fn, w);
-    if (fs_c < (long long)H * W || fs_n < fs_c * C) return lift_fail(fn, "d feat planes overlap (fs_c >= H * W and fs_n >= C * fs_c required)");
-    if (!((gs_a == 1 && gs_c == A) || (gs_c == 1 && gs_a == C))) return lift_fail(fn, "d out strides must be (gs_a, gs_c) = (1, A) or (C, 1)");
-    if (B == 0) return 0;
-    if (!dfeat) return lift_fail(fn, "NULL pointer");
-    if (A == 0) {       // no samples: every element of d feat is zero (one fill per plane-contiguous tensor, else per image)
-        const size_t es = dtype == IGS_DTYPE_F16 ? 2 : 4;
-        if (fs_c == (long long)H * W && fs_n == fs_c * C)
-            HIP_TRY(zero_fill_async((hipStream_t)stream, dfeat, (size_t)B * V * C * H * W * es), "zero d feat");
-        else
-            for (long long n = 0; n < (long long)B * V; n++)
-                for (int c = 0; c < C; c++)
-                    HIP_TRY(zero_fill_async((hipStream_t)stream, (char*)dfeat + ((size_t)n * fs_n + (size_t)c * fs_c) * es, (size_t)H * W * es), "zero d feat");
-        return 0;
-    }
-    if (!points || !w2c || !intr || !dout || !scratch) return lift_fail(fn, "NULL pointer");
-    HIP_TRY(launch_lift_bwd((hipStream_t)stream, B, V, A, C, H, W, dtype, points, w2c, intr, dout, (size_t)gs_a, (size_t)gs_c, dfeat, (size_t)fs_n,
-                            (size_t)fs_c, scratch), "anchor lift bwd launch");
-    return 0;
-}
-
-// ray conditioning and fused LayerNorm + modulation (cond.hip; the contract is in include/igs_rast.h)
-extern "C" int igs_ray_condition_fwd(void* stream, int N, int H, int W, int Hd, int Wd, const float* rays, const float* depth, float* cond)
-{
-    const char* fn = "igs_ray_condition_fwd";
-    if (N < 0 || N > IGS_COND_MAX_PIXELS) return lift_fail(fn, "N out of range");
-    if (H < 1 || H > IGS_COND_MAX_HW) return lift_fail(fn, "H out of range (1..IGS_COND_MAX_HW)");
-    if (W < 1 || W > IGS_COND_MAX_HW) return lift_fail(fn, "W out of range (1..IGS_COND_MAX_HW)");
-    if (Hd < 1 || Hd > IGS_COND_MAX_HW) return lift_fail(fn, "Hd out of range (1..IGS_COND_MAX_HW)");
-    if (Wd < 1 || Wd > IGS_COND_MAX_HW) return lift_fail(fn, "Wd out of range (1..IGS_COND_MAX_HW)");
-    if ((long long)N * H * W > IGS_COND_MAX_PIXELS) return lift_fail(fn, "N * H * W out of range (IGS_COND_MAX_PIXELS)");
-    if (N == 0) return 0;
-    if (!rays || !depth || !cond) return lift_fail(fn, "NULL pointer");
-    HIP_TRY(launch_ray_condition((hipStream_t)stream, N, H, W, Hd, Wd, rays, depth, cond), "ray condition launch");
-    return 0;
-}
-static const char* modln_size_error(int N, int C, int H, int W)
-{
-    if (N < 0 || N > IGS_COND_MAX_PIXELS) return "N out of range";
-    if (C < 1 || C > IGS_MODLN_MAX_C) return "C out of range (1..IGS_MODLN_MAX_C)";
-    if (H < 1 || H > IGS_COND_MAX_HW) return "H out of range (1..IGS_COND_MAX_HW)";
-    if (W < 1 || W > IGS_COND_MAX_HW) return "W out of range (1..IGS_COND_MAX_HW)";
-    if ((long long)N * H * W > IGS_COND_MAX_PIXELS) return "N * H * W out of range (IGS_COND_MAX_PIXELS)";
-    return nullptr;
-}
-extern "C" size_t igs_modln_bwd_scratch_bytes(int N, int C, int H, int W)
-{
-    if (modln_size_error(N, C, H, W)) return 0;
-    return modln_bwd_scratch_bytes(N, C, H * W) + 256;
-}
-extern "C" int igs_modln_fwd(void* stream, int N, int C, int H, int W, int x_dtype, const void* x, long long xs_n, long long xs_c, long long xs_h,
-                             long long xs_w, int mod_dtype, const void* mod, const float* weight, const float* bias, float eps, float* out,
-                             float* mean, float* rstd)
-{
-    const char* fn = "igs_modln_fwd";
-    if (const char* w = modln_size_error(N, C, H, W)) return lift_fail(fn, w);
-    if (!dtype_ok(x_dtype) || !dtype_ok(mod_dtype)) return lift_fail(fn, "unknown dtype code");
-    if (const char* w = lift_stride_error(C, H, W, xs_n, xs_c, xs_h, xs_w)) return lift_fail(fn, w);
-    if (!(eps >= 0.f)) return lift_fail(fn, "eps must be >= 0");
-    if ((mean == nullptr) != (rstd == nullptr)) return lift_fail(fn, "mean and rstd go together (both or neither)");
-    if (N == 0) return 0;
-    if (!x || !mod || !weight || !bias || !out) return lift_fail(fn, "NULL pointer");
-    HIP_TRY(launch_modln_fwd((hipStream_t)stream, N, C, H * W, x_dtype, x, (size_t)xs_n, (size_t)xs_c, mod_dtype, mod, weight, bias, eps, out, mean,
-                             rstd), "modln fwd launch");
-    return 0;
-}
-extern "C" int igs_modln_bwd(void* stream, int N, int C, int H, int W, int x_dtype, const void* x, long long xs_n, long long xs_c, long long xs_h,
-                             long long xs_w, int mod_dtype, const void* mod, const float* weight, const float* bias, const float* mean,
-                             const float* rstd, const float* gout, void* dx, void* dmod, float* dweight, float* dbias, void* scratch)
-{
-    const char* fn = "igs_modln_bwd";
-    if (const char* w = modln_size_error(N, C, H, W)) return lift_fail(fn, w);
-    if (!dtype_ok(x_dtype) || !dtype_ok(mod_dtype)) return lift_fail(fn, "unknown dtype code");
-    if (const char* w = lift_stride_error(C, H, W, xs_n, xs_c, xs_h, xs_w)) return lift_fail(fn, w);
-    if (N == 0 || (!dx && !dmod && !dweight && !dbias)) return 0;
-    if (!x || !mod || !weight || !bias || !mean || !rstd || !gout) return lift_fail(fn, "NULL pointer");
-    if ((dweight || dbias) && !scratch) return lift_fail(fn, "NULL pointer (scratch is required for d weight / d bias)");
-    HIP_TRY(launch_modln_bwd((hipStream_t)stream, N, C, H * W, x_dtype, x, (size_t)xs_n, (size_t)xs_c, mod_dtype, mod, weight, bias, mean, rstd, gout,
-                             dx, dmod, dweight, dbias, scratch), "modln bwd launch");
-    return 0;
-}
-
-// Test support: the per-tile sort of the slab binning on caller-made slabs (sort.hip: launch_tile_sort).  tile_count[T] instances per
-// tile (reset to zero by the launch), pairs[T * slab] = depth bits << 32 | Gaussian id, out: point_list[T * slab] (ids, sorted by the
-// 64-bit key inside every tile's slab), ranges[2 T], stats[4] ([1] = largest tile that overflowed its slab).  Everything device memory.
-extern "C" int igs_debug_tile_sort(void* stream, int T, uint32_t* tile_count, const unsigned long long* pairs, uint32_t* point_list,
-                                   uint32_t* ranges, int slab, uint32_t* stats, int P)
-{
-    if (T <= 0 || slab <= 0 || P <= 0) return fail(IGS_RAST_E_INVALID, "igs_debug_tile_sort: bad sizes");
-    if (!tile_count || !pairs || !point_list || !ranges || !stats) return fail(IGS_RAST_E_INVALID, "igs_debug_tile_sort: NULL pointer");
-    HIP_TRY(launch_tile_sort((hipStream_t)stream, (uint32_t)T, tile_count, (const uint64_t*)pairs, point_list, ranges, (uint32_t)slab, stats,
-                             nullptr, (uint32_t)P), "tile_sort launch");
-    return 0;
-}
-
 extern "C" int igs_rast_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix,
                                      const float* projmatrix, uint8_t* present)
 {
@@ -1371,56 +1068,4 @@ extern "C" int igs_rast_debug_poison_lds(void* stream)
     // is swept several times whatever the placement
     hipLaunchKernelGGL(poison_lds_kernel, dim3(2048), dim3(256), 64000, (hipStream_t)stream, (float*)nullptr);
     return hipGetLastError() == hipSuccess ? 0 : IGS_RAST_E_HIP;
-}
-
-extern "C" int igs_sh_grad_from_view_colors(void* stream, int P, int D, int M, int n_views, const float* means3D, const float* campos,
-                                            const float* color_grads, float clamp_grads, float* dL_dsh)
-{
-    if (P < 0 || M < 0 || M > 16 || D < 0 || D > 3 || n_views < 0 || n_views > IGS_MAX_EXCHANGE_VIEWS)
-        return fail(IGS_RAST_E_INVALID, "igs_sh_grad_from_view_colors: bad sizes (at most 64 views)");
-    if (P == 0 || M == 0) return 0;
-    if (!means3D || !dL_dsh || (n_views > 0 && (!campos || !color_grads))) return fail(IGS_RAST_E_INVALID, "igs_sh_grad_from_view_colors: NULL pointer");
-    HIP_TRY(launch_sh_grad_views((hipStream_t)stream, P, D, M, n_views, means3D, campos, color_grads, clamp_grads, dL_dsh), "sh_grad_views launch");
-    return 0;
-}
-
-extern "C" int igs_adam_sh_from_view_colors(void* stream, int P, int D, int M, int n_views, const float* means3D, const float* campos,
-                                            const float* color_grads, float clamp_grads, float* param_sh, float* exp_avg_sh, float* exp_avg_sq_sh,
-                                            float lr, float beta1, float beta2, float eps, float bias_correction1, float bias_correction2_sqrt)
-{
-    if (P < 0 || M < 0 || M > 16 || D < 0 || D > 3 || n_views < 0 || n_views > IGS_MAX_EXCHANGE_VIEWS)
-        return fail(IGS_RAST_E_INVALID, "igs_adam_sh_from_view_colors: bad sizes (at most 64 views)");
-    if (P == 0 || M == 0) return 0;
-    if (!means3D || !param_sh || !exp_avg_sh || !exp_avg_sq_sh || (n_views > 0 && (!campos || !color_grads)))
-        return fail(IGS_RAST_E_INVALID, "igs_adam_sh_from_view_colors: NULL pointer");
-    HIP_TRY(launch_sh_adam_views((hipStream_t)stream, P, D, M, n_views, means3D, campos, color_grads, clamp_grads, param_sh, exp_avg_sh, exp_avg_sq_sh,
-                                 lr / bias_correction1, beta1, beta2, eps, 1.0f / bias_correction2_sqrt), "sh_adam_views launch");
-    return 0;
-}
-
-// The whole optimiser step of an N > 1 rank in ONE launch (after the exchange): dL/dSH rebuilt from the gathered per-view colour
-// gradients and applied as in igs_adam_sh_from_view_colors, and the four small groups updated from their all-reduced gradients in
-// `grad` -- same arithmetic as igs_adam_step_groups.  param / exp_avg / exp_avg_sq / grad are the flat buffers of igs_refine_step,
-// off_* float offsets into them.  The directions use the positions as they are BEFORE this update (every thread reads its own
-// Gaussian's position first).
-extern "C" int igs_adam_exchange_step(void* stream, int P, int D, int M, int n_views, const float* campos, const float* color_grads,
-                                      float clamp_grads, float* param, float* exp_avg, float* exp_avg_sq, const float* grad,
-                                      size_t off_xyz, size_t off_rot, size_t off_sh, size_t off_opacity, size_t off_scale,
-                                      float lr_xyz, float lr_rot, float lr_sh, float lr_opacity, float lr_scale,
-                                      float beta1, float beta2, float eps, float bias_correction1, float bias_correction2_sqrt)
-{
-    if (P < 0 || M < 0 || M > 16 || D < 0 || D > 3 || n_views < 0 || n_views > IGS_MAX_EXCHANGE_VIEWS)
-        return fail(IGS_RAST_E_INVALID, "igs_adam_exchange_step: bad sizes (at most 64 views)");
-    if (P == 0) return 0;
-    if (!param || !exp_avg || !exp_avg_sq || !grad || (n_views > 0 && (!campos || !color_grads)))
-        return fail(IGS_RAST_E_INVALID, "igs_adam_exchange_step: NULL pointer");
-    SmallGroupsAdam sm;
-    sm.param = param; sm.exp_avg = exp_avg; sm.exp_avg_sq = exp_avg_sq; sm.grad = grad;
-    sm.off[0] = off_xyz; sm.off[1] = off_rot; sm.off[2] = off_opacity; sm.off[3] = off_scale;
-    sm.lr_over_bc1[0] = lr_xyz / bias_correction1; sm.lr_over_bc1[1] = lr_rot / bias_correction1;
-    sm.lr_over_bc1[2] = lr_opacity / bias_correction1; sm.lr_over_bc1[3] = lr_scale / bias_correction1;
-    HIP_TRY(launch_sh_adam_views((hipStream_t)stream, P, D, M, n_views, param + off_xyz, campos, color_grads, clamp_grads, param + off_sh,
-                                 exp_avg + off_sh, exp_avg_sq + off_sh, lr_sh / bias_correction1, beta1, beta2, eps, 1.0f / bias_correction2_sqrt,
-                                 &sm), "adam_exchange_step launch");
-    return 0;
 }

@@ -144,43 +144,6 @@ hipError_t launch_mark_visible(hipStream_t s, int P, const float* means3D, const
 // except table 0, which the producer of keys_a filled with the first pass's per-block digit counts.
 hipError_t radix_sort_pairs(hipStream_t s, uint32_t n, uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a, uint32_t* vals_b,
                             uint32_t* hist, int bit_lo, int bit_hi, uint32_t** out_keys, uint32_t** out_vals);
-size_t morton_scratch_bytes(int P);
-hipError_t launch_morton_order(hipStream_t s, int P, const float* xyz, const float* lohi, int bits, void* scratch, int* perm);
-size_t knn_scratch_bytes(int P);
-hipError_t launch_knn_mean_dist2(hipStream_t s, int P, const float* xyz, void* scratch, float* out);    // knn.hip
-hipError_t launch_knn_bbox(hipStream_t s, int P, const float* xyz, float* part, float* lohi);          // knn.hip (phase 1 alone)
-size_t select_scratch_bytes(int N);                                                                      // anchors.hip
-hipError_t launch_bbox_select(hipStream_t s, int B, int N, const float* xyz, const int* ptr, const float* box, void* scratch,
-                              float* out_xyz, int64_t* out_idx, int* count);
-size_t fps_scratch_bytes(int B, int N, int max_n);
-hipError_t launch_fps(hipStream_t s, int B, int N, int max_n, const float* xyz, const int* ptr, const int* start, const int* out_ptr,
-                      int total, float init_d2, void* scratch, int64_t* out);
-hipError_t launch_knn_query(hipStream_t s, int Nx, int Ny, int B, const float* x, const float* y, const int* ptr_x, const int* ptr_y,
-                            int k, float scale, int64_t* out_idx, float* out_d2, float* out_w);
-hipError_t launch_interp_fwd(hipStream_t s, int N, int K, int D, int A, int dtype, const void* F, const int64_t* col, const float* w,
-                             float* out);                                                                // motion.hip
-size_t interp_scratch_bytes(int N, int K, int A, int D);
-hipError_t launch_interp_index(hipStream_t s, int N, int K, int A, int D, const int64_t* col, void* scratch);
-hipError_t launch_interp_bwd(hipStream_t s, int N, int K, int D, int A, int dtype, const void* F, const float* w, const float* dout,
-                             void* scratch, void* dF, float* dw);
-size_t lift_scratch_bytes(int B, int V, int A, int H, int W, bool backward);                             // lift.hip
-hipError_t launch_lift_fwd(hipStream_t s, int B, int V, int A, int C, int H, int W, int dtype, const void* feat, size_t fs_n, size_t fs_c,
-                           const float* points, const float* w2c, const float* intr, float* out, size_t os_a, size_t os_c, void* scratch);
-hipError_t launch_lift_bwd(hipStream_t s, int B, int V, int A, int C, int H, int W, int dtype, const float* points, const float* w2c,
-                           const float* intr, const float* dout, size_t gs_a, size_t gs_c, void* dfeat, size_t fs_n, size_t fs_c,
-                           void* scratch);
-hipError_t launch_ray_condition(hipStream_t s, int N, int H, int W, int Hd, int Wd, const float* rays, const float* depth,
-                                float* cond);                                                            // cond.hip
-hipError_t launch_modln_fwd(hipStream_t s, int N, int C, int HW, int x_dtype, const void* x, size_t xs_n, size_t xs_c, int mod_dtype,
-                            const void* mod, const float* w, const float* b, float eps, float* out, float* mean, float* rstd);
-size_t modln_bwd_scratch_bytes(int N, int C, int HW);
-hipError_t launch_modln_bwd(hipStream_t s, int N, int C, int HW, int x_dtype, const void* x, size_t xs_n, size_t xs_c, int mod_dtype,
-                            const void* mod, const float* w, const float* b, const float* mean, const float* rstd, const float* gout, void* dx,
-                            void* dmod, float* dw, float* db, void* scratch);
-hipError_t launch_deform_fwd(hipStream_t s, int P, int M, int dtype, const float* xyz, const float* rot, const int64_t* mask,
-                             const void* dxyz, const void* drot, float* xyz_out, float* rot_out);
-hipError_t launch_deform_bwd(hipStream_t s, int P, int M, int dtype, const float* rot, const int64_t* mask, const void* drot,
-                             const float* g_xyz, const float* g_rot, float* d_xyz, float* d_rot, void* d_dxyz, void* d_drot);
 hipError_t launch_count_sorted(hipStream_t s, int P, const uint32_t* order, const uint32_t* tiles, uint32_t* blocksum);
 hipError_t launch_scan_blocksums(hipStream_t s, int nblocks, uint32_t* blocksum);
 hipError_t launch_emit_instances(hipStream_t s, int P, int gx, int gy, const uint32_t* order, const uint32_t* tiles,
@@ -276,14 +239,6 @@ struct RefineFuse {
 };
 hipError_t launch_geom_bwd_adam(hipStream_t s, const GeomBwdArgs& a, const RefineFuse& f);
 hipError_t launch_extract_view_colors(hipStream_t s, int P, const int* radii, const float* rec, const double* gacc, int gacc_compact, bool have_sh, float* color_out);
-#define IGS_MAX_EXCHANGE_VIEWS 64
-hipError_t launch_sh_grad_views(hipStream_t s, int P, int D, int M, int V, const float* means3D, const float* campos_host, const float* gc,
-                                float clamp, float* dsh_out);
-// flat optimiser state + flat gradient and the float offsets of {xyz, rotation, opacity, scale} in them (lr already divided by bias_correction1)
-struct SmallGroupsAdam { float *param, *exp_avg, *exp_avg_sq; const float* grad; size_t off[4]; float lr_over_bc1[4]; };
-hipError_t launch_sh_adam_views(hipStream_t s, int P, int D, int M, int V, const float* means3D, const float* campos_host, const float* gc,
-                                float clamp, float* param_sh, float* exp_avg_sh, float* exp_avg_sq_sh, float lr_over_bc1, float b1, float b2,
-                                float eps, float inv_sqrt_bc2, const SmallGroupsAdam* sm = nullptr);
 hipError_t launch_depth_normal(hipStream_t s, int W, int H, float fx, float fy, const float* depth, const float* mdepth, const float* normal,
                                float weight, float depth_ratio, float* g_depth, float* g_mdepth, float* g_normal, float* loss_shards);
 // 0.8 L1 + 0.2 (1 - SSIM)-style loss, forward + backward (loss_ops.hip); scratch: igs_ssim_l1_scratch_bytes

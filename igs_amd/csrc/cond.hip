@@ -14,7 +14,7 @@
 //       the pixel pass; every workgroup leaves one row of d weight / d bias partial sums, modln_param_reduce_kernel adds the rows in
 //       workgroup order (in two rounds): no float atomics, bitwise reproducible.
 #include "common.h"
-#include "../../include/igs_rast.h"
+#include "host_api.h"
 
 #define COND_THREADS 256
 #define COND_CH 33
@@ -113,7 +113,7 @@ ray_condition_kernel(uint32_t NPIX, int H, int W, int Hd, int Wd, float sy, floa
     for (uint32_t i = tid; i < count; i += COND_THREADS) dst[i] = tile[i];
 }
 
-hipError_t launch_ray_condition(hipStream_t s, int N, int H, int W, int Hd, int Wd, const float* rays, const float* depth, float* cond)
+static hipError_t launch_ray_condition(hipStream_t s, int N, int H, int W, int Hd, int Wd, const float* rays, const float* depth, float* cond)
 {
     const uint32_t NPIX = (uint32_t)((size_t)N * H * W);
     hipLaunchKernelGGL(ray_condition_kernel, dim3((NPIX + COND_THREADS - 1) / COND_THREADS), dim3(COND_THREADS), 0, s, NPIX, H, W, Hd, Wd,
@@ -256,8 +256,8 @@ static ModlnVec modln_vec(int C, int HW, int x_dtype, const void* x, size_t xs_n
     return v;
 }
 
-hipError_t launch_modln_fwd(hipStream_t s, int N, int C, int HW, int x_dtype, const void* x, size_t xs_n, size_t xs_c, int mod_dtype,
-                            const void* mod, const float* w, const float* b, float eps, float* out, float* mean, float* rstd)
+static hipError_t launch_modln_fwd(hipStream_t s, int N, int C, int HW, int x_dtype, const void* x, size_t xs_n, size_t xs_c, int mod_dtype,
+                                   const void* mod, const float* w, const float* b, float eps, float* out, float* mean, float* rstd)
 {
     const int lp = modln_tile_log2(C, 1, 6), P = 1 << lp, tpi = (HW + P - 1) / P;
     const size_t lds = modln_lds_bytes(C, P, 1);
@@ -277,7 +277,7 @@ hipError_t launch_modln_fwd(hipStream_t s, int N, int C, int HW, int x_dtype, co
 // ---------------------------------------------------------------------------------------------------------------------------------
 static int modln_bwd_log2(int C) { return modln_tile_log2(C, 2, 5); }
 static size_t modln_bwd_tiles(int N, int C, int HW) { const int P = 1 << modln_bwd_log2(C); return (size_t)N * ((HW + P - 1) / P); }
-size_t modln_bwd_scratch_bytes(int N, int C, int HW) { return align_up((modln_bwd_tiles(N, C, HW) + MODLN_REDUCE_GROUPS) * 2 * C * 4, 256) + 256; }
+static size_t modln_bwd_scratch_bytes(int N, int C, int HW) { return align_up((modln_bwd_tiles(N, C, HW) + MODLN_REDUCE_GROUPS) * 2 * C * 4, 256) + 256; }
 
 // With xh = (x - mu) r, y = xh w + b, gh = g (1 + scale):  d shift = g, d scale = g y, d weight = sum gh xh, d bias = sum gh,
 // d x = r (gh w - mean_c(gh w) - xh mean_c(gh w xh)).  part[(tile * 2 + 0) * C + c] / [(tile * 2 + 1) * C + c]: the tile's sums over its pixels.
@@ -425,9 +425,9 @@ modln_param_reduce_kernel(int C, uint32_t T, const float* __restrict__ part, flo
     }
 }
 
-hipError_t launch_modln_bwd(hipStream_t s, int N, int C, int HW, int x_dtype, const void* x, size_t xs_n, size_t xs_c, int mod_dtype,
-                            const void* mod, const float* w, const float* b, const float* mean, const float* rstd, const float* gout, void* dx,
-                            void* dmod, float* dw, float* db, void* scratch)
+static hipError_t launch_modln_bwd(hipStream_t s, int N, int C, int HW, int x_dtype, const void* x, size_t xs_n, size_t xs_c, int mod_dtype,
+                                   const void* mod, const float* w, const float* b, const float* mean, const float* rstd, const float* gout, void* dx,
+                                   void* dmod, float* dw, float* db, void* scratch)
 {
     const int lp = modln_bwd_log2(C), P = 1 << lp, tpi = (HW + P - 1) / P;
     const size_t lds = modln_lds_bytes(C, P, 2);
@@ -452,4 +452,65 @@ hipError_t launch_modln_bwd(hipStream_t s, int N, int C, int HW, int x_dtype, co
     hipLaunchKernelGGL(modln_param_reduce_kernel, dim3((C + 63) / 64, 2, 1), rb, 0, s, C, (uint32_t)MODLN_REDUCE_GROUPS, (const float*)part2, dw, db,
                        (size_t)0);
     return hipGetLastError();
+}
+
+// the entry points (the contract is in include/igs_rast.h)
+extern "C" int igs_ray_condition_fwd(void* stream, int N, int H, int W, int Hd, int Wd, const float* rays, const float* depth, float* cond)
+{
+    const char* fn = "igs_ray_condition_fwd";
+    if (N < 0 || N > IGS_COND_MAX_PIXELS) return fail_in(fn, "N out of range");
+    if (H < 1 || H > IGS_COND_MAX_HW) return fail_in(fn, "H out of range (1..IGS_COND_MAX_HW)");
+    if (W < 1 || W > IGS_COND_MAX_HW) return fail_in(fn, "W out of range (1..IGS_COND_MAX_HW)");
+    if (Hd < 1 || Hd > IGS_COND_MAX_HW) return fail_in(fn, "Hd out of range (1..IGS_COND_MAX_HW)");
+    if (Wd < 1 || Wd > IGS_COND_MAX_HW) return fail_in(fn, "Wd out of range (1..IGS_COND_MAX_HW)");
+    if ((long long)N * H * W > IGS_COND_MAX_PIXELS) return fail_in(fn, "N * H * W out of range (IGS_COND_MAX_PIXELS)");
+    if (N == 0) return 0;
+    if (!rays || !depth || !cond) return fail_in(fn, "NULL pointer");
+    HIP_TRY(launch_ray_condition((hipStream_t)stream, N, H, W, Hd, Wd, rays, depth, cond), "ray condition launch");
+    return 0;
+}
+static const char* modln_size_error(int N, int C, int H, int W)
+{
+    if (N < 0 || N > IGS_COND_MAX_PIXELS) return "N out of range";
+    if (C < 1 || C > IGS_MODLN_MAX_C) return "C out of range (1..IGS_MODLN_MAX_C)";
+    if (H < 1 || H > IGS_COND_MAX_HW) return "H out of range (1..IGS_COND_MAX_HW)";
+    if (W < 1 || W > IGS_COND_MAX_HW) return "W out of range (1..IGS_COND_MAX_HW)";
+    if ((long long)N * H * W > IGS_COND_MAX_PIXELS) return "N * H * W out of range (IGS_COND_MAX_PIXELS)";
+    return nullptr;
+}
+extern "C" size_t igs_modln_bwd_scratch_bytes(int N, int C, int H, int W)
+{
+    if (modln_size_error(N, C, H, W)) return 0;
+    return modln_bwd_scratch_bytes(N, C, H * W) + 256;
+}
+extern "C" int igs_modln_fwd(void* stream, int N, int C, int H, int W, int x_dtype, const void* x, long long xs_n, long long xs_c, long long xs_h,
+                             long long xs_w, int mod_dtype, const void* mod, const float* weight, const float* bias, float eps, float* out,
+                             float* mean, float* rstd)
+{
+    const char* fn = "igs_modln_fwd";
+    if (const char* w = modln_size_error(N, C, H, W)) return fail_in(fn, w);
+    if (!dtype_ok(x_dtype) || !dtype_ok(mod_dtype)) return fail_in(fn, "unknown dtype code");
+    if (const char* w = plane_stride_error(C, H, W, xs_n, xs_c, xs_h, xs_w)) return fail_in(fn, w);
+    if (!(eps >= 0.f)) return fail_in(fn, "eps must be >= 0");
+    if ((mean == nullptr) != (rstd == nullptr)) return fail_in(fn, "mean and rstd go together (both or neither)");
+    if (N == 0) return 0;
+    if (!x || !mod || !weight || !bias || !out) return fail_in(fn, "NULL pointer");
+    HIP_TRY(launch_modln_fwd((hipStream_t)stream, N, C, H * W, x_dtype, x, (size_t)xs_n, (size_t)xs_c, mod_dtype, mod, weight, bias, eps, out, mean,
+                             rstd), "modln fwd launch");
+    return 0;
+}
+extern "C" int igs_modln_bwd(void* stream, int N, int C, int H, int W, int x_dtype, const void* x, long long xs_n, long long xs_c, long long xs_h,
+                             long long xs_w, int mod_dtype, const void* mod, const float* weight, const float* bias, const float* mean,
+                             const float* rstd, const float* gout, void* dx, void* dmod, float* dweight, float* dbias, void* scratch)
+{
+    const char* fn = "igs_modln_bwd";
+    if (const char* w = modln_size_error(N, C, H, W)) return fail_in(fn, w);
+    if (!dtype_ok(x_dtype) || !dtype_ok(mod_dtype)) return fail_in(fn, "unknown dtype code");
+    if (const char* w = plane_stride_error(C, H, W, xs_n, xs_c, xs_h, xs_w)) return fail_in(fn, w);
+    if (N == 0 || (!dx && !dmod && !dweight && !dbias)) return 0;
+    if (!x || !mod || !weight || !bias || !mean || !rstd || !gout) return fail_in(fn, "NULL pointer");
+    if ((dweight || dbias) && !scratch) return fail_in(fn, "NULL pointer (scratch is required for d weight / d bias)");
+    HIP_TRY(launch_modln_bwd((hipStream_t)stream, N, C, H * W, x_dtype, x, (size_t)xs_n, (size_t)xs_c, mod_dtype, mod, weight, bias, mean, rstd, gout,
+                             dx, dmod, dweight, dbias, scratch), "modln bwd launch");
+    return 0;
 }

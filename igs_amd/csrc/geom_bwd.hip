@@ -11,7 +11,7 @@
 //  * the conic backward adds kernel_size to a and c, the forward conic does not (backward.cu:377-379);
 //  * no quaternion-normalisation backward (backward.cu:554).
 #include "geom_math.h"
-#include "../../include/igs_rast.h"      // IGS_GROUP_* (masked refine step)
+#include "host_api.h"      // (also include/igs_rast.h: IGS_GROUP_*, masked refine step)
 
 __constant__ float BSH_C0 = 0.28209479177387814f;
 __constant__ float BSH_C1 = 0.4886025119029199f;
@@ -153,6 +153,7 @@ __device__ __forceinline__ float3 sh_backward_dir_only(int deg, const float* __r
 // gather the 3-float colour gradients of every view (12 bytes per Gaussian and view) instead of all-reducing the 48-float SH
 // gradients, and every rank rebuilds the sum here, views in rank order -- the same bits everywhere.  The basis expressions
 // and the order of operations are those of sh_backward above (W(k, b): b * g, then clamp for the clamp variant, then the sum).
+#define IGS_MAX_EXCHANGE_VIEWS 64
 struct ShViewCams { float pos[3 * IGS_MAX_EXCHANGE_VIEWS]; };
 struct ShAdam { float *param, *exp_avg, *exp_avg_sq; float lr_over_bc1, b1, b2, eps, inv_sqrt_bc2;     // SH spans ([P][M][3]) of the optimiser state
                 // optional: the four small groups (xyz 3 | rotation 4 | opacity 1 | scale 3 floats per Gaussian) updated by the same
@@ -279,8 +280,8 @@ sh_grad_views_kernel(int P, int D, int M, int V, const float* __restrict__ means
         if (k < M) { dst[3 * k] = acc[3 * k]; dst[3 * k + 1] = acc[3 * k + 1]; dst[3 * k + 2] = acc[3 * k + 2]; }
 }
 
-hipError_t launch_sh_grad_views(hipStream_t s, int P, int D, int M, int V, const float* means3D, const float* campos_host, const float* gc,
-                                float clamp, float* dsh_out)
+static hipError_t launch_sh_grad_views(hipStream_t s, int P, int D, int M, int V, const float* means3D, const float* campos_host, const float* gc,
+                                       float clamp, float* dsh_out)
 {
     ShViewCams cams;                                  // camera centres travel in the kernel arguments: no device buffer, no copy
     for (int i = 0; i < 3 * V; i++) cams.pos[i] = campos_host[i];
@@ -288,9 +289,11 @@ hipError_t launch_sh_grad_views(hipStream_t s, int P, int D, int M, int V, const
     return hipGetLastError();
 }
 
-hipError_t launch_sh_adam_views(hipStream_t s, int P, int D, int M, int V, const float* means3D, const float* campos_host, const float* gc,
-                                float clamp, float* param_sh, float* exp_avg_sh, float* exp_avg_sq_sh, float lr_over_bc1, float b1, float b2,
-                                float eps, float inv_sqrt_bc2, const SmallGroupsAdam* sm)
+// flat optimiser state + flat gradient and the float offsets of {xyz, rotation, opacity, scale} in them (lr already divided by bias_correction1)
+struct SmallGroupsAdam { float *param, *exp_avg, *exp_avg_sq; const float* grad; size_t off[4]; float lr_over_bc1[4]; };
+static hipError_t launch_sh_adam_views(hipStream_t s, int P, int D, int M, int V, const float* means3D, const float* campos_host, const float* gc,
+                                       float clamp, float* param_sh, float* exp_avg_sh, float* exp_avg_sq_sh, float lr_over_bc1, float b1, float b2,
+                                       float eps, float inv_sqrt_bc2, const SmallGroupsAdam* sm = nullptr)
 {
     ShViewCams cams;
     for (int i = 0; i < 3 * V; i++) cams.pos[i] = campos_host[i];
@@ -302,6 +305,59 @@ hipError_t launch_sh_adam_views(hipStream_t s, int P, int D, int M, int V, const
     }
     hipLaunchKernelGGL(sh_grad_views_kernel<true>, dim3((P + 127) / 128), dim3(128), 0, s, P, D, M, V, means3D, cams, gc, clamp, (float*)nullptr, ad);
     return hipGetLastError();
+}
+
+// the N > 1 exchange's entry points (the contracts are in include/igs_rast.h)
+extern "C" int igs_sh_grad_from_view_colors(void* stream, int P, int D, int M, int n_views, const float* means3D, const float* campos,
+                                            const float* color_grads, float clamp_grads, float* dL_dsh)
+{
+    if (P < 0 || M < 0 || M > 16 || D < 0 || D > 3 || n_views < 0 || n_views > IGS_MAX_EXCHANGE_VIEWS)
+        return fail(IGS_RAST_E_INVALID, "igs_sh_grad_from_view_colors: bad sizes (at most 64 views)");
+    if (P == 0 || M == 0) return 0;
+    if (!means3D || !dL_dsh || (n_views > 0 && (!campos || !color_grads))) return fail(IGS_RAST_E_INVALID, "igs_sh_grad_from_view_colors: NULL pointer");
+    HIP_TRY(launch_sh_grad_views((hipStream_t)stream, P, D, M, n_views, means3D, campos, color_grads, clamp_grads, dL_dsh), "sh_grad_views launch");
+    return 0;
+}
+
+extern "C" int igs_adam_sh_from_view_colors(void* stream, int P, int D, int M, int n_views, const float* means3D, const float* campos,
+                                            const float* color_grads, float clamp_grads, float* param_sh, float* exp_avg_sh, float* exp_avg_sq_sh,
+                                            float lr, float beta1, float beta2, float eps, float bias_correction1, float bias_correction2_sqrt)
+{
+    if (P < 0 || M < 0 || M > 16 || D < 0 || D > 3 || n_views < 0 || n_views > IGS_MAX_EXCHANGE_VIEWS)
+        return fail(IGS_RAST_E_INVALID, "igs_adam_sh_from_view_colors: bad sizes (at most 64 views)");
+    if (P == 0 || M == 0) return 0;
+    if (!means3D || !param_sh || !exp_avg_sh || !exp_avg_sq_sh || (n_views > 0 && (!campos || !color_grads)))
+        return fail(IGS_RAST_E_INVALID, "igs_adam_sh_from_view_colors: NULL pointer");
+    HIP_TRY(launch_sh_adam_views((hipStream_t)stream, P, D, M, n_views, means3D, campos, color_grads, clamp_grads, param_sh, exp_avg_sh, exp_avg_sq_sh,
+                                 lr / bias_correction1, beta1, beta2, eps, 1.0f / bias_correction2_sqrt), "sh_adam_views launch");
+    return 0;
+}
+
+// The whole optimiser step of an N > 1 rank in ONE launch (after the exchange): dL/dSH rebuilt from the gathered per-view colour
+// gradients and applied as in igs_adam_sh_from_view_colors, and the four small groups updated from their all-reduced gradients in
+// `grad` -- same arithmetic as igs_adam_step_groups.  param / exp_avg / exp_avg_sq / grad are the flat buffers of igs_refine_step,
+// off_* float offsets into them.  The directions use the positions as they are BEFORE this update (every thread reads its own
+// Gaussian's position first).
+extern "C" int igs_adam_exchange_step(void* stream, int P, int D, int M, int n_views, const float* campos, const float* color_grads,
+                                      float clamp_grads, float* param, float* exp_avg, float* exp_avg_sq, const float* grad,
+                                      size_t off_xyz, size_t off_rot, size_t off_sh, size_t off_opacity, size_t off_scale,
+                                      float lr_xyz, float lr_rot, float lr_sh, float lr_opacity, float lr_scale,
+                                      float beta1, float beta2, float eps, float bias_correction1, float bias_correction2_sqrt)
+{
+    if (P < 0 || M < 0 || M > 16 || D < 0 || D > 3 || n_views < 0 || n_views > IGS_MAX_EXCHANGE_VIEWS)
+        return fail(IGS_RAST_E_INVALID, "igs_adam_exchange_step: bad sizes (at most 64 views)");
+    if (P == 0) return 0;
+    if (!param || !exp_avg || !exp_avg_sq || !grad || (n_views > 0 && (!campos || !color_grads)))
+        return fail(IGS_RAST_E_INVALID, "igs_adam_exchange_step: NULL pointer");
+    SmallGroupsAdam sm;
+    sm.param = param; sm.exp_avg = exp_avg; sm.exp_avg_sq = exp_avg_sq; sm.grad = grad;
+    sm.off[0] = off_xyz; sm.off[1] = off_rot; sm.off[2] = off_opacity; sm.off[3] = off_scale;
+    sm.lr_over_bc1[0] = lr_xyz / bias_correction1; sm.lr_over_bc1[1] = lr_rot / bias_correction1;
+    sm.lr_over_bc1[2] = lr_opacity / bias_correction1; sm.lr_over_bc1[3] = lr_scale / bias_correction1;
+    HIP_TRY(launch_sh_adam_views((hipStream_t)stream, P, D, M, n_views, param + off_xyz, campos, color_grads, clamp_grads, param + off_sh,
+                                 exp_avg + off_sh, exp_avg_sq + off_sh, lr_sh / bias_correction1, beta1, beta2, eps, 1.0f / bias_correction2_sqrt,
+                                 &sm), "adam_exchange_step launch");
+    return 0;
 }
 
 struct GBArgs { GeomBwdArgs a; RefineFuse f; };

@@ -23,6 +23,7 @@
 // and under any permutation of the input.
 #include "common.h"
 #include "knn_common.h"
+#include "host_api.h"
 #include <float.h>
 
 #define KNN_K 3                    // neighbours averaged (simple-knn: best[3]); the insertion below is written for 3
@@ -260,9 +261,9 @@ knn_query_kernel(int P, int L, int Nn, const float4* __restrict__ pts, const flo
     if (s < P) out[perm[s]] = (w.b0 + w.b1 + w.b2) / 3.0f;       // simple-knn: (best[0] + best[1] + best[2]) / 3.0f, left to right
 }
 
-size_t knn_scratch_bytes(int P) { return KnnLayout(P).total; }
+static size_t knn_scratch_bytes(int P) { return KnnLayout(P).total; }
 
-hipError_t launch_knn_mean_dist2(hipStream_t s, int P, const float* xyz, void* scratch, float* out)
+static hipError_t launch_knn_mean_dist2(hipStream_t s, int P, const float* xyz, void* scratch, float* out)
 {
     if (P <= 0) return hipSuccess;
     const KnnLayout K(P);
@@ -300,6 +301,20 @@ hipError_t launch_knn_mean_dist2(hipStream_t s, int P, const float* xyz, void* s
     hipLaunchKernelGGL(knn_query_kernel, gl, dim3(256), 0, s, P, K.L, K.Nn, (const float4*)pts, (const float4*)leafbox,
                        (const float4*)nodebox, (const uint32_t*)sv, out);
     return hipGetLastError();
+}
+// the entry points (the contract is in include/igs_rast.h)
+extern "C" size_t igs_knn_scratch_bytes(int P)
+{
+    if (P < 0 || P > IGS_KNN_MAX_POINTS) return 0;
+    return knn_scratch_bytes(P) + 256;
+}
+extern "C" int igs_knn_mean_dist2(void* stream, int P, const float* xyz, void* scratch, float* out)
+{
+    if (P < 0 || P > IGS_KNN_MAX_POINTS) return fail(IGS_RAST_E_INVALID, "igs_knn_mean_dist2: P out of range (0..IGS_KNN_MAX_POINTS)");
+    if (P == 0) return 0;
+    if (!xyz || !scratch || !out) return fail(IGS_RAST_E_INVALID, "igs_knn_mean_dist2: NULL pointer");
+    HIP_TRY(launch_knn_mean_dist2((hipStream_t)stream, P, xyz, scratch, out), "knn launch");
+    return 0;
 }
 
 // phase 1 alone, for anchors.hip: lohi[6] = box of the finite points of xyz[P], part: KNN_BBOX_PARTS * 8 floats of scratch

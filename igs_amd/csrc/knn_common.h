@@ -5,6 +5,8 @@
 
 #define KNN_BITS 21                // Morton bits per axis
 #define KNN_BBOX_PARTS 1024        // phase-1 partial boxes (one wave each)
+// knn.hip, phase 1 alone: lohi[6] = box of the finite points of xyz[P], part: KNN_BBOX_PARTS * 8 floats of scratch
+hipError_t launch_knn_bbox(hipStream_t s, int P, const float* xyz, float* part, float* lohi);
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 

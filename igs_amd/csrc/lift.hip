@@ -15,7 +15,7 @@
 //       per sorted edge; lift_bwd_kernel, one workgroup per (b, v, LIFT_BWD_CH channels), holds d out[b, c, :] in LDS and every thread
 //       sums the edges of its pixels in list order and writes d feat coalesced, every element (zero where no sample landed).
 #include "common.h"
-#include "../../include/igs_rast.h"
+#include "host_api.h"
 
 #define LIFT_THREADS 512              // forward workgroup
 #define LIFT_APT 8                    // anchors per thread, accumulated in registers
@@ -66,7 +66,7 @@ struct LiftLayout {            // offsets from a 256-byte aligned base; the inde
     }
 };
 
-size_t lift_scratch_bytes(int B, int V, int A, int H, int W, bool backward) { return LiftLayout(B, V, A, H, W, backward).total; }
+static size_t lift_scratch_bytes(int B, int V, int A, int H, int W, bool backward) { return LiftLayout(B, V, A, H, W, backward).total; }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // (1) the sample table
@@ -178,8 +178,8 @@ lift_fwd_kernel(int V, int A, int C, int H, int W, int band_rows, int nchunk, co
 
 static int lift_band_rows(int H, int W) { const int r = LIFT_LDS_FLOATS / W; return r < H ? r : H; }
 
-hipError_t launch_lift_fwd(hipStream_t s, int B, int V, int A, int C, int H, int W, int dtype, const void* feat, size_t fs_n, size_t fs_c,
-                           const float* points, const float* w2c, const float* intr, float* out, size_t os_a, size_t os_c, void* scratch)
+static hipError_t launch_lift_fwd(hipStream_t s, int B, int V, int A, int C, int H, int W, int dtype, const void* feat, size_t fs_n, size_t fs_c,
+                                  const float* points, const float* w2c, const float* intr, float* out, size_t os_a, size_t os_c, void* scratch)
 {
     const LiftLayout L(B, V, A, H, W, false);
     char* base = align_ptr((const char*)scratch);
@@ -289,9 +289,9 @@ lift_bwd_kernel(int V, int A, int C, int HW, int ncg, int use_lds, const uint32_
     }
 }
 
-hipError_t launch_lift_bwd(hipStream_t s, int B, int V, int A, int C, int H, int W, int dtype, const float* points, const float* w2c,
-                           const float* intr, const float* dout, size_t gs_a, size_t gs_c, void* dfeat, size_t fs_n, size_t fs_c,
-                           void* scratch)
+static hipError_t launch_lift_bwd(hipStream_t s, int B, int V, int A, int C, int H, int W, int dtype, const float* points, const float* w2c,
+                                  const float* intr, const float* dout, size_t gs_a, size_t gs_c, void* dfeat, size_t fs_n, size_t fs_c,
+                                  void* scratch)
 {
     const LiftLayout L(B, V, A, H, W, true);
     char* base = align_ptr((const char*)scratch);
@@ -326,4 +326,70 @@ hipError_t launch_lift_bwd(hipStream_t s, int B, int V, int A, int C, int H, int
         hipLaunchKernelGGL((lift_bwd_kernel<float>), g, blk, lds, s, V, A, C, H * W, ncg, use_lds, (const uint32_t*)start, (const uint32_t*)ea,
                            (const float*)ew, dout, gs_a, gs_c, (float*)dfeat, fs_n, fs_c);
     return hipGetLastError();
+}
+
+// the entry points (the contract is in include/igs_rast.h)
+static const char* lift_size_error(int B, int V, int A, int C, int H, int W)
+{
+    if (B < 0 || B > IGS_LIFT_MAX_SAMPLES) return "B out of range";
+    if (V < 1 || V > IGS_LIFT_MAX_V) return "V out of range (1..IGS_LIFT_MAX_V)";
+    if (A < 0 || A > IGS_LIFT_MAX_SAMPLES) return "A out of range";
+    if (C < 1 || C > IGS_LIFT_MAX_C) return "C out of range (1..IGS_LIFT_MAX_C)";
+    if (H < 1 || H > IGS_LIFT_MAX_HW) return "H out of range (1..IGS_LIFT_MAX_HW)";
+    if (W < 1 || W > IGS_LIFT_MAX_HW) return "W out of range (1..IGS_LIFT_MAX_HW)";
+    if ((long long)B * A > IGS_LIFT_MAX_SAMPLES) return "B * A out of range (IGS_LIFT_MAX_SAMPLES)";
+    if ((long long)B * V * H * W > IGS_LIFT_MAX_PIXELS) return "B * V * H * W out of range (IGS_LIFT_MAX_PIXELS)";
+    return nullptr;
+}
+extern "C" size_t igs_anchor_lift_scratch_bytes(int B, int V, int A, int C, int H, int W, int dtype)
+{
+    if (lift_size_error(B, V, A, C, H, W) || !dtype_ok(dtype)) return 0;
+    return lift_scratch_bytes(B, V, A, H, W, false) + 256;
+}
+extern "C" size_t igs_anchor_lift_bwd_scratch_bytes(int B, int V, int A, int C, int H, int W, int dtype)
+{
+    if (lift_size_error(B, V, A, C, H, W) || !dtype_ok(dtype)) return 0;
+    return lift_scratch_bytes(B, V, A, H, W, true) + 256;
+}
+extern "C" int igs_anchor_lift_fwd(void* stream, int B, int V, int A, int C, int H, int W, int dtype, const void* feat, long long fs_n,
+                                   long long fs_c, long long fs_h, long long fs_w, const float* points, const float* w2c, const float* intr,
+                                   float* out, long long os_a, long long os_c, void* scratch)
+{
+    const char* fn = "igs_anchor_lift_fwd";
+    if (const char* w = lift_size_error(B, V, A, C, H, W)) return fail_in(fn, w);
+    if (!dtype_ok(dtype)) return fail_in(fn, "unknown dtype code");
+    if (const char* w = plane_stride_error(C, H, W, fs_n, fs_c, fs_h, fs_w)) return fail_in(fn, w);
+    if (!((os_a == 1 && os_c == A) || (os_c == 1 && os_a == C))) return fail_in(fn, "output strides must be (os_a, os_c) = (1, A) or (C, 1)");
+    if (A == 0 || B == 0) return 0;
+    if (!feat || !points || !w2c || !intr || !out || !scratch) return fail_in(fn, "NULL pointer");
+    HIP_TRY(launch_lift_fwd((hipStream_t)stream, B, V, A, C, H, W, dtype, feat, (size_t)fs_n, (size_t)fs_c, points, w2c, intr, out, (size_t)os_a,
+                            (size_t)os_c, scratch), "anchor lift fwd launch");
+    return 0;
+}
+extern "C" int igs_anchor_lift_bwd(void* stream, int B, int V, int A, int C, int H, int W, int dtype, const float* points, const float* w2c,
+                                   const float* intr, const float* dout, long long gs_a, long long gs_c, void* dfeat, long long fs_n,
+                                   long long fs_c, long long fs_h, long long fs_w, void* scratch)
+{
+    const char* fn = "igs_anchor_lift_bwd";
+    if (const char* w = lift_size_error(B, V, A, C, H, W)) return fail_in(fn, w);
+    if (!dtype_ok(dtype)) return fail_in(fn, "unknown dtype code");
+    if (const char* w = plane_stride_error(C, H, W, fs_n, fs_c, fs_h, fs_w)) return fail_in(fn, w);
+    if (fs_c < (long long)H * W || fs_n < fs_c * C) return fail_in(fn, "d feat planes overlap (fs_c >= H * W and fs_n >= C * fs_c required)");
+    if (!((gs_a == 1 && gs_c == A) || (gs_c == 1 && gs_a == C))) return fail_in(fn, "d out strides must be (gs_a, gs_c) = (1, A) or (C, 1)");
+    if (B == 0) return 0;
+    if (!dfeat) return fail_in(fn, "NULL pointer");
+    if (A == 0) {       // no samples: every element of d feat is zero (one fill per plane-contiguous tensor, else per image)
+        const size_t es = dtype == IGS_DTYPE_F16 ? 2 : 4;
+        if (fs_c == (long long)H * W && fs_n == fs_c * C)
+            HIP_TRY(zero_fill_async((hipStream_t)stream, dfeat, (size_t)B * V * C * H * W * es), "zero d feat");
+        else
+            for (long long n = 0; n < (long long)B * V; n++)
+                for (int c = 0; c < C; c++)
+                    HIP_TRY(zero_fill_async((hipStream_t)stream, (char*)dfeat + ((size_t)n * fs_n + (size_t)c * fs_c) * es, (size_t)H * W * es), "zero d feat");
+        return 0;
+    }
+    if (!points || !w2c || !intr || !dout || !scratch) return fail_in(fn, "NULL pointer");
+    HIP_TRY(launch_lift_bwd((hipStream_t)stream, B, V, A, C, H, W, dtype, points, w2c, intr, dout, (size_t)gs_a, (size_t)gs_c, dfeat, (size_t)fs_n,
+                            (size_t)fs_c, scratch), "anchor lift bwd launch");
+    return 0;
 }

@@ -10,7 +10,7 @@
 // (b) Gaussian deform, GaussianModel.deform (gs.py:347-375) with quaternion_multiply (igs/utils/general_utils.py:177-200):
 //     xyz[mask] += dxyz, rot[mask] = qmul(nrm(rot[mask]), nrm(drot)), and its backward through both normalisations.
 #include "common.h"
-#include "../../include/igs_rast.h"
+#include "host_api.h"
 
 #define IW 4                          // waves per workgroup of the row / chunk kernels
 #define ISLOTS 4                      // slots whose rows are in flight together in the forward (and edges in the backward)
@@ -128,8 +128,8 @@ static hipError_t interp_fwd_t(hipStream_t s, int N, int K, int D, int A, const 
     return hipGetLastError();
 }
 
-hipError_t launch_interp_fwd(hipStream_t s, int N, int K, int D, int A, int dtype, const void* F, const int64_t* col, const float* w,
-                             float* out)
+static hipError_t launch_interp_fwd(hipStream_t s, int N, int K, int D, int A, int dtype, const void* F, const int64_t* col, const float* w,
+                                    float* out)
 {
     if (dtype == IGS_DTYPE_F16) return interp_fwd_t(s, N, K, D, A, (const _Float16*)F, col, w, out);
     return interp_fwd_t(s, N, K, D, A, (const float*)F, col, w, out);
@@ -138,7 +138,7 @@ hipError_t launch_interp_fwd(hipStream_t s, int N, int K, int D, int A, int dtyp
 // ---------------------------------------------------------------------------------------------------------------------------------
 // (a) the inverse index: edges sorted by anchor, per-anchor starts and chunk offsets
 // ---------------------------------------------------------------------------------------------------------------------------------
-size_t interp_scratch_bytes(int N, int K, int A, int D) { return InterpLayout(N, K, A, D).total; }
+static size_t interp_scratch_bytes(int N, int K, int A, int D) { return InterpLayout(N, K, A, D).total; }
 
 __global__ void __launch_bounds__(256)
 interp_keys_kernel(uint32_t E, int A, const int64_t* __restrict__ col, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
@@ -173,7 +173,7 @@ interp_nchunks_kernel(int A, uint32_t chunk, const uint32_t* __restrict__ start,
     choff[a] = a < A ? (start[a + 1] - start[a] + chunk - 1) / chunk : 0u;
 }
 
-hipError_t launch_interp_index(hipStream_t s, int N, int K, int A, int D, const int64_t* col, void* scratch)
+static hipError_t launch_interp_index(hipStream_t s, int N, int K, int A, int D, const int64_t* col, void* scratch)
 {
     const InterpLayout L(N, K, A, D);
     char* base = align_ptr((const char*)scratch);
@@ -311,8 +311,8 @@ static hipError_t interp_bwd_t(hipStream_t s, int N, int K, int D, int A, const 
     return hipGetLastError();
 }
 
-hipError_t launch_interp_bwd(hipStream_t s, int N, int K, int D, int A, int dtype, const void* F, const float* w, const float* dout,
-                             void* scratch, void* dF, float* dw)
+static hipError_t launch_interp_bwd(hipStream_t s, int N, int K, int D, int A, int dtype, const void* F, const float* w, const float* dout,
+                                    void* scratch, void* dF, float* dw)
 {
     if (dtype == IGS_DTYPE_F16) return interp_bwd_t(s, N, K, D, A, (const _Float16*)F, w, dout, scratch, (_Float16*)dF, dw);
     return interp_bwd_t(s, N, K, D, A, (const float*)F, w, dout, scratch, (float*)dF, dw);
@@ -383,8 +383,8 @@ deform_fwd_kernel(int P, int M, const float* __restrict__ xyz, const float* __re
     o[0] = q.w; o[1] = q.x; o[2] = q.y; o[3] = q.z;
 }
 
-hipError_t launch_deform_fwd(hipStream_t s, int P, int M, int dtype, const float* xyz, const float* rot, const int64_t* mask,
-                             const void* dxyz, const void* drot, float* xyz_out, float* rot_out)
+static hipError_t launch_deform_fwd(hipStream_t s, int P, int M, int dtype, const float* xyz, const float* rot, const int64_t* mask,
+                                    const void* dxyz, const void* drot, float* xyz_out, float* rot_out)
 {
     hipError_t e = launch_copy2(s, (size_t)P * 3, xyz, xyz_out, (size_t)P * 4, rot, rot_out);
     if (e != hipSuccess || M == 0) return e;
@@ -435,8 +435,8 @@ deform_bwd_kernel(int P, int M, const float* __restrict__ rot, const int64_t* __
     }
 }
 
-hipError_t launch_deform_bwd(hipStream_t s, int P, int M, int dtype, const float* rot, const int64_t* mask, const void* drot,
-                             const float* g_xyz, const float* g_rot, float* d_xyz, float* d_rot, void* d_dxyz, void* d_drot)
+static hipError_t launch_deform_bwd(hipStream_t s, int P, int M, int dtype, const float* rot, const int64_t* mask, const void* drot,
+                                    const float* g_xyz, const float* g_rot, float* d_xyz, float* d_rot, void* d_dxyz, void* d_drot)
 {
     // pass-through: d_xyz = g_xyz everywhere, d_rot = g_rot outside the mask (a missing upstream gradient is zero)
     hipError_t e = hipSuccess;
@@ -453,4 +453,77 @@ hipError_t launch_deform_bwd(hipStream_t s, int P, int M, int dtype, const float
         hipLaunchKernelGGL((deform_bwd_kernel<float>), g, dim3(256), 0, s, P, M, rot, mask, (const float*)drot, g_xyz, g_rot, d_rot,
                            (float*)d_dxyz, (float*)d_drot);
     return hipGetLastError();
+}
+
+// the entry points (the contracts are in include/igs_rast.h)
+static const char* interp_size_error(int N, int K, int D, int A)
+{
+    if (N < 0 || N > IGS_INTERP_MAX_ROWS) return "N out of range (0..IGS_INTERP_MAX_ROWS)";
+    if (K < 1 || K > IGS_INTERP_MAX_K) return "K out of range (1..IGS_INTERP_MAX_K)";
+    if (D < 1 || D > IGS_INTERP_MAX_D) return "D out of range (1..IGS_INTERP_MAX_D)";
+    if (A < 1 || A > IGS_INTERP_MAX_ANCHORS) return "A_total out of range (1..IGS_INTERP_MAX_ANCHORS)";
+    if ((long long)N * K > IGS_INTERP_MAX_EDGES) return "N * K out of range (IGS_INTERP_MAX_EDGES)";
+    return nullptr;
+}
+extern "C" int igs_anchor_interp_fwd(void* stream, int N, int K, int D, int A_total, int dtype, const void* F, const int64_t* col,
+                                     const float* w, float* out)
+{
+    if (const char* e = interp_size_error(N, K, D, A_total)) return fail_in("igs_anchor_interp_fwd", e);
+    if (!dtype_ok(dtype)) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_fwd: unknown dtype code");
+    if (N == 0) return 0;
+    if (!F || !col || !w || !out) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_fwd: NULL pointer");
+    HIP_TRY(launch_interp_fwd((hipStream_t)stream, N, K, D, A_total, dtype, F, col, w, out), "anchor interp fwd launch");
+    return 0;
+}
+extern "C" size_t igs_anchor_interp_index_bytes(int N, int K, int A_total, int D)
+{
+    if (interp_size_error(N, K, D, A_total)) return 0;
+    return interp_scratch_bytes(N, K, A_total, D) + 256;
+}
+extern "C" int igs_anchor_interp_index(void* stream, int N, int K, int A_total, int D, const int64_t* col, void* scratch)
+{
+    if (const char* e = interp_size_error(N, K, D, A_total)) return fail_in("igs_anchor_interp_index", e);
+    if (N == 0) return 0;
+    if (!col || !scratch) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_index: NULL pointer");
+    HIP_TRY(launch_interp_index((hipStream_t)stream, N, K, A_total, D, col, scratch), "anchor interp index launch");
+    return 0;
+}
+extern "C" int igs_anchor_interp_bwd(void* stream, int N, int K, int D, int A_total, int dtype, const void* F, const float* w,
+                                     const float* dout, void* scratch, void* dF, float* dw)
+{
+    if (const char* e = interp_size_error(N, K, D, A_total)) return fail_in("igs_anchor_interp_bwd", e);
+    if (!dtype_ok(dtype)) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_bwd: unknown dtype code");
+    if (!dF && !dw) return 0;
+    if (N == 0) {       // no edges: every anchor's gradient is zero
+        if (dF) HIP_TRY(zero_fill_async((hipStream_t)stream, dF, (size_t)A_total * D * (dtype == IGS_DTYPE_F16 ? 2 : 4)), "zero dF");
+        return 0;
+    }
+    if (!w || !dout || !scratch || (dw && !F)) return fail(IGS_RAST_E_INVALID, "igs_anchor_interp_bwd: NULL pointer");
+    HIP_TRY(launch_interp_bwd((hipStream_t)stream, N, K, D, A_total, dtype, F, w, dout, scratch, dF, dw), "anchor interp bwd launch");
+    return 0;
+}
+extern "C" int igs_gaussian_deform_fwd(void* stream, int P, int M, int dtype, const float* xyz, const float* rot, const int64_t* mask,
+                                       const void* dxyz, const void* drot, float* xyz_out, float* rot_out)
+{
+    if (P < 0 || P > IGS_DEFORM_MAX_POINTS) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_fwd: P out of range (0..IGS_DEFORM_MAX_POINTS)");
+    if (M < 0 || M > P) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_fwd: M out of range (0..P)");
+    if (!dtype_ok(dtype)) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_fwd: unknown dtype code");
+    if (P == 0) return 0;
+    if (!xyz || !rot || !xyz_out || !rot_out || (M > 0 && (!mask || !dxyz || !drot)))
+        return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_fwd: NULL pointer");
+    HIP_TRY(launch_deform_fwd((hipStream_t)stream, P, M, dtype, xyz, rot, mask, dxyz, drot, xyz_out, rot_out), "gaussian deform fwd launch");
+    return 0;
+}
+extern "C" int igs_gaussian_deform_bwd(void* stream, int P, int M, int dtype, const float* rot, const int64_t* mask, const void* drot,
+                                       const float* g_xyz, const float* g_rot, float* d_xyz, float* d_rot, void* d_dxyz, void* d_drot)
+{
+    if (P < 0 || P > IGS_DEFORM_MAX_POINTS) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_bwd: P out of range (0..IGS_DEFORM_MAX_POINTS)");
+    if (M < 0 || M > P) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_bwd: M out of range (0..P)");
+    if (!dtype_ok(dtype)) return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_bwd: unknown dtype code");
+    if (P == 0 || (!d_xyz && !d_rot && !d_dxyz && !d_drot)) return 0;
+    if (M > 0 && (!mask || ((d_rot || d_drot) && (!rot || !drot))))
+        return fail(IGS_RAST_E_INVALID, "igs_gaussian_deform_bwd: NULL pointer");
+    HIP_TRY(launch_deform_bwd((hipStream_t)stream, P, M, dtype, rot, mask, drot, g_xyz, g_rot, d_xyz, d_rot, d_dxyz, d_drot),
+            "gaussian deform bwd launch");
+    return 0;
 }

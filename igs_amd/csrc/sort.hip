@@ -10,6 +10,7 @@
 // Stability of every pass makes the result identical to a stable sort on (tile, depth) with ties in Gaussian-index
 // order, which is what the reference's stable LSD sort yields.
 #include "common.h"
+#include "host_api.h"
 
 #define RADIX 256
 
@@ -783,6 +784,18 @@ hipError_t launch_tile_sort(hipStream_t s, uint32_t T, uint32_t* tile_count, con
     }
     return hipGetLastError();
 }
+// Test support: the per-tile sort of the slab binning on caller-made slabs (launch_tile_sort).  tile_count[T] instances per
+// tile (reset to zero by the launch), pairs[T * slab] = depth bits << 32 | Gaussian id, out: point_list[T * slab] (ids, sorted by the
+// 64-bit key inside every tile's slab), ranges[2 T], stats[4] ([1] = largest tile that overflowed its slab).  Everything device memory.
+extern "C" int igs_debug_tile_sort(void* stream, int T, uint32_t* tile_count, const unsigned long long* pairs, uint32_t* point_list,
+                                   uint32_t* ranges, int slab, uint32_t* stats, int P)
+{
+    if (T <= 0 || slab <= 0 || P <= 0) return fail(IGS_RAST_E_INVALID, "igs_debug_tile_sort: bad sizes");
+    if (!tile_count || !pairs || !point_list || !ranges || !stats) return fail(IGS_RAST_E_INVALID, "igs_debug_tile_sort: NULL pointer");
+    HIP_TRY(launch_tile_sort((hipStream_t)stream, (uint32_t)T, tile_count, (const uint64_t*)pairs, point_list, ranges, (uint32_t)slab, stats,
+                             nullptr, (uint32_t)P), "tile_sort launch");
+    return 0;
+}
 
 // ---- debug / test support: gather per-tile lists (slab or compact) into the reference's compact layout --------------------
 __global__ void __launch_bounds__(1024)
@@ -857,12 +870,12 @@ morton_keys_kernel(int P, const float* __restrict__ xyz, const float* __restrict
     keys[i] = code; vals[i] = (uint32_t)i;
     atomicAdd(&hist0[((uint32_t)i / per_block) * RADIX + (code & 255u)], 1u);
 }
-size_t morton_scratch_bytes(int P)
+static size_t morton_scratch_bytes(int P)
 {
     const size_t n = (size_t)(P > 0 ? P : 0);
     return 4 * ((n * 4 + 255) & ~(size_t)255) + (size_t)SORT_MAX_PASSES * RADIX * SORT_MAX_BLOCKS * 4 + 256;
 }
-hipError_t launch_morton_order(hipStream_t s, int P, const float* xyz, const float* lohi, int bits, void* scratch, int* perm)
+static hipError_t launch_morton_order(hipStream_t s, int P, const float* xyz, const float* lohi, int bits, void* scratch, int* perm)
 {
     if (P <= 0) return hipSuccess;
     const size_t seg = ((size_t)P * 4 + 255) & ~(size_t)255;
@@ -878,4 +891,15 @@ hipError_t launch_morton_order(hipStream_t s, int P, const float* xyz, const flo
     e = radix_sort_pairs(s, (uint32_t)P, ka, kb, va, vb, hist, 0, 3 * bits, &sk, &sv);
     if (e != hipSuccess) return e;
     return hipMemcpyAsync(perm, sv, (size_t)P * 4, hipMemcpyDeviceToDevice, s);
+}
+// The entry points (contract in include/igs_rast.h): perm[i] = index of the Gaussian that comes i-th along the Z-order curve of
+// xyz quantised to `bits` bits per axis inside the box lohi = {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z} (device memory).
+extern "C" size_t igs_morton_order_scratch_bytes(int P) { return morton_scratch_bytes(P) + 256; }
+extern "C" int igs_morton_order(void* stream, int P, const float* xyz, const float* lohi, int bits, void* scratch, int* perm)
+{
+    if (P < 0 || bits < 1 || bits > 10) return fail(IGS_RAST_E_INVALID, "igs_morton_order: bad sizes (1..10 bits per axis)");
+    if (P == 0) return 0;
+    if (!xyz || !lohi || !scratch || !perm) return fail(IGS_RAST_E_INVALID, "igs_morton_order: NULL pointer");
+    HIP_TRY(launch_morton_order((hipStream_t)stream, P, xyz, lohi, bits, scratch, perm), "morton order launch");
+    return 0;
 }

@@ -26,6 +26,37 @@ def test_cabi_library_exports_every_declared_symbol():
     assert set(_cabi.EXPORTS) <= names | {"igs_rast_last_error", "igs_rast_version"}
 
 
+def test_cabi_signatures_have_the_declared_number_of_arguments():
+    """Every argtypes list of _cabi.SIGNATURES is as long as the parameter list include/igs_rast.h declares for that function (ctypes
+    checks nothing: a wrong count reads or writes the wrong registers), and the table leaves out no function of the header."""
+    from igs_amd import _cabi
+    hdr = open(os.path.join(ROOT, "include", "igs_rast.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    declared = {}
+    for m in re.finditer(r"\b(igs_[a-z0-9_]+)\s*\(", hdr):
+        depth, commas, i = 1, 0, m.end()
+        while depth:
+            c = hdr[i]
+            depth += (c == "(") - (c == ")")
+            commas += c == "," and depth == 1
+            i += 1
+        params = hdr[m.end():i - 1].strip()
+        declared[m.group(1)] = 0 if params in ("", "void") else commas + 1
+    assert "igs_rast_alloc_fn" not in declared        # (the allocator callback's typedef, not a function of the library)
+    assert declared["igs_rast_version"] == 0 and declared["igs_rast_mark_visible"] == 6 and declared["igs_refine_step_masked"] == 2
+    # test-support entry points may go unbound; the igs_debug_*_timeline ones exist in debug builds only and are in neither place
+    debug_names = {"igs_debug_tile_sort"}
+    assert {n for n in declared if n.startswith("igs_debug_")} == debug_names
+    checked = set()
+    for name, (restype, argtypes) in _cabi.SIGNATURES.items():
+        if name in declared:
+            assert len(argtypes) == declared[name], "%s: %d argtypes, the header declares %d parameters" % (name, len(argtypes), declared[name])
+            checked.add(name)
+    assert len(checked) >= len(declared) - len(debug_names)
+    assert set(declared) - checked <= debug_names, sorted(set(declared) - checked)
+    assert _cabi.EXPORTS == list(_cabi.SIGNATURES)
+
+
 def test_product_path_fails_loudly_without_gpu_and_validates_arguments():
     import diff_gaussian_rasterization_rade as D
     from igs_amd.rasterizer import RasterizerError
