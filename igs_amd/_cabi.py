@@ -138,6 +138,10 @@ SIGNATURES = {
     "igs_modln_bwd_scratch_bytes": (_sz, [_i] * 4),
     "igs_modln_fwd": (_i, [_vp] + [_i] * 5 + [_vp] + [_ll] * 4 + [_i] + [_vp] * 3 + [_f] + [_vp] * 3),
     "igs_modln_bwd": (_i, [_vp] + [_i] * 5 + [_vp] + [_ll] * 4 + [_i] + [_vp] * 11),
+    # attn.hip
+    "igs_attn_bwd_scratch_bytes": (_sz, [_i] * 6),
+    "igs_attn_fwd": (_i, [_vp] + [_i] * 6 + ([_vp] + [_ll] * 3) * 3 + [_f] + [_vp] + [_ll] * 3 + [_vp]),
+    "igs_attn_bwd": (_i, [_vp] + [_i] * 6 + ([_vp] + [_ll] * 3) * 4 + [_vp] + [_vp] + [_ll] * 3 + [_f] + ([_vp] + [_ll] * 3) * 3 + [_vp]),
 }
 EXPORTS = list(SIGNATURES)
 

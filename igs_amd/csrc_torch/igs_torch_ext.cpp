@@ -12,6 +12,7 @@
 // And the two consumers of the anchor graph under igs_amd.motion: motion_interp_fwd / _index / _bwd (anchor feature interpolation) and
 // motion_deform_fwd / _bwd (GaussianModel.deform); unsupported dtypes raise NotImplementedError.
 // And IGS.condition3D's native parts: cond_ray_fwd (the ray / depth condition) and modln_fwd / modln_bwd (LayerNorm + adaLN modulation).
+// And the anchor transformer's fused attention: attn_fwd / attn_bwd (attn.hip) on [B, H, A, 64] views of any acceptable strides.
 // Extensions over the reference's signatures are keyword-only extras with defaults (the positional lists are the reference's):
 //   rasterize_gaussians(..., scratch=None, out_images=None, out_radii=None, mode=0, scratch_clean=False)
 //   rasterize_gaussians_backward(..., workspace=None, out_*=None)         any upstream gradient may be None (= zeros)
@@ -669,6 +670,96 @@ std::tuple<OptTensor, OptTensor, OptTensor, OptTensor> modln_bwd(const Tensor& x
     return {dx, dmod, dw, db};
 }
 
+// ---- fused attention for the anchor transformer (attn.hip; contract in include/igs_rast.h) ----
+struct AttnSizes { int64_t B, H, Aq, Ak; int dt; };
+static void attn_view_check(const char* fn, const Tensor& t, const char* name, const Tensor& like, int64_t B, int64_t H, int64_t A)
+{
+    if (t.dim() != 4 || t.size(0) != B || t.size(1) != H || t.size(2) != A || t.size(3) != 64)
+        throw RasterizerError(std::string(fn) + ": " + name + " has shape " + c10::str(t.sizes()) + ", expected " +
+                              c10::str(at::IntArrayRef({B, H, A, (int64_t)64})));
+    if (t.scalar_type() != like.scalar_type()) throw NotImplemented(std::string(fn) + ": " + name + " must have q's dtype");
+    if (t.stride(3) != 1) throw RasterizerError(std::string(fn) + ": " + name + " must have stride 1 on its last dimension");
+}
+static AttnSizes attn_check(const char* fn, const Tensor& q, const Tensor& k, const Tensor& v)
+{
+    AttnSizes z;
+    z.dt = motion_dtype(q, fn, "q");
+    if (q.dim() != 4 || k.dim() != 4 || v.dim() != 4)
+        throw RasterizerError(std::string(fn) + ": q, k, v must be [B, H, A, D] views (got " + c10::str(q.sizes()) + ", " + c10::str(k.sizes()) +
+                              ", " + c10::str(v.sizes()) + ")");
+    if (q.size(3) != 64) throw NotImplemented(std::string(fn) + ": the head size must be 64 (got " + std::to_string(q.size(3)) + ")");
+    z.B = q.size(0); z.H = q.size(1); z.Aq = q.size(2); z.Ak = k.size(2);
+    attn_view_check(fn, q, "q", q, z.B, z.H, z.Aq);
+    attn_view_check(fn, k, "k", q, z.B, z.H, z.Ak);
+    attn_view_check(fn, v, "v", q, z.B, z.H, z.Ak);
+    if (z.Aq < 1 || z.Ak < 1 || z.Aq > IGS_ATTN_MAX_TOKENS || z.Ak > IGS_ATTN_MAX_TOKENS || z.H < 1 || z.H > IGS_ATTN_MAX_HEADS ||
+        z.B > IGS_ATTN_MAX_BATCH)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (B <= 65535, 1 <= H <= 1024, 1 <= Aq, Ak <= 2^20)");
+    return z;
+}
+// [B, H, A, 64] as indexed; token-major ([B, A, H, 64] in memory) or head-major
+static Tensor attn_empty(const Tensor& like, int64_t B, int64_t H, int64_t A, bool token_major)
+{
+    return token_major ? at::empty({B, A, H, 64}, like.options()).permute({0, 2, 1, 3}) : at::empty({B, H, A, 64}, like.options());
+}
+
+// (out, lse or None): q [B, H, Aq, 64], k, v [B, H, Ak, 64] float32 / float16 views with stride 1 on the last dimension
+std::tuple<Tensor, OptTensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool token_major, bool want_lse)
+{
+    const char* fn = "attn_fwd";
+    const AttnSizes z = attn_check(fn, q, k, v);
+    require_gpu(q, fn, "q");
+    same_device(k, q, fn, "k");
+    same_device(v, q, fn, "v");
+    const c10::Device dev = q.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    Tensor out = attn_empty(q, z.B, z.H, z.Aq, token_major);
+    OptTensor lse;
+    if (want_lse) lse = at::empty({z.B, z.H, z.Aq}, q.options().dtype(at::kFloat));
+    if (z.B == 0) return {out, lse};
+    check(igs_attn_fwd(cur_stream(dev), (int)z.B, (int)z.H, (int)z.Aq, (int)z.Ak, 64, z.dt, q.data_ptr(), q.stride(0), q.stride(1), q.stride(2),
+                       k.data_ptr(), k.stride(0), k.stride(1), k.stride(2), v.data_ptr(), v.stride(0), v.stride(1), v.stride(2), (float)scale,
+                       out.data_ptr(), out.stride(0), out.stride(1), out.stride(2), lse ? lse->data_ptr<float>() : nullptr), "igs_attn_fwd");
+    return {out, lse};
+}
+
+// (d q, d k, d v), each None unless wanted, laid out like attn_fwd's out
+std::tuple<OptTensor, OptTensor, OptTensor> attn_bwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& out, const Tensor& lse,
+                                                     const Tensor& grad_out, double scale, bool token_major, bool want_q, bool want_k,
+                                                     bool want_v)
+{
+    const char* fn = "attn_bwd";
+    const AttnSizes z = attn_check(fn, q, k, v);
+    attn_view_check(fn, out, "out", q, z.B, z.H, z.Aq);
+    attn_view_check(fn, grad_out, "grad_out", q, z.B, z.H, z.Aq);
+    motion_expect(lse, fn, "lse", at::kFloat, {z.B, z.H, z.Aq});
+    require_gpu(q, fn, "q");
+    same_device(k, q, fn, "k");
+    same_device(v, q, fn, "v");
+    same_device(out, q, fn, "out");
+    same_device(lse, q, fn, "lse");
+    same_device(grad_out, q, fn, "grad_out");
+    const c10::Device dev = q.device();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    OptTensor dq, dk, dv;
+    if (want_q) dq = attn_empty(q, z.B, z.H, z.Aq, token_major);
+    if (want_k) dk = attn_empty(q, z.B, z.H, z.Ak, token_major);
+    if (want_v) dv = attn_empty(q, z.B, z.H, z.Ak, token_major);
+    if (z.B == 0 || !(want_q || want_k || want_v)) return {dq, dk, dv};
+    const Tensor ls = lse.contiguous();
+    Tensor scratch = at::empty({(int64_t)igs_attn_bwd_scratch_bytes((int)z.B, (int)z.H, (int)z.Aq, (int)z.Ak, 64, z.dt)}, q.options().dtype(at::kByte));
+    const Tensor none;
+    const Tensor& tq = dq ? *dq : none; const Tensor& tk = dk ? *dk : none; const Tensor& tv = dv ? *dv : none;
+#define ATTN_VIEW(t) (t).data_ptr(), (t).stride(0), (t).stride(1), (t).stride(2)
+#define ATTN_OPT(t) (t).defined() ? (t).data_ptr() : nullptr, (t).defined() ? (t).stride(0) : 0, (t).defined() ? (t).stride(1) : 0, (t).defined() ? (t).stride(2) : 0
+    check(igs_attn_bwd(cur_stream(dev), (int)z.B, (int)z.H, (int)z.Aq, (int)z.Ak, 64, z.dt, ATTN_VIEW(q), ATTN_VIEW(k), ATTN_VIEW(v), ATTN_VIEW(out),
+                       ls.data_ptr<float>(), ATTN_VIEW(grad_out), (float)scale, ATTN_OPT(tq), ATTN_OPT(tk), ATTN_OPT(tv), scratch.data_ptr()),
+          "igs_attn_bwd");
+#undef ATTN_VIEW
+#undef ATTN_OPT
+    return {dq, dk, dv};
+}
+
 static void deform_checks(const char* fn, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot, int* dt)
 {
     motion_expect(rot, fn, "rotation", at::kFloat, {-1, 4});
@@ -946,6 +1037,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("save_stats") = false, py::call_guard<py::gil_scoped_release>());
     m.def("modln_bwd", &modln_bwd, py::arg("x"), py::arg("mod"), py::arg("weight"), py::arg("bias"), py::arg("mean"), py::arg("rstd"),
           py::arg("grad_out"), py::arg("want_x") = true, py::arg("want_mod") = true, py::arg("want_weight") = true, py::arg("want_bias") = true,
+          py::call_guard<py::gil_scoped_release>());
+    m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"), py::arg("token_major") = false,
+          py::arg("want_lse") = false, py::call_guard<py::gil_scoped_release>());
+    m.def("attn_bwd", &attn_bwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("grad_out"), py::arg("scale"),
+          py::arg("token_major") = false, py::arg("want_q") = true, py::arg("want_k") = true, py::arg("want_v") = true,
           py::call_guard<py::gil_scoped_release>());
     m.def("motion_deform_fwd", &motion_deform_fwd, py::arg("xyz"), py::arg("rotation"), py::arg("mask"), py::arg("res_xyz"),
           py::arg("res_rotation"), py::call_guard<py::gil_scoped_release>());

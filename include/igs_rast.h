@@ -696,6 +696,39 @@ int igs_modln_bwd(void* stream, int N, int C, int H, int W, int x_dtype, const v
                   long long xs_w, int mod_dtype, const void* mod, const float* weight, const float* bias, const float* mean, const float* rstd,
                   const float* gout, void* dx, void* dmod, float* dweight, float* dbias, void* scratch);
 
+/* Fused attention for the anchor transformer (attn.hip): out = softmax(scale * Q K^T) V in one pass over the keys, the
+ * self-attention of GridEncoder.conv's Transformer1D (igs/models/transformers.py:673-907: 8 heads of 64 channels over 8192 anchors, no mask,
+ * no dropout).  The score matrix is never stored.  Everything runs on `stream`, reads nothing back and allocates nothing.
+ *   - q [B, H, Aq, D], k and v [B, H, Ak, D], out [B, H, Aq, D] in `dtype` (IGS_DTYPE_F32 / IGS_DTYPE_F16), each given by its base pointer and
+ *     the element strides of b, h and a; the stride of d is 1.  Head-major [B, H, A, D] tensors, the token-major [B, A, H * D] tensors that
+ *     to_q / to_k / to_v produce (strides A * H * D, D, H * D) and slices of one fused QKV buffer are all read in place, and out can be
+ *     written token-major.  Base pointers and the three strides (in bytes) must be multiples of 16.  Aq != Ak is allowed.
+ *   - D must be 64; 1 <= Aq, Ak <= IGS_ATTN_MAX_TOKENS; 1 <= H <= IGS_ATTN_MAX_HEADS; 0 <= B <= IGS_ATTN_MAX_BATCH.  Anything else, an
+ *     unknown dtype code, a negative or misaligned stride, an output whose rows alias (a stride below D on a dimension longer than 1), a
+ *     scale that is not finite, a NULL required pointer or a misaligned pointer returns
+ *     IGS_RAST_E_INVALID with a message before any HIP call; B == 0 returns 0 without a launch.
+ *   - IGS_DTYPE_F16: v_mfma_f32_32x32x16_f16 with float32 accumulation; scores, running max, running sum and rescale are float32; P is rounded
+ *     to half once, as the operand of the P V product; out is half.  IGS_DTYPE_F32: the exact v_mfma_f32_32x32x2_f32 (a float32 fma chain),
+ *     no half value anywhere; out is float32.  exp is exp2 with scale * log2(e) folded into the scores.
+ * igs_attn_fwd: lse [B, H, Aq] float32 contiguous receives log(sum_j exp(scale * q_i . k_j)) for the backward; NULL when none follows.
+ * igs_attn_bwd: from q, k, v, out, lse and dout (= d out, laid out like out with its own strides) the gradients dq [B, H, Aq, D], dk and
+ *   dv [B, H, Ak, D] in `dtype`, each with its own strides and each optional (NULL = not wanted); every element of a non-NULL output is
+ *   written.  P is recomputed from lse.  No float atomics: d K / d V accumulate in the registers of the workgroup that owns the key tile, d Q
+ *   in a second pass that owns the query tile, each in a fixed order, so two runs agree bit for bit.  `scratch`
+ *   (igs_attn_bwd_scratch_bytes(...) bytes, at most 4 B H Aq + 512) holds rowsum(dout * out). */
+#define IGS_ATTN_MAX_BATCH 65535
+#define IGS_ATTN_MAX_HEADS 1024
+#define IGS_ATTN_MAX_TOKENS (1 << 20)
+size_t igs_attn_bwd_scratch_bytes(int B, int H, int Aq, int Ak, int D, int dtype);
+int igs_attn_fwd(void* stream, int B, int H, int Aq, int Ak, int D, int dtype, const void* q, long long qs_b, long long qs_h, long long qs_a,
+                 const void* k, long long ks_b, long long ks_h, long long ks_a, const void* v, long long vs_b, long long vs_h, long long vs_a,
+                 float scale, void* out, long long os_b, long long os_h, long long os_a, float* lse);
+int igs_attn_bwd(void* stream, int B, int H, int Aq, int Ak, int D, int dtype, const void* q, long long qs_b, long long qs_h, long long qs_a,
+                 const void* k, long long ks_b, long long ks_h, long long ks_a, const void* v, long long vs_b, long long vs_h, long long vs_a,
+                 const void* out, long long os_b, long long os_h, long long os_a, const float* lse, const void* dout, long long gs_b,
+                 long long gs_h, long long gs_a, float scale, void* dq, long long dqs_b, long long dqs_h, long long dqs_a, void* dk,
+                 long long dks_b, long long dks_h, long long dks_a, void* dv, long long dvs_b, long long dvs_h, long long dvs_a, void* scratch);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).
