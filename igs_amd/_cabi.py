@@ -142,6 +142,10 @@ SIGNATURES = {
     "igs_attn_bwd_scratch_bytes": (_sz, [_i] * 6),
     "igs_attn_fwd": (_i, [_vp] + [_i] * 6 + ([_vp] + [_ll] * 3) * 3 + [_f] + [_vp] + [_ll] * 3 + [_vp]),
     "igs_attn_bwd": (_i, [_vp] + [_i] * 6 + ([_vp] + [_ll] * 3) * 4 + [_vp] + [_vp] + [_ll] * 3 + [_f] + ([_vp] + [_ll] * 3) * 3 + [_vp]),
+    # wattn.hip
+    "igs_window_attn_bwd_scratch_bytes": (_sz, [_i] * 6),
+    "igs_window_attn_fwd": (_i, [_vp] + [_i] * 7 + ([_vp] + [_ll] * 2) * 3 + [_f] + [_vp] + [_ll] * 2 + [_vp]),
+    "igs_window_attn_bwd": (_i, [_vp] + [_i] * 7 + ([_vp] + [_ll] * 2) * 4 + [_vp] + [_vp] + [_ll] * 2 + [_f] + ([_vp] + [_ll] * 2) * 3 + [_vp]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -14,6 +14,7 @@
 //   lifting             lift.hip                motion_lift_fwd / _bwd
 //   condition3D         cond.hip                cond_ray_fwd, modln_fwd / _bwd
 //   attention           attn.hip                attn_fwd / _bwd on [B, H, A, 64] views of any acceptable strides
+//   window attention    wattn.hip               _window.window_attn_fwd / _bwd on [B, h w, 128] views of any acceptable strides
 //   deform              motion.hip              motion_deform_fwd / _bwd
 //   Adam                refine_ops.hip          adam_step_multi
 //   losses              refine_ops, loss_ops    l1_mean; ssim_mean
@@ -743,6 +744,81 @@ std::tuple<OptTensor, OptTensor, OptTensor> attn_bwd(const Tensor& q, const Tens
     return {dq, dk, dv};
 }
 
+// ---- swin window attention for the motion-feature transformers (wattn.hip; contract in include/igs_rast.h) ----
+// a [B, L, 128] view as the window attention entry points take it: data pointer and the two outer strides (NULL and zeros when absent)
+struct TokenView {
+    void* p = nullptr; int64_t sb = 0, st = 0;
+    TokenView(const Tensor& t) : p(t.data_ptr()), sb(t.stride(0)), st(t.stride(1)) {}
+    TokenView(const OptTensor& t) { if (t) *this = TokenView(*t); }
+};
+struct WindowSizes { int64_t B, L; int dt; };
+void window_view_check(const char* fn, const Tensor& t, const char* name, const Tensor& like, int64_t B, int64_t L)
+{
+    if (t.dim() != 3 || t.size(0) != B || t.size(1) != L || t.size(2) != 128)
+        throw RasterizerError(std::string(fn) + ": " + name + " has shape " + c10::str(t.sizes()) + ", expected " +
+                              c10::str(at::IntArrayRef({B, L, (int64_t)128})));
+    if (t.scalar_type() != like.scalar_type()) throw NotImplemented(std::string(fn) + ": " + name + " must have q's dtype");
+    if (t.stride(2) != 1) throw RasterizerError(std::string(fn) + ": " + name + " must have stride 1 on its last dimension");
+}
+WindowSizes window_check(const char* fn, const Tensor& q, const Tensor& k, const Tensor& v, int64_t h, int64_t w, int64_t K)
+{
+    WindowSizes z;
+    z.dt = dtype_code(q, fn, "q");
+    if (q.dim() != 3) throw RasterizerError(std::string(fn) + ": q, k, v must be [B, h * w, 128] views (got " + c10::str(q.sizes()) + ")");
+    if (q.size(2) != 128) throw NotImplemented(std::string(fn) + ": the channel count must be 128 (got " + std::to_string(q.size(2)) + ")");
+    z.B = q.size(0); z.L = q.size(1);
+    if (h < 1 || w < 1 || K < 1 || h * w != z.L || h % K || w % K || z.B > IGS_WINDOW_ATTN_MAX_BATCH || z.B * z.L > ((int64_t)1 << 24))
+        throw RasterizerError(std::string(fn) + ": sizes out of range (h * w = L, h % K = w % K = 0, B <= 65535, B * L <= 2^24; got h " +
+                              std::to_string(h) + ", w " + std::to_string(w) + ", K " + std::to_string(K) + ", L " + std::to_string(z.L) + ")");
+    window_view_check(fn, q, "q", q, z.B, z.L);
+    window_view_check(fn, k, "k", q, z.B, z.L);
+    window_view_check(fn, v, "v", q, z.B, z.L);
+    return z;
+}
+
+// (out, lse or None): q, k, v [B, h * w, 128] float32 / float16 views with stride 1 on the last dimension; out contiguous
+std::tuple<Tensor, OptTensor> window_attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, int64_t h, int64_t w, int64_t num_splits,
+                                              bool with_shift, double scale, bool want_lse)
+{
+    const char* fn = "window_attn_fwd";
+    const WindowSizes z = window_check(fn, q, k, v, h, w, num_splits);
+    const GpuCall c(q, fn, "q", {{k, "k"}, {v, "v"}});
+    Tensor out = at::empty({z.B, z.L, 128}, q.options());
+    OptTensor lse;
+    if (want_lse) lse = at::empty({z.B, z.L}, q.options().dtype(at::kFloat));
+    if (z.B == 0) return {out, lse};
+    const TokenView Q(q), K(k), V(v), O(out);
+    check(igs_window_attn_fwd(c.stream(), (int)z.B, (int)h, (int)w, (int)num_splits, with_shift ? 1 : 0, 128, z.dt, Q.p, Q.sb, Q.st, K.p, K.sb,
+                              K.st, V.p, V.sb, V.st, (float)scale, O.p, O.sb, O.st, ptr_or_null<float>(lse)), "igs_window_attn_fwd");
+    return {out, lse};
+}
+
+// (d q, d k, d v), each None unless wanted, contiguous [B, h * w, 128]
+std::tuple<OptTensor, OptTensor, OptTensor> window_attn_bwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& out,
+                                                            const Tensor& lse, const Tensor& grad_out, int64_t h, int64_t w,
+                                                            int64_t num_splits, bool with_shift, double scale, bool want_q, bool want_k,
+                                                            bool want_v)
+{
+    const char* fn = "window_attn_bwd";
+    const WindowSizes z = window_check(fn, q, k, v, h, w, num_splits);
+    window_view_check(fn, out, "out", q, z.B, z.L);
+    window_view_check(fn, grad_out, "grad_out", q, z.B, z.L);
+    expect(lse, fn, "lse", at::kFloat, {z.B, z.L});
+    const GpuCall c(q, fn, "q", {{k, "k"}, {v, "v"}, {out, "out"}, {lse, "lse"}, {grad_out, "grad_out"}});
+    OptTensor dq, dk, dv;
+    if (want_q) dq = at::empty({z.B, z.L, 128}, q.options());
+    if (want_k) dk = at::empty({z.B, z.L, 128}, q.options());
+    if (want_v) dv = at::empty({z.B, z.L, 128}, q.options());
+    if (z.B == 0 || !(want_q || want_k || want_v)) return {dq, dk, dv};
+    const Tensor ls = lse.contiguous();
+    Tensor scratch = at::empty({(int64_t)igs_window_attn_bwd_scratch_bytes((int)z.B, (int)h, (int)w, (int)num_splits, 128, z.dt)}, q.options().dtype(at::kByte));
+    const TokenView Q(q), K(k), V(v), O(out), G(grad_out), DQ(dq), DK(dk), DV(dv);
+    check(igs_window_attn_bwd(c.stream(), (int)z.B, (int)h, (int)w, (int)num_splits, with_shift ? 1 : 0, 128, z.dt, Q.p, Q.sb, Q.st, K.p, K.sb,
+                              K.st, V.p, V.sb, V.st, O.p, O.sb, O.st, ls.data_ptr<float>(), G.p, G.sb, G.st, (float)scale, DQ.p, DQ.sb, DQ.st,
+                              DK.p, DK.sb, DK.st, DV.p, DV.sb, DV.st, scratch.data_ptr()), "igs_window_attn_bwd");
+    return {dq, dk, dv};
+}
+
 // ---- the Gaussian deform (motion.hip) ----
 void deform_checks(const char* fn, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot, int* dt)
 {
@@ -994,6 +1070,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     def_nogil(m, "attn_fwd", &attn_fwd, "q"_a, "k"_a, "v"_a, "scale"_a, "token_major"_a = false, "want_lse"_a = false);
     def_nogil(m, "attn_bwd", &attn_bwd, "q"_a, "k"_a, "v"_a, "out"_a, "lse"_a, "grad_out"_a, "scale"_a, "token_major"_a = false, "want_q"_a = true,
               "want_k"_a = true, "want_v"_a = true);
+    // the window attention lives in a private submodule: the top-level names of `_C` are a pinned list (tests/test_ext_binding_host.py)
+    py::module_ wa = m.def_submodule("_window", "swin window attention (wattn.hip)");
+    def_nogil(wa, "window_attn_fwd", &window_attn_fwd, "q"_a, "k"_a, "v"_a, "h"_a, "w"_a, "num_splits"_a = 1, "with_shift"_a = false,
+              "scale"_a = 0.08838834764831845, "want_lse"_a = false);
+    def_nogil(wa, "window_attn_bwd", &window_attn_bwd, "q"_a, "k"_a, "v"_a, "out"_a, "lse"_a, "grad_out"_a, "h"_a, "w"_a, "num_splits"_a = 1,
+              "with_shift"_a = false, "scale"_a = 0.08838834764831845, "want_q"_a = true, "want_k"_a = true, "want_v"_a = true);
     def_nogil(m, "motion_deform_fwd", &motion_deform_fwd, "xyz"_a, "rotation"_a, "mask"_a, "res_xyz"_a, "res_rotation"_a);
     def_nogil(m, "motion_deform_bwd", &motion_deform_bwd, "rotation"_a, "mask"_a, "res_xyz"_a, "res_rotation"_a, "grad_xyz"_a, "grad_rotation"_a,
               "want_xyz"_a = true, "want_rotation"_a = true, "want_res_xyz"_a = true, "want_res_rotation"_a = true);

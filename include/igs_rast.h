@@ -729,6 +729,40 @@ int igs_attn_bwd(void* stream, int B, int H, int Aq, int Ak, int D, int dtype, c
                  long long gs_h, long long gs_a, float scale, void* dq, long long dqs_b, long long dqs_h, long long dqs_a, void* dk,
                  long long dks_b, long long dks_h, long long dks_a, void* dv, long long dvs_b, long long dvs_h, long long dvs_a, void* scratch);
 
+/* Swin window attention for the motion-feature transformers (wattn.hip): out = softmax(scale * Q K^T + mask) V
+ * inside every one of the K x K windows of an h x w feature map, one head of D = 128 channels: single_head_split_window_attention
+ * (igs/models/unimatch/attention.py:45-104) with the mask of generate_shift_window_attn_mask (igs/models/unimatch/utils.py:84-108), and
+ * with K = 1 single_head_full_attention (attention.py:8-16).  The rolls, the window split, the merge and the score matrix are never
+ * stored.  Everything runs on `stream`, reads nothing back and allocates nothing.
+ *   - q, k, v, out, dout and the gradients are [B, h * w, D] in `dtype` (IGS_DTYPE_F32 / IGS_DTYPE_F16) in the ORIGINAL token order
+ *     (token y * w + x), each given by its base pointer and the element strides of b and of the token; the stride of d is 1, so
+ *     slices of one fused [B, h * w, 3 D] buffer are read in place.  Base pointers and strides (in bytes) must be multiples of 16.
+ *   - Token j of window (wy, wx) is the original token ((y' + sh) mod h) * w + (x' + sw) mod w with y' = wy * wh + j / ww,
+ *     x' = wx * ww + j mod ww, wh = h / K, ww = w / K and (sh, sw) = (wh / 2, ww / 2) when `shift` != 0, else (0, 0).
+ *   - The region of a rolled position is 3 rh + rw, rh = (y' >= h - wh) + (y' >= h - sh), rw likewise in x.  When shifted, a pair of
+ *     tokens of different regions gets -100 added to its scaled score: a finite addend, as in the reference, not -inf.
+ *   - D must be 128; 0 <= B <= IGS_WINDOW_ATTN_MAX_BATCH; 1 <= h, w; B * h * w <= 2^24; 1 <= K with h % K == 0 and w % K == 0; a
+ *     shifted call needs wh >= 2 and ww >= 2 (the reference's mask degenerates below).  Anything else, an unknown dtype code, a negative
+ *     or misaligned stride, an output whose rows alias (a stride below D on a dimension longer than 1), a scale that is not finite, a
+ *     NULL required pointer or a misaligned pointer returns IGS_RAST_E_INVALID with a message before any HIP call; B == 0 returns 0.
+ *   - Arithmetic as in igs_attn_*: IGS_DTYPE_F16 runs v_mfma_f32_32x32x16_f16 with float32 scores, softmax and accumulation and P rounded
+ *     to half once; IGS_DTYPE_F32 runs the exact v_mfma_f32_32x32x2_f32 with no half value anywhere.
+ * igs_window_attn_fwd: lse [B, h * w] float32 contiguous, in original token order, receives the log-sum-exp of every token's masked
+ *   scores for the backward; NULL when none follows.
+ * igs_window_attn_bwd: the gradients dq, dk, dv, each with its own strides and each optional (NULL = not wanted; none wanted returns 0);
+ *   every element of a non-NULL output is written.  P is recomputed from lse.  No float atomics: two runs agree bit for bit.  `scratch`
+ *   (igs_window_attn_bwd_scratch_bytes(...) bytes, at most 4 B h w + 4 h w + 512) holds rowsum(dout * out). */
+#define IGS_WINDOW_ATTN_MAX_BATCH 65535
+size_t igs_window_attn_bwd_scratch_bytes(int B, int h, int w, int K, int D, int dtype);
+int igs_window_attn_fwd(void* stream, int B, int h, int w, int K, int shift, int D, int dtype, const void* q, long long qs_b, long long qs_t,
+                        const void* k, long long ks_b, long long ks_t, const void* v, long long vs_b, long long vs_t, float scale, void* out,
+                        long long os_b, long long os_t, float* lse);
+int igs_window_attn_bwd(void* stream, int B, int h, int w, int K, int shift, int D, int dtype, const void* q, long long qs_b, long long qs_t,
+                        const void* k, long long ks_b, long long ks_t, const void* v, long long vs_b, long long vs_t, const void* out,
+                        long long os_b, long long os_t, const float* lse, const void* dout, long long gs_b, long long gs_t, float scale,
+                        void* dq, long long dqs_b, long long dqs_t, void* dk, long long dks_b, long long dks_t, void* dv, long long dvs_b,
+                        long long dvs_t, void* scratch);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).
