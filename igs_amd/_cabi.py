@@ -146,6 +146,10 @@ SIGNATURES = {
     "igs_window_attn_bwd_scratch_bytes": (_sz, [_i] * 6),
     "igs_window_attn_fwd": (_i, [_vp] + [_i] * 7 + ([_vp] + [_ll] * 2) * 3 + [_f] + [_vp] + [_ll] * 2 + [_vp]),
     "igs_window_attn_bwd": (_i, [_vp] + [_i] * 7 + ([_vp] + [_ll] * 2) * 4 + [_vp] + [_vp] + [_ll] * 2 + [_f] + ([_vp] + [_ll] * 2) * 3 + [_vp]),
+    # inorm.hip
+    "igs_instance_norm_fwd": (_i, [_vp] * 4 + [_ll] * 2 + [_i] * 2 + [_f]),
+    "igs_instance_norm_resident_max": (_ll, [_i] * 2),
+    "igs_position_add": (_i, [_vp] * 5 + [_i] * 6),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -15,6 +15,7 @@
 //   condition3D         cond.hip                cond_ray_fwd, modln_fwd / _bwd
 //   attention           attn.hip                attn_fwd / _bwd on [B, H, A, 64] views of any acceptable strides
 //   window attention    wattn.hip               _window.window_attn_fwd / _bwd on [B, h w, 128] views of any acceptable strides
+//   encoder norms       inorm.hip               _encoder.instance_norm_fwd, _encoder.position_add on contiguous [N, C, H, W] tensors
 //   deform              motion.hip              motion_deform_fwd / _bwd
 //   Adam                refine_ops.hip          adam_step_multi
 //   losses              refine_ops, loss_ops    l1_mean; ssim_mean
@@ -819,6 +820,53 @@ std::tuple<OptTensor, OptTensor, OptTensor> window_attn_bwd(const Tensor& q, con
     return {dq, dk, dv};
 }
 
+// ---- the unimatch CNN encoder's instance norms and position add (inorm.hip; contract in include/igs_rast.h) ----
+// [N, C, H, W], float32 / float16, contiguous (the Python layer copies what is not)
+int encoder_check(const char* fn, const Tensor& t, const char* name)
+{
+    const int dt = dtype_code(t, fn, name);
+    if (t.dim() != 4) throw RasterizerError(std::string(fn) + ": " + name + " must have shape [N, C, H, W] (got " + c10::str(t.sizes()) + ")");
+    if (!t.is_contiguous()) throw RasterizerError(std::string(fn) + ": " + name + " must be contiguous");
+    return dt;
+}
+void encoder_same(const char* fn, const Tensor& t, const char* name, const Tensor& like)
+{
+    if (t.scalar_type() != like.scalar_type()) throw NotImplemented(std::string(fn) + ": " + name + " must have x's dtype");
+    if (t.sizes() != like.sizes())
+        throw RasterizerError(std::string(fn) + ": " + name + " has shape " + c10::str(t.sizes()) + ", expected " + c10::str(like.sizes()));
+    if (t.dim() != 4 || !t.is_contiguous()) throw RasterizerError(std::string(fn) + ": " + name + " must be contiguous");
+}
+// out (x itself when inplace): mode is an IGS_INORM_* code; skip is read in the two modes that have one
+Tensor instance_norm_fwd(const Tensor& x, const OptTensor& skip, int64_t mode, double eps, bool inplace)
+{
+    const char* fn = "instance_norm_fwd";
+    const int dt = encoder_check(fn, x, "x");
+    const bool has_skip = mode == IGS_INORM_RELU_ADD_RELU || mode == IGS_INORM_RELU_ADDNORM_RELU;
+    if (has_skip && !skip) throw RasterizerError(std::string(fn) + ": this mode needs skip");
+    if (has_skip) encoder_same(fn, *skip, "skip", x);
+    if (x.size(2) * x.size(3) < 2) throw RasterizerError(std::string(fn) + ": Expected more than 1 spatial element (got " + c10::str(x.sizes()) + ")");
+    const GpuCall c(x, fn, "x");
+    if (has_skip) same_device(x, fn, {{*skip, "skip"}});
+    Tensor out = inplace ? x : at::empty_like(x);
+    check(igs_instance_norm_fwd(c.stream(), x.data_ptr(), has_skip ? skip->data_ptr() : nullptr, out.data_ptr(), x.size(0) * x.size(1),
+                                x.size(2) * x.size(3), dt, (int)mode, (float)eps), "igs_instance_norm_fwd");
+    return out;
+}
+// (feature0 + position, feature1 + position), written into the inputs when inplace
+std::tuple<Tensor, Tensor> position_add(const Tensor& f0, const Tensor& f1, int64_t splits, bool inplace)
+{
+    const char* fn = "position_add";
+    const int dt = encoder_check(fn, f0, "feature0");
+    encoder_same(fn, f1, "feature1", f0);
+    if (f0.size(0) > INT_MAX || f0.size(1) > INT_MAX || f0.size(2) > INT_MAX || f0.size(3) > INT_MAX || splits > INT_MAX || splits < INT_MIN)
+        throw RasterizerError(std::string(fn) + ": sizes out of range");
+    const GpuCall c(f0, fn, "feature0", {{f1, "feature1"}});
+    Tensor o0 = inplace ? f0 : at::empty_like(f0), o1 = inplace ? f1 : at::empty_like(f1);
+    check(igs_position_add(c.stream(), f0.data_ptr(), f1.data_ptr(), o0.data_ptr(), o1.data_ptr(), (int)f0.size(0), (int)f0.size(1), (int)f0.size(2),
+                           (int)f0.size(3), (int)splits, dt), "igs_position_add");
+    return {o0, o1};
+}
+
 // ---- the Gaussian deform (motion.hip) ----
 void deform_checks(const char* fn, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot, int* dt)
 {
@@ -1076,6 +1124,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
               "scale"_a = 0.08838834764831845, "want_lse"_a = false);
     def_nogil(wa, "window_attn_bwd", &window_attn_bwd, "q"_a, "k"_a, "v"_a, "out"_a, "lse"_a, "grad_out"_a, "h"_a, "w"_a, "num_splits"_a = 1,
               "with_shift"_a = false, "scale"_a = 0.08838834764831845, "want_q"_a = true, "want_k"_a = true, "want_v"_a = true);
+    // ... and so do the encoder's norms and position add
+    py::module_ en = m.def_submodule("_encoder", "unimatch CNN encoder: fused instance norms and position add (inorm.hip)");
+    def_nogil(en, "instance_norm_fwd", &instance_norm_fwd, "x"_a, "skip"_a = none, "mode"_a = 0, "eps"_a = 1e-5, "inplace"_a = false);
+    def_nogil(en, "position_add", &position_add, "feature0"_a, "feature1"_a, "splits"_a, "inplace"_a = false);
+    en.def("resident_max", [](int64_t dtype, int64_t mode) { return (int64_t)igs_instance_norm_resident_max((int)dtype, (int)mode); }, "dtype"_a, "mode"_a);
     def_nogil(m, "motion_deform_fwd", &motion_deform_fwd, "xyz"_a, "rotation"_a, "mask"_a, "res_xyz"_a, "res_rotation"_a);
     def_nogil(m, "motion_deform_bwd", &motion_deform_bwd, "rotation"_a, "mask"_a, "res_xyz"_a, "res_rotation"_a, "grad_xyz"_a, "grad_rotation"_a,
               "want_xyz"_a = true, "want_rotation"_a = true, "want_res_xyz"_a = true, "want_res_rotation"_a = true);

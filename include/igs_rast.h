@@ -763,6 +763,44 @@ int igs_window_attn_bwd(void* stream, int B, int h, int w, int K, int shift, int
                         void* dq, long long dqs_b, long long dqs_t, void* dk, long long dks_b, long long dks_t, void* dv, long long dvs_b,
                         long long dvs_t, void* scratch);
 
+/* The unimatch CNN encoder's instance norms and position add (inorm.hip).  Forward only: the backbone is frozen in
+ * IGS (igs/IGS.py:76-77) and its inputs are images, so no backward exists.  Everything runs on `stream`, reads nothing back and allocates
+ * nothing.  Every refusal below returns IGS_RAST_E_INVALID with a message before any HIP call.
+ * igs_instance_norm_fwd: nn.InstanceNorm2d with affine = False and no running statistics (igs/models/unimatch/backbone.py:17-20,51) fused
+ *   with what follows it.  x, skip, out: `planes` = N * C contiguous runs of `hw` = H * W elements of an NCHW tensor, all in `dtype`
+ *   (IGS_DTYPE_F32 / IGS_DTYPE_F16); arithmetic is float32.  IN(t) = (t - mean) / sqrt(var + eps) per plane with the biased variance
+ *   taken from centred values.  `mode`:
+ *     IGS_INORM_PLAIN              IN(x)                           a bare norm
+ *     IGS_INORM_RELU               relu(IN(x))                     the stem and norm1 of every block (backbone.py:30,105-107)
+ *     IGS_INORM_RELU_ADD_RELU      relu(skip + relu(IN(x)))        the tail of a block with an identity skip (backbone.py:31,36)
+ *     IGS_INORM_RELU_ADDNORM_RELU  relu(IN(skip) + relu(IN(x)))    the tail of a block with a downsample branch (backbone.py:25-26,31-36)
+ *   - out == x is allowed and gives bitwise what a separate out gives (the reference's ReLU is in place); any other overlap of out with
+ *     x or skip is refused.  relu is torch.relu: a NaN stays a NaN.  A plane that holds a NaN or an infinity comes out all NaN, as in
+ *     PyTorch; the other planes are untouched by it.  No atomics; two runs agree bit for bit.
+ *   - Refused: hw < 2 (PyTorch: "Expected more than 1 spatial element"), hw > IGS_INORM_MAX_HW, planes < 0 or > IGS_INORM_MAX_PLANES, a
+ *     NULL x or out, a NULL skip in the two modes that read it (ignored in the others), a pointer not aligned to its element size, an
+ *     unknown mode or dtype code, an eps that is negative or not finite.  planes == 0 returns 0 without a launch.
+ *   - Planes of at most igs_instance_norm_resident_max(dtype, mode) elements are read once (the workgroup holds its plane in registers);
+ *     larger ones are read twice by the same workgroup.  Plane bases need no alignment beyond the element size.
+ * igs_instance_norm_resident_max: that limit (two planes are live in IGS_INORM_RELU_ADDNORM_RELU, so it is lower there); 0 for an
+ *   unknown dtype or mode.
+ * igs_position_add: feature_add_position (igs/models/unimatch/utils.py:111-131) for both features in one launch, no split, position or
+ *   merge tensor: f0, f1, out0, out1 [B, C, H, W] contiguous in `dtype`; with n = C / 2, wh = H / splits, ww = W / splits channel c < n adds
+ *   s(c, (y mod wh) + 1, wh) and channel c >= n adds s(c - n, (x mod ww) + 1, ww), s(i, p, L) = f(p / (L + 1e-6) * 2 pi /
+ *   10000^(2 floor(i / 2) / n)) with f = sin for even i and cos for odd i (igs/models/unimatch/position.py:29-46), in float32.
+ *   out0 == f0 and out1 == f1 are allowed; any other overlap with an output is refused, as are C % 4 != 0, H or W not divisible by
+ *   splits, splits < 1, sizes out of range, an unknown dtype code and a NULL pointer.  B == 0 returns 0 without a launch. */
+#define IGS_INORM_PLAIN 0
+#define IGS_INORM_RELU 1
+#define IGS_INORM_RELU_ADD_RELU 2
+#define IGS_INORM_RELU_ADDNORM_RELU 3
+#define IGS_INORM_MAX_HW (1LL << 30)
+#define IGS_INORM_MAX_PLANES 2147483647LL
+int igs_instance_norm_fwd(void* stream, const void* x, const void* skip, void* out, long long planes, long long hw, int dtype, int mode,
+                          float eps);
+long long igs_instance_norm_resident_max(int dtype, int mode);
+int igs_position_add(void* stream, const void* f0, const void* f1, void* out0, void* out1, int B, int C, int H, int W, int splits, int dtype);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).
