@@ -14,10 +14,13 @@ with a matching flat gradient buffer, so the multi-GPU exchange is a single RCCL
 is five contiguous fused-kernel launches.  Views are sharded over ranks: at step s rank r renders view perm[s*N + r];
 every rank applies the same averaged gradient, so replicas stay identical without a broadcast.
 """
+import contextlib
+import ctypes as C
 import math
 import os
 
 import torch
+import torch.distributed as dist
 import torch.nn.functional as F      # (F.normalize of the raw quaternion: the caller-side activation)
 
 from . import _cabi
@@ -106,6 +109,8 @@ class GaussianParams:
         self.device = device
         self.lrs = dict(DEFAULT_LRS if lrs is None else lrs)
         self.betas, self.eps, self.step_count = betas, eps, 0
+        # order[i] = index Gaussian i had when the store was created (None: never reordered); spatial_sort's scratch, grown on demand
+        self.order, self._morton_scratch = None, None
         if refine_item is None and mask is not None:
             refine_item = dict(use_mask=True)          # (a mask on its own means "train what it selects")
         self.refine_item = parse_refine_item(refine_item)
@@ -157,9 +162,7 @@ class GaussianParams:
         self.flat, self.exp_avg, self.exp_avg_sq = flat, exp_avg, exp_avg_sq
         self.grad = torch.zeros(flat.numel(), dtype=torch.float32, device=self.device)
         self.spans, self.leaves = {}, {}
-        for key in ("_adam_groups", "_adam_groups_small"):
-            if hasattr(self, key):
-                delattr(self, key)
+        self._adam_groups = {}             # skip_sh -> adam_step's ctypes group tables for these spans
         o = 0
         for name, k in GROUPS:
             n = k * P
@@ -176,12 +179,11 @@ class GaussianParams:
         once per (workgroup, tile) instead of once per instance (preprocess.hip).  The rasterizer's results do not depend on
         the order (apart from which of two splats at EXACTLY the same depth comes first); `self.order[i]` is the index Gaussian i
         had when the store was created -- `original_order()` undoes every sort so far."""
-        import ctypes as C
         xyz = self.leaves["xyz"].detach().contiguous()
         Lb = _cabi.lib()
         perm = torch.empty(self.P, dtype=torch.int32, device=self.device)
         need = Lb.igs_morton_order_scratch_bytes(self.P)
-        if getattr(self, "_morton_scratch", None) is None or self._morton_scratch.numel() < need:
+        if self._morton_scratch is None or self._morton_scratch.numel() < need:
             self._morton_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
         # a partitioned store is sorted part by part: frozen Gaussians stay in [0, trainable_from), trainable ones behind them
         F = self.trainable_from
@@ -207,9 +209,8 @@ class GaussianParams:
                                                new[0].data_ptr(), new[1].data_ptr(), new[2].data_ptr(), off)
         if rc != 0:
             raise RuntimeError("igs_densify_remap failed: %d" % rc)
-        prev = getattr(self, "order", None)
         self._bind(P, *new)
-        self.order = compose_order(prev if prev is not None and prev.numel() == P else None, perm)
+        self.order = compose_order(self.order if self.order is not None and self.order.numel() == P else None, perm)
         return perm
 
     def original_order(self):
@@ -217,7 +218,7 @@ class GaussianParams:
         (convert2stream, gaussian_model.py:350-367; valid while no densification changed the set)."""
         out = {}
         inv = None
-        if getattr(self, "order", None) is not None and self.order.numel() == self.P:
+        if self.order is not None and self.order.numel() == self.P:
             inv = inverse_order(self.order)
         for k, v in self.leaves.items():
             out[k] = v.detach()[inv] if inv is not None else v.detach()
@@ -240,28 +241,28 @@ class GaussianParams:
     def zero_grad(self):
         self.grad.zero_()
 
+    def _bias_corrections(self, t):
+        """(1 - beta1^t, sqrt(1 - beta2^t)) of Adam step `t`, as every native Adam entry point takes them."""
+        b1, b2 = self.betas
+        return 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t)
+
     def adam_step(self, skip_sh=False):
         """torch.optim.Adam semantics, all parameter groups in one fused HIP launch (`skip_sh`: every group but the SH
         coefficients -- the multi-GPU exchange updates those itself, igs_adam_sh_from_view_colors)."""
         L = _cabi.lib()
         self.step_count += 1
-        b1, b2 = self.betas
-        bc1 = 1.0 - b1 ** self.step_count
-        bc2s = math.sqrt(1.0 - b2 ** self.step_count)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        key = "_adam_groups_small" if skip_sh else "_adam_groups"
-        if not hasattr(self, key):
-            import ctypes as C
+        if skip_sh not in self._adam_groups:
             # (a partially trained store: the trainable sub-span of every group that is not frozen)
             spans = [(n, o, c) for n, o, c in self.trainable_spans() if not (skip_sh and n == "shs") and c > 0]
             k = len(spans)
-            setattr(self, key, ((C.c_size_t * k)(*[o for _, o, _ in spans]), (C.c_size_t * k)(*[c for _, _, c in spans]),
-                                (C.c_float * k)(*[self.lrs[n] for n, _, _ in spans]), k))
-        off, cnt, lrs, k = getattr(self, key)
+            self._adam_groups[skip_sh] = ((C.c_size_t * k)(*[o for _, o, _ in spans]), (C.c_size_t * k)(*[c for _, _, c in spans]),
+                                          (C.c_float * k)(*[self.lrs[n] for n, _, _ in spans]), k)
+        off, cnt, lrs, k = self._adam_groups[skip_sh]
         if k == 0:
             return                      # (everything frozen)
         rc = L.igs_adam_step_groups(stream, k, off, cnt, lrs, self.flat.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
-                                    self.exp_avg_sq.data_ptr(), b1, b2, self.eps, bc1, bc2s)
+                                    self.exp_avg_sq.data_ptr(), *self.betas, self.eps, *self._bias_corrections(self.step_count))
         if rc != 0:
             raise RuntimeError("igs_adam_step_groups failed: %d" % rc)
 
@@ -292,7 +293,8 @@ class L1Fused:
         self.device = device
         self.loss_sum = torch.zeros(1024, dtype=torch.float32, device=device)      # 64 shards, 16 floats apart
 
-    def __call__(self, pred, gt, grad_out, weight=1.0):
+    def __call__(self, pred, gt, grad_out, weight=1.0, gt_stats=None):
+        """(`gt_stats`: L1SsimFused's argument; the L1 loss has no statistics to cache.)"""
         L = _cabi.lib()
         n = pred.numel()
         self.loss_sum.zero_()
@@ -385,11 +387,14 @@ class L1SsimFused:
 
 
 class Refiner:
-    """One refine step = one view per rank: render, loss, backward, gradient all-reduce (N > 1), Adam."""
+    """One refine step = one view per rank: render, loss, backward, gradient all-reduce (N > 1), Adam.  Every option is a constructor
+    argument kept as a plain attribute of the same name (assignable between steps); what a step allocates later starts as None here."""
 
     def __init__(self, params, cams, gt_images, bg, loss="l1", lambda_l1=0.8, world_size=1, rank=0, seed=0,
                  render_fn=None, adam_fn=None, native=True, fused=True, densify=None, densify_seed=0,
-                 lambda_depth_normal=0.0):
+                 lambda_depth_normal=0.0, *, require_geometry=True, clamp=False, want_viewspace_grad=None, exchange="colors",
+                 overlap_exchange=True, direct_adam=False, fused_activations=False, loss_scale=1.0, cache_gt_stats=True,
+                 ssim_fn=None, depth_normal_fn=None):
         self.params, self.cams, self.gt, self.bg = params, cams, gt_images, bg
         self.loss, self.lambda_l1 = loss, lambda_l1
         self.world_size, self.rank = world_size, rank
@@ -398,14 +403,20 @@ class Refiner:
         self.adam_fn = params.adam_step if adam_fn is None else adam_fn
         self.l1 = L1Fused(params.device) if loss == "l1" else L1SsimFused(params.device, 1.0 - lambda_l1)
         self.gt_stats = GtStatsCache(params.device) if loss != "l1" else None      # the ground truth's SSIM statistics, per view (GtStatsCache)
-        self.cache_gt_stats = True
+        self.cache_gt_stats = cache_gt_stats
         # RaDe-GS depth-normal regulariser (train.py:143-164; BASELINE cfg-5 uses 0.05): needs dL/d depth, mdepth, normal -- the
         # fused step evaluates it in one HIP launch and runs the <depth, normal> backward instance; the unfused native path does
         # not implement it (the autograd path does, through igs_amd.losses.depth_normal_loss = the same kernel)
         self.lambda_depth_normal = float(lambda_depth_normal)
         self.native = native          # drive the C ABI directly instead of going through autograd
         self.fused = fused            # ... and on a single GPU run the whole iteration as one library call (igs_refine_step)
-        self.grad_img = None
+        self.require_geometry = require_geometry      # fused step: also render coord / depth / normal (the reference's loop always does)
+        self.clamp = clamp                            # gradients clamped to +-15 as the reference's clamp rasterizer does (igs/models/gs.py:39)
+        self.loss_scale = loss_scale                  # factor on the loss (tests drive the clamp with it)
+        self.direct_adam = direct_adam                # autograd path on one GPU: gradients straight to the fused Adam (`_mode()`: "direct")
+        self.fused_activations = fused_activations    # autograd path: the three activations from one autograd Function
+        # autograd path: other differentiable implementations of the two loss terms (tests inject the PyTorch restatements)
+        self.ssim_fn, self.depth_normal_fn = ssim_fn, depth_normal_fn
         self.gen = torch.Generator().manual_seed(seed)      # same seed on every rank -> same view permutation
         self.order = []
         self.last_num_rendered = 0
@@ -413,42 +424,41 @@ class Refiner:
         self.densify = densify
         # fused step: also return dL/d(screen-space mean) with its absolute-gradient column (what the densification statistics read);
         # off = the colour-only blend backward drops that moment
-        self.want_viewspace_grad = densify is not None
+        self.want_viewspace_grad = (densify is not None) if want_viewspace_grad is None else want_viewspace_grad
         # N > 1: "colors" = gather the per-view colour gradients and rebuild dL/dSH locally (_colour_exchange_step);
-        # "gradients" = one all-reduce of the flat gradient
-        self.exchange = "colors"
-        self.iteration = 0
-        self.densify_state = None
-        self.densify_gen = None
-        self.densify_seed = densify_seed
-        self.densify_log = []
+        # "gradients" = one all-reduce of the flat gradient; `overlap_exchange`: the gather runs underneath the step's last kernel
+        self.exchange, self.overlap_exchange = exchange, overlap_exchange
+        self.iteration, self.densify_state, self.densify_gen = 0, None, None
+        self.densify_seed, self.densify_log = densify_seed, []
         # bench.py: HIP-event pairs around the collectives of the N > 1 step (None = not recorded)
         self.exchange_events = None
-        if getattr(params, "partial", False):
+        # ---- step state: allocated on first use and again when its key (P, (H, W), the scratch set) changes
+        self._view, self.last_picks = None, None          # this step's view; the views of every rank this step
+        self.grad_img, self.last_depth_normal_loss = None, None      # unfused paths: dL/d image; the regulariser's last value
+        self._bufs = _rast.RasterBuffers()                # render outputs and scratch (empty until its get())
+        self._act, self._dact, self._tmp, self._empty = None, None, None, torch.Tensor([])      # _native_step: activations, their gradients, temporaries
+        self._fused, self._cb_of, self._cb = None, None, None      # _fused_step: dL/dmean2D + loss value; the scratch set whose allocation callback is kept
+        self._loss_scratch, self._loss_scratch_key = None, None
+        self._gc, self._gc_mine, self._campos_host = None, None, {}      # _colour_exchange_step: gathered / own colour gradients, camera positions
+        self._color_event, self._comm_stream = None, None
+        if params.partial:
             # masked refinement (refine_item / mask of GaussianParams) is built for one GPU and a fixed Gaussian set
             if densify is not None:
                 raise NotImplementedError("densify-and-prune with a mask or frozen groups (refine_item) is not supported")
             if world_size > 1:
                 raise NotImplementedError("multi-GPU refinement (world_size > 1) with a mask or frozen groups (refine_item) is not supported")
 
-    class _Timed:
+    @contextlib.contextmanager
+    def _timed(self):
         """Brackets a group of collectives with events on the current stream (the collective's own stream is joined to it)."""
-
-        def __init__(self, owner):
-            self.o = owner
-
-        def __enter__(self):
-            if self.o.exchange_events is not None:
-                self.e0 = torch.cuda.Event(enable_timing=True)
-                self.e0.record()
-            return self
-
-        def __exit__(self, *exc):
-            if self.o.exchange_events is not None:
-                e1 = torch.cuda.Event(enable_timing=True)
-                e1.record()
-                self.o.exchange_events.append((self.e0, e1))
-            return False
+        events = self.exchange_events
+        if events is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        yield
+        if events is not None:
+            e1.record()
+            events.append((e0, e1))
 
     def exchange_ms_per_step(self, steps):
         """Mean time per step spent in the collectives since `exchange_events` was set to [] (synchronises)."""
@@ -473,20 +483,31 @@ class Refiner:
         self.last_picks = picks          # the views of every rank this step (same permutation everywhere)
         return picks[self.rank]
 
+    def _clamp_value(self):
+        return 15.0 if self.clamp else 0.0          # the bound on the gradients as the C ABI takes it (0 = off)
+
+    def _cached_gt_stats(self, gt):
+        """(pointer, valid) of the cached SSIM statistics of `gt` as this step's view's ground truth, or None when this step does not
+        use the cache; the caller confirms the entry once the launch that fills it succeeded."""
+        if self.gt_stats is None or not self.cache_gt_stats or self._view is None:
+            return None
+        return self.gt_stats.get(self._view, gt)
+
+    def _grad_img_like(self, img):
+        if self.grad_img is None or self.grad_img.shape != img.shape:
+            self.grad_img = torch.empty_like(img)
+        return self.grad_img
+
     def _native_step(self, cam, gt, defer=True):
         """render -> fused L1 -> backward -> activation backward, driving the C ABI directly (no autograd graph): the
         rasterizer writes dL/dxyz and dL/dsh straight into their spans of the flat gradient buffer."""
         p = self.params
         L = _cabi.lib()
         dev, P = p.device, p.P
-        if not hasattr(self, "_bufs"):
-            self._bufs = _rast.RasterBuffers()
-        if getattr(self, "_native_P", None) != P:
-            self._native_P = P
+        if self._act is None or self._act.numel() != 8 * P:
             self._act = torch.empty(8 * P, dtype=torch.float32, device=dev)       # opacity P | scale 3P | rot 4P
             self._dact = torch.empty(8 * P, dtype=torch.float32, device=dev)
             self._tmp = torch.empty(12 * P, dtype=torch.float32, device=dev)      # means2D 3 | colors 3 | cov3D 6
-            self._empty = torch.Tensor([])
         stream = torch.cuda.current_stream(dev).cuda_stream
         raw = p.leaves
         opac, scal, rotn = self._act[:P].view(P, 1), self._act[P:4 * P].view(P, 3), self._act[4 * P:].view(P, 4)
@@ -500,13 +521,10 @@ class Refiner:
                                             raw["shs"].detach(), 3, cam.camera_center, False, True, True, False, buffers=self._bufs,
                                             defer=defer)
             nr, color, coord, mcoord, alpha, normal, depth, mdepth, radii, gb, bb, ib = out
-            if self.grad_img is None or self.grad_img.shape != color.shape:
-                self.grad_img = torch.empty_like(color)
-            if self.gt_stats is not None and self.cache_gt_stats and getattr(self, "_view", None) is not None:
-                self.l1(color, gt, self.grad_img, weight=1.0 / self.world_size, gt_stats=self.gt_stats.get(self._view, gt))
+            stats = self._cached_gt_stats(gt)
+            self.l1(color, gt, self._grad_img_like(color), weight=1.0 / self.world_size, gt_stats=stats)      # L1 or L1 + D-SSIM, fused fwd + bwd
+            if stats is not None:
                 self.gt_stats.confirm(self._view)          # (l1 raises when the launch fails)
-            else:
-                self.l1(color, gt, self.grad_img, weight=1.0 / self.world_size)      # L1 or L1 + D-SSIM, fused fwd + bwd
             G = p.grad
             def span(name, shape):
                 o, n = p.spans[name]
@@ -536,20 +554,17 @@ class Refiner:
     def _fused_step(self, cam, gt, grads_only=False, color_out=None, color_event=None):
         """Single-GPU step entirely inside the library: `igs_refine_step` (include/igs_rast.h) -- activations, render, L1,
         backward and the Adam update in 5 launches; no gradient array is materialised."""
-        import ctypes as C
         p = self.params
         L = _cabi.lib()
         dev, P = p.device, p.P
         H, W = int(cam.height), int(cam.width)
-        if not hasattr(self, "_bufs"):
-            self._bufs = _rast.RasterBuffers()
         imgs, radii, ss = self._bufs.get(P, H, W, dev)
-        if not hasattr(self, "_fused") or self._fused["m2d"].shape[0] != P:
+        if self._fused is None or self._fused["m2d"].shape[0] != P:
             self._fused = dict(m2d=torch.zeros((P, 3), dtype=torch.float32, device=dev),
                                loss=torch.zeros(1, dtype=torch.float32, device=dev))
         a = _cabi.RefineStepArgs()
         a.stream = torch.cuda.current_stream(dev).cuda_stream
-        if getattr(self, "_cb_of", None) is not ss:          # (callback address + the set's three `user` words, valid while `ss` lives)
+        if self._cb_of is not ss:          # (callback address + the set's three `user` words, valid while `ss` lives)
             cb, ug, ub, ui = ss.callbacks()
             self._cb_of, self._cb = ss, (_cabi.ALLOC_FN(cb), ug, ub, ui)
         fn, ug, ub, ui = self._cb
@@ -569,23 +584,23 @@ class Refiner:
         a.viewmatrix, a.projmatrix = cam.world_view_transform.data_ptr(), cam.full_proj_transform.data_ptr()
         a.cam_pos = cam.camera_center.data_ptr()
         a.tan_fovx, a.tan_fovy = cam.tanfovx, cam.tanfovy
-        a.gt, a.loss_weight = gt.data_ptr(), getattr(self, "loss_scale", 1.0) / self.world_size      # gradients are averaged over the views of a step
+        a.gt, a.loss_weight = gt.data_ptr(), self.loss_scale / self.world_size      # gradients are averaged over the views of a step
         a.lambda_depth_normal, a.depth_ratio = self.lambda_depth_normal, 0.6
         if self.loss == "l1_ssim" or self.lambda_depth_normal > 0.0:
-            if getattr(self, "_loss_scratch_key", None) != (H, W):
+            if self._loss_scratch_key != (H, W):
                 self._loss_scratch_key = (H, W)
                 self._loss_scratch = torch.empty(L.igs_refine_loss_scratch_bytes(W, H), dtype=torch.uint8, device=dev)
             a.lambda_dssim = (1.0 - self.lambda_l1) if self.loss == "l1_ssim" else 0.0
             a.loss_scratch = self._loss_scratch.data_ptr()
-            if self.loss == "l1_ssim" and self.gt_stats is not None and self.cache_gt_stats and getattr(self, "_view", None) is not None:
-                a.gt_stats, a.gt_stats_valid = self.gt_stats.get(self._view, gt)
+            if self.loss == "l1_ssim":
+                a.gt_stats, a.gt_stats_valid = self._cached_gt_stats(gt) or (None, 0)
         else:
             a.lambda_dssim, a.loss_scratch = 0.0, None
         a.out_images, a.radii = imgs.data_ptr(), radii.data_ptr()
         a.dL_dmean2D, a.loss_out = (self._fused["m2d"].data_ptr() if self.want_viewspace_grad else None), self._fused["loss"].data_ptr()
-        rq = 1 if getattr(self, "require_geometry", True) else 0      # the reference's loop always renders coord / depth / normal
+        rq = 1 if self.require_geometry else 0      # the reference's loop always renders coord / depth / normal
         a.require_coord, a.require_depth = rq, rq
-        a.clamp_grads = 15.0 if getattr(self, "clamp", False) else 0.0
+        a.clamp_grads = self._clamp_value()
         a.color_grad_out = color_out.data_ptr() if color_out is not None else None
         if color_event is not None:
             h = color_event.cuda_event                         # ctypes.c_void_p of the hipEvent_t
@@ -611,23 +626,20 @@ class Refiner:
     def _ssim_value(self, img, gt):
         """Autograd path: mean SSIM from the fused HIP kernels (igs_amd.losses.ssim); `ssim_fn` lets a test inject another
         differentiable implementation (the PyTorch restatement of the test tree) for an independent comparison."""
-        fn = getattr(self, "ssim_fn", None)
-        if fn is not None:
-            return fn(img, gt)
+        if self.ssim_fn is not None:
+            return self.ssim_fn(img, gt)
         from .losses import ssim as fused_ssim
         return fused_ssim(img, gt.unsqueeze(0), size_average=False).squeeze()
 
     def _depth_normal_value(self, pkg, cam):
-        fn = getattr(self, "depth_normal_fn", None)
-        if fn is not None:
-            return fn(pkg, cam)
+        if self.depth_normal_fn is not None:
+            return self.depth_normal_fn(pkg, cam)
         from .losses import depth_normal_loss
         return depth_normal_loss(pkg, cam)
 
     def start_frame(self):
         """A new frame of the stream begins (infer_batch.py:270-278): iteration counter and densification statistics restart."""
-        self.iteration = 0
-        self.densify_state = None
+        self.iteration, self.densify_state = 0, None
 
     def _densify_hooks(self, pkg, did_adam):
         """infer_batch.py:308-321, after the backward of iteration `self.iteration`: statistics, then (every `interval`
@@ -654,10 +666,14 @@ class Refiner:
         return (cfg is not None and self.iteration < cfg.until_iter and self.iteration > cfg.from_iter
                 and self.iteration % cfg.interval == 0)
 
-    def _native_then_adam(self, cam, gt):
-        pkg = self._native_step(cam, gt)
-        self.adam_fn()
-        return pkg
+    def _reduce_small_groups(self):
+        """All-reduces the flat gradient on both sides of the SH span: xyz | rotation | opacity | scaling, 11 floats per Gaussian."""
+        g, (sh0, shn) = self.params.grad, self.params.spans["shs"]
+        with self._timed():
+            if sh0 > 0:
+                dist.all_reduce(g[:sh0], op=dist.ReduceOp.SUM)
+            if sh0 + shn < g.numel():
+                dist.all_reduce(g[sh0 + shn:], op=dist.ReduceOp.SUM)
 
     def _colour_exchange_step(self, cam, gt, picks):
         """N > 1: the step's gradient with 3.4x fewer bytes on the wire than an all-reduce of the flat buffer.  dL/dSH (48 of the 59
@@ -665,19 +681,18 @@ class Refiner:
         the [P,3] colour gradients (12 B per Gaussian and view), every rank rebuilds the SH gradient of the whole step itself
         (`igs_sh_grad_from_view_colors`, views in rank order: identical bits everywhere), and only the 11 small-group floats go
         through all-reduces.  At N = 8, 200k Gaussians: 19 MB gathered + 8.8 MB reduced instead of 47 MB reduced."""
-        import torch.distributed as dist
         p = self.params
         L = _cabi.lib()
         P, N, dev = p.P, self.world_size, p.device
-        if getattr(self, "_gc", None) is None or self._gc.shape[1] != P:
+        if self._gc is None or self._gc.shape[1] != P:
             self._gc = torch.zeros((N, P, 3), dtype=torch.float32, device=dev)
             self._gc_mine = torch.zeros((P, 3), dtype=torch.float32, device=dev)
             self._campos_host = {}
         # The view's colour gradients are final right after the blend backward, one kernel before the step ends: the library writes them
         # there and records an event (igs_refine_step_args::color_ready_event); the all-gather waits for THAT on a side stream and runs
         # underneath the per-Gaussian kernel (geom_bwd, ~70 us) instead of behind it.  `overlap_exchange = False`: gather after the step.
-        overlap = getattr(self, "overlap_exchange", True) and dev.type == "cuda"
-        if overlap and getattr(self, "_color_event", None) is None:
+        overlap = self.overlap_exchange and dev.type == "cuda"
+        if overlap and self._color_event is None:
             self._color_event = torch.cuda.Event()
             self._color_event.record(torch.cuda.current_stream(dev))       # (creates the hipEvent_t the library will record)
             self._comm_stream = torch.cuda.Stream(device=dev)
@@ -693,48 +708,34 @@ class Refiner:
             self._comm_stream.wait_event(self._color_event)
             with torch.cuda.stream(self._comm_stream):
                 gather()
-            with self._Timed(self):
+            with self._timed():
                 main.wait_stream(self._comm_stream)                    # (what is left of the gather once geom_bwd is done)
         else:
-            with self._Timed(self):
+            with self._timed():
                 gather()
-        import ctypes as C
         for v in picks:
             if v not in self._campos_host:          # (one device read per camera, the first time it is used)
                 self._campos_host[v] = [float(x) for x in self.cams[v].camera_center.reshape(3).tolist()]
         campos = (C.c_float * (3 * N))(*[x for v in picks for x in self._campos_host[v]])
-        (sh0, shn) = p.spans["shs"]
-        clamp = 15.0 if getattr(self, "clamp", False) else 0.0
+        clamp = self._clamp_value()
         stream = torch.cuda.current_stream(dev).cuda_stream
         if self.adam_fn == p.adam_step:
-            # the library's own optimiser: the SH update straight from the gathered colours (no SH gradient in HBM), the 11 small
-            # floats through the all-reduce and the grouped Adam launch
-            b1, b2 = p.betas
-            t = p.step_count + 1
-            with self._Timed(self):
-                if sh0 > 0:
-                    dist.all_reduce(p.grad[:sh0], op=dist.ReduceOp.SUM)
-                if sh0 + shn < p.grad.numel():
-                    dist.all_reduce(p.grad[sh0 + shn:], op=dist.ReduceOp.SUM)
-            # ONE launch for the whole optimiser step: SH coefficients from the gathered colours, the 11 small floats from their
-            # all-reduced gradients (igs_adam_exchange_step)
+            # the library's own optimiser, ONE launch for the whole step (igs_adam_exchange_step): the SH update straight from the
+            # gathered colours (no SH gradient in HBM), the 11 small floats from their all-reduced gradients
+            self._reduce_small_groups()
             sp = p.spans
             rc = L.igs_adam_exchange_step(stream, P, 3, 16, N, C.cast(campos, C.c_void_p), self._gc.data_ptr(), clamp, p.flat.data_ptr(),
                                           p.exp_avg.data_ptr(), p.exp_avg_sq.data_ptr(), p.grad.data_ptr(), sp["xyz"][0], sp["rotation"][0],
                                           sp["shs"][0], sp["opacity"][0], sp["scaling"][0], p.lrs["xyz"], p.lrs["rotation"], p.lrs["shs"],
-                                          p.lrs["opacity"], p.lrs["scaling"], b1, b2, p.eps, 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t))
+                                          p.lrs["opacity"], p.lrs["scaling"], *p.betas, p.eps, *p._bias_corrections(p.step_count + 1))
             _rast._check(rc, "igs_adam_exchange_step")
             p.step_count += 1
             return pkg
         rc = L.igs_sh_grad_from_view_colors(stream, P, 3, 16, N, p.flat.data_ptr() + 4 * p.spans["xyz"][0],
                                             C.cast(campos, C.c_void_p), self._gc.data_ptr(), clamp,
-                                            p.grad.data_ptr() + 4 * sh0)
+                                            p.grad.data_ptr() + 4 * p.spans["shs"][0])
         _rast._check(rc, "igs_sh_grad_from_view_colors")
-        with self._Timed(self):
-            if sh0 > 0:
-                dist.all_reduce(p.grad[:sh0], op=dist.ReduceOp.SUM)             # xyz | rotation | opacity | scaling: 11 floats per Gaussian
-            if sh0 + shn < p.grad.numel():
-                dist.all_reduce(p.grad[sh0 + shn:], op=dist.ReduceOp.SUM)
+        self._reduce_small_groups()
         self.adam_fn()
         return pkg
 
@@ -742,14 +743,13 @@ class Refiner:
         """N > 1 (or an injected optimiser): the same fused launches, ending in the flat gradient instead of the update; then the
         exchange over RCCL / xGMI and the identical Adam step on every rank."""
         p = self.params
-        picks = getattr(self, "last_picks", None) if explicit_view is None else None
+        picks = self.last_picks if explicit_view is None else None
         if 1 < self.world_size <= 64 and self.fused and self.exchange == "colors" and picks is not None:      # (the library takes at most 64 views)
             return self._colour_exchange_step(cam, gt, picks)
         # (a partially trained store: the native launches end in the full gradient, the optimiser steps the trainable spans only)
         pkg = self._fused_step(cam, gt, grads_only=True) if self.fused and not p.partial else self._native_step(cam, gt)
         if self.world_size > 1:
-            import torch.distributed as dist
-            with self._Timed(self):
+            with self._timed():
                 dist.all_reduce(p.grad, op=dist.ReduceOp.SUM)      # one flat 59*P-float buffer over RCCL / xGMI
         self.adam_fn()
         return pkg
@@ -776,7 +776,7 @@ class Refiner:
             return "densify"
         if self._native_ok():
             return "fused" if (self.fused and self.world_size == 1 and own_adam) else "exchange"
-        if (self.world_size == 1 and own_adam and self.render_fn is render and p.flat.is_cuda and getattr(self, "direct_adam", False)):
+        if (self.world_size == 1 and own_adam and self.render_fn is render and p.flat.is_cuda and self.direct_adam):
             return "direct"          # opt-in: tests and callers that read `.grad` keep the flat buffer
         return "autograd"
 
@@ -808,7 +808,11 @@ class Refiner:
             self._densify_hooks(pkg, did_adam=False)
             return pkg
         if self.world_size == 1:
-            pkg = self._fused_step(cam, gt) if self.fused else self._native_then_adam(cam, gt)
+            if self.fused:
+                pkg = self._fused_step(cam, gt)
+            else:
+                pkg = self._native_step(cam, gt)
+                self.adam_fn()
         else:
             pkg = self._exchange_step(cam, gt, explicit_view)
         if self.iteration < self.densify.until_iter:
@@ -824,7 +828,7 @@ class Refiner:
         if self.lambda_depth_normal > 0.0:
             self.last_depth_normal_loss = self._depth_normal_value(pkg, cam)
             loss = loss + self.lambda_depth_normal * self.last_depth_normal_loss
-        return loss * getattr(self, "loss_scale", 1.0)
+        return loss * self.loss_scale
 
     def _step_autograd(self, cam, gt, direct):
         """The reference's own loop through the autograd Function.  `direct`: `optimizer.zero_grad(set_to_none=True)` semantics
@@ -834,17 +838,13 @@ class Refiner:
         p = self.params
         if not direct:
             p.zero_grad()
-        act = p.activated(fused=getattr(self, "fused_activations", False) and self.render_fn is render and p.flat.is_cuda)
-        if getattr(self, "clamp", False) and self.render_fn is render:
-            pkg = self.render_fn(act, cam, self.bg, clamp=True)
-        else:
-            pkg = self.render_fn(act, cam, self.bg)
+        act = p.activated(fused=self.fused_activations and self.render_fn is render and p.flat.is_cuda)
+        clamp = dict(clamp=True) if self.clamp and self.render_fn is render else {}      # (an injected render_fn takes no such argument)
+        pkg = self.render_fn(act, cam, self.bg, **clamp)
         img = pkg["images_pred"]
         pure_l1 = self.loss == "l1" and self.lambda_depth_normal == 0.0
         if pure_l1:         # fused L1 forward + gradient in one launch, handed to autograd as the upstream gradient of the image
-            if self.grad_img is None or self.grad_img.shape != img.shape:
-                self.grad_img = torch.empty_like(img)
-            self.l1(img, gt, self.grad_img, weight=1.0 if direct else 1.0 / self.world_size)      # (gradients are averaged over the views of a step)
+            self.l1(img, gt, self._grad_img_like(img), weight=1.0 if direct else 1.0 / self.world_size)      # (gradients are averaged over the views of a step)
         if direct:
             names = [n for n, _ in GROUPS]
             leaves = [p.leaves[n] for n in names]
@@ -852,8 +852,7 @@ class Refiner:
                      else torch.autograd.grad([self._autograd_loss(pkg, cam, gt)], leaves))
             L = _cabi.lib()
             p.step_count += 1
-            b1, b2 = p.betas
-            bc1, bc2s = 1.0 - b1 ** p.step_count, math.sqrt(1.0 - b2 ** p.step_count)
+            adam = (*p.betas, p.eps, *p._bias_corrections(p.step_count))
             stream = torch.cuda.current_stream(p.device).cuda_stream
             live = {n: (o, cnt) for n, o, cnt in p.trainable_spans()}          # (a masked store: trainable sub-spans of unfrozen groups)
             for n, g in zip(names, grads):
@@ -862,7 +861,7 @@ class Refiner:
                 o, cnt = live[n]
                 g = g.contiguous().view(-1)[o - p.spans[n][0]:]
                 rc = L.igs_adam_step(stream, cnt, p.flat.data_ptr() + 4 * o, g.data_ptr(), p.exp_avg.data_ptr() + 4 * o,
-                                     p.exp_avg_sq.data_ptr() + 4 * o, p.lrs[n], b1, b2, p.eps, bc1, bc2s)
+                                     p.exp_avg_sq.data_ptr() + 4 * o, p.lrs[n], *adam)
                 if rc != 0:
                     raise RuntimeError("igs_adam_step failed: %d" % rc)
             return pkg
@@ -871,7 +870,6 @@ class Refiner:
         else:
             (self._autograd_loss(pkg, cam, gt) / self.world_size).backward()
         if self.world_size > 1:
-            import torch.distributed as dist
             dist.all_reduce(p.grad, op=dist.ReduceOp.SUM)      # one flat 59*P-float buffer over RCCL / xGMI
         self.adam_fn()
         return pkg

@@ -285,3 +285,40 @@ def test_unfused_paths_agree_with_the_fused_masked_step(dev, mode):
     assert torch.equal(pu.flat[o:o + n], start[o:o + n])
     got, want = _leaves(pu), _leaves(pf)
     _assert_close_to_restatement({k: v[F:] for k, v in got.items()}, {k: v[F:] for k, v in want.items()}, steps, mode)
+
+
+@pytest.fixture(scope="module")
+def small_scene(dev):
+    return _scene(dev)
+
+
+def _attribute_cases():
+    from igs_amd.densify import DensifyConfig
+    return {
+        "fused_l1": (dict(loss="l1"), {}, "fused"),
+        "fused_l1_ssim_depth_normal": (dict(loss="l1_ssim", lambda_depth_normal=0.05), {}, "fused"),
+        "native": (dict(fused=False), {}, "exchange"),
+        "autograd": (dict(native=False), {}, "autograd"),
+        "direct": (dict(native=False, direct_adam=True), {}, "direct"),
+        "masked": ({}, dict(refine_item=dict(use_mask=True, no_scaling=True), mask=_index_mask(P0)), "fused"),
+        "densify": (dict(densify=DensifyConfig(from_iter=0, interval=2, until_iter=10)), {}, "densify"),
+    }
+
+
+@pytest.mark.parametrize("case", ["fused_l1", "fused_l1_ssim_depth_normal", "native", "autograd", "direct", "masked", "densify"])
+def test_a_step_adds_no_attribute(small_scene, dev, case):
+    """Everything a Refiner and its GaussianParams can carry is declared at construction: 4 steps in every mode (the densify case
+    rebuilds the store through _bind in its third) leave the attribute sets of both objects as they were."""
+    from igs_amd.refine import GaussianParams, Refiner
+    raw, cams, gts, bg = small_scene
+    refiner_kw, store_kw, mode = _attribute_cases()[case]
+    p = GaussianParams(raw, dev, **store_kw)
+    r = Refiner(p, cams, gts, bg, **refiner_kw)
+    before = set(vars(r)), set(vars(p))
+    for _ in range(4):
+        r.step()
+    torch.cuda.synchronize()
+    assert r._mode() == mode
+    assert (set(vars(r)), set(vars(p))) == before
+    if case == "densify":
+        assert [e[0] for e in r.densify_log] == [2]          # (the rebuild did happen, at iteration 2)

@@ -170,3 +170,77 @@ def test_refiner_refuses_densify_and_multi_gpu_with_a_mask():
         with pytest.raises(NotImplementedError, match="world_size > 1"):
             Refiner(p, cams, gts, bg, world_size=2)
     Refiner(GaussianParams(raw, torch.device("cpu")), cams, gts, bg, world_size=2)      # (no mask: unchanged)
+
+
+REFINER_OPTIONS = dict(require_geometry=True, clamp=False, want_viewspace_grad=None, exchange="colors", overlap_exchange=True,
+                       direct_adam=False, fused_activations=False, loss_scale=1.0, cache_gt_stats=True, ssim_fn=None, depth_normal_fn=None)
+
+
+def _cpu_refiner(**kw):
+    from igs_amd.refine import GaussianParams, Refiner
+    p = GaussianParams(_raw(8), torch.device("cpu"))
+    if kw.get("adam_fn") == "injected":
+        kw["adam_fn"] = lambda: None
+    return Refiner(p, [None], [torch.zeros(3, 4, 4)], torch.zeros(3), **kw)
+
+
+def test_refiner_constructor_owns_every_option():
+    """Every option the step code reads is a keyword-only argument of Refiner.__init__ and a plain attribute of the fresh object, with
+    the default the step code used to assume; `want_viewspace_grad=None` resolves to `densify is not None`."""
+    import inspect
+    from igs_amd.refine import Refiner
+    from igs_amd.densify import DensifyConfig
+    sig = inspect.signature(Refiner.__init__).parameters
+    r = _cpu_refiner()
+    for name, default in REFINER_OPTIONS.items():
+        assert sig[name].kind is inspect.Parameter.KEYWORD_ONLY and sig[name].default == default, name
+        assert name in vars(r), name
+        assert vars(r)[name] == (False if name == "want_viewspace_grad" else default), name
+    assert _cpu_refiner(densify=DensifyConfig()).want_viewspace_grad is True
+    assert _cpu_refiner(densify=DensifyConfig(), want_viewspace_grad=False).want_viewspace_grad is False
+    assert list(sig)[:17] == ["self", "params", "cams", "gt_images", "bg", "loss", "lambda_l1", "world_size", "rank", "seed", "render_fn",
+                              "adam_fn", "native", "fused", "densify", "densify_seed", "lambda_depth_normal"]      # (positional order unmoved)
+    other = dict(require_geometry=False, clamp=True, want_viewspace_grad=True, exchange="gradients", overlap_exchange=False, direct_adam=True,
+                 fused_activations=True, loss_scale=3.0, cache_gt_stats=False, ssim_fn=len, depth_normal_fn=max)
+    assert set(other) == set(REFINER_OPTIONS)
+    r = _cpu_refiner(**other)
+    assert all(vars(r)[k] is v or vars(r)[k] == v for k, v in other.items())
+
+
+def _fake_render(act, cam, bg):
+    raise AssertionError("not called")
+
+
+MODE_TABLE = [
+    (dict(), "fused"),
+    (dict(loss="l1_ssim"), "fused"),
+    (dict(lambda_depth_normal=0.05), "fused"),
+    (dict(world_size=2), "exchange"),
+    (dict(adam_fn="injected"), "exchange"),
+    (dict(fused=False), "exchange"),
+    (dict(fused=False, lambda_depth_normal=0.05), "autograd"),
+    (dict(native=False), "autograd"),
+    (dict(native=False, direct_adam=True), "autograd"),          # (a CPU store; on a CUDA store: "direct")
+    (dict(render_fn=_fake_render), "autograd"),
+    (dict(densify=True), "densify"),
+    (dict(densify=True, fused=False), "densify"),
+    (dict(densify=True, world_size=2), "densify"),
+    (dict(densify=True, adam_fn="injected"), NotImplementedError),
+    (dict(densify=True, native=False), NotImplementedError),
+]
+
+
+@pytest.mark.parametrize("kw,want", MODE_TABLE, ids=[",".join("%s=%s" % (k, getattr(v, "__name__", v)) for k, v in kw.items()) or "defaults"
+                                                     for kw, _ in MODE_TABLE])
+def test_refiner_mode_table(kw, want):
+    """`_mode()` for every way a Refiner is set up (taken from the class before its options moved into the constructor)."""
+    from igs_amd.densify import DensifyConfig
+    kw = dict(kw)
+    if kw.get("densify"):
+        kw["densify"] = DensifyConfig()
+    r = _cpu_refiner(**kw)
+    if want is NotImplementedError:
+        with pytest.raises(NotImplementedError):
+            r._mode()
+    else:
+        assert r._mode() == want

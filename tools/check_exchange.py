@@ -1,5 +1,5 @@
 """Two (or more) ranks on the visible GPU(s): one refine step with the flat-gradient all-reduce and one with the colour-gradient
-exchange (Refiner.exchange = "gradients" / "colors") from the same state must leave the same gradient and the same parameters
+exchange (Refiner(exchange="gradients" / "colors")) from the same state must leave the same gradient and the same parameters
 on every rank.  Launch:  python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 tools/check_exchange.py
 [--backend gloo|nccl]   (gloo rehearses the path on a one-GPU box; every rank then uses cuda:0)."""
 import argparse, os, sys
@@ -67,9 +67,8 @@ def main():
     # side stream; "colors_serial": the same exchange behind the last kernel of the step -- the two must agree (to rounding)
     for mode in ("gradients", "colors", "colors_serial"):
         p = GaussianParams(raw, dev)
-        r = Refiner(p, cams, gts, bg, loss=args.loss, world_size=world, rank=rank, seed=3)
-        r.exchange, r.clamp = mode.split("_")[0], args.clamp
-        r.overlap_exchange = mode == "colors"
+        r = Refiner(p, cams, gts, bg, loss=args.loss, world_size=world, rank=rank, seed=3, exchange=mode.split("_")[0], clamp=args.clamp,
+                    overlap_exchange=(mode == "colors"))
         for _ in range(3):
             if world > 1:
                 r.step()
@@ -109,8 +108,7 @@ def main():
         # one rank: the exchange step (gradients to HBM, collectives over a one-rank communicator, igs_adam_exchange_step) must land where
         # the single-GPU fused step (igs_refine_step applying Adam itself) lands from the same start with the same views
         p = GaussianParams(raw, dev)
-        r = Refiner(p, cams, gts, bg, loss=args.loss, seed=3)
-        r.clamp = args.clamp
+        r = Refiner(p, cams, gts, bg, loss=args.loss, seed=3, clamp=args.clamp)
         for _ in range(3):
             r.step()
         torch.cuda.synchronize()
@@ -130,8 +128,7 @@ def main():
             gts = [render(activate(gt_raw), c, bg)["images_pred"].clone() for c in cams]
         for mode in ("gradients", "colors"):
             p = GaussianParams(raw, dev); p.spatial_sort()
-            r = Refiner(p, cams, gts, bg, loss="l1", world_size=world, rank=rank, seed=3)
-            r.exchange = mode
+            r = Refiner(p, cams, gts, bg, loss="l1", world_size=world, rank=rank, seed=3, exchange=mode)
 
             def one():
                 if world > 1:

@@ -28,11 +28,7 @@ for fused in (True, False):
     r.adam_fn = lambda: None
     pk = r.step(view=0)
     torch.cuda.synchronize()
-    bufs = [v for v in r.__dict__.values() if isinstance(v, R.RasterBuffers)]
-    if not bufs:
-        print("no RasterBuffers on this Refiner (mode %s); attributes: %s" % (r._mode(), sorted(r.__dict__)))
-        sys.exit(0)
-    ss = bufs[0].scratch
+    ss = r._bufs.scratch
     nr = int(pk.get("num_rendered", 0)) if isinstance(pk, dict) and "num_rendered" in pk else 0
     d = R.debug_dump(P, 0, cam.width, cam.height, ss.geom, ss.binning, ss.img)
     recs.append(d["rec"].cpu().numpy()); imgs.append(pk["images_pred"].detach().cpu().numpy())

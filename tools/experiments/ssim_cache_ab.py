@@ -14,8 +14,7 @@ with torch.no_grad():
 
 def run(cache, steps=200):
     p = GaussianParams(raw, dev); p.spatial_sort()
-    r = Refiner(p, cams, gts, bg, loss="l1_ssim", seed=7)
-    r.cache_gt_stats = cache
+    r = Refiner(p, cams, gts, bg, loss="l1_ssim", seed=7, cache_gt_stats=cache)
     for _ in range(30):
         r.step()
     torch.cuda.synchronize(); t = time.perf_counter()

@@ -49,7 +49,7 @@ def n_view(raw, cams, bg, gts, dev, steps, N, loss="l1_ssim", seed=0, at=(), lr_
         r._next_view()
         acc.zero_()
         for v in r.last_picks:                       # what the N ranks of a step render, one after the other on this GPU
-            r._view = v
+            r._view = v                              # (what step() sets: the view whose cached gt statistics the call may use)
             r._fused_step(cams[v], gts[v], grads_only=True)
             acc += p.grad
         p.grad.copy_(acc)
