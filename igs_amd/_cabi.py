@@ -150,6 +150,12 @@ SIGNATURES = {
     "igs_instance_norm_fwd": (_i, [_vp] * 4 + [_ll] * 2 + [_i] * 2 + [_f]),
     "igs_instance_norm_resident_max": (_ll, [_i] * 2),
     "igs_position_add": (_i, [_vp] * 5 + [_i] * 6),
+    # tokens.hip
+    "igs_layer_norm_fwd": (_i, [_vp, _ll, _i] + [_i, _vp, _ll] * 2 + [_vp, _vp, _f] + [_i, _vp, _ll]),
+    "igs_layer_norm_bwd_scratch_bytes": (_sz, [_ll, _i]),
+    "igs_layer_norm_bwd": (_i, [_vp, _ll, _i] + [_i, _vp, _ll] + [_vp, _f] + [_i, _vp, _ll] * 2 + [_vp] * 3),
+    "igs_geglu_fwd": (_i, [_vp, _ll, _i, _i, _vp, _ll, _vp]),
+    "igs_geglu_bwd": (_i, [_vp, _ll, _i, _i, _vp, _ll, _vp, _vp]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -16,6 +16,7 @@
 //   attention           attn.hip                attn_fwd / _bwd on [B, H, A, 64] views of any acceptable strides
 //   window attention    wattn.hip               _window.window_attn_fwd / _bwd on [B, h w, 128] views of any acceptable strides
 //   encoder norms       inorm.hip               _encoder.instance_norm_fwd, _encoder.position_add on contiguous [N, C, H, W] tensors
+//   token ops           tokens.hip              _tokens.layer_norm_fwd / _bwd, _tokens.geglu_fwd / _bwd on [N, C] rows with a row stride
 //   deform              motion.hip              motion_deform_fwd / _bwd
 //   Adam                refine_ops.hip          adam_step_multi
 //   losses              refine_ops, loss_ops    l1_mean; ssim_mean
@@ -867,6 +868,113 @@ std::tuple<Tensor, Tensor> position_add(const Tensor& f0, const Tensor& f1, int6
     return {o0, o1};
 }
 
+// ---- LayerNorm and GEGLU of the two transformers (tokens.hip; contract in include/igs_rast.h) ----
+// [N, C] rows, float32 / float16, stride 1 inside a row and a row stride of at least C (the Python layer copies what is not)
+int token_rows_check(const char* fn, const Tensor& t, const char* name)
+{
+    const int dt = dtype_code(t, fn, name);
+    if (t.dim() != 2) throw RasterizerError(std::string(fn) + ": " + name + " must have shape [N, C] (got " + c10::str(t.sizes()) + ")");
+    if ((t.size(1) > 1 && t.stride(1) != 1) || (t.size(0) > 1 && t.stride(0) < t.size(1)))
+        throw RasterizerError(std::string(fn) + ": " + name + " must have stride 1 inside a row and a row stride of at least the row length");
+    return dt;
+}
+// the row stride for the C call (a single row's own stride is arbitrary in PyTorch)
+int64_t token_row_stride(const Tensor& t) { return t.size(0) > 1 ? t.stride(0) : t.size(1); }
+void token_param_check(const char* fn, const OptTensor& p, const char* name, int64_t C)
+{
+    if (p) expect(*p, fn, name, at::kFloat, {C});
+}
+// out [N, C] contiguous, float16 when out_half, else float32: (residual +) LN(x) * weight + bias
+Tensor layer_norm_fwd(const Tensor& x, const OptTensor& weight, const OptTensor& bias, double eps, const OptTensor& residual, bool out_half)
+{
+    const char* fn = "layer_norm_fwd";
+    const int xdt = token_rows_check(fn, x, "x");
+    const int64_t N = x.size(0), C = x.size(1);
+    token_param_check(fn, weight, "weight", C);
+    token_param_check(fn, bias, "bias", C);
+    if (weight.has_value() != bias.has_value()) throw RasterizerError(std::string(fn) + ": weight and bias go together (both or neither)");
+    int rdt = IGS_DTYPE_F32;
+    if (residual) {
+        rdt = token_rows_check(fn, *residual, "residual");
+        if (residual->sizes() != x.sizes())
+            throw RasterizerError(std::string(fn) + ": residual has shape " + c10::str(residual->sizes()) + ", expected " + c10::str(x.sizes()));
+    }
+    if (C < 1 || C > IGS_LN_MAX_C || N > IGS_LN_MAX_ROWS)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (1 <= C <= " + std::to_string(IGS_LN_MAX_C) + ", N <= 2^24)");
+    const GpuCall c(x, fn, "x");
+    if (weight) same_device(x, fn, {{*weight, "weight"}, {*bias, "bias"}});
+    if (residual) same_device(x, fn, {{*residual, "residual"}});
+    Tensor out = at::empty({N, C}, x.options().dtype(out_half ? at::kHalf : at::kFloat));
+    if (N == 0) return out;
+    OptTensor wc, bc;
+    if (weight) { wc = weight->contiguous(); bc = bias->contiguous(); }
+    check(igs_layer_norm_fwd(c.stream(), N, (int)C, xdt, x.data_ptr(), token_row_stride(x), rdt, ptr_or_null(residual), residual ? token_row_stride(*residual) : C,
+                             ptr_or_null<float>(wc), ptr_or_null<float>(bc), (float)eps, out_half ? IGS_DTYPE_F16 : IGS_DTYPE_F32, out.data_ptr(), C),
+          "igs_layer_norm_fwd");
+    return out;
+}
+// (d x [N, C] contiguous in x's dtype, d weight, d bias [C] float32), each None unless wanted; d residual is grad_out itself
+std::tuple<OptTensor, OptTensor, OptTensor> layer_norm_bwd(const Tensor& x, const OptTensor& weight, double eps, const Tensor& grad_out, bool want_x,
+                                                           bool want_weight, bool want_bias)
+{
+    const char* fn = "layer_norm_bwd";
+    const int xdt = token_rows_check(fn, x, "x"), gdt = token_rows_check(fn, grad_out, "grad_out");
+    const int64_t N = x.size(0), C = x.size(1);
+    token_param_check(fn, weight, "weight", C);
+    if (grad_out.sizes() != x.sizes())
+        throw RasterizerError(std::string(fn) + ": grad_out has shape " + c10::str(grad_out.sizes()) + ", expected " + c10::str(x.sizes()));
+    if (C < 1 || C > IGS_LN_MAX_C || N > IGS_LN_MAX_ROWS)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (1 <= C <= " + std::to_string(IGS_LN_MAX_C) + ", N <= 2^24)");
+    const GpuCall c(x, fn, "x", {{grad_out, "grad_out"}});
+    if (weight) same_device(x, fn, {{*weight, "weight"}});
+    OptTensor dx, dw, db, scratch, wc;
+    const auto fo = x.options().dtype(at::kFloat);
+    if (want_x) dx = at::empty({N, C}, x.options());
+    if (want_weight) dw = N == 0 ? at::zeros({C}, fo) : at::empty({C}, fo);
+    if (want_bias) db = N == 0 ? at::zeros({C}, fo) : at::empty({C}, fo);
+    if (N == 0 || !(want_x || want_weight || want_bias)) return {dx, dw, db};
+    if (want_weight || want_bias) scratch = at::empty({(int64_t)igs_layer_norm_bwd_scratch_bytes(N, (int)C)}, x.options().dtype(at::kByte));
+    if (weight) wc = weight->contiguous();
+    check(igs_layer_norm_bwd(c.stream(), N, (int)C, xdt, x.data_ptr(), token_row_stride(x), ptr_or_null<float>(wc), (float)eps, gdt, grad_out.data_ptr(),
+                             token_row_stride(grad_out), xdt, ptr_or_null(dx), C, ptr_or_null<float>(dw), ptr_or_null<float>(db), ptr_or_null(scratch)),
+          "igs_layer_norm_bwd");
+    return {dx, dw, db};
+}
+int64_t geglu_check(const char* fn, const Tensor& proj)
+{
+    if (proj.size(1) % 2) throw RasterizerError(std::string(fn) + ": proj must have an even row length 2 D (got " + c10::str(proj.sizes()) + ")");
+    const int64_t D = proj.size(1) / 2;
+    if (D < 1 || D > IGS_GEGLU_MAX_D || proj.size(0) * D > IGS_GEGLU_MAX_ELEMS)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (1 <= D <= " + std::to_string(IGS_GEGLU_MAX_D) + ", N * D <= 2^30)");
+    return D;
+}
+// out [N, D] contiguous in proj's dtype: proj[:, :D] * gelu(proj[:, D:])
+Tensor geglu_fwd(const Tensor& proj)
+{
+    const char* fn = "geglu_fwd";
+    const int dt = token_rows_check(fn, proj, "proj");
+    const int64_t N = proj.size(0), D = geglu_check(fn, proj);
+    const GpuCall c(proj, fn, "proj");
+    Tensor out = at::empty({N, D}, proj.options());
+    if (N == 0) return out;
+    check(igs_geglu_fwd(c.stream(), N, (int)D, dt, proj.data_ptr(), token_row_stride(proj), out.data_ptr()), "igs_geglu_fwd");
+    return out;
+}
+// d proj [N, 2 D] contiguous in proj's dtype, both halves
+Tensor geglu_bwd(const Tensor& proj, const Tensor& grad_out)
+{
+    const char* fn = "geglu_bwd";
+    const int dt = token_rows_check(fn, proj, "proj");
+    const int64_t N = proj.size(0), D = geglu_check(fn, proj);
+    expect(grad_out, fn, "grad_out", proj.scalar_type(), {N, D});
+    const GpuCall c(proj, fn, "proj", {{grad_out, "grad_out"}});
+    Tensor dp = at::empty({N, 2 * D}, proj.options());
+    if (N == 0) return dp;
+    const Tensor gc = grad_out.contiguous();
+    check(igs_geglu_bwd(c.stream(), N, (int)D, dt, proj.data_ptr(), token_row_stride(proj), gc.data_ptr(), dp.data_ptr()), "igs_geglu_bwd");
+    return dp;
+}
+
 // ---- the Gaussian deform (motion.hip) ----
 void deform_checks(const char* fn, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot, int* dt)
 {
@@ -1129,6 +1237,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     def_nogil(en, "instance_norm_fwd", &instance_norm_fwd, "x"_a, "skip"_a = none, "mode"_a = 0, "eps"_a = 1e-5, "inplace"_a = false);
     def_nogil(en, "position_add", &position_add, "feature0"_a, "feature1"_a, "splits"_a, "inplace"_a = false);
     en.def("resident_max", [](int64_t dtype, int64_t mode) { return (int64_t)igs_instance_norm_resident_max((int)dtype, (int)mode); }, "dtype"_a, "mode"_a);
+    // ... and the transformers' LayerNorm and GEGLU
+    py::module_ tk = m.def_submodule("_tokens", "LayerNorm and GEGLU of the two transformers (tokens.hip)");
+    def_nogil(tk, "layer_norm_fwd", &layer_norm_fwd, "x"_a, "weight"_a = none, "bias"_a = none, "eps"_a = 1e-5, "residual"_a = none, "out_half"_a = false);
+    def_nogil(tk, "layer_norm_bwd", &layer_norm_bwd, "x"_a, "weight"_a, "eps"_a, "grad_out"_a, "want_x"_a = true, "want_weight"_a = true,
+              "want_bias"_a = true);
+    def_nogil(tk, "geglu_fwd", &geglu_fwd, "proj"_a);
+    def_nogil(tk, "geglu_bwd", &geglu_bwd, "proj"_a, "grad_out"_a);
     def_nogil(m, "motion_deform_fwd", &motion_deform_fwd, "xyz"_a, "rotation"_a, "mask"_a, "res_xyz"_a, "res_rotation"_a);
     def_nogil(m, "motion_deform_bwd", &motion_deform_bwd, "rotation"_a, "mask"_a, "res_xyz"_a, "res_rotation"_a, "grad_xyz"_a, "grad_rotation"_a,
               "want_xyz"_a = true, "want_rotation"_a = true, "want_res_xyz"_a = true, "want_res_rotation"_a = true);

@@ -1,0 +1,294 @@
+"""The per-token work of AGM-Net's two transformers, up to their GEMMs, on the MI355X-native library (igs_amd/csrc/tokens.hip,
+include/igs_rast.h).
+
+GridEncoder.conv is a Transformer1D of 4 BasicTransformerBlocks (igs/models/transformers.py:290-397, configs/train.yaml:168-178; dim 512,
+8192 anchors per example): each runs two nn.LayerNorm(512) and a GEGLU feed-forward (transformers.py:482-506) whose chunk / gelu / multiply
+go over a [B * 8192, 4096] projection.  The unimatch FeatureTransformer and FeatureTransformerMy run a TransformerLayer
+(igs/models/unimatch/transformer.py:44-146) per attention: around the attention, norm1(merge(message)), with the FFN a cat, the MLP and
+norm2, then `source + message`, and a three-launch `is_self_attn` test whose result attn_type = 'swin' never reads.  Here:
+
+    layer_norm(x, weight, bias, eps, residual=None, out_dtype=None)     (residual +) LN(x) * weight + bias, one launch, one read of x
+    geglu(proj)                                                         proj[..., :D] * gelu(proj[..., D:]), one launch; the backward
+                                                                        writes both halves of d proj in one launch
+    use_native_block_ops(grid_encoder)                                  binds norm1, norm3 and ff.net[0] of every BasicTransformerBlock
+    use_native_transformer_layers(feature_transformer)                  binds the forward of every unimatch TransformerLayer
+
+Both have autograd (Transformer1D and FeatureTransformerMy are trained); the LayerNorm saves nothing but x and recomputes the row
+statistics in its backward, the GEGLU saves nothing but proj.  Both backwards are deterministic (no float atomics).  They compose with
+igs_amd.attention: use_native_attention replaces the block's attention, and the bound layer forward looks the two unimatch attention
+functions up, at call time, in the module that defines the layer's class, which is where use_native_window_attention sets them.
+
+Measured on one MI355X (medians of 20 against the eager sequences): the GEGLU is 2.0-2.5 x faster in float32,
+forward and with its backward, at 0.83-0.92 of the copy roof and half the peak memory; the LayerNorm forward 1.2-2.0 x, the layer tail
+forward 4.1-5.4 x.  Forward + backward of the LayerNorm is launch- and overhead-bound below about 100 MB: SLOWER than eager at [8192, 512]
+in both dtypes (0.79 x float32, 0.88 x float16), level for the float16 tail at [32768, 128], 1.4-2.9 x ahead at [40960, 512] and
+[65536, 128].  A whole block gains 2-5 %, a whole layer 1-5 %, within the spread of the measurement.
+
+There is no CPU and no PyTorch fallback: CPU tensors raise RuntimeError, bfloat16 / float64 raise NotImplementedError, wrong shapes raise
+ValueError.  Not provided: Transformer1D's GroupNorm and its two transposes; the GELU inside the unimatch MLP (a single eager kernel
+already); splitting the MLP's first weight to avoid the cat (it changes the GEMM's summation order); bfloat16; fusing any GEMM; the ada
+norms, cross-attention (norm2 / attn2) and the other feed-forward activations of BasicTransformerBlock; attn_type other than 'swin' and
+nhead > 1 of TransformerLayer.
+"""
+import sys
+import types
+
+import torch
+import torch.nn as nn
+
+from ._cabi import ext as _ext
+
+DTYPES = (torch.float32, torch.float16)
+LN_MAX_C = 1024                                                    # IGS_LN_MAX_C (include/igs_rast.h)
+GEGLU_MAX_D = 8192                                                 # IGS_GEGLU_MAX_D
+
+# The attributes of the reference's BasicTransformerBlock, FeedForward and GEGLU that the installer touches, as igs/models/transformers.py
+# names them (the classes come from diffusers, which is not part of this stack)
+BLOCK_NORM1, BLOCK_NORM2, BLOCK_NORM3, BLOCK_ATTN1, BLOCK_ATTN2, BLOCK_FF = "norm1", "norm2", "norm3", "attn1", "attn2", "ff"
+BLOCK_ADA_FLAGS = ("use_ada_layer_norm", "use_ada_layer_norm_zero", "use_ada_layer_norm_continuous")
+FF_NET, GEGLU_PROJ = "net", "proj"
+GELU_ONLY_ATTRS = ("approximate",)                                 # what GELU has and GEGLU has not
+# ... and of the unimatch TransformerLayer (igs/models/unimatch/transformer.py:11-42) with the two functions its forward calls
+LAYER_Q, LAYER_K, LAYER_V, LAYER_MERGE, LAYER_NORM1, LAYER_NO_FFN, LAYER_NHEAD = "q_proj", "k_proj", "v_proj", "merge", "norm1", "no_ffn", "nhead"
+LAYER_MLP, LAYER_NORM2 = "mlp", "norm2"
+ATTN_SPLIT, ATTN_FULL = "single_head_split_window_attention", "single_head_full_attention"
+
+
+def _rows(t):
+    """t [..., C] as [N, C] with stride 1 inside a row and a row stride of at least C: a view where the strides allow it (slices of a wider
+    buffer included), one copy otherwise."""
+    C = t.shape[-1]
+    if C == 1 or t.stride(-1) == 1:
+        try:
+            v = t.view(-1, C)
+            if v.shape[0] <= 1 or v.stride(0) >= C:
+                return v
+        except RuntimeError:
+            pass
+    return t.contiguous().view(-1, C)
+
+
+def _refuse(fn, named):
+    """The refusals that do not depend on the shapes, in an order that does not depend on where the tensors live: dtypes, then the device."""
+    for t, name in named:
+        if t.dtype not in DTYPES:
+            raise NotImplementedError(f"{fn}: {name} must be float32 or float16 (got {t.dtype})")
+    like = named[0][0]
+    if any(not t.is_cuda or t.device != like.device for t, _ in named):
+        raise RuntimeError(f"{fn}: tensors must be on one GPU (no CPU fallback)")
+
+
+class _LayerNorm(torch.autograd.Function):
+    """x, residual: [N, C] rows; weight, bias: [C] float32 or None."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, eps, out_half):
+        out = _ext()._tokens.layer_norm_fwd(x, weight, bias, eps, residual, out_half)
+        ctx.save_for_backward(x, weight)                           # the view itself: nothing is copied, no statistics are kept
+        ctx.eps = eps
+        ctx.res_dtype = residual.dtype if residual is not None else None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors
+        nx, nw, nb, nr = ctx.needs_input_grad[:4]
+        dx = dw = db = None
+        if nx or nw or nb:
+            dx, dw, db = _ext()._tokens.layer_norm_bwd(x, weight, ctx.eps, _rows(g), nx, nw and weight is not None, nb and weight is not None)
+        return dx, dw, db, (g.to(ctx.res_dtype) if nr else None), None, None
+
+
+def layer_norm(x, weight, bias, eps=1e-5, residual=None, out_dtype=None):
+    """F.layer_norm(x, (C,), weight, bias, eps) over the last dimension, plus `residual` when given, as one launch that reads every row
+    once and keeps it in registers between the statistics and the write (tokens.hip).  x: [..., C] float32 or float16 on a GPU, C <= 1024;
+    rows with stride 1 on C are read in place through a row stride, anything else is copied once.  weight and bias: [C], both or neither
+    (float16 parameters are widened to float32, the kernel's parameter dtype).  residual: x's shape, float32 or float16 of its own.
+    out_dtype (float32 or float16) defaults to x.dtype; the result is contiguous.  Arithmetic is float32 with the variance from centred
+    values; a constant row gives exactly bias (+ residual), a row with a NaN or an infinity comes out all NaN.  Autograd reaches x, weight,
+    bias and residual (whose gradient is the upstream gradient itself); only x is saved, and under no_grad nothing is."""
+    fn = "layer_norm"
+    if x.dim() < 1 or x.shape[-1] < 1:
+        raise ValueError(f"{fn}: x must be [..., C] with C >= 1 (got {list(x.shape)})")
+    C = x.shape[-1]
+    if C > LN_MAX_C:
+        raise ValueError(f"{fn}: C = {C} is above the supported {LN_MAX_C}")
+    if (weight is None) != (bias is None):
+        raise ValueError(f"{fn}: weight and bias go together (both or neither)")
+    named = [(x, "x")]
+    if weight is not None:
+        for p, name in ((weight, "weight"), (bias, "bias")):
+            if tuple(p.shape) != (C,):
+                raise ValueError(f"{fn}: {name} has shape {list(p.shape)}, expected {[C]}")
+            named.append((p, name))
+    if residual is not None:
+        if tuple(residual.shape) != tuple(x.shape):
+            raise ValueError(f"{fn}: residual has shape {list(residual.shape)}, expected {list(x.shape)}")
+        named.append((residual, "residual"))
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if out_dtype not in DTYPES:
+        raise NotImplementedError(f"{fn}: out_dtype must be float32 or float16 (got {out_dtype})")
+    _refuse(fn, named)
+    if weight is not None:
+        weight, bias = weight.float(), bias.float()
+    x2 = _rows(x)
+    r2 = _rows(residual) if residual is not None else None
+    half = out_dtype == torch.float16
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x2, weight, bias, r2)):
+        out = _LayerNorm.apply(x2, weight, bias, r2, float(eps), half)
+    else:
+        out = _ext()._tokens.layer_norm_fwd(x2, weight, bias, float(eps), r2, half)
+    return out.view(x.shape)
+
+
+class _Geglu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, proj):
+        ctx.save_for_backward(proj)
+        return _ext()._tokens.geglu_fwd(proj)
+
+    @staticmethod
+    def backward(ctx, g):
+        (proj,) = ctx.saved_tensors
+        if g.dtype != proj.dtype:
+            g = g.to(proj.dtype)
+        return _ext()._tokens.geglu_bwd(proj, g)
+
+
+def geglu(proj):
+    """hidden * gelu(gate) for hidden, gate = proj.chunk(2, dim=-1), the exact (erf) GELU: [..., 2 D] -> [..., D] contiguous in proj's dtype
+    (float32 or float16), D <= 8192, as one launch that reads proj once (tokens.hip); rows with stride 1 are read in place through a row
+    stride.  With autograd: only proj is saved, and the backward writes both halves of d proj in one launch, so chunk's backward (a cat)
+    costs nothing."""
+    fn = "geglu"
+    if proj.dim() < 1 or proj.shape[-1] < 2 or proj.shape[-1] % 2:
+        raise ValueError(f"{fn}: proj must be [..., 2 D] with D >= 1 (got {list(proj.shape)})")
+    D = proj.shape[-1] // 2
+    if D > GEGLU_MAX_D:
+        raise ValueError(f"{fn}: D = {D} is above the supported {GEGLU_MAX_D}")
+    _refuse(fn, [(proj, "proj")])
+    p2 = _rows(proj)
+    out = _Geglu.apply(p2) if torch.is_grad_enabled() and p2.requires_grad else _ext()._tokens.geglu_fwd(p2)
+    return out.view(proj.shape[:-1] + (D,))
+
+
+def _autocast_out_dtype(default):
+    """float32 whenever GPU autocast is enabled, whatever its dtype: layer_norm is on autocast's float32 list, so eager runs and answers
+    in float32 there, and the bound forwards give the dtypes eager PyTorch gives."""
+    return torch.float32 if torch.is_autocast_enabled() else default
+
+
+# ---------------------------------------------------------------- BasicTransformerBlock: norm1, norm3, GEGLU
+def _norm_forward(self, x):
+    """nn.LayerNorm.forward on the native path."""
+    return layer_norm(x, self.weight, self.bias, self.eps, out_dtype=_autocast_out_dtype(None))
+
+
+def _geglu_forward(self, hidden_states, scale=1.0):
+    """GEGLU.forward (igs/models/transformers.py:503-506): the projection as it is, then chunk, gelu and multiply as one launch."""
+    return geglu(getattr(self, GEGLU_PROJ)(hidden_states))
+
+
+def _is_block(m):
+    return all(hasattr(m, a) for a in (BLOCK_NORM1, BLOCK_NORM2, BLOCK_NORM3, BLOCK_ATTN1, BLOCK_ATTN2, BLOCK_FF))
+
+
+def _layer_norm_ok(n):
+    return isinstance(n, nn.LayerNorm) and len(n.normalized_shape) == 1 and (n.weight is None) == (n.bias is None)
+
+
+def _block_targets(fn, b):
+    """(norm1, norm3, the feed-forward's GEGLU) of one block, or NotImplementedError."""
+    for flag in BLOCK_ADA_FLAGS:
+        if getattr(b, flag, False):
+            raise NotImplementedError(f"{fn}: {flag} is set: the ada norms are not provided")
+    for name in (BLOCK_NORM2, BLOCK_ATTN2):
+        if getattr(b, name) is not None:
+            raise NotImplementedError(f"{fn}: {name} is present: cross-attention blocks are not provided")
+    n1, n3 = getattr(b, BLOCK_NORM1), getattr(b, BLOCK_NORM3)
+    for n in (n1, n3):
+        if not _layer_norm_ok(n):
+            raise NotImplementedError(f"{fn}: norm1 and norm3 must be nn.LayerNorm over the last dimension with weight and bias together (got {n})")
+    if n1.elementwise_affine != n3.elementwise_affine:
+        raise NotImplementedError(f"{fn}: a LayerNorm without affine parameters alongside one with them is not provided")
+    net = getattr(getattr(b, BLOCK_FF), FF_NET, None)
+    act = net[0] if net is not None and len(net) >= 3 else None
+    proj = getattr(act, GEGLU_PROJ, None)
+    if (not isinstance(proj, nn.Linear) or any(hasattr(act, a) for a in GELU_ONLY_ATTRS) or not isinstance(net[2], nn.Linear)
+            or proj.out_features != 2 * net[2].in_features):
+        raise NotImplementedError(f"{fn}: the feed-forward activation must be GEGLU (a projection to twice the inner width); "
+                                  f"gelu, gelu-approximate and geglu-approximate are not provided")
+    return n1, n3, act
+
+
+def use_native_block_ops(module):
+    """Binds a forward on norm1, norm3 and the feed-forward's GEGLU (ff.net[0]: its proj, then `geglu`) of every BasicTransformerBlock
+    under `module`, found by the attribute names above; returns the number of bound modules (3 per block, 12 for the shipped
+    Transformer1D).  state_dict() keys and the classes are untouched.  Raises NotImplementedError, before anything is changed, for the ada
+    norms, a LayerNorm without affine parameters alongside one with, a feed-forward activation other than GEGLU, and norm2 / attn2
+    present.  Under float16 autocast the bound norms answer in float32 and the GEGLU in the projection's dtype, as eager PyTorch does."""
+    fn = "use_native_block_ops"
+    targets = [_block_targets(fn, m) for m in module.modules() if _is_block(m)]
+    n = 0
+    for n1, n3, act in targets:
+        n1.forward = types.MethodType(_norm_forward, n1)
+        n3.forward = types.MethodType(_norm_forward, n3)
+        act.forward = types.MethodType(_geglu_forward, act)
+        n += 3
+    return n
+
+
+# ---------------------------------------------------------------- the unimatch TransformerLayer
+def _layer_forward(self, source, target, height=None, width=None, shifted_window_attn_mask=None, shifted_window_attn_mask_1d=None,
+                   attn_type="swin", with_shift=False, attn_num_splits=None):
+    """TransformerLayer.forward (igs/models/unimatch/transformer.py:44-146) for attn_type = 'swin': the three projections, the attention
+    function of the layer's own module (looked up now, so whatever use_native_window_attention set there is used), merge, then
+    source + LN1(message) as one launch, or LN1, cat, mlp and source + LN2(message) as one launch.  is_self_attn is not computed: 'swin'
+    never reads it."""
+    fn = "TransformerLayer"
+    if attn_type != "swin":
+        raise NotImplementedError(f"{fn}: attn_type = {attn_type!r} is not provided (IGS uses 'swin' only)")
+    if getattr(self, LAYER_NHEAD) > 1:
+        raise NotImplementedError(f"{fn}: nhead > 1 is not provided")
+    namespace = sys.modules[type(self).__module__]
+    query, key, value = getattr(self, LAYER_Q)(source), getattr(self, LAYER_K)(target), getattr(self, LAYER_V)(target)
+    if attn_num_splits is not None and attn_num_splits > 1:
+        message = getattr(namespace, ATTN_SPLIT)(query, key, value, num_splits=attn_num_splits, with_shift=with_shift, h=height, w=width,
+                                                 attn_mask=shifted_window_attn_mask)
+    else:
+        message = getattr(namespace, ATTN_FULL)(query, key, value)
+    message = getattr(self, LAYER_MERGE)(message)
+    n1 = getattr(self, LAYER_NORM1)
+    if getattr(self, LAYER_NO_FFN):
+        return layer_norm(message, n1.weight, n1.bias, n1.eps, residual=source,
+                          out_dtype=_autocast_out_dtype(torch.promote_types(message.dtype, source.dtype)))
+    message = layer_norm(message, n1.weight, n1.bias, n1.eps, out_dtype=_autocast_out_dtype(None))
+    message = getattr(self, LAYER_MLP)(torch.cat([source, message], dim=-1))
+    n2 = getattr(self, LAYER_NORM2)
+    return layer_norm(message, n2.weight, n2.bias, n2.eps, residual=source,
+                      out_dtype=_autocast_out_dtype(torch.promote_types(message.dtype, source.dtype)))
+
+
+def _is_layer(m):
+    return all(hasattr(m, a) for a in (LAYER_Q, LAYER_K, LAYER_V, LAYER_MERGE, LAYER_NORM1, LAYER_NO_FFN, LAYER_NHEAD))
+
+
+def use_native_transformer_layers(module):
+    """Binds a forward on every unimatch TransformerLayer under `module`, found by q_proj, k_proj, v_proj, merge, norm1, no_ffn, nhead (and
+    mlp, norm2 when it has an FFN); returns how many.  state_dict() keys and the classes are untouched.  Raises NotImplementedError, before
+    anything is changed, for nhead > 1 and for norms that are not nn.LayerNorm over the last dimension; attn_type other than 'swin' raises
+    at the call."""
+    fn = "use_native_transformer_layers"
+    layers = [m for m in module.modules() if _is_layer(m)]
+    for m in layers:
+        if getattr(m, LAYER_NHEAD) > 1:
+            raise NotImplementedError(f"{fn}: nhead > 1 is not provided")
+        names = (LAYER_NORM1,) if getattr(m, LAYER_NO_FFN) else (LAYER_NORM1, LAYER_NORM2, LAYER_MLP)
+        if not all(hasattr(m, a) for a in names):
+            raise NotImplementedError(f"{fn}: a layer with an FFN must have {LAYER_MLP} and {LAYER_NORM2}")
+        for a in names[:2]:
+            if not _layer_norm_ok(getattr(m, a)):
+                raise NotImplementedError(f"{fn}: {a} must be nn.LayerNorm over the last dimension (got {getattr(m, a)})")
+    for m in layers:
+        m.forward = types.MethodType(_layer_forward, m)
+    return len(layers)

@@ -801,6 +801,50 @@ int igs_instance_norm_fwd(void* stream, const void* x, const void* skip, void* o
 long long igs_instance_norm_resident_max(int dtype, int mode);
 int igs_position_add(void* stream, const void* f0, const void* f1, void* out0, void* out1, int B, int C, int H, int W, int splits, int dtype);
 
+/* The per-token work of the two transformers up to their GEMMs (tokens.hip): the LayerNorms of BasicTransformerBlock
+ * (igs/models/transformers.py:304-365) and of the unimatch TransformerLayer with the add behind them (igs/models/unimatch/transformer.py:
+ * 140-146), and the GEGLU of the block's feed-forward (transformers.py:503-506).  Everything runs on `stream`, reads nothing back and
+ * allocates nothing; arithmetic is float32, half operands are widened on load and rounded once on store; no float atomics, two runs
+ * agree bit for bit.  Every refusal below returns IGS_RAST_E_INVALID with a message before any HIP call.  Rows are given by a base pointer
+ * and a row stride in elements (the stride inside a row is 1), so slices of a wider buffer are read and written in place.  "Overlap"
+ * means the byte ranges from an operand's first to its last element.
+ * igs_layer_norm_fwd: out[n, :] = (res[n, :] +) LN(x[n, :]) * weight + bias over x [N, C], LN(t) = (t - mean) / sqrt(var + eps) per row
+ *   with the biased variance taken from centred values.  x, res and out each have their own dtype code (IGS_DTYPE_F32 / IGS_DTYPE_F16) and
+ *   row stride; res is optional (NULL; its dtype code and stride are then ignored); weight and bias are [C] float32, both given or both
+ *   NULL (no affine step).  A row is read once and stays in registers between the statistics and the write.  A constant row gives exactly
+ *   bias (+ res); a row that holds a NaN or an infinity comes out all NaN, as in PyTorch; the other rows are untouched by it.
+ *   - out == res with one dtype and one row stride is allowed (the in-place residual update) and gives the bits of a separate out; every
+ *     other overlap of out with x, res, weight or bias is refused.
+ *   - Refused: C < 1 or > IGS_LN_MAX_C, N < 0 or > IGS_LN_MAX_ROWS, a row stride below C or above IGS_TOKENS_MAX_STRIDE, an unknown dtype
+ *     code, an eps that is negative or not finite, weight without bias or bias without weight, a NULL x or out, a pointer not aligned to
+ *     its element size.  N == 0 returns 0 without a launch.  Four-element loads are used when C, every row stride and every base pointer
+ *     (16 bytes for float32, 8 for float16) allow them, scalar loads otherwise: nothing else depends on alignment.
+ * igs_layer_norm_bwd: from x, weight (NULL = ones) and dout = d out [N, C] the gradients dx [N, C] (own dtype and stride), dweight and
+ *   dbias [C] float32; each is optional (NULL = not wanted; none wanted returns 0) and every element of a non-NULL output is written.
+ *   The statistics are recomputed from x: the forward saves nothing.  d res is dout itself.  dweight and dbias need `scratch`
+ *   (igs_layer_norm_bwd_scratch_bytes(N, C) bytes; 0 for sizes out of range): one partial row per workgroup, added in workgroup order by a
+ *   second launch.  Refusals as above, plus a NULL dout, a NULL scratch when dweight or dbias is wanted, and any overlap of an output or
+ *   the scratch with an input or with one another.
+ * igs_geglu_fwd: out[n, d] = p[n, d] * gelu(p[n, D + d]) over p [N, 2 D] with a row stride, out [N, D] contiguous, one dtype for both;
+ *   gelu(g) = 0.5 g (1 + erf(g / sqrt 2)), the exact form.
+ * igs_geglu_bwd: from p and dout [N, D] contiguous, dp [N, 2 D] contiguous in one launch, both halves written:
+ *   dp[n, d] = dout gelu(g), dp[n, D + d] = dout h (Phi(g) + g phi(g)) with h = p[n, d], g = p[n, D + d].
+ *   Refused by both: D < 1 or > IGS_GEGLU_MAX_D, N < 0 or N * D > IGS_GEGLU_MAX_ELEMS, a row stride below 2 D or above
+ *   IGS_TOKENS_MAX_STRIDE, an unknown dtype code, a NULL or misaligned pointer, an output that overlaps an input.  N == 0 returns 0. */
+#define IGS_LN_MAX_C 1024
+#define IGS_LN_MAX_ROWS (1LL << 24)
+#define IGS_TOKENS_MAX_STRIDE (1LL << 31)
+#define IGS_GEGLU_MAX_D 8192
+#define IGS_GEGLU_MAX_ELEMS (1LL << 30)
+int igs_layer_norm_fwd(void* stream, long long N, int C, int x_dtype, const void* x, long long xs, int res_dtype, const void* res,
+                       long long rs, const float* weight, const float* bias, float eps, int out_dtype, void* out, long long os);
+size_t igs_layer_norm_bwd_scratch_bytes(long long N, int C);
+int igs_layer_norm_bwd(void* stream, long long N, int C, int x_dtype, const void* x, long long xs, const float* weight, float eps,
+                       int dout_dtype, const void* dout, long long gs, int dx_dtype, void* dx, long long dxs, float* dweight, float* dbias,
+                       void* scratch);
+int igs_geglu_fwd(void* stream, long long N, int D, int dtype, const void* p, long long ps, void* out);
+int igs_geglu_bwd(void* stream, long long N, int D, int dtype, const void* p, long long ps, const void* dout, void* dp);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).
