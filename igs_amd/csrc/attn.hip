@@ -125,10 +125,10 @@ attn_fwd_kernel(AttnArgs a)
     attn_acc o0 = {}, o1 = {};
     float m = -INFINITY, l = 0.f;                             // the running max of the log2-domain scores; this lane's share of the sum
     for (int k0 = 0; k0 < a.Ak; k0 += ATTN_ROWS) {
-        attn_barrier();
+        wg_barrier();
         sk.write_rows(kimg);
         sv.write_columns(vimg);
-        attn_barrier();
+        wg_barrier();
         if (k0 + ATTN_ROWS < a.Ak) {
             sk.load(kb, a.k.sa, k0 + ATTN_ROWS, a.Ak);
             sv.load(vb, a.v.sa, k0 + ATTN_ROWS, a.Ak);
@@ -185,11 +185,11 @@ attn_fwd_kernel(AttnArgs a)
     for (int g = 0; g < 4; g++) {
         const int d = 8 * g + 4 * h;
         if constexpr (C::HALF != 0) {
-            attn_h4 x0, x1;
+            h4_t x0, x1;
 #pragma unroll
             for (int e = 0; e < 4; e++) { x0[e] = (_Float16)(o0[4 * g + e] / lt); x1[e] = (_Float16)(o1[4 * g + e] / lt); }
-            *(attn_h4*)(op + d) = x0;
-            *(attn_h4*)(op + 32 + d) = x1;
+            *(h4_t*)(op + d) = x0;
+            *(h4_t*)(op + 32 + d) = x1;
         } else {
             attn_f4 x0, x1;
 #pragma unroll
@@ -260,12 +260,12 @@ attn_dkdv_kernel(AttnArgs a)
     }
     attn_acc dk0 = {}, dk1 = {}, dv0 = {}, dv1 = {};
     for (int q0 = 0; q0 < a.Aq; q0 += ATTN_ROWS) {
-        attn_barrier();
+        wg_barrier();
         sq.write_rows(qimg);
         sg.write_rows(gimg);
         if constexpr (C::HALF != 0) { sq.write_transposed(qcol); sg.write_transposed(gcol); }
         if (threadIdx.x < ATTN_ROWS) { lse2[threadIdx.x] = nl; dlt[threadIdx.x] = nd; }
-        attn_barrier();
+        wg_barrier();
         if (q0 + ATTN_ROWS < a.Aq) {
             sq.load(qb, a.q.sa, q0 + ATTN_ROWS, a.Aq);
             sg.load(gb, a.go.sa, q0 + ATTN_ROWS, a.Aq);
@@ -333,11 +333,11 @@ attn_dq_kernel(AttnArgs a)
     sv.load(vb, a.v.sa, 0, a.Ak);
     attn_acc dq0 = {}, dq1 = {};
     for (int k0 = 0; k0 < a.Ak; k0 += ATTN_ROWS) {
-        attn_barrier();
+        wg_barrier();
         sk.write_rows(kimg);
         sv.write_rows(vimg);
         if constexpr (C::HALF != 0) sk.write_transposed(kcol);
-        attn_barrier();
+        wg_barrier();
         if (k0 + ATTN_ROWS < a.Ak) {
             sk.load(kb, a.k.sa, k0 + ATTN_ROWS, a.Ak);
             sv.load(vb, a.v.sa, k0 + ATTN_ROWS, a.Ak);
@@ -395,7 +395,6 @@ static const char* attn_out_error(int B, int H, int A, long long sb, long long s
     if ((A > 1 && sa < ATTN_D) || (H > 1 && sh < ATTN_D) || (B > 1 && sb < ATTN_D)) return "output strides overlap (a stride below D on a dimension longer than 1)";
     return nullptr;
 }
-static bool attn_aligned(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 static AttnView attn_view(const void* p, long long sb, long long sh, long long sa) { AttnView t; t.p = (void*)p; t.sb = sb; t.sh = sh; t.sa = sa; return t; }
 
 extern "C" size_t igs_attn_bwd_scratch_bytes(int B, int H, int Aq, int Ak, int D, int dtype)
@@ -418,7 +417,7 @@ extern "C" int igs_attn_fwd(void* stream, int B, int H, int Aq, int Ak, int D, i
     if (!(fabsf(scale) <= 3.0e38f)) return fail_in(fn, "scale must be finite");
     if (B == 0) return 0;
     if (!q || !k || !v || !out) return fail_in(fn, "NULL pointer");
-    if (!attn_aligned(q) || !attn_aligned(k) || !attn_aligned(v) || !attn_aligned(out)) return fail_in(fn, "base pointers must be 16-byte aligned");
+    if (!ptr_aligned(q, 16) || !ptr_aligned(k, 16) || !ptr_aligned(v, 16) || !ptr_aligned(out, 16)) return fail_in(fn, "base pointers must be 16-byte aligned");
     AttnArgs a = {};
     a.H = H; a.Aq = Aq; a.Ak = Ak; a.tiles = (Aq + ATTN_OWN - 1) / ATTN_OWN;
     a.scale = scale; a.c = (float)((double)scale * 1.4426950408889634);
@@ -455,8 +454,8 @@ extern "C" int igs_attn_bwd(void* stream, int B, int H, int Aq, int Ak, int D, i
     if (!(fabsf(scale) <= 3.0e38f)) return fail_in(fn, "scale must be finite");
     if (B == 0 || (!dq && !dk && !dv)) return 0;
     if (!q || !k || !v || !out || !lse || !dout || !scratch) return fail_in(fn, "NULL pointer");
-    if (!attn_aligned(q) || !attn_aligned(k) || !attn_aligned(v) || !attn_aligned(out) || !attn_aligned(dout) || !attn_aligned(dq) ||
-        !attn_aligned(dk) || !attn_aligned(dv))
+    if (!ptr_aligned(q, 16) || !ptr_aligned(k, 16) || !ptr_aligned(v, 16) || !ptr_aligned(out, 16) || !ptr_aligned(dout, 16) || !ptr_aligned(dq, 16) ||
+        !ptr_aligned(dk, 16) || !ptr_aligned(dv, 16))
         return fail_in(fn, "base pointers must be 16-byte aligned");
     AttnArgs a = {};
     a.H = H; a.Aq = Aq; a.Ak = Ak;

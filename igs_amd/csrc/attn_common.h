@@ -1,18 +1,11 @@
-// attn_common.h -- what the attention kernels share (attn.hip, wattn.hip): the vector types, the barrier, the accumulator tile's row order
+// attn_common.h -- what the attention kernels share (attn.hip, wattn.hip): the vector types, the accumulator tile's row order
 // and the wrappers of the matrix instructions.  attn.hip states the tile layout.
 #pragma once
+#include "elem_common.h"      // wg_barrier, h4_t
 
 typedef _Float16 attn_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 attn_h4 __attribute__((ext_vector_type(4)));
 typedef float attn_f4 __attribute__((ext_vector_type(4)));
 typedef float attn_acc __attribute__((ext_vector_type(16)));
-
-// __syncthreads() with its release side spelled out (blend_common.h: tile_barrier): no LDS store is outstanding when the barrier opens
-__device__ __forceinline__ void attn_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-}
 
 template <typename T> struct AttnCfg;
 template <> struct AttnCfg<_Float16> { enum { LS = 72, EPC = 8, CPR = 8, NCH = 2, HALF = 1 }; typedef attn_h8 vec; };

@@ -1,6 +1,7 @@
 // blend_common.h -- helpers shared by the forward and backward tile-blend kernels (device only).
 #pragma once
 #include "common.h"
+#include "elem_common.h"      // wg_barrier
 
 // Gaussian exponent exactly as the reference associates it (forward.cu:555, backward.cu:847), WITHOUT fused
 // multiply-adds: the sign of a power that rounds to +-1e-8 next to a splat centre decides `if (power > 0) continue`,
@@ -64,24 +65,6 @@ __device__ __forceinline__ uint32_t quad_reach_mask(float4 q0, float4 q1, float 
         if (qmin > two_tau) m &= ~(1u << q);                                   // (a NaN keeps the quad)
     }
     return m;
-}
-
-// Workgroup barrier of the tile kernels: __syncthreads() with its release side spelled out.
-// Round 3: the forward's round loop ends with `wave_done[wid] = ...` (ds_write_b32) and begins with __syncthreads() followed by the
-// read of all four flags that decides `break` -- and hipcc emitted a bare s_barrier at that loop header, with no s_waitcnt lgkmcnt(0)
-// behind the store (its waitcnt scoreboard took the counter for zero across the back edge).  A wave whose store is still queued
-// when the barrier opens lets the waves that read first see a stale 0: they go round again while the others break.  In the
-// stand-alone forward that only costs the stragglers a redundant round (their pixels are finished; waves that have ended no
-// longer count at barriers).  In the fused forward + backward kernel it is fatal: the stragglers stage FORWARD records into the LDS
-// the others already use for the BACKWARD -- Gaussian ids read from that are garbage, and the accumulator atomic faults
-// (dense diagnostic scene, where nearly every tile ends its forward early; found with the ROCm debug agent: LDS dump of the faulting
-// workgroup).  The wait costs nothing where the compiler would have put it anyway.
-__device__ __forceinline__ void tile_barrier()
-{
-#ifndef IGS_NO_RELEASE_WAIT
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-    __syncthreads();
 }
 
 // wave-uniform copy of a 64-bit value (readfirstlane returns a SIGNED int: widen through uint32_t, not int)

@@ -58,7 +58,7 @@ blend_count_kernel(const BlendFwdArgs a, int* __restrict__ count)
 
     if (tid < 4) wave_done[tid] = 0;
     for (int i = 0; i < rounds; i++) {
-        tile_barrier();                                           // previous chunk consumed (and its hits written), wave_done published
+        wg_barrier();                                           // previous chunk consumed (and its hits written), wave_done published
         flush();
         if (wave_done[0] & wave_done[1] & wave_done[2] & wave_done[3]) break;
         const int progress = i * FWD_CHUNK + (int)tid;
@@ -85,7 +85,7 @@ blend_count_kernel(const BlendFwdArgs a, int* __restrict__ count)
                 if (lane == 0) quad_bits[q][wid] = b;
             }
         }
-        tile_barrier();
+        wg_barrier();
         if (__ballot(Tl != 0.0f) != 0ull) {
             bool wave_finished = false;
             for (int sw = 0; sw < FWD_NSW && !wave_finished; sw++) {
@@ -119,7 +119,7 @@ blend_count_kernel(const BlendFwdArgs a, int* __restrict__ count)
         const bool all_done = __ballot(Tl != 0.0f) == 0ull;
         if (lane == 0) wave_done[wid] = all_done ? 1 : 0;
     }
-    tile_barrier();                                               // the last chunk's hits (a no-op for a tile that left early)
+    wg_barrier();                                               // the last chunk's hits (a no-op for a tile that left early)
     flush();
 
     if (inside) {

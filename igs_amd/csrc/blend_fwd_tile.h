@@ -53,7 +53,7 @@ __device__ __forceinline__ void blend_fwd_tile(const BlendFwdArgs& a, const uint
 
     if (tid < 4) wave_done[tid] = 0;
     for (int i = 0; i < rounds; i++) {
-        tile_barrier();                                           // previous chunk consumed, wave_done published
+        wg_barrier();                                           // previous chunk consumed, wave_done published
         if (wave_done[0] & wave_done[1] & wave_done[2] & wave_done[3]) break;
         const int progress = i * FWD_CHUNK + (int)tid;
         uint32_t qmask = 0;
@@ -76,7 +76,7 @@ __device__ __forceinline__ void blend_fwd_tile(const BlendFwdArgs& a, const uint
                 if (lane == 0) quad_bits[q][wid] = b;
             }
         }
-        tile_barrier();
+        wg_barrier();
         // one (wave, splat) row; `r`: the staged record(s) the lanes read (wave-uniform address, or one per half), `slot`: its position
         // in the chunk (scalar or per-lane)
         auto blend_row = [&](const float4* r, const auto slot) {

@@ -66,7 +66,7 @@ blend_step_kernel(const BlendFwdArgs f, const BlendBwdArgs b)
     BTL(3, (unsigned long long)(f.ranges[2 * tile + 1] - f.ranges[2 * tile]));
     FwdPix px;
     blend_fwd_tile<COORD, DEPTH, NORMAL, true, false>(f, tile, (float4*)smem, quad_bits_f, wave_done, px);
-    tile_barrier();           // every wave is done with the forward's staged records: the backward takes the LDS over
+    wg_barrier();           // every wave is done with the forward's staged records: the backward takes the LDS over
     BTL(1, wall_clock64());
     blend_bwd_tile<false, false, false, ABS, true, MASK>(b, tile, (float4*)smem, nullptr, quad_bits_b, wave_max, (float*)(smem + BWD_CHUNK_BYTES), &px);
     BTL(2, wall_clock64());

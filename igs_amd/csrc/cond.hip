@@ -11,43 +11,17 @@
 //       runs with lanes across channels (16 lanes x 4 channels, four pixels per wave, so that the transposed LDS access touches 64
 //       different banks) and overwrites xs in place; the result leaves with lanes across pixels again.
 //   (3) modln_bwd_kernel: the same tile with d out next to x (so half the pixels).  d shift / d scale leave in the channel pass, d x in
-//       the pixel pass; every workgroup leaves one row of d weight / d bias partial sums, modln_param_reduce_kernel adds the rows in
+//       the pixel pass; every workgroup leaves one row of d weight / d bias partial sums, param_reduce.h adds the rows in
 //       workgroup order (in two rounds): no float atomics, bitwise reproducible.
 #include "common.h"
+#include "elem_common.h"
 #include "host_api.h"
+#include "param_reduce.h"
 
 #define COND_THREADS 256
 #define COND_CH 33
 #define MODLN_THREADS 256
 #define MODLN_LDS_BYTES 65536
-#define MODLN_REDUCE_WAVES 16
-#define MODLN_REDUCE_GROUPS 64
-
-// __syncthreads() with its release side spelled out (blend_common.h: tile_barrier): no LDS store is outstanding when the barrier opens
-__device__ __forceinline__ void cond_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-}
-
-typedef _Float16 cond_h4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float cond_ld(const float* p) { return *p; }
-__device__ __forceinline__ float cond_ld(const _Float16* p) { return (float)*p; }
-__device__ __forceinline__ void cond_st(float* p, float v) { *p = v; }
-__device__ __forceinline__ void cond_st(_Float16* p, float v) { *p = (_Float16)v; }
-__device__ __forceinline__ float4 cond_ld4(const float* p) { return *(const float4*)p; }
-__device__ __forceinline__ float4 cond_ld4(const _Float16* p)
-{
-    const cond_h4 h = *(const cond_h4*)p;
-    return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
-}
-__device__ __forceinline__ void cond_st4(float* p, float4 v) { *(float4*)p = v; }
-__device__ __forceinline__ void cond_st4(_Float16* p, float4 v)
-{
-    cond_h4 h;
-    h.x = (_Float16)v.x; h.y = (_Float16)v.y; h.z = (_Float16)v.z; h.w = (_Float16)v.w;
-    *(cond_h4*)p = h;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // (1) the ray condition
@@ -106,7 +80,7 @@ ray_condition_kernel(uint32_t NPIX, int H, int W, int Hd, int Wd, float sy, floa
         const float v10 = dm[(size_t)y1 * Wd + x0], v11 = dm[(size_t)y1 * Wd + x1];
         t[32] = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
     }
-    cond_barrier();
+    wg_barrier();
     const uint32_t left = NPIX - pix0;
     const uint32_t count = (left < COND_THREADS ? left : COND_THREADS) * COND_CH;
     float* dst = cond + (size_t)pix0 * COND_CH;
@@ -132,7 +106,6 @@ static int modln_tile_log2(int C, int planes, int lp_max)
     while (lp > 2 && modln_lds_bytes(C, 1 << lp, planes) > MODLN_LDS_BYTES) lp--;
     return lp;                                                 // C = 1024: 8 pixels forward, 4 backward (40 KB)
 }
-static bool modln_aligned(const void* p, size_t bytes) { return (((uintptr_t)p) & (bytes - 1)) == 0; }
 
 // a tile of `planes` NCHW operands into LDS, lanes across pixels: dst[c * S + p] = src[c * sc + p], p < npix
 template <typename T>
@@ -144,7 +117,7 @@ __device__ __forceinline__ void modln_load_tile(float* dst, const T* src, size_t
         for (int i = threadIdx.x; i < nq; i += MODLN_THREADS) {
             const int c = i >> lq, p = (i - (c << lq)) << 2;
             if (p < npix) {                                    // (vec: npix is a multiple of four)
-                const float4 v = cond_ld4(src + (size_t)c * sc + p);
+                const float4 v = ld4(src + (size_t)c * sc + p);
                 float* d = dst + c * S + p;
                 d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
             }
@@ -153,7 +126,7 @@ __device__ __forceinline__ void modln_load_tile(float* dst, const T* src, size_t
         const int ne = C << lp;
         for (int i = threadIdx.x; i < ne; i += MODLN_THREADS) {
             const int c = i >> lp, p = i - (c << lp);
-            if (p < npix) dst[c * S + p] = cond_ld(src + (size_t)c * sc + p);
+            if (p < npix) dst[c * S + p] = ld(src + (size_t)c * sc + p);
         }
     }
 }
@@ -181,24 +154,24 @@ modln_fwd_kernel(int C, int HW, int lp, int tiles_per_img, int vx, int vm, int v
     const int n = blockIdx.x / tiles_per_img, p0 = (blockIdx.x - n * tiles_per_img) << lp;
     const int npix = min(P, HW - p0);
     modln_load_tile(xs, x + (size_t)n * xs_n + p0, xs_c, C, lp, npix, vx);
-    cond_barrier();
+    wg_barrier();
     // statistics: thread (p, q) sums channels q, q + parts, ... of pixel p; the mean first, then the squares of the centred values
     const int p = tid & (P - 1), q = tid >> lp, parts = MODLN_THREADS >> lp;
     float s = 0.f;
     if (p < npix) for (int c = q; c < C; c += parts) s += xs[c * S + p];
     red[tid] = s;
-    cond_barrier();
+    wg_barrier();
     const float m = modln_sum_parts(red, p, lp) / (float)C;
     float v = 0.f;
     if (p < npix) for (int c = q; c < C; c += parts) { const float a = xs[c * S + p] - m; v = fmaf(a, a, v); }
     red[MODLN_THREADS + tid] = v;
-    cond_barrier();
+    wg_barrier();
     if (q == 0 && p < npix) {
         const float r = 1.f / sqrtf(modln_sum_parts(red + MODLN_THREADS, p, lp) / (float)C + eps);
         mu[p] = m; rs[p] = r;
         if (mean) { mean[(size_t)n * HW + p0 + p] = m; rstd[(size_t)n * HW + p0 + p] = r; }
     }
-    cond_barrier();
+    wg_barrier();
     // modulation, lanes across channels: a wave takes four pixels, 16 lanes each
     const int wv = tid >> 6, lane = tid & 63, pg = lane >> 4, l = lane & 15;
     for (int pb = 0; pb < npix; pb += 16) {
@@ -208,7 +181,7 @@ modln_fwd_kernel(int C, int HW, int lp, int tiles_per_img, int vx, int vm, int v
         const TM* row = mod + ((size_t)n * HW + p0 + pp) * 2 * C;
         if (vm) {
             for (int c = 4 * l; c < C; c += 64) {
-                const float4 sh = cond_ld4(row + c), sc = cond_ld4(row + C + c), ww = *(const float4*)(w + c), bb = *(const float4*)(b + c);
+                const float4 sh = ld4(row + c), sc = ld4(row + C + c), ww = *(const float4*)(w + c), bb = *(const float4*)(b + c);
                 float* d = xs + c * S + pp;
                 d[0] = fmaf(fmaf((d[0] - pm) * pr, ww.x, bb.x), 1.f + sc.x, sh.x);
                 d[S] = fmaf(fmaf((d[S] - pm) * pr, ww.y, bb.y), 1.f + sc.y, sh.y);
@@ -218,11 +191,11 @@ modln_fwd_kernel(int C, int HW, int lp, int tiles_per_img, int vx, int vm, int v
         } else {
             for (int c = l; c < C; c += 16) {
                 float* d = xs + c * S + pp;
-                d[0] = fmaf(fmaf((d[0] - pm) * pr, w[c], b[c]), 1.f + cond_ld(row + C + c), cond_ld(row + c));
+                d[0] = fmaf(fmaf((d[0] - pm) * pr, w[c], b[c]), 1.f + ld(row + C + c), ld(row + c));
             }
         }
     }
-    cond_barrier();
+    wg_barrier();
     // the result, lanes across pixels again
     float* ob = out + (size_t)n * C * HW + p0;
     if (vo) {
@@ -251,8 +224,8 @@ static ModlnVec modln_vec(int C, int HW, int x_dtype, const void* x, size_t xs_n
 {
     ModlnVec v;
     v.hw = (HW & 3) == 0;
-    v.x = v.hw && (xs_n & 3) == 0 && (xs_c & 3) == 0 && modln_aligned(x, x_dtype == IGS_DTYPE_F16 ? 8 : 16);
-    v.m = (C & 3) == 0 && modln_aligned(mod, mod_dtype == IGS_DTYPE_F16 ? 8 : 16) && modln_aligned(w, 16) && modln_aligned(b, 16);
+    v.x = v.hw && (xs_n & 3) == 0 && (xs_c & 3) == 0 && ptr_aligned(x, vec_grid_bytes(x_dtype));
+    v.m = (C & 3) == 0 && ptr_aligned(mod, vec_grid_bytes(mod_dtype)) && ptr_aligned(w, 16) && ptr_aligned(b, 16);
     return v;
 }
 
@@ -262,7 +235,7 @@ static hipError_t launch_modln_fwd(hipStream_t s, int N, int C, int HW, int x_dt
     const int lp = modln_tile_log2(C, 1, 6), P = 1 << lp, tpi = (HW + P - 1) / P;
     const size_t lds = modln_lds_bytes(C, P, 1);
     const ModlnVec v = modln_vec(C, HW, x_dtype, x, xs_n, xs_c, mod_dtype, mod, w, b);
-    const int vo = v.hw && modln_aligned(out, 16);
+    const int vo = v.hw && ptr_aligned(out, 16);
     const dim3 g((unsigned)((size_t)N * tpi)), blk(MODLN_THREADS);
 #define MODLN_FWD(TX, TM) hipLaunchKernelGGL((modln_fwd_kernel<TX, TM>), g, blk, lds, s, C, HW, lp, tpi, v.x, v.m, vo, (const TX*)x, xs_n, xs_c, \
                                              (const TM*)mod, w, b, eps, out, mean, rstd)
@@ -277,7 +250,7 @@ static hipError_t launch_modln_fwd(hipStream_t s, int N, int C, int HW, int x_dt
 // ---------------------------------------------------------------------------------------------------------------------------------
 static int modln_bwd_log2(int C) { return modln_tile_log2(C, 2, 5); }
 static size_t modln_bwd_tiles(int N, int C, int HW) { const int P = 1 << modln_bwd_log2(C); return (size_t)N * ((HW + P - 1) / P); }
-static size_t modln_bwd_scratch_bytes(int N, int C, int HW) { return align_up((modln_bwd_tiles(N, C, HW) + MODLN_REDUCE_GROUPS) * 2 * C * 4, 256) + 256; }
+static size_t modln_bwd_scratch_bytes(int N, int C, int HW) { return align_up((modln_bwd_tiles(N, C, HW) + PARAM_REDUCE_GROUPS) * 2 * C * 4, 256) + 256; }
 
 // With xh = (x - mu) r, y = xh w + b, gh = g (1 + scale):  d shift = g, d scale = g y, d weight = sum gh xh, d bias = sum gh,
 // d x = r (gh w - mean_c(gh w) - xh mean_c(gh w xh)).  part[(tile * 2 + 0) * C + c] / [(tile * 2 + 1) * C + c]: the tile's sums over its pixels.
@@ -302,7 +275,7 @@ modln_bwd_kernel(int C, int HW, int lp, int tiles_per_img, int vx, int vm, int v
     if (tid < npix) { mu[tid] = mean[(size_t)n * HW + p0 + tid]; rs[tid] = rstd[(size_t)n * HW + p0 + tid]; }
     modln_load_tile(xs, x + (size_t)n * xs_n + p0, xs_c, C, lp, npix, vx);
     modln_load_tile(gs, g + (size_t)n * C * HW + p0, (size_t)HW, C, lp, npix, vg);
-    cond_barrier();
+    wg_barrier();
     // channel pass: xs <- xh, gs <- gh; d shift and d scale leave as rows
     const int wv = tid >> 6, lane = tid & 63, pg = lane >> 4, l = lane & 15;
     for (int pb = 0; pb < npix; pb += 16) {
@@ -313,14 +286,14 @@ modln_bwd_kernel(int C, int HW, int lp, int tiles_per_img, int vx, int vm, int v
         const TM* row = mod + ro;
         if (vm) {
             for (int c = 4 * l; c < C; c += 64) {
-                const float4 sc = cond_ld4(row + C + c), ww = *(const float4*)(w + c), bb = *(const float4*)(b + c);
+                const float4 sc = ld4(row + C + c), ww = *(const float4*)(w + c), bb = *(const float4*)(b + c);
                 float* d = xs + c * S + pp;
                 float* e = gs + c * S + pp;
                 const float4 xh = make_float4((d[0] - pm) * pr, (d[S] - pm) * pr, (d[2 * S] - pm) * pr, (d[3 * S] - pm) * pr);
                 const float4 gg = make_float4(e[0], e[S], e[2 * S], e[3 * S]);
                 if (dmod) {
-                    cond_st4(dmod + ro + c, gg);
-                    cond_st4(dmod + ro + C + c, make_float4(gg.x * fmaf(xh.x, ww.x, bb.x), gg.y * fmaf(xh.y, ww.y, bb.y),
+                    st4(dmod + ro + c, gg);
+                    st4(dmod + ro + C + c, make_float4(gg.x * fmaf(xh.x, ww.x, bb.x), gg.y * fmaf(xh.y, ww.y, bb.y),
                                                             gg.z * fmaf(xh.z, ww.z, bb.z), gg.w * fmaf(xh.w, ww.w, bb.w)));
                 }
                 d[0] = xh.x; d[S] = xh.y; d[2 * S] = xh.z; d[3 * S] = xh.w;
@@ -331,13 +304,13 @@ modln_bwd_kernel(int C, int HW, int lp, int tiles_per_img, int vx, int vm, int v
                 float* d = xs + c * S + pp;
                 float* e = gs + c * S + pp;
                 const float xh = (d[0] - pm) * pr, gg = e[0];
-                if (dmod) { cond_st(dmod + ro + c, gg); cond_st(dmod + ro + C + c, gg * fmaf(xh, w[c], b[c])); }
+                if (dmod) { st(dmod + ro + c, gg); st(dmod + ro + C + c, gg * fmaf(xh, w[c], b[c])); }
                 d[0] = xh;
-                e[0] = gg * (1.f + cond_ld(row + C + c));
+                e[0] = gg * (1.f + ld(row + C + c));
             }
         }
     }
-    cond_barrier();
+    wg_barrier();
     // the tile's row of parameter partial sums: one thread per channel, pixels in order
     if (part) {
         float* pw = part + (size_t)blockIdx.x * 2 * C;
@@ -354,12 +327,12 @@ modln_bwd_kernel(int C, int HW, int lp, int tiles_per_img, int vx, int vm, int v
     if (p < npix)
         for (int c = q; c < C; c += parts) { const float gw = gs[c * S + p] * w[c]; s1 += gw; s2 = fmaf(gw, xs[c * S + p], s2); }
     red[tid] = s1; red[MODLN_THREADS + tid] = s2;
-    cond_barrier();
+    wg_barrier();
     if (q == 0 && p < npix) {
         m1[p] = modln_sum_parts(red, p, lp) / (float)C;
         m2[p] = modln_sum_parts(red + MODLN_THREADS, p, lp) / (float)C;
     }
-    cond_barrier();
+    wg_barrier();
     TX* db = dx + (size_t)n * C * HW + p0;
     if (vd) {
         const int lq = lp - 2, nq = C << lq;
@@ -374,54 +347,15 @@ modln_bwd_kernel(int C, int HW, int lp, int tiles_per_img, int vx, int vm, int v
                 o.y = rs[pp + 1] * (fmaf(e[1], wc, -m1[pp + 1]) - d[1] * m2[pp + 1]);
                 o.z = rs[pp + 2] * (fmaf(e[2], wc, -m1[pp + 2]) - d[2] * m2[pp + 2]);
                 o.w = rs[pp + 3] * (fmaf(e[3], wc, -m1[pp + 3]) - d[3] * m2[pp + 3]);
-                cond_st4(db + (size_t)c * HW + pp, o);
+                st4(db + (size_t)c * HW + pp, o);
             }
         }
     } else {
         const int ne = C << lp;
         for (int i = tid; i < ne; i += MODLN_THREADS) {
             const int c = i >> lp, pp = i - (c << lp);
-            if (pp < npix) cond_st(db + (size_t)c * HW + pp, rs[pp] * (fmaf(gs[c * S + pp], w[c], -m1[pp]) - xs[c * S + pp] * m2[pp]));
+            if (pp < npix) st(db + (size_t)c * HW + pp, rs[pp] * (fmaf(gs[c * S + pp], w[c], -m1[pp]) - xs[c * S + pp] * m2[pp]));
         }
-    }
-}
-
-// Adds rows of parameter partial sums in row order.  blockIdx.y = 0: d weight, 1: d bias; blockIdx.z = g: the g-th contiguous share of
-// the T rows of `part` ([T][2][C]) goes to out0 / out1 + g * out_stride.  A workgroup owns 64 channels; wave k adds its contiguous part
-// of the share in row order (eight loads in flight, added in order), then the 16 waves' sums are added in wave order.  Two rounds:
-// T rows -> MODLN_REDUCE_GROUPS rows -> one, so that no wave walks more than T / 1024 rows behind one another's latency.
-__global__ void __launch_bounds__(64 * MODLN_REDUCE_WAVES)
-modln_param_reduce_kernel(int C, uint32_t T, const float* __restrict__ part, float* __restrict__ out0, float* __restrict__ out1,
-                          size_t out_stride)
-{
-    __shared__ float sm[MODLN_REDUCE_WAVES * 64];
-    const int which = blockIdx.y;
-    float* dst = which ? out1 : out0;
-    if (!dst) return;                                          // (uniform)
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, c = blockIdx.x * 64 + lane;
-    const uint32_t gshare = (T + gridDim.z - 1) / gridDim.z;
-    const uint32_t g0 = min(blockIdx.z * gshare, T), g1 = min(g0 + gshare, T);
-    const uint32_t share = (g1 - g0 + MODLN_REDUCE_WAVES - 1) / MODLN_REDUCE_WAVES;
-    const uint32_t t0 = min(g0 + (uint32_t)wv * share, g1), t1 = min(t0 + share, g1);
-    float s = 0.f;
-    if (c < C) {
-        const float* src = part + (size_t)which * C + c;
-        uint32_t t = t0;
-        for (; t + 8 <= t1; t += 8) {
-            float a[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) a[k] = src[(size_t)(t + k) * 2 * C];
-#pragma unroll
-            for (int k = 0; k < 8; k++) s += a[k];
-        }
-        for (; t < t1; t++) s += src[(size_t)t * 2 * C];
-    }
-    sm[wv * 64 + lane] = s;
-    cond_barrier();
-    if (wv == 0 && c < C) {
-        float tot = 0.f;
-        for (int k = 0; k < MODLN_REDUCE_WAVES; k++) tot += sm[k * 64 + lane];
-        dst[(size_t)blockIdx.z * out_stride + c] = tot;
     }
 }
 
@@ -432,9 +366,9 @@ static hipError_t launch_modln_bwd(hipStream_t s, int N, int C, int HW, int x_dt
     const int lp = modln_bwd_log2(C), P = 1 << lp, tpi = (HW + P - 1) / P;
     const size_t lds = modln_lds_bytes(C, P, 2);
     const ModlnVec v = modln_vec(C, HW, x_dtype, x, xs_n, xs_c, mod_dtype, mod, w, b);
-    const int vm = v.m && (!dmod || modln_aligned(dmod, mod_dtype == IGS_DTYPE_F16 ? 8 : 16));
-    const int vg = v.hw && modln_aligned(gout, 16);
-    const int vd = v.hw && modln_aligned(dx, x_dtype == IGS_DTYPE_F16 ? 8 : 16);
+    const int vm = v.m && (!dmod || ptr_aligned(dmod, vec_grid_bytes(mod_dtype)));
+    const int vg = v.hw && ptr_aligned(gout, 16);
+    const int vd = v.hw && ptr_aligned(dx, vec_grid_bytes(x_dtype));
     float* part = (dw || db) ? (float*)align_ptr((const char*)scratch) : nullptr;
     const uint32_t T = (uint32_t)((size_t)N * tpi);
     const dim3 g(T), blk(MODLN_THREADS);
@@ -445,13 +379,7 @@ static hipError_t launch_modln_bwd(hipStream_t s, int N, int C, int HW, int x_dt
 #undef MODLN_BWD
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !part) return e;
-    float* part2 = part + (size_t)T * 2 * C;                   // MODLN_REDUCE_GROUPS rows behind the workgroups' rows
-    const dim3 rb(64 * MODLN_REDUCE_WAVES);
-    hipLaunchKernelGGL(modln_param_reduce_kernel, dim3((C + 63) / 64, 2, MODLN_REDUCE_GROUPS), rb, 0, s, C, T, (const float*)part, part2, part2 + C,
-                       (size_t)2 * C);
-    hipLaunchKernelGGL(modln_param_reduce_kernel, dim3((C + 63) / 64, 2, 1), rb, 0, s, C, (uint32_t)MODLN_REDUCE_GROUPS, (const float*)part2, dw, db,
-                       (size_t)0);
-    return hipGetLastError();
+    return launch_param_reduce(s, C, T, part, part + (size_t)T * 2 * C, dw, db);      // (staged behind the workgroups' rows)
 }
 
 // the entry points (the contract is in include/igs_rast.h)

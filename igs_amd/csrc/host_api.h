@@ -1,4 +1,5 @@
-// host_api.h -- the error plumbing of the C entry points (include/igs_rast.h), for every .hip file that defines some next to its kernels.
+// host_api.h -- the error plumbing of the C entry points (include/igs_rast.h) and the argument checks they share, for every .hip file that
+// defines some next to its kernels.
 // Host code only.  The message buffer behind igs_rast_last_error() is thread-local in api.hip, which defines fail() and fail_in().
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,6 +11,15 @@ int fail_in(const char* fn, const char* what);                        // IGS_RAS
 #define HIP_TRY(expr, what) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(IGS_RAST_E_HIP, what, e_); } while (0)
 
 static inline bool dtype_ok(int dtype) { return dtype == IGS_DTYPE_F32 || dtype == IGS_DTYPE_F16; }
+static inline size_t dtype_bytes(int dtype) { return dtype == IGS_DTYPE_F16 ? 2 : 4; }
+// the grid that the kernels' four-element loads and stores of a dtype need their addresses on
+static inline size_t vec_grid_bytes(int dtype) { return 4 * dtype_bytes(dtype); }
+static inline bool ptr_aligned(const void* p, size_t bytes) { return (((uintptr_t)p) & (bytes - 1)) == 0; }      // (bytes: a power of two)
+static inline bool eps_ok(float eps) { return eps >= 0.f && eps < 3.0e38f; }                                     // finite and >= 0; a NaN is not
+// the bytes [lo, hi) of an operand
+struct ByteSpan { uintptr_t lo, hi; };
+static inline ByteSpan byte_span(const void* p, size_t bytes) { return ByteSpan{(uintptr_t)p, (uintptr_t)p + bytes}; }
+static inline bool spans_overlap(ByteSpan a, ByteSpan b) { return a.lo < b.hi && b.lo < a.hi; }
 // the [n][c][H][W] layouts read in place: every H x W plane contiguous (NCHW and any slicing of n or c); channels-last has no kernels here
 static inline const char* plane_stride_error(int C, int H, int W, long long fs_n, long long fs_c, long long fs_h, long long fs_w)
 {

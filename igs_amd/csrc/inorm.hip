@@ -20,6 +20,7 @@
 //   (3) position_add_kernel: both features in one launch; the sine embedding is a function of (channel, y mod wh) or (channel, x mod ww),
 //       evaluated in float32 with the accurate sinf / cosf, never stored.
 #include "common.h"
+#include "elem_common.h"
 #include "host_api.h"
 
 #define INORM_MAX_THREADS 1024
@@ -27,31 +28,6 @@
 #define INORM_RESIDENT_MAX_TWO 32768
 #define POSADD_THREADS 256
 
-// __syncthreads() with its release side spelled out (blend_common.h: tile_barrier): no LDS store is outstanding when the barrier opens
-__device__ __forceinline__ void inorm_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-}
-
-typedef _Float16 inorm_h4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float inorm_ld(const float* p) { return *p; }
-__device__ __forceinline__ float inorm_ld(const _Float16* p) { return (float)*p; }
-__device__ __forceinline__ void inorm_st(float* p, float v) { *p = v; }
-__device__ __forceinline__ void inorm_st(_Float16* p, float v) { *p = (_Float16)v; }
-__device__ __forceinline__ float4 inorm_ld4(const float* p) { return *(const float4*)p; }
-__device__ __forceinline__ float4 inorm_ld4(const _Float16* p)
-{
-    const inorm_h4 h = *(const inorm_h4*)p;
-    return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
-}
-__device__ __forceinline__ void inorm_st4(float* p, float4 v) { *(float4*)p = v; }
-__device__ __forceinline__ void inorm_st4(_Float16* p, float4 v)
-{
-    inorm_h4 h;
-    h.x = (_Float16)v.x; h.y = (_Float16)v.y; h.z = (_Float16)v.z; h.w = (_Float16)v.w;
-    *(inorm_h4*)p = h;
-}
 // torch.relu: a NaN stays a NaN (fmaxf would drop it)
 __device__ __forceinline__ float inorm_relu(float v) { return v < 0.f ? 0.f : v; }
 
@@ -76,11 +52,7 @@ __device__ __forceinline__ uint32_t inorm_edge_index(const InormGeom& g, uint32_
 template <int THREADS, int N>
 __device__ __forceinline__ void inorm_block_sum(float (&a)[N], float* red)
 {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int i = 0; i < N; i++) a[i] += __shfl_xor(a[i], off, 64);
-    }
+    lane_sum<64>(a);
     if (THREADS == 64) return;
     constexpr int NW = THREADS / 64;
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -88,7 +60,7 @@ __device__ __forceinline__ void inorm_block_sum(float (&a)[N], float* red)
 #pragma unroll
         for (int i = 0; i < N; i++) red[i * NW + wv] = a[i];
     }
-    inorm_barrier();
+    wg_barrier();
 #pragma unroll
     for (int i = 0; i < N; i++) {
         float s = 0.f;
@@ -96,16 +68,6 @@ __device__ __forceinline__ void inorm_block_sum(float (&a)[N], float* red)
         for (int k = 0; k < NW; k++) s += red[i * NW + k];
         a[i] = s;
     }
-}
-
-// mean and 1 / sqrt(var + eps) from the centre m and the sums of d = v - m and of d d over the n elements
-__device__ __forceinline__ void inorm_finish(float m, float s1, float s2, float n, float eps, float& mean, float& rstd)
-{
-    const float dm = s1 / n;
-    float var = s2 / n - dm * dm;
-    var = var < 0.f ? 0.f : var;                               // (keeps a NaN)
-    mean = m + dm;
-    rstd = 1.f / sqrtf(var + eps);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -123,10 +85,10 @@ struct InormPlane {
 #pragma unroll
         for (int j = 0; j < NV; j++) {
             float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (vec_ok(g, j)) q = inorm_ld4(p + g.head + 4 * ((uint32_t)(j * THREADS) + threadIdx.x));
+            if (vec_ok(g, j)) q = ld4(p + g.head + 4 * ((uint32_t)(j * THREADS) + threadIdx.x));
             v[j][0] = q.x; v[j][1] = q.y; v[j][2] = q.z; v[j][3] = q.w;
         }
-        if (edge_ok(g)) e = inorm_ld(p + inorm_edge_index(g, threadIdx.x));
+        if (edge_ok(g)) e = ld(p + inorm_edge_index(g, threadIdx.x));
     }
     __device__ __forceinline__ float sum() const                // (the slots outside the plane hold zero)
     {
@@ -194,8 +156,8 @@ inorm_resident_kernel(const T* x, const T* skip, T* out, uint32_t hw, int mode, 
     if (TWO) pk.centred(g, m[NP - 1], c[2 * NP - 2], c[2 * NP - 1]);
     inorm_block_sum<THREADS, 2 * NP>(c, red + NP * NW);
     float mean, rstd, kmean = 0.f, krstd = 1.f;
-    inorm_finish(m[0], c[0], c[1], n, eps, mean, rstd);
-    if (TWO) inorm_finish(m[NP - 1], c[2 * NP - 2], c[2 * NP - 1], n, eps, kmean, krstd);
+    norm_finish(m[0], c[0], c[1], n, eps, mean, rstd);
+    if (TWO) norm_finish(m[NP - 1], c[2 * NP - 2], c[2 * NP - 1], n, eps, kmean, krstd);
     const bool raw_skip = !TWO && mode == INORM_RELU_ADD_RELU;
     T* op = out + base;
     const T* kp = skip + base;                                 // (dereferenced only in the two modes that have a skip)
@@ -208,7 +170,7 @@ inorm_resident_kernel(const T* x, const T* skip, T* out, uint32_t hw, int mode, 
 #pragma unroll
             for (int i = 0; i < 4; i++) k[i] = (pk.v[j][i] - kmean) * krstd;
         } else if (raw_skip) {
-            const float4 q = inorm_ld4(kp + at);
+            const float4 q = ld4(kp + at);
             k[0] = q.x; k[1] = q.y; k[2] = q.z; k[3] = q.w;
         }
         float4 o;
@@ -216,12 +178,12 @@ inorm_resident_kernel(const T* x, const T* skip, T* out, uint32_t hw, int mode, 
         o.y = inorm_apply(mode, (px.v[j][1] - mean) * rstd, k[1]);
         o.z = inorm_apply(mode, (px.v[j][2] - mean) * rstd, k[2]);
         o.w = inorm_apply(mode, (px.v[j][3] - mean) * rstd, k[3]);
-        inorm_st4(op + at, o);
+        st4(op + at, o);
     }
     if (px.edge_ok(g)) {
         const uint32_t at = inorm_edge_index(g, threadIdx.x);
-        const float k = TWO ? (pk.e - kmean) * krstd : raw_skip ? inorm_ld(kp + at) : 0.f;
-        inorm_st(op + at, inorm_apply(mode, (px.e - mean) * rstd, k));
+        const float k = TWO ? (pk.e - kmean) * krstd : raw_skip ? ld(kp + at) : 0.f;
+        st(op + at, inorm_apply(mode, (px.e - mean) * rstd, k));
     }
 }
 
@@ -233,23 +195,23 @@ inorm_resident_kernel(const T* x, const T* skip, T* out, uint32_t hw, int mode, 
 template <typename T>
 __device__ __forceinline__ void inorm_stream_sums(const T* p, const InormGeom& g, float& m, float& s1, float& s2)
 {
-    m = g.hw >= 4 ? ((inorm_ld(p) + inorm_ld(p + 1)) + (inorm_ld(p + 2) + inorm_ld(p + 3))) * 0.25f : inorm_ld(p);
+    m = g.hw >= 4 ? ((ld(p) + ld(p + 1)) + (ld(p + 2) + ld(p + 3))) * 0.25f : ld(p);
     float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
     if (g.vec) {
         for (uint32_t i = threadIdx.x; i < g.nvec; i += INORM_MAX_THREADS) {
-            const float4 q = inorm_ld4(p + g.head + 4 * i);
+            const float4 q = ld4(p + g.head + 4 * i);
             const float d0 = q.x - m, d1 = q.y - m, d2 = q.z - m, d3 = q.w - m;
             a[0] += d0; a[1] += d1; a[2] += d2; a[3] += d3;
             b[0] = fmaf(d0, d0, b[0]); b[1] = fmaf(d1, d1, b[1]); b[2] = fmaf(d2, d2, b[2]); b[3] = fmaf(d3, d3, b[3]);
         }
         if (threadIdx.x < g.head + g.tail) {
-            const float d = inorm_ld(p + inorm_edge_index(g, threadIdx.x)) - m;
+            const float d = ld(p + inorm_edge_index(g, threadIdx.x)) - m;
             a[0] += d; b[0] = fmaf(d, d, b[0]);
         }
     } else {
         uint32_t k = 0;
         for (uint32_t i = threadIdx.x; i < g.hw; i += INORM_MAX_THREADS, k = (k + 1) & 3) {
-            const float d = inorm_ld(p + i) - m;
+            const float d = ld(p + i) - m;
             if (k == 0) { a[0] += d; b[0] = fmaf(d, d, b[0]); }
             else if (k == 1) { a[1] += d; b[1] = fmaf(d, d, b[1]); }
             else if (k == 2) { a[2] += d; b[2] = fmaf(d, d, b[2]); }
@@ -277,34 +239,34 @@ inorm_streamed_kernel(const T* x, const T* skip, T* out, uint32_t hw, int mode, 
     if (TWO) inorm_stream_sums(kp, g, m[NP - 1], c[2 * NP - 2], c[2 * NP - 1]);
     inorm_block_sum<INORM_MAX_THREADS, 2 * NP>(c, red);       // (its barrier also orders every first read before any write of out == x)
     float mean, rstd, kmean = 0.f, krstd = 1.f;
-    inorm_finish(m[0], c[0], c[1], n, eps, mean, rstd);
-    if (TWO) inorm_finish(m[NP - 1], c[2 * NP - 2], c[2 * NP - 1], n, eps, kmean, krstd);
+    norm_finish(m[0], c[0], c[1], n, eps, mean, rstd);
+    if (TWO) norm_finish(m[NP - 1], c[2 * NP - 2], c[2 * NP - 1], n, eps, kmean, krstd);
     const bool has_skip = TWO || mode == INORM_RELU_ADD_RELU;
     if (g.vec) {
         for (uint32_t i = threadIdx.x; i < g.nvec; i += INORM_MAX_THREADS) {
             const uint32_t at = g.head + 4 * i;
-            const float4 q = inorm_ld4(xp + at);
+            const float4 q = ld4(xp + at);
             float4 k = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (has_skip) k = inorm_ld4(kp + at);
+            if (has_skip) k = ld4(kp + at);
             if (TWO) { k.x = (k.x - kmean) * krstd; k.y = (k.y - kmean) * krstd; k.z = (k.z - kmean) * krstd; k.w = (k.w - kmean) * krstd; }
             float4 o;
             o.x = inorm_apply(mode, (q.x - mean) * rstd, k.x);
             o.y = inorm_apply(mode, (q.y - mean) * rstd, k.y);
             o.z = inorm_apply(mode, (q.z - mean) * rstd, k.z);
             o.w = inorm_apply(mode, (q.w - mean) * rstd, k.w);
-            inorm_st4(op + at, o);
+            st4(op + at, o);
         }
         if (threadIdx.x < g.head + g.tail) {
             const uint32_t at = inorm_edge_index(g, threadIdx.x);
-            float k = has_skip ? inorm_ld(kp + at) : 0.f;
+            float k = has_skip ? ld(kp + at) : 0.f;
             if (TWO) k = (k - kmean) * krstd;
-            inorm_st(op + at, inorm_apply(mode, (inorm_ld(xp + at) - mean) * rstd, k));
+            st(op + at, inorm_apply(mode, (ld(xp + at) - mean) * rstd, k));
         }
     } else {
         for (uint32_t i = threadIdx.x; i < g.hw; i += INORM_MAX_THREADS) {
-            float k = has_skip ? inorm_ld(kp + i) : 0.f;
+            float k = has_skip ? ld(kp + i) : 0.f;
             if (TWO) k = (k - kmean) * krstd;
-            inorm_st(op + i, inorm_apply(mode, (inorm_ld(xp + i) - mean) * rstd, k));
+            st(op + i, inorm_apply(mode, (ld(xp + i) - mean) * rstd, k));
         }
     }
 }
@@ -376,14 +338,14 @@ position_add_kernel(const T* f0, const T* f1, T* out0, T* out1, int C, int W, ui
     }
     const size_t at = (size_t)plane * hw + el;
     if (V == 4) {
-        float4 a = inorm_ld4(f0 + at), b = inorm_ld4(f1 + at);
+        float4 a = ld4(f0 + at), b = ld4(f1 + at);
         a.x += add[0]; a.y += add[1]; a.z += add[2]; a.w += add[3];
         b.x += add[0]; b.y += add[1]; b.z += add[2]; b.w += add[3];
-        inorm_st4(out0 + at, a);
-        inorm_st4(out1 + at, b);
+        st4(out0 + at, a);
+        st4(out1 + at, b);
     } else {
-        inorm_st(out0 + at, inorm_ld(f0 + at) + add[0]);
-        inorm_st(out1 + at, inorm_ld(f1 + at) + add[0]);
+        st(out0 + at, ld(f0 + at) + add[0]);
+        st(out1 + at, ld(f1 + at) + add[0]);
     }
 }
 
@@ -405,11 +367,7 @@ static hipError_t launch_position_add(hipStream_t s, const T* f0, const T* f1, T
 // ---------------------------------------------------------------------------------------------------------------------------------
 static bool inorm_mode_ok(int mode) { return mode >= INORM_PLAIN && mode <= INORM_RELU_ADDNORM_RELU; }
 // [a, a + bytes) and [b, b + bytes) share a byte without being the same range
-static bool inorm_partial_overlap(const void* a, const void* b, size_t bytes)
-{
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa != pb && pa < pb + bytes && pb < pa + bytes;
-}
+static bool inorm_partial_overlap(const void* a, const void* b, size_t bytes) { return a != b && spans_overlap(byte_span(a, bytes), byte_span(b, bytes)); }
 
 extern "C" long long igs_instance_norm_resident_max(int dtype, int mode)
 {
@@ -426,12 +384,12 @@ extern "C" int igs_instance_norm_fwd(void* stream, const void* x, const void* sk
     if (hw < 2) return fail_in(fn, "hw < 2: an instance norm needs more than 1 spatial element");
     if (hw > IGS_INORM_MAX_HW) return fail_in(fn, "hw out of range (IGS_INORM_MAX_HW)");
     if (planes < 0 || planes > IGS_INORM_MAX_PLANES) return fail_in(fn, "planes out of range (0..IGS_INORM_MAX_PLANES)");
-    if (!(eps >= 0.f) || !(eps < 3.0e38f)) return fail_in(fn, "eps must be finite and >= 0");
+    if (!eps_ok(eps)) return fail_in(fn, "eps must be finite and >= 0");
     if (planes == 0) return 0;
     const bool has_skip = mode == INORM_RELU_ADD_RELU || mode == INORM_RELU_ADDNORM_RELU;
     if (!x || !out) return fail_in(fn, "NULL pointer");
     if (has_skip && !skip) return fail_in(fn, "NULL pointer (this mode needs skip)");
-    const size_t es = dtype == IGS_DTYPE_F16 ? 2 : 4, bytes = (size_t)planes * (size_t)hw * es;
+    const size_t es = dtype_bytes(dtype), bytes = (size_t)planes * (size_t)hw * es;
     if ((((uintptr_t)x) | ((uintptr_t)out) | (has_skip ? (uintptr_t)skip : 0)) & (es - 1)) return fail_in(fn, "a pointer is not aligned to its element size");
     if (inorm_partial_overlap(x, out, bytes)) return fail_in(fn, "out overlaps x without being x (only out == x may alias)");
     if (has_skip && (skip == (const void*)out || inorm_partial_overlap(skip, out, bytes))) return fail_in(fn, "out overlaps skip (only out == x may alias)");
@@ -457,7 +415,7 @@ extern "C" int igs_position_add(void* stream, const void* f0, const void* f1, vo
     if (planes * chunks > IGS_INORM_MAX_PLANES) return fail_in(fn, "B * C * H * W out of range");
     if (B == 0) return 0;
     if (!f0 || !f1 || !out0 || !out1) return fail_in(fn, "NULL pointer");
-    const size_t es = dtype == IGS_DTYPE_F16 ? 2 : 4, bytes = (size_t)planes * H * W * es;
+    const size_t es = dtype_bytes(dtype), bytes = (size_t)planes * H * W * es;
     if ((((uintptr_t)f0) | ((uintptr_t)f1) | ((uintptr_t)out0) | ((uintptr_t)out1)) & (es - 1)) return fail_in(fn, "a pointer is not aligned to its element size");
     if (inorm_partial_overlap(f0, out0, bytes) || inorm_partial_overlap(f1, out1, bytes) || out0 == out1 || inorm_partial_overlap(out0, out1, bytes) ||
         (const void*)out0 == f1 || inorm_partial_overlap(f1, out0, bytes) || (const void*)out1 == f0 || inorm_partial_overlap(f0, out1, bytes))

@@ -15,6 +15,7 @@
 //       per sorted edge; lift_bwd_kernel, one workgroup per (b, v, LIFT_BWD_CH channels), holds d out[b, c, :] in LDS and every thread
 //       sums the edges of its pixels in list order and writes d feat coalesced, every element (zero where no sample landed).
 #include "common.h"
+#include "elem_common.h"
 #include "host_api.h"
 
 #define LIFT_THREADS 512              // forward workgroup
@@ -24,11 +25,6 @@
 #define LIFT_BWD_THREADS 1024
 #define LIFT_BWD_CH 2                 // channels per backward workgroup: 2 x 8192 anchors of d out = 64 KB
 #define LIFT_OUTSIDE 0xFFFFFFFFu      // cell mark of a sample that touches no pixel (or is not finite)
-
-__device__ __forceinline__ float lift_ld(const float* p) { return *p; }
-__device__ __forceinline__ float lift_ld(const _Float16* p) { return (float)*p; }
-__device__ __forceinline__ void lift_st(float* p, float v) { *p = v; }
-__device__ __forceinline__ void lift_st(_Float16* p, float v) { *p = (_Float16)v; }      // round to nearest even, once
 
 // corner q of a sample: 0 = (x0, y0), 1 = (x0 + 1, y0), 2 = (x0, y0 + 1), 3 = (x0 + 1, y0 + 1); tx = ix - x0, ty = iy - y0
 __device__ __forceinline__ float lift_weight(int q, float tx, float ty)
@@ -146,7 +142,6 @@ lift_fwd_kernel(int V, int A, int C, int H, int W, int band_rows, int nchunk, co
                     float4 f;
                     if constexpr (sizeof(T) == 4) f = ((const float4*)band)[i];
                     else {
-                        typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
                         const h4_t h = ((const h4_t*)band)[i];
                         f = make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
                     }
@@ -154,7 +149,7 @@ lift_fwd_kernel(int V, int A, int C, int H, int W, int band_rows, int nchunk, co
                 }
                 done = n4 << 2;
             }
-            for (int i = done + tid; i < n; i += LIFT_THREADS) plane[i] = lift_ld(band + i);
+            for (int i = done + tid; i < n; i += LIFT_THREADS) plane[i] = ld(band + i);
             __syncthreads();
 #pragma unroll
             for (int j = 0; j < LIFT_APT; j++) {
@@ -267,9 +262,9 @@ lift_bwd_kernel(int V, int A, int C, int HW, int ncg, int use_lds, const uint32_
                 for (int a = tid; a < A; a += LIFT_BWD_THREADS) gl[ch * A + a] = g[(size_t)a * gs_a + (size_t)(c0 + ch) * gs_c];
         __syncthreads();
     }
-    const uint32_t* st = start + bv * HW;
+    const uint32_t* first = start + bv * HW;
     for (int p = tid; p < HW; p += LIFT_BWD_THREADS) {
-        const uint32_t lo = st[p], hi = st[p + 1];
+        const uint32_t lo = first[p], hi = first[p + 1];
         float acc[LIFT_BWD_CH];
 #pragma unroll
         for (int ch = 0; ch < LIFT_BWD_CH; ch++) acc[ch] = 0.f;
@@ -285,7 +280,7 @@ lift_bwd_kernel(int V, int A, int C, int HW, int ncg, int use_lds, const uint32_
         }
 #pragma unroll
         for (int ch = 0; ch < LIFT_BWD_CH; ch++)
-            if (c0 + ch < C) lift_st(dfeat + bv * fs_n + (size_t)(c0 + ch) * fs_c + p, acc[ch] / (float)V);
+            if (c0 + ch < C) st(dfeat + bv * fs_n + (size_t)(c0 + ch) * fs_c + p, acc[ch] / (float)V);
     }
 }
 

@@ -10,6 +10,7 @@
 // (b) Gaussian deform, GaussianModel.deform (gs.py:347-375) with quaternion_multiply (igs/utils/general_utils.py:177-200):
 //     xyz[mask] += dxyz, rot[mask] = qmul(nrm(rot[mask]), nrm(drot)), and its backward through both normalisations.
 #include "common.h"
+#include "elem_common.h"
 #include "host_api.h"
 
 #define IW 4                          // waves per workgroup of the row / chunk kernels
@@ -18,18 +19,6 @@
 // ---------------------------------------------------------------------------------------------------------------------------------
 // shared helpers
 // ---------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float ld(const float* p) { return *p; }
-__device__ __forceinline__ float ld(const _Float16* p) { return (float)*p; }
-__device__ __forceinline__ void st(float* p, float v) { *p = v; }
-__device__ __forceinline__ void st(_Float16* p, float v) { *p = (_Float16)v; }      // round to nearest even, once
-
-__device__ __forceinline__ float wave_sum(float v)        // fixed butterfly order: the same result on every run
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // chunk length of the backward's edge lists: a quarter of one wave's share of the edges with 16 waves on each of 256 CUs, as a power of
 // two in [64, 512] (cdna_hip_programming.md Appendix B: split the long lists, add the partials in chunk order)
 static uint32_t interp_chunk(uint64_t E)
@@ -252,7 +241,7 @@ interp_chunk_kernel(int K, int D, int A, uint32_t chunk, const T* __restrict__ F
                 float t = 0.f;
 #pragma unroll
                 for (int v = 0; v < DV; v++) t = fmaf(g[q][v], fr[v], t);
-                t = wave_sum(t);
+                t = lane_sum<64>(t);
                 if (lane == 0) dw[ed[q]] = t;
             }
         }

@@ -13,43 +13,26 @@
 //       is the rounding error of m, so a constant row gives d = s1 / C exactly, and so exactly `bias`).  A row that holds a NaN or an
 //       infinity comes out all NaN.  The backward recomputes the statistics from the row it has to read anyway; per workgroup the lanes
 //       keep the column sums of dout x_hat and dout over the rows they meet, the workgroup's row groups are added through LDS in a fixed
-//       order into one partial row of the caller's scratch, and ln_param_reduce_kernel adds the partial rows in workgroup order.
+//       order into one partial row of the caller's scratch, and param_reduce.h adds the partial rows in workgroup order (one round).
 //       Four-element loads where every base pointer, every row stride and C allow them (VEC), scalar loads of the same lane mapping
 //       otherwise.  The three dtypes of a call are wave-uniform runtime codes: one kernel per (LPR, NV, VEC).
 //   (2) geglu_fwd_kernel / geglu_bwd_kernel: elementwise over [N, D], four columns per thread where D, the stride and the pointers allow.
 //       Exact GELU: g Phi(g) with Phi(g) = 0.5 (1 + erf(g / sqrt 2)); the backward writes both halves of d p in one launch.
-#include "blend_common.h"                                      // tile_barrier: the audited workgroup barrier
+#include "common.h"
+#include "elem_common.h"
 #include "host_api.h"
+#include "param_reduce.h"
 
 #define LN_THREADS 256
 #define LN_BWD_MAX_GROUPS 1024                                 // workgroups (= partial parameter rows) of one backward
-#define LN_REDUCE_WAVES 16
 #define GEGLU_THREADS 256
 
-typedef _Float16 tok_h4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float tok_ld(const float* p) { return *p; }
-__device__ __forceinline__ float tok_ld(const _Float16* p) { return (float)*p; }
-__device__ __forceinline__ void tok_st(float* p, float v) { *p = v; }
-__device__ __forceinline__ void tok_st(_Float16* p, float v) { *p = (_Float16)v; }
-__device__ __forceinline__ float4 tok_ld4(const float* p) { return *(const float4*)p; }
-__device__ __forceinline__ float4 tok_ld4(const _Float16* p)
-{
-    const tok_h4 h = *(const tok_h4*)p;
-    return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
-}
-__device__ __forceinline__ void tok_st4(float* p, float4 v) { *(float4*)p = v; }
-__device__ __forceinline__ void tok_st4(_Float16* p, float4 v)
-{
-    tok_h4 h;
-    h.x = (_Float16)v.x; h.y = (_Float16)v.y; h.z = (_Float16)v.z; h.w = (_Float16)v.w;
-    *(tok_h4*)p = h;
-}
 // an operand whose dtype is a runtime code (half != 0: float16), addressed in elements
 struct TokPtr { const void* p; int half; };
-__device__ __forceinline__ float tok_ld(TokPtr t, size_t i) { return t.half ? tok_ld((const _Float16*)t.p + i) : tok_ld((const float*)t.p + i); }
-__device__ __forceinline__ float4 tok_ld4(TokPtr t, size_t i) { return t.half ? tok_ld4((const _Float16*)t.p + i) : tok_ld4((const float*)t.p + i); }
-__device__ __forceinline__ void tok_st(TokPtr t, size_t i, float v) { if (t.half) tok_st((_Float16*)t.p + i, v); else tok_st((float*)t.p + i, v); }
-__device__ __forceinline__ void tok_st4(TokPtr t, size_t i, float4 v) { if (t.half) tok_st4((_Float16*)t.p + i, v); else tok_st4((float*)t.p + i, v); }
+__device__ __forceinline__ float ld(TokPtr t, size_t i) { return t.half ? ld((const _Float16*)t.p + i) : ld((const float*)t.p + i); }
+__device__ __forceinline__ float4 ld4(TokPtr t, size_t i) { return t.half ? ld4((const _Float16*)t.p + i) : ld4((const float*)t.p + i); }
+__device__ __forceinline__ void st(TokPtr t, size_t i, float v) { if (t.half) st((_Float16*)t.p + i, v); else st((float*)t.p + i, v); }
+__device__ __forceinline__ void st4(TokPtr t, size_t i, float4 v) { if (t.half) st4((_Float16*)t.p + i, v); else st4((float*)t.p + i, v); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // (1) LayerNorm
@@ -66,11 +49,11 @@ struct LnRow {
             const int c = col(j, l);
             if (VEC) {
                 float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (c < C) q = tok_ld4(t, base + c);
+                if (c < C) q = ld4(t, base + c);
                 v[j][0] = q.x; v[j][1] = q.y; v[j][2] = q.z; v[j][3] = q.w;
             } else {
 #pragma unroll
-                for (int k = 0; k < 4; k++) v[j][k] = c + k < C ? tok_ld(t, base + c + k) : 0.f;
+                for (int k = 0; k < 4; k++) v[j][k] = c + k < C ? ld(t, base + c + k) : 0.f;
             }
         }
     }
@@ -96,26 +79,15 @@ struct LnRow {
         for (int j = 0; j < NV; j++) {
             const int c = col(j, l);
             if (VEC) {
-                if (c < C) tok_st4(t, base + c, make_float4(v[j][0], v[j][1], v[j][2], v[j][3]));
+                if (c < C) st4(t, base + c, make_float4(v[j][0], v[j][1], v[j][2], v[j][3]));
             } else {
 #pragma unroll
                 for (int k = 0; k < 4; k++)
-                    if (c + k < C) tok_st(t, base + c + k, v[j][k]);
+                    if (c + k < C) st(t, base + c + k, v[j][k]);
             }
         }
     }
 };
-
-// the sums of a and of b over the LPR lanes of the row, the same bits in every one of them
-template <int LPR>
-__device__ __forceinline__ void ln_row_sum(float& a, float& b)
-{
-#pragma unroll
-    for (int off = LPR / 2; off > 0; off >>= 1) {
-        a += __shfl_xor(a, off, 64);
-        b += __shfl_xor(b, off, 64);
-    }
-}
 
 // r.v <- x_hat = (v - mean) * rstd (zero outside the row); returns rstd
 template <int LPR, int NV, bool VEC>
@@ -127,9 +99,7 @@ __device__ __forceinline__ float ln_normalise(LnRow<LPR, NV, VEC>& r, int C, int
     for (int j = 0; j < NV; j++)
 #pragma unroll
         for (int k = 0; k < 4; k++) s[k] += r.v[j][k];                  // (the slots outside the row hold zero)
-    float sum = (s[0] + s[1]) + (s[2] + s[3]), unused = 0.f;
-    ln_row_sum<LPR>(sum, unused);
-    const float m = sum / n;
+    const float m = lane_sum<LPR>((s[0] + s[1]) + (s[2] + s[3])) / n;
     float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < NV; j++)
@@ -138,12 +108,10 @@ __device__ __forceinline__ float ln_normalise(LnRow<LPR, NV, VEC>& r, int C, int
             const float d = r.col(j, l) + k < C ? r.v[j][k] - m : 0.f;
             a[k] += d; b[k] = fmaf(d, d, b[k]);
         }
-    float s1 = (a[0] + a[1]) + (a[2] + a[3]), s2 = (b[0] + b[1]) + (b[2] + b[3]);
-    ln_row_sum<LPR>(s1, s2);
-    const float dm = s1 / n;
-    float var = s2 / n - dm * dm;
-    var = var < 0.f ? 0.f : var;                                       // (keeps a NaN)
-    const float mean = m + dm, rstd = 1.f / sqrtf(var + eps);
+    float c[2] = {(a[0] + a[1]) + (a[2] + a[3]), (b[0] + b[1]) + (b[2] + b[3])};
+    lane_sum<LPR>(c);
+    float mean, rstd;
+    norm_finish(m, c[0], c[1], n, eps, mean, rstd);
 #pragma unroll
     for (int j = 0; j < NV; j++)
 #pragma unroll
@@ -217,9 +185,9 @@ ln_bwd_kernel(uint32_t N, int C, TokPtr x, size_t xs, const float* __restrict__ 
                 a[k] += gw; b[k] = fmaf(gw, r.v[j][k], b[k]);
             }
         if (!dx.p) continue;                                           // (uniform)
-        float s1 = (a[0] + a[1]) + (a[2] + a[3]), s2 = (b[0] + b[1]) + (b[2] + b[3]);
-        ln_row_sum<LPR>(s1, s2);
-        const float m1 = s1 / n, m2 = s2 / n;
+        float c[2] = {(a[0] + a[1]) + (a[2] + a[3]), (b[0] + b[1]) + (b[2] + b[3])};
+        lane_sum<LPR>(c);
+        const float m1 = c[0] / n, m2 = c[1] / n;
 #pragma unroll
         for (int j = 0; j < NV; j++)
 #pragma unroll
@@ -233,7 +201,7 @@ ln_bwd_kernel(uint32_t N, int C, TokPtr x, size_t xs, const float* __restrict__ 
     for (int j = 0; j < NV; j++) {
 #pragma unroll
         for (int k = 0; k < 4; k++) { red[k * LN_THREADS + threadIdx.x] = aw.v[j][k]; red[(4 + k) * LN_THREADS + threadIdx.x] = ab.v[j][k]; }
-        tile_barrier();
+        wg_barrier();
         if (sub == 0) {
             float t[8];
 #pragma unroll
@@ -252,42 +220,7 @@ ln_bwd_kernel(uint32_t N, int C, TokPtr x, size_t xs, const float* __restrict__ 
                     if (c + k < C) { pd[c + k] = t[k]; pd[C + c + k] = t[4 + k]; }
             }
         }
-        tile_barrier();
-    }
-}
-
-// Adds the T rows of `part` ([T][2][C]) in row order: blockIdx.y = 0 gives d weight, 1 d bias.  A workgroup owns 64 channels; wave k adds
-// its contiguous share of the rows in row order (eight loads in flight, added in order), then the waves' sums are added in wave order.
-// (cond.hip's modln_param_reduce_kernel in one round: T <= LN_BWD_MAX_GROUPS, so no wave walks more than 64 rows.)
-__global__ void __launch_bounds__(64 * LN_REDUCE_WAVES)
-ln_param_reduce_kernel(int C, uint32_t T, const float* __restrict__ part, float* __restrict__ dw, float* __restrict__ db)
-{
-    __shared__ float sm[LN_REDUCE_WAVES * 64];
-    const int which = blockIdx.y;
-    float* dst = which ? db : dw;
-    if (!dst) return;                                                  // (uniform)
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, c = blockIdx.x * 64 + lane;
-    const uint32_t share = (T + LN_REDUCE_WAVES - 1) / LN_REDUCE_WAVES;
-    const uint32_t t0 = min((uint32_t)wv * share, T), t1 = min(t0 + share, T);
-    float s = 0.f;
-    if (c < C) {
-        const float* src = part + (size_t)which * C + c;
-        uint32_t t = t0;
-        for (; t + 8 <= t1; t += 8) {
-            float a[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) a[k] = src[(size_t)(t + k) * 2 * C];
-#pragma unroll
-            for (int k = 0; k < 8; k++) s += a[k];
-        }
-        for (; t < t1; t++) s += src[(size_t)t * 2 * C];
-    }
-    sm[wv * 64 + lane] = s;
-    tile_barrier();
-    if (wv == 0 && c < C) {
-        float tot = 0.f;
-        for (int k = 0; k < LN_REDUCE_WAVES; k++) tot += sm[k * 64 + lane];
-        dst[c] = tot;
+        wg_barrier();
     }
 }
 
@@ -298,9 +231,8 @@ static uint32_t ln_bwd_groups(long long N, int C)
     const long long rpb = ln_rows_per_group(C), groups = (N + rpb - 1) / rpb;
     return (uint32_t)(groups < LN_BWD_MAX_GROUPS ? groups : LN_BWD_MAX_GROUPS);
 }
-static bool tok_aligned(const void* p, size_t a) { return (((uintptr_t)p) & (a - 1)) == 0; }
 // the four-element path of an operand: base on the 4-element grid of its dtype, row stride a multiple of four
-static bool ln_vec_ok(const void* p, int dtype, long long stride) { return !p || (tok_aligned(p, dtype == IGS_DTYPE_F16 ? 8 : 16) && (stride & 3) == 0); }
+static bool ln_vec_ok(const void* p, int dtype, long long stride) { return !p || (ptr_aligned(p, vec_grid_bytes(dtype)) && (stride & 3) == 0); }
 
 #define LN_LAUNCH(KERNEL, GRID, ...)                                                                                                        \
     do {                                                                                                                                    \
@@ -324,7 +256,7 @@ static hipError_t launch_ln_fwd(hipStream_t s, long long N, int C, int x_dtype, 
                                 long long rs, const float* w, const float* b, float eps, int out_dtype, void* out, long long os)
 {
     const bool vec = (C & 3) == 0 && ln_vec_ok(x, x_dtype, xs) && ln_vec_ok(res, res_dtype, rs) && ln_vec_ok(out, out_dtype, os) &&
-                     (!w || (tok_aligned(w, 16) && tok_aligned(b, 16)));
+                     (!w || (ptr_aligned(w, 16) && ptr_aligned(b, 16)));
     const TokPtr tx = {x, x_dtype == IGS_DTYPE_F16}, tr = {res, res && res_dtype == IGS_DTYPE_F16}, to = {out, out_dtype == IGS_DTYPE_F16};
     const long long rpb = ln_rows_per_group(C);
     LN_LAUNCH(ln_fwd_kernel, (unsigned)((N + rpb - 1) / rpb), (uint32_t)N, C, tx, (size_t)xs, tr, (size_t)rs, w, b, eps, to, (size_t)os);
@@ -335,15 +267,14 @@ static hipError_t launch_ln_bwd(hipStream_t s, long long N, int C, int x_dtype, 
                                 const void* dout, long long gs, int dx_dtype, void* dx, long long dxs, float* dw, float* db, void* scratch)
 {
     const bool vec = (C & 3) == 0 && ln_vec_ok(x, x_dtype, xs) && ln_vec_ok(dout, g_dtype, gs) && ln_vec_ok(dx, dx_dtype, dxs) &&
-                     (!w || tok_aligned(w, 16));
+                     (!w || ptr_aligned(w, 16));
     const TokPtr tx = {x, x_dtype == IGS_DTYPE_F16}, tg = {dout, g_dtype == IGS_DTYPE_F16}, td = {dx, dx && dx_dtype == IGS_DTYPE_F16};
     float* part = (dw || db) ? (float*)align_ptr((const char*)scratch) : nullptr;
     const uint32_t T = ln_bwd_groups(N, C);
     LN_LAUNCH(ln_bwd_kernel, T, (uint32_t)N, C, tx, (size_t)xs, w, eps, tg, (size_t)gs, td, (size_t)dxs, part);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !part) return e;
-    hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((C + 63) / 64, 2), dim3(64 * LN_REDUCE_WAVES), 0, s, C, T, (const float*)part, dw, db);
-    return hipGetLastError();
+    return launch_param_reduce(s, C, T, part, nullptr, dw, db);      // (T <= LN_BWD_MAX_GROUPS: no wave walks more than 64 rows)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -363,11 +294,11 @@ geglu_fwd_kernel(uint32_t total, uint32_t dv, int D, const T* __restrict__ p, si
     const T* row = p + (size_t)n * ps + d;
     T* o = out + (size_t)n * D + d;
     if (V == 4) {
-        const float4 h = tok_ld4(row), g = tok_ld4(row + D);
-        tok_st4(o, make_float4(h.x * (g.x * geglu_cdf(g.x)), h.y * (g.y * geglu_cdf(g.y)), h.z * (g.z * geglu_cdf(g.z)), h.w * (g.w * geglu_cdf(g.w))));
+        const float4 h = ld4(row), g = ld4(row + D);
+        st4(o, make_float4(h.x * (g.x * geglu_cdf(g.x)), h.y * (g.y * geglu_cdf(g.y)), h.z * (g.z * geglu_cdf(g.z)), h.w * (g.w * geglu_cdf(g.w))));
     } else {
-        const float h = tok_ld(row), g = tok_ld(row + D);
-        tok_st(o, h * (g * geglu_cdf(g)));
+        const float h = ld(row), g = ld(row + D);
+        st(o, h * (g * geglu_cdf(g)));
     }
 }
 
@@ -390,19 +321,19 @@ geglu_bwd_kernel(uint32_t total, uint32_t dv, int D, const T* __restrict__ p, si
     const T* u = dout + (size_t)n * D + d;
     T* o = dp + (size_t)n * 2 * D + d;
     if (V == 4) {
-        const float4 h = tok_ld4(row), g = tok_ld4(row + D), uu = tok_ld4(u);
+        const float4 h = ld4(row), g = ld4(row + D), uu = ld4(u);
         float4 dh, dg;
         geglu_grad(h.x, g.x, uu.x, dh.x, dg.x);
         geglu_grad(h.y, g.y, uu.y, dh.y, dg.y);
         geglu_grad(h.z, g.z, uu.z, dh.z, dg.z);
         geglu_grad(h.w, g.w, uu.w, dh.w, dg.w);
-        tok_st4(o, dh);
-        tok_st4(o + D, dg);
+        st4(o, dh);
+        st4(o + D, dg);
     } else {
         float dh, dg;
-        geglu_grad(tok_ld(row), tok_ld(row + D), tok_ld(u), dh, dg);
-        tok_st(o, dh);
-        tok_st(o + D, dg);
+        geglu_grad(ld(row), ld(row + D), ld(u), dh, dg);
+        st(o, dh);
+        st(o + D, dg);
     }
 }
 
@@ -410,7 +341,7 @@ template <typename T>
 static hipError_t launch_geglu(hipStream_t s, long long N, int D, const T* p, long long ps, const T* dout, T* dst)
 {
     const size_t grid = 4 * sizeof(T);
-    const bool v4 = (D & 3) == 0 && (ps & 3) == 0 && tok_aligned(p, grid) && tok_aligned(dst, grid) && (!dout || tok_aligned(dout, grid));
+    const bool v4 = (D & 3) == 0 && (ps & 3) == 0 && ptr_aligned(p, grid) && ptr_aligned(dst, grid) && (!dout || ptr_aligned(dout, grid));
     const uint32_t dv = (uint32_t)(v4 ? D / 4 : D), total = (uint32_t)N * dv;
     const dim3 g((total + GEGLU_THREADS - 1) / GEGLU_THREADS), blk(GEGLU_THREADS);
     if (dout) {
@@ -427,17 +358,11 @@ static hipError_t launch_geglu(hipStream_t s, long long N, int D, const T* p, lo
 // the entry points (the contract is in include/igs_rast.h)
 // ---------------------------------------------------------------------------------------------------------------------------------
 // the bytes [lo, hi) that N rows of `len` elements at a row stride of `stride` elements span
-struct TokSpan { uintptr_t lo, hi; };
-static TokSpan tok_span(const void* p, long long N, long long len, long long stride, int dtype)
+static ByteSpan tok_span(const void* p, long long N, long long len, long long stride, int dtype)
 {
-    const size_t es = dtype == IGS_DTYPE_F16 ? 2 : 4;
-    TokSpan sp;
-    sp.lo = (uintptr_t)p;
-    sp.hi = sp.lo + ((size_t)(N - 1) * (size_t)stride + (size_t)len) * es;
-    return sp;
+    return byte_span(p, ((size_t)(N - 1) * (size_t)stride + (size_t)len) * dtype_bytes(dtype));
 }
-static bool tok_overlap(TokSpan a, TokSpan b) { return a.lo < b.hi && b.lo < a.hi; }
-static bool tok_misaligned(const void* p, int dtype) { return !tok_aligned(p, dtype == IGS_DTYPE_F16 ? 2 : 4); }
+static bool tok_misaligned(const void* p, int dtype) { return !ptr_aligned(p, dtype_bytes(dtype)); }
 
 static const char* ln_size_error(long long N, int C)
 {
@@ -446,7 +371,6 @@ static const char* ln_size_error(long long N, int C)
     return nullptr;
 }
 static bool tok_stride_bad(long long stride, long long len) { return stride < len || stride > IGS_TOKENS_MAX_STRIDE; }
-static bool ln_eps_bad(float eps) { return !(eps >= 0.f) || !(eps < 3.0e38f); }
 
 extern "C" int igs_layer_norm_fwd(void* stream, long long N, int C, int x_dtype, const void* x, long long xs, int res_dtype, const void* res,
                                   long long rs, const float* weight, const float* bias, float eps, int out_dtype, void* out, long long os)
@@ -456,20 +380,20 @@ extern "C" int igs_layer_norm_fwd(void* stream, long long N, int C, int x_dtype,
     if (const char* w = ln_size_error(N, C)) return fail_in(fn, w);
     if (tok_stride_bad(xs, C) || tok_stride_bad(os, C) || (res && tok_stride_bad(rs, C)))
         return fail_in(fn, "a row stride is below the row length C or above IGS_TOKENS_MAX_STRIDE");
-    if (ln_eps_bad(eps)) return fail_in(fn, "eps must be finite and >= 0");
+    if (!eps_ok(eps)) return fail_in(fn, "eps must be finite and >= 0");
     if ((weight == nullptr) != (bias == nullptr)) return fail_in(fn, "weight and bias go together (both or neither)");
     if (N == 0) return 0;
     if (!x || !out) return fail_in(fn, "NULL pointer");
-    if (tok_misaligned(x, x_dtype) || tok_misaligned(out, out_dtype) || (res && tok_misaligned(res, res_dtype)) || !tok_aligned(weight, 4) ||
-        !tok_aligned(bias, 4))
+    if (tok_misaligned(x, x_dtype) || tok_misaligned(out, out_dtype) || (res && tok_misaligned(res, res_dtype)) || !ptr_aligned(weight, 4) ||
+        !ptr_aligned(bias, 4))
         return fail_in(fn, "a pointer is not aligned to its element size");
-    const TokSpan sx = tok_span(x, N, C, xs, x_dtype), so = tok_span(out, N, C, os, out_dtype);
-    if (tok_overlap(sx, so)) return fail_in(fn, "out overlaps x (only out == res may alias)");
-    if (res && tok_overlap(tok_span(res, N, C, rs, res_dtype), so) && !(res == (const void*)out && rs == os && res_dtype == out_dtype))
+    const ByteSpan sx = tok_span(x, N, C, xs, x_dtype), so = tok_span(out, N, C, os, out_dtype);
+    if (spans_overlap(sx, so)) return fail_in(fn, "out overlaps x (only out == res may alias)");
+    if (res && spans_overlap(tok_span(res, N, C, rs, res_dtype), so) && !(res == (const void*)out && rs == os && res_dtype == out_dtype))
         return fail_in(fn, "out overlaps res without being res (only out == res with one dtype and one row stride may alias)");
     if (weight) {
-        const TokSpan sw = tok_span(weight, 1, C, C, IGS_DTYPE_F32), sb = tok_span(bias, 1, C, C, IGS_DTYPE_F32);
-        if (tok_overlap(sw, so) || tok_overlap(sb, so)) return fail_in(fn, "out overlaps weight or bias");
+        const ByteSpan sw = tok_span(weight, 1, C, C, IGS_DTYPE_F32), sb = tok_span(bias, 1, C, C, IGS_DTYPE_F32);
+        if (spans_overlap(sw, so) || spans_overlap(sb, so)) return fail_in(fn, "out overlaps weight or bias");
     }
     HIP_TRY(launch_ln_fwd((hipStream_t)stream, N, C, x_dtype, x, xs, res_dtype, res, rs, weight, bias, eps, out_dtype, out, os), "layer norm fwd launch");
     return 0;
@@ -490,22 +414,22 @@ extern "C" int igs_layer_norm_bwd(void* stream, long long N, int C, int x_dtype,
     if (const char* w = ln_size_error(N, C)) return fail_in(fn, w);
     if (tok_stride_bad(xs, C) || tok_stride_bad(gs, C) || (dx && tok_stride_bad(dxs, C)))
         return fail_in(fn, "a row stride is below the row length C or above IGS_TOKENS_MAX_STRIDE");
-    if (ln_eps_bad(eps)) return fail_in(fn, "eps must be finite and >= 0");
+    if (!eps_ok(eps)) return fail_in(fn, "eps must be finite and >= 0");
     if (N == 0 || (!dx && !dweight && !dbias)) return 0;
     if (!x || !dout) return fail_in(fn, "NULL pointer");
     if ((dweight || dbias) && !scratch) return fail_in(fn, "NULL pointer (scratch is required for d weight / d bias)");
-    if (tok_misaligned(x, x_dtype) || tok_misaligned(dout, dout_dtype) || (dx && tok_misaligned(dx, dx_dtype)) || !tok_aligned(weight, 4) ||
-        !tok_aligned(dweight, 4) || !tok_aligned(dbias, 4))
+    if (tok_misaligned(x, x_dtype) || tok_misaligned(dout, dout_dtype) || (dx && tok_misaligned(dx, dx_dtype)) || !ptr_aligned(weight, 4) ||
+        !ptr_aligned(dweight, 4) || !ptr_aligned(dbias, 4))
         return fail_in(fn, "a pointer is not aligned to its element size");
-    const TokSpan sx = tok_span(x, N, C, xs, x_dtype), sg = tok_span(dout, N, C, gs, dout_dtype);
-    const TokSpan outs[4] = {dx ? tok_span(dx, N, C, dxs, dx_dtype) : TokSpan{0, 0}, dweight ? tok_span(dweight, 1, C, C, IGS_DTYPE_F32) : TokSpan{0, 0},
-                             dbias ? tok_span(dbias, 1, C, C, IGS_DTYPE_F32) : TokSpan{0, 0},
-                             (dweight || dbias) ? TokSpan{(uintptr_t)scratch, (uintptr_t)scratch + igs_layer_norm_bwd_scratch_bytes(N, C)} : TokSpan{0, 0}};
+    const ByteSpan sx = tok_span(x, N, C, xs, x_dtype), sg = tok_span(dout, N, C, gs, dout_dtype);
+    const ByteSpan outs[4] = {dx ? tok_span(dx, N, C, dxs, dx_dtype) : ByteSpan{0, 0}, dweight ? tok_span(dweight, 1, C, C, IGS_DTYPE_F32) : ByteSpan{0, 0},
+                              dbias ? tok_span(dbias, 1, C, C, IGS_DTYPE_F32) : ByteSpan{0, 0},
+                              (dweight || dbias) ? byte_span(scratch, igs_layer_norm_bwd_scratch_bytes(N, C)) : ByteSpan{0, 0}};
     for (int i = 0; i < 4; i++) {
-        if (tok_overlap(outs[i], sx) || tok_overlap(outs[i], sg) || (weight && tok_overlap(outs[i], tok_span(weight, 1, C, C, IGS_DTYPE_F32))))
+        if (spans_overlap(outs[i], sx) || spans_overlap(outs[i], sg) || (weight && spans_overlap(outs[i], tok_span(weight, 1, C, C, IGS_DTYPE_F32))))
             return fail_in(fn, "an output overlaps x, dout or weight");
         for (int k = i + 1; k < 4; k++)
-            if (tok_overlap(outs[i], outs[k])) return fail_in(fn, "the outputs (dx, dweight, dbias, scratch) overlap one another");
+            if (spans_overlap(outs[i], outs[k])) return fail_in(fn, "the outputs (dx, dweight, dbias, scratch) overlap one another");
     }
     HIP_TRY(launch_ln_bwd((hipStream_t)stream, N, C, x_dtype, x, xs, weight, eps, dout_dtype, dout, gs, dx_dtype, dx, dxs, dweight, dbias, scratch),
             "layer norm bwd launch");
@@ -528,7 +452,7 @@ extern "C" int igs_geglu_fwd(void* stream, long long N, int D, int dtype, const 
     if (N == 0) return 0;
     if (!p || !out) return fail_in(fn, "NULL pointer");
     if (tok_misaligned(p, dtype) || tok_misaligned(out, dtype)) return fail_in(fn, "a pointer is not aligned to its element size");
-    if (tok_overlap(tok_span(p, N, 2LL * D, ps, dtype), tok_span(out, N, D, D, dtype))) return fail_in(fn, "out overlaps p");
+    if (spans_overlap(tok_span(p, N, 2LL * D, ps, dtype), tok_span(out, N, D, D, dtype))) return fail_in(fn, "out overlaps p");
     hipError_t e;
     if (dtype == IGS_DTYPE_F16) e = launch_geglu((hipStream_t)stream, N, D, (const _Float16*)p, ps, (const _Float16*)nullptr, (_Float16*)out);
     else e = launch_geglu((hipStream_t)stream, N, D, (const float*)p, ps, (const float*)nullptr, (float*)out);
@@ -544,8 +468,8 @@ extern "C" int igs_geglu_bwd(void* stream, long long N, int D, int dtype, const 
     if (N == 0) return 0;
     if (!p || !dout || !dp) return fail_in(fn, "NULL pointer");
     if (tok_misaligned(p, dtype) || tok_misaligned(dout, dtype) || tok_misaligned(dp, dtype)) return fail_in(fn, "a pointer is not aligned to its element size");
-    const TokSpan sd = tok_span(dp, N, 2LL * D, 2LL * D, dtype);
-    if (tok_overlap(tok_span(p, N, 2LL * D, ps, dtype), sd) || tok_overlap(tok_span(dout, N, D, D, dtype), sd)) return fail_in(fn, "dp overlaps p or dout");
+    const ByteSpan sd = tok_span(dp, N, 2LL * D, 2LL * D, dtype);
+    if (spans_overlap(tok_span(p, N, 2LL * D, ps, dtype), sd) || spans_overlap(tok_span(dout, N, D, D, dtype), sd)) return fail_in(fn, "dp overlaps p or dout");
     hipError_t e;
     if (dtype == IGS_DTYPE_F16) e = launch_geglu((hipStream_t)stream, N, D, (const _Float16*)p, ps, (const _Float16*)dout, (_Float16*)dp);
     else e = launch_geglu((hipStream_t)stream, N, D, (const float*)p, ps, (const float*)dout, (float*)dp);

@@ -233,11 +233,11 @@ wattn_fwd_kernel(WattnArgs a)
     attn_acc o[4] = {};
     float m = -INFINITY, l = 0.f;                             // the running max of the exp2-domain scores; this lane's share of the sum
     for (int k0 = 0; k0 < g.Lw; k0 += WATTN_ROWS) {
-        attn_barrier();
+        wg_barrier();
         sk.write_rows(kimg);
         sv.write_columns(vimg);
         if (blk.masked) rows.write_regions(kreg);
-        attn_barrier();
+        wg_barrier();
         if (k0 + WATTN_ROWS < g.Lw) {
             rows.find(g, blk, k0 + WATTN_ROWS);
             sk.load(kb, a.k.st, rows);
@@ -306,10 +306,10 @@ wattn_fwd_kernel(WattnArgs a)
         for (int gq = 0; gq < 4; gq++) {
             const int d = 32 * t + 8 * gq + 4 * h;
             if constexpr (C::HALF != 0) {
-                attn_h4 x;
+                h4_t x;
 #pragma unroll
                 for (int e = 0; e < 4; e++) x[e] = (_Float16)(o[t][4 * gq + e] / lt);
-                *(attn_h4*)(op + d) = x;
+                *(h4_t*)(op + d) = x;
             } else {
                 attn_f4 x;
 #pragma unroll
@@ -393,12 +393,12 @@ wattn_dkdv_kernel(WattnArgs a)
     side(0);
     attn_acc dk[2 * NB] = {}, dv[2 * NB] = {};
     for (int q0 = 0; q0 < g.Lw; q0 += WATTN_ROWS) {
-        attn_barrier();
+        wg_barrier();
         sq.write_rows(qimg);
         sg.write_rows(gimg);
         if constexpr (C::HALF != 0) { sq.write_transposed(qcol); sg.write_transposed(gcol); }
         if (threadIdx.x < WATTN_ROWS) { lse2[threadIdx.x] = nl; dlt[threadIdx.x] = nd; qreg[threadIdx.x] = nr; }
-        attn_barrier();
+        wg_barrier();
         if (q0 + WATTN_ROWS < g.Lw) {
             rows.find(g, blk, q0 + WATTN_ROWS);
             sq.load(qb, a.q.st, rows);
@@ -473,12 +473,12 @@ wattn_dq_kernel(WattnArgs a)
     sv.load(vb, a.v.st, rows);
     attn_acc dq[4] = {};
     for (int k0 = 0; k0 < g.Lw; k0 += WATTN_ROWS) {
-        attn_barrier();
+        wg_barrier();
         sk.write_rows(kimg);
         sv.write_rows(vimg);
         if constexpr (C::HALF != 0) sk.write_transposed(kcol);
         if (blk.masked) rows.write_regions(kreg);
-        attn_barrier();
+        wg_barrier();
         if (k0 + WATTN_ROWS < g.Lw) {
             rows.find(g, blk, k0 + WATTN_ROWS);
             sk.load(kb, a.k.st, rows);
@@ -538,7 +538,6 @@ static const char* wattn_out_error(int B, long long L, long long sb, long long s
     if ((L > 1 && st < WATTN_D) || (B > 1 && sb < WATTN_D)) return "output strides overlap (a stride below D on a dimension longer than 1)";
     return nullptr;
 }
-static bool wattn_aligned(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 static WattnView wattn_view(const void* p, long long sb, long long st) { WattnView t; t.p = (void*)p; t.sb = sb; t.st = st; return t; }
 static WattnGeom wattn_geom(int h, int w, int K, int shift)
 {
@@ -571,7 +570,7 @@ extern "C" int igs_window_attn_fwd(void* stream, int B, int h, int w, int K, int
     if (!(fabsf(scale) <= 3.0e38f)) return fail_in(fn, "scale must be finite");
     if (B == 0) return 0;
     if (!q || !k || !v || !out) return fail_in(fn, "NULL pointer");
-    if (!wattn_aligned(q) || !wattn_aligned(k) || !wattn_aligned(v) || !wattn_aligned(out)) return fail_in(fn, "base pointers must be 16-byte aligned");
+    if (!ptr_aligned(q, 16) || !ptr_aligned(k, 16) || !ptr_aligned(v, 16) || !ptr_aligned(out, 16)) return fail_in(fn, "base pointers must be 16-byte aligned");
     WattnArgs a = {};
     a.g = wattn_geom(h, w, K, shift);
     a.scale = scale; a.c = (float)((double)scale * 1.4426950408889634);
@@ -608,8 +607,8 @@ extern "C" int igs_window_attn_bwd(void* stream, int B, int h, int w, int K, int
     if (!(fabsf(scale) <= 3.0e38f)) return fail_in(fn, "scale must be finite");
     if (B == 0 || (!dq && !dk && !dv)) return 0;
     if (!q || !k || !v || !out || !lse || !dout || !scratch) return fail_in(fn, "NULL pointer");
-    if (!wattn_aligned(q) || !wattn_aligned(k) || !wattn_aligned(v) || !wattn_aligned(out) || !wattn_aligned(dout) || !wattn_aligned(dq) ||
-        !wattn_aligned(dk) || !wattn_aligned(dv))
+    if (!ptr_aligned(q, 16) || !ptr_aligned(k, 16) || !ptr_aligned(v, 16) || !ptr_aligned(out, 16) || !ptr_aligned(dout, 16) || !ptr_aligned(dq, 16) ||
+        !ptr_aligned(dk, 16) || !ptr_aligned(dv, 16))
         return fail_in(fn, "base pointers must be 16-byte aligned");
     WattnArgs a = {};
     a.g = wattn_geom(h, w, K, shift);

@@ -215,6 +215,45 @@ def test_modln_side_stream_empty_and_bitwise_backward():
     e.sum().backward()
 
 
+@pytest.mark.parametrize("H,W,T", [(9, 8, 3), (80, 80, 200), (512, 513, 8208)])
+def test_modln_parameter_gradients_are_the_partial_rows_added_in_the_documented_order(H, W, T):
+    """igs_modln_bwd through the C ABI, float32, N = 1, C = 4 (backward tiles of 32 pixels): rows 0 .. T - 1 of the scratch (from its
+    pointer rounded up to 256 bytes, [2][C] floats each) are the tiles' partial sums and the next 64 rows the staged group sums.  Round one
+    gives group g the g-th contiguous share of ceil(T / 64) rows, round two reduces the 64 staged rows; each as param_rows_sum states it.
+    The staged rows, d weight and d bias bit for bit.  T = 3: most groups empty; 200: group shares of 4, wave shares of 1; 8208: group
+    shares of 129, wave shares of 9 (the eight-load loop and its remainder)."""
+    import token_ops_restatement as TR
+    from igs_amd import _cabi
+    L, C, G = _cabi.lib(), 4, 64
+    lp = 5                                                               # the launcher's tile: the largest 2^lp <= 32 pixels within 64 KB of LDS
+    while lp > 2 and (2 * C * ((1 << lp) + 1) + 2 * 256 + 4 * (1 << lp)) * 4 > 65536:
+        lp -= 1
+    assert -(-H * W // (1 << lp)) == T
+    nbytes = L.igs_modln_bwd_scratch_bytes(1, C, H, W)
+    assert nbytes == -(-(T + G) * 2 * C * 4 // 256) * 256 + 512
+    x, mod, w, b, gout = _modln_case(1, C, H, W, seed=H + W)
+    out, mean, rstd = torch.empty_like(x), torch.empty(H * W, device=DEV), torch.empty(H * W, device=DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+    rc = L.igs_modln_fwd(stream, 1, C, H, W, 0, x.data_ptr(), C * H * W, H * W, W, 1, 0, mod.data_ptr(), w.data_ptr(), b.data_ptr(), EPS,
+                         out.data_ptr(), mean.data_ptr(), rstd.data_ptr())
+    assert rc == 0, _cabi.last_error()
+    scratch = torch.zeros(nbytes, dtype=torch.uint8, device=DEV)
+    dw, db = torch.full((C,), float("nan"), device=DEV), torch.full((C,), float("nan"), device=DEV)
+    rc = L.igs_modln_bwd(stream, 1, C, H, W, 0, x.data_ptr(), C * H * W, H * W, W, 1, 0, mod.data_ptr(), w.data_ptr(), b.data_ptr(), mean.data_ptr(),
+                         rstd.data_ptr(), gout.data_ptr(), None, None, dw.data_ptr(), db.data_ptr(), scratch.data_ptr())
+    assert rc == 0, _cabi.last_error()
+    torch.cuda.synchronize()
+    at = -scratch.data_ptr() % 256
+    rows = scratch[at:at + (T + G) * 2 * C * 4].view(torch.float32).view(T + G, 2 * C).cpu()
+    share = -(-T // G)
+    staged = torch.stack([TR.param_rows_sum(rows[min(g * share, T):min(g * share + share, T)]) for g in range(G)])
+    want = TR.param_rows_sum(staged)
+    print("%d x %d: T %d, max |dweight| %.3e" % (H, W, T, dw.abs().max().item()))
+    bits = lambda t: t.contiguous().view(torch.int32)                    # noqa: E731
+    assert torch.equal(bits(rows[T:]), bits(staged))
+    assert torch.equal(bits(dw.cpu()), bits(want[:C])) and torch.equal(bits(db.cpu()), bits(want[C:]))
+
+
 def _fixture():
     z = np.load(os.path.join(ROOT, "tests", "golden", "ref_condition3d.npz"))
     return {k: torch.from_numpy(z[k]) for k in z.files}

@@ -661,7 +661,7 @@ def test_fused_tile_kernel_on_dense_saturating_tiles(dev):
     """igs_refine_step's fused forward + backward tile kernel (blend_step.hip) where its forward ends EARLY: large splats, hundreds to
     thousands of instances per tile, every pixel saturated long before the list is through -- the regime of the dense diagnostic scene,
     in which round 3's first version faulted (a wave that missed the `every quad is finished` flag went on staging forward records
-    into LDS the others already used for the backward: blend_common.h, tile_barrier).  Against the unfused native step (separate
+    into LDS the others already used for the backward: elem_common.h, wg_barrier).  Against the unfused native step (separate
     kernels), several steps, LDS poisoned; the gradients through the moments of BOTH paths must agree."""
     from igs_amd.refine import GaussianParams, Refiner, render
     from igs_amd.scenes import perturbed_copy

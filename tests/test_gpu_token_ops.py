@@ -194,6 +194,31 @@ def test_every_optional_gradient_left_out_in_turn(C):
             assert a is None or torch.equal(a, c), want
 
 
+@pytest.mark.parametrize("N,C", [(67, 132), (4200, 132), (3, 12)])
+def test_parameter_gradients_are_the_partial_rows_added_in_the_documented_order(N, C):
+    """d weight / d bias bit for bit from the [T][2][C] partial rows that the backward leaves in its scratch (from the scratch pointer
+    rounded up to 256 bytes; T = min(ceil(N / rows per workgroup), 1024) with 16 rows per workgroup for C <= 128 and 4 above): 16 contiguous
+    shares of ceil(T / 16) rows, each added row by row, then the 16 sums added in order.  (67, 132): T = 17, shares of 2, waves 9 to 15
+    empty; (4200, 132): T = 1024, shares of 64, the eight-at-a-time loop; (3, 12): T = 1."""
+    x = TR.row_inputs(N, C, F32, DEV, seed=N + C)
+    g = torch.randn(N, C, generator=torch.Generator().manual_seed(N), dtype=F32).to(DEV)
+    w, _ = TR.affine_inputs(C, DEV, C)
+    rpg = 16 if C <= 128 else 4
+    T = min(-(-N // rpg), 1024)
+    nbytes = _lib().igs_layer_norm_bwd_scratch_bytes(N, C)
+    assert nbytes == -(-T * 2 * C * 4 // 256) * 256 + 256
+    scratch = torch.zeros(nbytes, dtype=torch.uint8, device=DEV)
+    dw, db = torch.full((C,), float("nan"), device=DEV), torch.full((C,), float("nan"), device=DEV)
+    _ok(_lib().igs_layer_norm_bwd(_stream(), N, C, 0, x.data_ptr(), C, w.data_ptr(), 1e-5, 0, g.data_ptr(), C, 0, None, C, dw.data_ptr(), db.data_ptr(),
+                                  scratch.data_ptr()))
+    torch.cuda.synchronize()
+    at = -scratch.data_ptr() % 256
+    part = scratch[at:at + T * 2 * C * 4].view(F32).view(T, 2 * C)
+    want = TR.param_rows_sum(part)
+    print("N %d C %d: T %d, max |dweight| %.3e" % (N, C, T, dw.abs().max().item()))
+    assert torch.equal(_bits(dw.cpu()), _bits(want[:C])) and torch.equal(_bits(db.cpu()), _bits(want[C:]))
+
+
 # ---------------------------------------------------------------- GEGLU through the C ABI
 # N, D, dtype, extra row stride, offset, scale
 GEGLU_CASES = [(1, 1, F32, 0, 0, 1.0), (5, 6, F32, 0, 0, 4.0), (67, 6, F16, 2, 1, 1.0), (5, 8, F32, 8, 0, 1.0), (67, 8, F16, 0, 0, 4.0), (67, 8, F32, 0, 1, 1.0),

@@ -8,8 +8,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_no_barrier_with_an_outstanding_lds_store_and_no_m0_hazard():
     """Every `s_barrier` of every kernel in libigs_rast.so: on no path into it may an LDS store be outstanding (round 3's GPU fault was a
-    bare s_barrier behind `wave_done[wid] = ...`; built with -DIGS_NO_RELEASE_WAIT the audit flags exactly that barrier in every
-    blend_step instance); every ds_write_addtid_b32 has at least one instruction between it and the last write of M0 (round 2's abort)."""
+    bare s_barrier behind `wave_done[wid] = ...`; built with -DIGS_NO_RELEASE_WAIT, which reaches every kernel that calls wg_barrier(), the
+    audit flags seven barriers: exactly that one in each of the six blend_step instances and one in blend_count_kernel, none in any other
+    kernel); every ds_write_addtid_b32 has at least one instruction between it and the last write of M0 (round 2's abort)."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from igs_amd import build
     build.build()

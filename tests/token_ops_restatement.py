@@ -150,6 +150,22 @@ ROW_MEANS = (0.0, 100.0, -1e3)
 ROW_STDS = (1.0, 1e-3, 30.0)
 
 
+def param_rows_sum(rows, waves=16):
+    """The float32 sum of [T, K] partial parameter rows in the documented order of the backward's reduction (igs_amd/csrc/param_reduce.h):
+    `waves` contiguous shares of ceil(T / waves) rows, each added row by row from 0.0f, then the share sums added in share order from
+    0.0f.  On the CPU, one float32 rounding per addition."""
+    rows = rows.detach().cpu().float()
+    T, K = rows.shape
+    share = -(-T // waves)
+    total = torch.zeros(K)
+    for k in range(waves):
+        s = torch.zeros(K)
+        for t in range(min(k * share, T), min(k * share + share, T)):
+            s = s + rows[t]
+        total = total + s
+    return total
+
+
 def row_inputs(N, C, dtype, device, seed, constant_row=None):
     """[N, C]: row n has the pair number q = (seed + 4 n) mod 9 of (mean, std) = (ROW_MEANS[q % 3], ROW_STDS[q // 3]), so three rows take
     three means and three stds and nine take every pair.  Row `constant_row` holds one value (one that no power-of-two count sums exactly)."""
