@@ -156,6 +156,11 @@ SIGNATURES = {
     "igs_layer_norm_bwd": (_i, [_vp, _ll, _i] + [_i, _vp, _ll] + [_vp, _f] + [_i, _vp, _ll] * 2 + [_vp] * 3),
     "igs_geglu_fwd": (_i, [_vp, _ll, _i, _i, _vp, _ll, _vp]),
     "igs_geglu_bwd": (_i, [_vp, _ll, _i, _i, _vp, _ll, _vp, _vp]),
+    # gnorm.hip
+    "igs_group_norm_tokens_fwd": (_i, [_vp, _i, _i, _i, _ll] + [_i, _vp, _ll, _ll] + [_vp, _vp, _f] + [_i, _vp, _ll] + [_vp]),
+    "igs_group_norm_tokens_bwd_scratch_bytes": (_sz, [_i, _i, _i, _ll]),
+    "igs_group_norm_tokens_bwd": (_i, [_vp, _i, _i, _i, _ll] + [_i, _vp, _ll, _ll] + [_vp, _vp] + [_i, _vp, _ll] + [_i, _vp, _ll, _ll] + [_vp] * 3),
+    "igs_tokens_add_residual": (_i, [_vp, _i, _i, _ll] + [_i, _vp, _ll] + [_i, _vp, _ll, _ll] + [_i, _vp, _ll]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -1,5 +1,6 @@
-// elem_common.h -- the small device helpers that every kernel file shares: the workgroup barrier, the float32 / float16 element access,
-// the lane-sum butterfly and the tail of the corrected two-pass statistics.  Device only; nothing of the rasterizer is included.
+// elem_common.h -- the small device helpers that every kernel file shares: the workgroup barrier, the float32 / float16 element access
+// (typed, or by a runtime dtype code), the lane-sum butterfly and the tail of the corrected two-pass statistics.  Device only; nothing
+// of the rasterizer is included.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -42,6 +43,13 @@ __device__ __forceinline__ void st4(_Float16* p, float4 v)
     h.x = (_Float16)v.x; h.y = (_Float16)v.y; h.z = (_Float16)v.z; h.w = (_Float16)v.w;
     *(h4_t*)p = h;
 }
+
+// an operand whose dtype is a runtime code (half != 0: float16), addressed in elements
+struct TokPtr { const void* p; int half; };
+__device__ __forceinline__ float ld(TokPtr t, size_t i) { return t.half ? ld((const _Float16*)t.p + i) : ld((const float*)t.p + i); }
+__device__ __forceinline__ float4 ld4(TokPtr t, size_t i) { return t.half ? ld4((const _Float16*)t.p + i) : ld4((const float*)t.p + i); }
+__device__ __forceinline__ void st(TokPtr t, size_t i, float v) { if (t.half) st((_Float16*)t.p + i, v); else st((float*)t.p + i, v); }
+__device__ __forceinline__ void st4(TokPtr t, size_t i, float4 v) { if (t.half) st4((_Float16*)t.p + i, v); else st4((float*)t.p + i, v); }
 
 // The sums of N values over every group of LANES neighbouring lanes of a wave (a power of two), the same bits in every lane of the
 // group: an xor butterfly, largest offset first, whose two operands commute.  A fixed order: the same result on every run.

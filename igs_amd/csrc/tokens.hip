@@ -27,13 +27,6 @@
 #define LN_BWD_MAX_GROUPS 1024                                 // workgroups (= partial parameter rows) of one backward
 #define GEGLU_THREADS 256
 
-// an operand whose dtype is a runtime code (half != 0: float16), addressed in elements
-struct TokPtr { const void* p; int half; };
-__device__ __forceinline__ float ld(TokPtr t, size_t i) { return t.half ? ld((const _Float16*)t.p + i) : ld((const float*)t.p + i); }
-__device__ __forceinline__ float4 ld4(TokPtr t, size_t i) { return t.half ? ld4((const _Float16*)t.p + i) : ld4((const float*)t.p + i); }
-__device__ __forceinline__ void st(TokPtr t, size_t i, float v) { if (t.half) st((_Float16*)t.p + i, v); else st((float*)t.p + i, v); }
-__device__ __forceinline__ void st4(TokPtr t, size_t i, float4 v) { if (t.half) st4((_Float16*)t.p + i, v); else st4((float*)t.p + i, v); }
-
 // ---------------------------------------------------------------------------------------------------------------------------------
 // (1) LayerNorm
 // ---------------------------------------------------------------------------------------------------------------------------------

@@ -17,6 +17,7 @@
 //   window attention    wattn.hip               _window.window_attn_fwd / _bwd on [B, h w, 128] views of any acceptable strides
 //   encoder norms       inorm.hip               _encoder.instance_norm_fwd, _encoder.position_add on contiguous [N, C, H, W] tensors
 //   token ops           tokens.hip              _tokens.layer_norm_fwd / _bwd, _tokens.geglu_fwd / _bwd on [N, C] rows with a row stride
+//   transformer ends    gnorm.hip               _gnorm.group_norm_tokens_fwd / _bwd, _gnorm.tokens_add_residual: [B, C, A] in, [B, A, C] out
 //   deform              motion.hip              motion_deform_fwd / _bwd
 //   Adam                refine_ops.hip          adam_step_multi
 //   losses              refine_ops, loss_ops    l1_mean; ssim_mean
@@ -975,6 +976,110 @@ Tensor geglu_bwd(const Tensor& proj, const Tensor& grad_out)
     return dp;
 }
 
+// ---- the two ends of Transformer1D: GroupNorm to token-major, token-major plus residual (gnorm.hip; contract in include/igs_rast.h) ----
+// [B, C, A] channel-major with stride 1 on A, a channel stride of at least A and a batch stride of at least a batch's extent, and
+// [B, A, C] token-major rows at one row stride through the batches (the Python layer copies what is not)
+struct ChannelMajor { int dt; int64_t bs, cs; };
+ChannelMajor channel_major_check(const char* fn, const Tensor& t, const char* name)
+{
+    ChannelMajor v;
+    v.dt = dtype_code(t, fn, name);
+    if (t.dim() != 3) throw RasterizerError(std::string(fn) + ": " + name + " must have shape [B, C, A] (got " + c10::str(t.sizes()) + ")");
+    const int64_t C = t.size(1), A = t.size(2);
+    v.cs = C > 1 ? t.stride(1) : A;
+    v.bs = t.size(0) > 1 ? t.stride(0) : (C - 1) * v.cs + A;
+    if ((A > 1 && t.stride(2) != 1) || v.cs < A || v.bs < (C - 1) * v.cs + A)
+        throw RasterizerError(std::string(fn) + ": " + name + " must have stride 1 on A, a channel stride of at least A and a batch stride of at least a batch's extent");
+    return v;
+}
+struct TokenMajor { int dt; int64_t rs; };
+TokenMajor token_major_check(const char* fn, const Tensor& t, const char* name)
+{
+    TokenMajor v;
+    v.dt = dtype_code(t, fn, name);
+    if (t.dim() != 3) throw RasterizerError(std::string(fn) + ": " + name + " must have shape [B, A, C] (got " + c10::str(t.sizes()) + ")");
+    const int64_t A = t.size(1), C = t.size(2);
+    v.rs = A > 1 ? t.stride(1) : C;
+    if ((C > 1 && t.stride(2) != 1) || v.rs < C || (t.size(0) > 1 && t.stride(0) != A * v.rs))
+        throw RasterizerError(std::string(fn) + ": " + name + " must be rows with stride 1 inside a row and one row stride of at least the row length through the batches");
+    return v;
+}
+void group_norm_sizes_check(const char* fn, int64_t B, int64_t C, int64_t G, int64_t A)
+{
+    if (C < 1 || C > IGS_GN_MAX_C || G < 1 || C % G != 0 || A < 1 || (C / G) * A > IGS_GN_MAX_GROUP_ELEMS || B * A > IGS_GN_MAX_TOKENS)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (1 <= C <= " + std::to_string(IGS_GN_MAX_C) + ", G >= 1 dividing C, A >= 1, (C / G) * A <= 2^30, B * A <= 2^24)");
+}
+// (out [B, A, C] contiguous, float16 when out_half, else float32; stats [B, G, 2] float32): GroupNorm(x) * weight + bias, written token-major
+std::tuple<Tensor, Tensor> group_norm_tokens_fwd(const Tensor& x, int64_t num_groups, const OptTensor& weight, const OptTensor& bias, double eps, bool out_half)
+{
+    const char* fn = "group_norm_tokens_fwd";
+    const ChannelMajor xv = channel_major_check(fn, x, "x");
+    const int64_t B = x.size(0), C = x.size(1), A = x.size(2);
+    token_param_check(fn, weight, "weight", C);
+    token_param_check(fn, bias, "bias", C);
+    if (weight.has_value() != bias.has_value()) throw RasterizerError(std::string(fn) + ": weight and bias go together (both or neither)");
+    group_norm_sizes_check(fn, B, C, num_groups, A);
+    const GpuCall c(x, fn, "x");
+    if (weight) same_device(x, fn, {{*weight, "weight"}, {*bias, "bias"}});
+    Tensor out = at::empty({B, A, C}, x.options().dtype(out_half ? at::kHalf : at::kFloat));
+    Tensor stats = at::empty({B, num_groups, 2}, x.options().dtype(at::kFloat));
+    if (B == 0) return {out, stats};
+    OptTensor wc, bc;
+    if (weight) { wc = weight->contiguous(); bc = bias->contiguous(); }
+    check(igs_group_norm_tokens_fwd(c.stream(), (int)B, (int)C, (int)num_groups, A, xv.dt, x.data_ptr(), xv.bs, xv.cs, ptr_or_null<float>(wc), ptr_or_null<float>(bc),
+                                    (float)eps, out_half ? IGS_DTYPE_F16 : IGS_DTYPE_F32, out.data_ptr(), C, stats.data_ptr<float>()),
+          "igs_group_norm_tokens_fwd");
+    return {out, stats};
+}
+// (d x [B, C, A] contiguous in x's dtype, d weight, d bias [C] float32), each None unless wanted
+std::tuple<OptTensor, OptTensor, OptTensor> group_norm_tokens_bwd(const Tensor& x, int64_t num_groups, const OptTensor& weight, const Tensor& stats,
+                                                                  const Tensor& grad_out, bool want_x, bool want_weight, bool want_bias)
+{
+    const char* fn = "group_norm_tokens_bwd";
+    const ChannelMajor xv = channel_major_check(fn, x, "x");
+    const TokenMajor gv = token_major_check(fn, grad_out, "grad_out");
+    const int64_t B = x.size(0), C = x.size(1), A = x.size(2);
+    token_param_check(fn, weight, "weight", C);
+    group_norm_sizes_check(fn, B, C, num_groups, A);
+    expect(stats, fn, "stats", at::kFloat, {B, num_groups, 2});
+    if (grad_out.size(0) != B || grad_out.size(1) != A || grad_out.size(2) != C)
+        throw RasterizerError(std::string(fn) + ": grad_out has shape " + c10::str(grad_out.sizes()) + ", expected " + c10::str(at::IntArrayRef({B, A, C})));
+    const GpuCall c(x, fn, "x", {{grad_out, "grad_out"}, {stats, "stats"}});
+    if (weight) same_device(x, fn, {{*weight, "weight"}});
+    OptTensor dx, dw, db, wc;
+    const auto fo = x.options().dtype(at::kFloat);
+    if (want_x) dx = at::empty({B, C, A}, x.options());
+    if (want_weight) dw = B == 0 ? at::zeros({C}, fo) : at::empty({C}, fo);
+    if (want_bias) db = B == 0 ? at::zeros({C}, fo) : at::empty({C}, fo);
+    if (B == 0 || !(want_x || want_weight || want_bias)) return {dx, dw, db};
+    const Tensor scratch = at::empty({(int64_t)igs_group_norm_tokens_bwd_scratch_bytes((int)B, (int)C, (int)num_groups, A)}, x.options().dtype(at::kByte));
+    const Tensor sc = stats.contiguous();
+    if (weight) wc = weight->contiguous();
+    check(igs_group_norm_tokens_bwd(c.stream(), (int)B, (int)C, (int)num_groups, A, xv.dt, x.data_ptr(), xv.bs, xv.cs, ptr_or_null<float>(wc), sc.data_ptr<float>(),
+                                    gv.dt, grad_out.data_ptr(), gv.rs, xv.dt, ptr_or_null(dx), C * A, A, ptr_or_null<float>(dw), ptr_or_null<float>(db),
+                                    scratch.data_ptr()),
+          "igs_group_norm_tokens_bwd");
+    return {dx, dw, db};
+}
+// out [B, A, C] contiguous, float16 when out_half, else float32: tokens + residual read channel-major
+Tensor tokens_add_residual(const Tensor& tokens, const Tensor& residual, bool out_half)
+{
+    const char* fn = "tokens_add_residual";
+    const TokenMajor tv = token_major_check(fn, tokens, "tokens");
+    const ChannelMajor rv = channel_major_check(fn, residual, "residual");
+    const int64_t B = tokens.size(0), A = tokens.size(1), C = tokens.size(2);
+    if (residual.size(0) != B || residual.size(1) != C || residual.size(2) != A)
+        throw RasterizerError(std::string(fn) + ": residual has shape " + c10::str(residual.sizes()) + ", expected " + c10::str(at::IntArrayRef({B, C, A})));
+    group_norm_sizes_check(fn, B, C, 1, A);
+    const GpuCall c(tokens, fn, "tokens", {{residual, "residual"}});
+    Tensor out = at::empty({B, A, C}, tokens.options().dtype(out_half ? at::kHalf : at::kFloat));
+    if (B == 0) return out;
+    check(igs_tokens_add_residual(c.stream(), (int)B, (int)C, A, tv.dt, tokens.data_ptr(), tv.rs, rv.dt, residual.data_ptr(), rv.bs, rv.cs,
+                                  out_half ? IGS_DTYPE_F16 : IGS_DTYPE_F32, out.data_ptr(), C),
+          "igs_tokens_add_residual");
+    return out;
+}
+
 // ---- the Gaussian deform (motion.hip) ----
 void deform_checks(const char* fn, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot, int* dt)
 {
@@ -1244,6 +1349,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
               "want_bias"_a = true);
     def_nogil(tk, "geglu_fwd", &geglu_fwd, "proj"_a);
     def_nogil(tk, "geglu_bwd", &geglu_bwd, "proj"_a, "grad_out"_a);
+    // ... and the two ends of Transformer1D
+    py::module_ gn = m.def_submodule("_gnorm", "GroupNorm to token-major and token-major plus residual: the ends of Transformer1D (gnorm.hip)");
+    def_nogil(gn, "group_norm_tokens_fwd", &group_norm_tokens_fwd, "x"_a, "num_groups"_a, "weight"_a = none, "bias"_a = none, "eps"_a = 1e-5, "out_half"_a = false);
+    def_nogil(gn, "group_norm_tokens_bwd", &group_norm_tokens_bwd, "x"_a, "num_groups"_a, "weight"_a, "stats"_a, "grad_out"_a, "want_x"_a = true,
+              "want_weight"_a = true, "want_bias"_a = true);
+    def_nogil(gn, "tokens_add_residual", &tokens_add_residual, "tokens"_a, "residual"_a, "out_half"_a = false);
     def_nogil(m, "motion_deform_fwd", &motion_deform_fwd, "xyz"_a, "rotation"_a, "mask"_a, "res_xyz"_a, "res_rotation"_a);
     def_nogil(m, "motion_deform_bwd", &motion_deform_bwd, "rotation"_a, "mask"_a, "res_xyz"_a, "res_rotation"_a, "grad_xyz"_a, "grad_rotation"_a,
               "want_xyz"_a = true, "want_rotation"_a = true, "want_res_xyz"_a = true, "want_res_rotation"_a = true);

@@ -1,5 +1,5 @@
 """The per-token work of AGM-Net's two transformers, up to their GEMMs, on the MI355X-native library (igs_amd/csrc/tokens.hip,
-include/igs_rast.h).
+igs_amd/csrc/gnorm.hip, include/igs_rast.h).
 
 GridEncoder.conv is a Transformer1D of 4 BasicTransformerBlocks (igs/models/transformers.py:290-397, configs/train.yaml:168-178; dim 512,
 8192 anchors per example): each runs two nn.LayerNorm(512) and a GEGLU feed-forward (transformers.py:482-506) whose chunk / gelu / multiply
@@ -12,6 +12,12 @@ norm2, then `source + message`, and a three-launch `is_self_attn` test whose res
                                                                         writes both halves of d proj in one launch
     use_native_block_ops(grid_encoder)                                  binds norm1, norm3 and ff.net[0] of every BasicTransformerBlock
     use_native_transformer_layers(feature_transformer)                  binds the forward of every unimatch TransformerLayer
+    group_norm_tokens(x, num_groups, weight, bias, eps)                 F.group_norm over [B, C, A] written token-major [B, A, C]: the
+                                                                        statistics, then one tile-transposing launch
+    add_residual_tokens(tokens, residual)                               tokens [B, A, C] + residual [B, C, A], one launch; a [B, C, A]-shaped
+                                                                        view of a token-major buffer
+    use_native_transformer_ends(grid_encoder)                           binds the forward of every Transformer1D: the two above around
+                                                                        proj_in, the blocks and proj_out (transformers.py:860-908)
 
 Both have autograd (Transformer1D and FeatureTransformerMy are trained); the LayerNorm saves nothing but x and recomputes the row
 statistics in its backward, the GEGLU saves nothing but proj.  Both backwards are deterministic (no float atomics).  They compose with
@@ -25,7 +31,16 @@ in both dtypes (0.79 x float32, 0.88 x float16), level for the float16 tail at [
 [65536, 128].  A whole block gains 2-5 %, a whole layer 1-5 %, within the spread of the measurement.
 
 There is no CPU and no PyTorch fallback: CPU tensors raise RuntimeError, bfloat16 / float64 raise NotImplementedError, wrong shapes raise
-ValueError.  Not provided: Transformer1D's GroupNorm and its two transposes; the GELU inside the unimatch MLP (a single eager kernel
+ValueError.
+
+The ends of Transformer1D: the GroupNorm keeps its [B, G, 2] statistics for a deterministic backward (per-tile
+partial sums added in tile order); the residual add's backward launches nothing.  The bound Transformer1D returns the reference's shape,
+dtype and values as a permuted view of a token-major buffer, so GridEncoder.forward's own permute(0, 2, 1) yields the contiguous
+[B, A, C] that interpolate_anchor_features reads in place.  The work is launch-bound at the shipped sizes: no speed-up is claimed beyond
+the figures of section 20.
+
+Not provided: norm types other than nn.GroupNorm with affine parameters at the ends of Transformer1D, gradient checkpointing and 2-D
+attention masks there, fusing proj_in / proj_out; the GELU inside the unimatch MLP (a single eager kernel
 already); splitting the MLP's first weight to avoid the cat (it changes the GEMM's summation order); bfloat16; fusing any GEMM; the ada
 norms, cross-attention (norm2 / attn2) and the other feed-forward activations of BasicTransformerBlock; attn_type other than 'swin' and
 nhead > 1 of TransformerLayer.
@@ -41,6 +56,9 @@ from ._cabi import ext as _ext
 DTYPES = (torch.float32, torch.float16)
 LN_MAX_C = 1024                                                    # IGS_LN_MAX_C (include/igs_rast.h)
 GEGLU_MAX_D = 8192                                                 # IGS_GEGLU_MAX_D
+GN_MAX_C = 1024                                                    # IGS_GN_MAX_C
+GN_MAX_TOKENS = 1 << 24                                            # IGS_GN_MAX_TOKENS: B * A
+GN_MAX_GROUP_ELEMS = 1 << 30                                       # IGS_GN_MAX_GROUP_ELEMS: (C / G) * A
 
 # The attributes of the reference's BasicTransformerBlock, FeedForward and GEGLU that the installer touches, as igs/models/transformers.py
 # names them (the classes come from diffusers, which is not part of this stack)
@@ -52,6 +70,8 @@ GELU_ONLY_ATTRS = ("approximate",)                                 # what GELU h
 LAYER_Q, LAYER_K, LAYER_V, LAYER_MERGE, LAYER_NORM1, LAYER_NO_FFN, LAYER_NHEAD = "q_proj", "k_proj", "v_proj", "merge", "norm1", "no_ffn", "nhead"
 LAYER_MLP, LAYER_NORM2 = "mlp", "norm2"
 ATTN_SPLIT, ATTN_FULL = "single_head_split_window_attention", "single_head_full_attention"
+# ... and of Transformer1D (igs/models/transformers.py:700-784)
+T1D_NORM, T1D_PROJ_IN, T1D_BLOCKS, T1D_PROJ_OUT, T1D_CHECKPOINTING = "norm", "proj_in", "transformer_blocks", "proj_out", "gradient_checkpointing"
 
 
 def _rows(t):
@@ -292,3 +312,167 @@ def use_native_transformer_layers(module):
     for m in layers:
         m.forward = types.MethodType(_layer_forward, m)
     return len(layers)
+
+
+# ---------------------------------------------------------------- the two ends of Transformer1D
+def _channel_major(t):
+    """t [B, C, A] as the kernels read it: stride 1 on A, a channel stride of at least A and a batch stride of at least a batch's extent
+    (slices of a wider buffer included); one copy otherwise."""
+    B, C, A = t.shape
+    cs = t.stride(1) if C > 1 else A
+    if (A == 1 or t.stride(2) == 1) and cs >= A and (B == 1 or t.stride(0) >= (C - 1) * cs + A):
+        return t
+    return t.contiguous()
+
+
+def _token_major(t):
+    """t [B, A, C] as rows with stride 1 on C and one row stride through the batches; one copy otherwise."""
+    B, A, C = t.shape
+    rs = t.stride(1) if A > 1 else C
+    if (C == 1 or t.stride(2) == 1) and rs >= C and (B == 1 or t.stride(0) == A * rs):
+        return t
+    return t.contiguous()
+
+
+def _ends_size_check(fn, B, C, G, A):
+    if C < 1 or A < 1:
+        raise ValueError(f"{fn}: C and A must be at least 1 (got C = {C}, A = {A})")
+    if C > GN_MAX_C:
+        raise ValueError(f"{fn}: C = {C} is above the supported {GN_MAX_C}")
+    if G < 1 or C % G:
+        raise ValueError(f"{fn}: num_groups = {G} must be at least 1 and divide C = {C}")
+    if B * A > GN_MAX_TOKENS or (C // G) * A > GN_MAX_GROUP_ELEMS:
+        raise ValueError(f"{fn}: B * A = {B * A} is above {GN_MAX_TOKENS} or (C / G) * A = {(C // G) * A} above {GN_MAX_GROUP_ELEMS}")
+
+
+class _GroupNormTokens(torch.autograd.Function):
+    """x: [B, C, A] channel-major; weight, bias: [C] float32 or None."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, num_groups, eps, out_half):
+        out, stats = _ext()._gnorm.group_norm_tokens_fwd(x, num_groups, weight, bias, eps, out_half)
+        ctx.save_for_backward(x, weight, stats)                    # x itself (no copy), the [B, G, 2] statistics
+        ctx.num_groups = num_groups
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, stats = ctx.saved_tensors
+        nx, nw, nb = ctx.needs_input_grad[:3]
+        dx = dw = db = None
+        if nx or nw or nb:
+            dx, dw, db = _ext()._gnorm.group_norm_tokens_bwd(x, ctx.num_groups, weight, stats, _token_major(g), nx, nw and weight is not None,
+                                                             nb and weight is not None)
+        return dx, dw, db, None, None, None
+
+
+def group_norm_tokens(x, num_groups, weight=None, bias=None, eps=1e-5, out_dtype=None):
+    """F.group_norm(x, num_groups, weight, bias, eps).permute(0, 2, 1) as a contiguous [B, A, C] tensor: one launch for the statistics of
+    every (example, group), one that reads x along the tokens, normalises, and writes along the channels through an LDS tile (gnorm.hip).
+    x: [B, C, A] float32 or float16 on a GPU, C <= 1024; read in place when A has stride 1 (slices of a wider buffer included), copied once
+    otherwise.  weight and bias: [C], both or neither (float16 parameters are widened to float32).  out_dtype (float32 or float16) defaults
+    to x.dtype.  Arithmetic is float32 with the variance from centred values; a constant group gives exactly bias, a group with a NaN or
+    an infinity comes out all NaN.  Autograd reaches x, weight and bias; x, weight and the [B, G, 2] statistics are saved, and the
+    backward is deterministic.  Under no_grad only the statistics are allocated besides the result."""
+    fn = "group_norm_tokens"
+    if x.dim() != 3:
+        raise ValueError(f"{fn}: x must be [B, C, A] (got {list(x.shape)})")
+    B, C, A = x.shape
+    _ends_size_check(fn, B, C, int(num_groups), A)
+    if (weight is None) != (bias is None):
+        raise ValueError(f"{fn}: weight and bias go together (both or neither)")
+    named = [(x, "x")]
+    if weight is not None:
+        for p, name in ((weight, "weight"), (bias, "bias")):
+            if tuple(p.shape) != (C,):
+                raise ValueError(f"{fn}: {name} has shape {list(p.shape)}, expected {[C]}")
+            named.append((p, name))
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if out_dtype not in DTYPES:
+        raise NotImplementedError(f"{fn}: out_dtype must be float32 or float16 (got {out_dtype})")
+    _refuse(fn, named)
+    if weight is not None:
+        weight, bias = weight.float(), bias.float()
+    xc = _channel_major(x)
+    half = out_dtype == torch.float16
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (xc, weight, bias)):
+        return _GroupNormTokens.apply(xc, weight, bias, int(num_groups), float(eps), half)
+    return _ext()._gnorm.group_norm_tokens_fwd(xc, int(num_groups), weight, bias, float(eps), half)[0]
+
+
+class _AddResidualTokens(torch.autograd.Function):
+    """tokens [B, A, C] + residual [B, C, A] -> the [B, C, A]-shaped view of a token-major buffer.  The backward launches nothing."""
+
+    @staticmethod
+    def forward(ctx, tokens, residual, out_half):
+        ctx.dtypes = (tokens.dtype, residual.dtype)
+        return _ext()._gnorm.tokens_add_residual(tokens, residual, out_half).permute(0, 2, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        nt, nr = ctx.needs_input_grad[:2]
+        return (g.permute(0, 2, 1).to(ctx.dtypes[0]) if nt else None), (g.to(ctx.dtypes[1]) if nr else None), None
+
+
+def add_residual_tokens(tokens, residual):
+    """tokens.permute(0, 2, 1) + residual for tokens [B, A, C] and residual [B, C, A] (float32 or float16 each, the result in their
+    promoted dtype), as one launch that reads both once and writes a contiguous token-major buffer (gnorm.hip).  Returns that buffer's
+    [B, C, A]-shaped permuted view: out.permute(0, 2, 1) is contiguous [B, A, C].  Both are read in place where their strides allow
+    (rows with stride 1 on C; stride 1 on A), copied once otherwise.  Autograd reaches both; the backward launches nothing: d residual is
+    the upstream gradient, d tokens its permuted view."""
+    fn = "add_residual_tokens"
+    if tokens.dim() != 3 or residual.dim() != 3:
+        raise ValueError(f"{fn}: tokens must be [B, A, C] and residual [B, C, A] (got {list(tokens.shape)} and {list(residual.shape)})")
+    B, A, C = tokens.shape
+    if tuple(residual.shape) != (B, C, A):
+        raise ValueError(f"{fn}: residual has shape {list(residual.shape)}, expected {[B, C, A]}")
+    _ends_size_check(fn, B, C, 1, A)
+    _refuse(fn, [(tokens, "tokens"), (residual, "residual")])
+    half = torch.promote_types(tokens.dtype, residual.dtype) == torch.float16
+    tm, cm = _token_major(tokens), _channel_major(residual)
+    if torch.is_grad_enabled() and (tm.requires_grad or cm.requires_grad):
+        return _AddResidualTokens.apply(tm, cm, half)
+    return _ext()._gnorm.tokens_add_residual(tm, cm, half).permute(0, 2, 1)
+
+
+def _ends_forward(self, hidden_states, encoder_hidden_states=None, timestep=None, modulation_cond=None, class_labels=None,
+                  cross_attention_kwargs=None, attention_mask=None, encoder_attention_mask=None):
+    """Transformer1D.forward (igs/models/transformers.py:786-908): the GroupNorm written token-major, proj_in, the blocks called as the
+    reference calls them, proj_out, and the residual add written token-major.  The result is a [B, C, A]-shaped view of that buffer."""
+    fn = "Transformer1D"
+    for name, mask in (("attention_mask", attention_mask), ("encoder_attention_mask", encoder_attention_mask)):
+        if mask is not None and mask.ndim == 2:
+            raise NotImplementedError(f"{fn}: a 2-D {name} (a keep / discard mask) is not provided: pass the additive bias [batch, 1, key_tokens]")
+    norm = getattr(self, T1D_NORM)
+    tokens = group_norm_tokens(hidden_states, norm.num_groups, norm.weight, norm.bias, norm.eps, out_dtype=_autocast_out_dtype(None))
+    tokens = getattr(self, T1D_PROJ_IN)(tokens)
+    for block in getattr(self, T1D_BLOCKS):
+        tokens = block(tokens, attention_mask=attention_mask, encoder_hidden_states=encoder_hidden_states,
+                       encoder_attention_mask=encoder_attention_mask, timestep=timestep, modulation_cond=modulation_cond,
+                       cross_attention_kwargs=cross_attention_kwargs, class_labels=class_labels)
+    return add_residual_tokens(getattr(self, T1D_PROJ_OUT)(tokens), hidden_states)
+
+
+def _is_transformer1d(m):
+    return all(hasattr(m, a) for a in (T1D_NORM, T1D_PROJ_IN, T1D_BLOCKS, T1D_PROJ_OUT))
+
+
+def use_native_transformer_ends(module):
+    """Binds a forward on every Transformer1D under `module`, found by norm, proj_in, transformer_blocks and proj_out: group_norm_tokens,
+    proj_in, the blocks, proj_out, add_residual_tokens; returns how many (1 for the shipped GridEncoder).  state_dict() keys and the
+    classes are untouched; composes with use_native_block_ops and use_native_attention.  The result has the reference's shape, dtype and
+    values but is a permuted view of a token-major buffer (add .contiguous() for the reference's layout).  Under float16 autocast the
+    norm answers in float32, as eager PyTorch does.  Raises NotImplementedError, before anything is changed, for a norm that is not
+    nn.GroupNorm with affine parameters and for gradient_checkpointing; a 2-D attention_mask or encoder_attention_mask raises at the
+    call."""
+    fn = "use_native_transformer_ends"
+    found = [m for m in module.modules() if _is_transformer1d(m)]
+    for m in found:
+        norm = getattr(m, T1D_NORM)
+        if not isinstance(norm, nn.GroupNorm) or norm.weight is None or norm.bias is None:
+            raise NotImplementedError(f"{fn}: norm must be nn.GroupNorm with affine parameters (got {norm})")
+        if getattr(m, T1D_CHECKPOINTING, False):
+            raise NotImplementedError(f"{fn}: gradient_checkpointing is set: checkpointed blocks are not provided")
+    for m in found:
+        m.forward = types.MethodType(_ends_forward, m)
+    return len(found)

@@ -845,6 +845,45 @@ int igs_layer_norm_bwd(void* stream, long long N, int C, int x_dtype, const void
 int igs_geglu_fwd(void* stream, long long N, int D, int dtype, const void* p, long long ps, void* out);
 int igs_geglu_bwd(void* stream, long long N, int D, int dtype, const void* p, long long ps, const void* dout, void* dp);
 
+/* The two ends of Transformer1D.forward around its blocks (gnorm.hip; igs/models/transformers.py:860-908): the
+ * GroupNorm whose result goes token-major to proj_in, and proj_out's result plus the residual.  Everything runs on `stream`, reads nothing
+ * back and allocates nothing; arithmetic is float32, half operands are widened on load and rounded once on store; no float atomics, every
+ * split of a sum depends on the shapes only, two runs agree bit for bit.  Every refusal below returns IGS_RAST_E_INVALID with a message
+ * before any HIP call.
+ *   - Channel-major operands (x, res, dx) are [B, C, A] with stride 1 on A and their own batch and channel strides in elements, so a
+ *     slice of a wider buffer is read or written in place.  Token-major operands (out, tok, dout) are rows [B * A, C] with stride 1 on C
+ *     and a row stride in elements; example b owns the rows b A .. b A + A - 1.  Each operand has its own dtype code (IGS_DTYPE_F32 /
+ *     IGS_DTYPE_F16).  weight, bias, dweight, dbias are [C] float32; stats is [B, G, 2] float32 = (mean, 1 / sqrt(var + eps)) per group.
+ * igs_group_norm_tokens_fwd: out[b, a, c] = (x[b, c, a] - mean[b, g]) rstd[b, g] weight[c] + bias[c], g = c / (C / G), with the biased
+ *   variance of the (C / G) A elements of a group taken from centred values; writes out and stats (two launches: the statistics, then
+ *   the tile transpose).  weight and bias both given or both NULL (no affine step).  A constant group gives exactly bias; a group that
+ *   holds a NaN or an infinity comes out all NaN, as in PyTorch, and no other group is touched by it.
+ * igs_group_norm_tokens_bwd: from x, weight (NULL = ones), the forward's stats and dout = d out the gradients dx (channel-major, own
+ *   dtype and strides), dweight and dbias; each is optional (NULL = not wanted; none wanted returns 0) and every element of a non-NULL
+ *   output is written.  `scratch` (igs_group_norm_tokens_bwd_scratch_bytes(B, C, G, A) bytes; 0 for sizes out of range) is always needed:
+ *   per tile of 64 tokens one row of the sums over its tokens of dout x_hat and dout, added in tile order per example, then over the
+ *   channels of a group (dx) and over the examples (dweight, dbias).
+ * igs_tokens_add_residual: out[b, a, c] = tok[b, a, c] + res[b, c, a] in float32, rounded once; one launch.
+ *   - Refused: C < 1 or > IGS_GN_MAX_C, G < 1 or not a divisor of C, A < 1 or (C / G) A > IGS_GN_MAX_GROUP_ELEMS (igs_tokens_add_residual:
+ *     G = 1), B < 0 or B A > IGS_GN_MAX_TOKENS; a channel stride below A, a batch stride below (C - 1) channel stride + A, a row stride
+ *     below C, a row or channel stride above IGS_TOKENS_MAX_STRIDE, a batch stride above IGS_GN_MAX_BATCH_STRIDE; an unknown dtype code;
+ *     an eps that is negative or not finite; weight without bias or bias without weight; a NULL x, out, stats, dout, tok, res or scratch;
+ *     a pointer not aligned to its element size; any overlap of an output or the scratch with an input or with one another.  B == 0
+ *     returns 0 without a launch.  Four-element access is used where C, A, the strides and the base pointers (16 bytes for float32, 8 for
+ *     float16) allow it, scalar access of the same lane mapping otherwise: nothing else depends on alignment. */
+#define IGS_GN_MAX_C 1024
+#define IGS_GN_MAX_TOKENS (1LL << 24)
+#define IGS_GN_MAX_GROUP_ELEMS (1LL << 30)
+#define IGS_GN_MAX_BATCH_STRIDE (1LL << 36)
+int igs_group_norm_tokens_fwd(void* stream, int B, int C, int G, long long A, int x_dtype, const void* x, long long x_bs, long long x_cs,
+                              const float* weight, const float* bias, float eps, int out_dtype, void* out, long long os, float* stats);
+size_t igs_group_norm_tokens_bwd_scratch_bytes(int B, int C, int G, long long A);
+int igs_group_norm_tokens_bwd(void* stream, int B, int C, int G, long long A, int x_dtype, const void* x, long long x_bs, long long x_cs,
+                              const float* weight, const float* stats, int dout_dtype, const void* dout, long long gs, int dx_dtype, void* dx,
+                              long long dx_bs, long long dx_cs, float* dweight, float* dbias, void* scratch);
+int igs_tokens_add_residual(void* stream, int B, int C, long long A, int tok_dtype, const void* tok, long long ts, int res_dtype,
+                            const void* res, long long r_bs, long long r_cs, int out_dtype, void* out, long long os);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).
