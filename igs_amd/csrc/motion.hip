@@ -394,7 +394,17 @@ deform_bwd_kernel(int P, int M, const float* __restrict__ rot, const int64_t* __
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= M) return;
     const int64_t i = mask[j];
-    if (i < 0 || i >= P) return;
+    if (i < 0 || i >= P) {                      // a skipped row took no part in the forward: its residuals' gradients are zero
+        if (d_dxyz) {
+#pragma unroll
+            for (int a = 0; a < 3; a++) st(d_dxyz + 3 * (size_t)j + a, 0.f);
+        }
+        if (d_drot) {
+#pragma unroll
+            for (int a = 0; a < 4; a++) st(d_drot + 4 * (size_t)j + a, 0.f);
+        }
+        return;
+    }
     if (d_dxyz) {
 #pragma unroll
         for (int a = 0; a < 3; a++) st(d_dxyz + 3 * (size_t)j + a, g_xyz ? g_xyz[3 * i + a] : 0.f);

@@ -587,9 +587,9 @@ int igs_knn_query(void* stream, int B, int Nx, int Ny, const float* x, const flo
  *   Two launches: the pass-through copy of both tensors, then the masked rows.  0 <= M <= P <= IGS_DEFORM_MAX_POINTS.
  * igs_gaussian_deform_bwd: the gradients of that map for the upstream g_xyz [P x 3] and g_rot [P x 4] (float32; NULL = zero):
  *   d_xyz [P x 3] = g_xyz; d_rot [P x 4] = g_rot outside the mask and the gradient through qmul and nrm(rot[i]) on it; d_dxyz [M x 3]
- *   = g_xyz[mask[j]] and d_drot [M x 4] through qmul and nrm(drot[j]), both in `dtype`.  Through nrm: (g - n <n, g>) / |q| where
- *   |q| >= 1e-12, g / 1e-12 below (F.normalize's clamp: division by the constant eps).  Any output may be NULL.  Two launches: the
- *   pass-through copy, then the masked rows.  Same limits as the forward. */
+ *   = g_xyz[mask[j]] and d_drot [M x 4] through qmul and nrm(drot[j]), both in `dtype` (zero rows for a skipped index).  Through
+ *   nrm: (g - n <n, g>) / |q| where |q| >= 1e-12, g / 1e-12 below (F.normalize's clamp: division by the constant eps).  Any output
+ *   may be NULL.  Two launches: the pass-through copy, then the masked rows.  Same limits as the forward. */
 #define IGS_DTYPE_F32 0
 #define IGS_DTYPE_F16 1
 #define IGS_INTERP_MAX_ROWS (1 << 24)

@@ -128,3 +128,159 @@ def select_restate(xyz_list, bbox):
             m = ((x >= b[0]) & (x <= b[1])).all(1)
         out.append(np.nonzero(m)[0].astype(np.int64))
     return out
+
+
+# ---------------------------------------------------------------- launch geometry, restated from anchors.hip (source lines cited)
+FPS_WAVES = 16                 # anchors.hip:20
+FPS_MAX_SLOTS = 4              # anchors.hip:21
+KNNQ_THREADS = 256             # anchors.hip:22  queries per kNN workgroup
+KNNQ_TILE = 2048               # anchors.hip:23  x points per LDS tile
+KNN_SLOT_CLASSES = (8, 16, 32, 100)       # anchors.hip:526-529  launch_knn_query's instantiations
+SELECT_BLOCK = 256             # anchors.hip:139  points per select workgroup (one block sum each)
+SCAN_THREADS = 1024            # sort.hip:34-40  the single-block scan: ceil(n / 1024) entries per thread
+
+
+def fps_geometry(max_n):
+    """anchors.hip:152-160 fps_geometry: (LS, R) = (rows per leaf, leaf records per lane) for a launch sized by max_n."""
+    m = 1
+    while max_n > FPS_WAVES * 64 * FPS_MAX_SLOTS * 64 * m:
+        m *= 2
+    leaves = (max_n + 64 * m - 1) // (64 * m)
+    r = 1
+    while FPS_WAVES * 64 * r < leaves:
+        r *= 2
+    return 64 * m, r
+
+
+def fps_example_bits(B):
+    """anchors.hip:418-420: bits of the example-keyed sort round (none for B = 1); ceil(bits / 8) radix passes."""
+    if B <= 1:
+        return 0
+    bits = 0
+    while (1 << bits) < B:
+        bits += 1
+    return bits
+
+
+def knn_slot_class(k):
+    """anchors.hip:526-529: the register slots K of the instantiation that serves k."""
+    return next(c for c in KNN_SLOT_CLASSES if k <= c)
+
+
+def knn_straddling_workgroups(ptr_y):
+    """Per kNN workgroup (256 consecutive queries, anchors.hip:453-459): True where its first and last query lie in different
+    examples -- the workgroups the masked instantiation serves."""
+    ptr_y = np.asarray(ptr_y)
+    ny = int(ptr_y[-1])
+    out = []
+    for first in range(0, ny, KNNQ_THREADS):
+        last = min(first + KNNQ_THREADS, ny) - 1
+        out.append(bool(np.searchsorted(ptr_y, first, "right") != np.searchsorted(ptr_y, last, "right")))
+    return out
+
+
+def select_scan_per_thread(n):
+    """Entries per thread of the single-block scan over the select's block sums (anchors.hip:139-141, sort.hip:40)."""
+    nb = (n + SELECT_BLOCK - 1) // SELECT_BLOCK
+    return (nb + SCAN_THREADS - 1) // SCAN_THREADS
+
+
+# ---------------------------------------------------------------- case builders of tests/test_gpu_anchors_edges.py
+def with_non_finite(x, rows, what=(np.nan, np.inf, -np.inf)):
+    """A copy of x whose `rows` carry, in turn, a NaN, +inf, -inf in the axis row % 3."""
+    x = np.array(x, np.float32)
+    for j, r in enumerate(rows):
+        x[r, r % 3] = what[j % len(what)]
+    return x
+
+
+def select_case(n, seed=0):
+    """(xyz [n, 3], box [2, 3]): the first n rows of a permuted half-integer lattice of side s (coordinates 0, 0.5, ...) and the box
+    [0.5, (s - 2) / 2]^3, so the lattice's second and second-to-last layers lie exactly on the faces (kept: lo <= p <= hi) and the
+    outermost layers half a step outside; about 1 % of the rows (three at least from 63 rows on) carry a NaN, +inf or -inf."""
+    s = max(4, int(np.ceil(n ** (1.0 / 3.0) - 1e-9)))
+    while s ** 3 < n:
+        s += 1
+    x = lattice(s, seed=seed, scale=0.5)[:n]
+    g = np.random.default_rng(seed + 1)
+    nbad = 0 if n < 63 else max(3, n // 100)
+    x = with_non_finite(x, g.choice(n, nbad, replace=False))
+    box = np.array([[0.5, 0.5, 0.5], [(s - 2) * 0.5] * 3], np.float32)
+    return x, box
+
+
+SELECT_BATCH_SIZES = (100, 0, 37, 1, 300)
+
+
+def select_batch_case(seed=0):
+    """(list of xyz, boxes [5, 2, 3]) for SELECT_BATCH_SIZES: example 0 all inside its box, 1 empty, 2 and 4 cut by face boxes (with
+    non-finite rows), 3 (a single point) all outside."""
+    xs, boxes = [], []
+    for b, n in enumerate(SELECT_BATCH_SIZES):
+        x, box = select_case(max(n, 1), seed=seed + 10 * b)
+        x = x[:n]
+        if b == 0:
+            x = lattice(5, seed=seed, scale=0.5)[:n]
+            box = np.array([[-1, -1, -1], [100, 100, 100]], np.float32)
+        if b == 3:
+            box = np.array([[50, 50, 50], [60, 60, 60]], np.float32)
+        xs.append(x)
+        boxes.append(box)
+    return xs, np.stack(boxes)
+
+
+def clustered(n, seed):
+    """A float cloud of ten Gaussian clusters of unequal widths."""
+    g = np.random.default_rng(seed)
+    c = g.normal(size=(10, 3)) * 3
+    w = g.uniform(0.01, 0.3, 10)
+    k = g.integers(0, 10, n)
+    return (c[k] + g.normal(size=(n, 3)) * w[k, None]).astype(np.float32)
+
+
+# name: (lattice side, samples, start, the (LS, R) class the case is there for)
+FPS_CLASS_CASES = {"R2": (41, 200, 40000, (64, 2)), "R4": (51, 200, 777, (64, 4)),
+                   "LS128": (65, 150, 123456, (128, 4)), "LS256": (81, 100, 500000, (256, 4))}
+FPS_CERT_R2 = (100000, 500)                # points, samples of the clustered float cloud at R = 2
+FPS_BATCH_SIDES = (8, 4, 10, 3)            # 512, 64, 1000 and 27 points
+FPS_BATCH_SAMPLES = (200, 64, 300, 27)     # examples 1 and 3 are sampled completely
+FPS_BATCH_STARTS = (5, 63, 999, 0)
+FPS_MANY = (300, 5, 10)                    # examples, lattice side, samples each
+
+
+def fps_batch_case():
+    """The four lattices of FPS_BATCH_SIDES, the 1000-point one with five non-finite rows (none of them its start)."""
+    xs = [lattice(s, seed=20 + b) for b, s in enumerate(FPS_BATCH_SIDES)]
+    xs[2] = with_non_finite(xs[2], [3, 100, 501, 777, 998])
+    return xs
+
+
+def knn_masked_case(seed=0):
+    """Integer coordinates in [0, 12): (x, y, ptr_x, ptr_y) with nx = [2049, 40, 300] (example 0 spans two LDS tiles, example 1 has
+    fewer than k = 100 points) and ny = [250, 20, 330] (workgroups 0 and 1 straddle examples, workgroup 2 does not)."""
+    g = np.random.default_rng(seed)
+    nx, ny = [2049, 40, 300], [250, 20, 330]
+    x = g.integers(0, 12, (sum(nx), 3)).astype(np.float32)
+    y = g.integers(0, 12, (sum(ny), 3)).astype(np.float32)
+    return x, y, np.concatenate([[0], np.cumsum(nx)]), np.concatenate([[0], np.cumsum(ny)])
+
+
+def knn_cut_case():
+    """(x, y): from the query at the origin (99 999, 0, 0) is kept and (100 000, 0, 0), at d2 = 1e10 exactly, dropped; rows of x carry
+    NaN and +-inf; query 1 is NaN (no neighbour at all), query 2 an ordinary point."""
+    x = np.array([[99999, 0, 0], [100000, 0, 0], [np.nan, 0, 0], [1, 2, 2], [0, np.inf, 0], [0, 3, 4], [-np.inf, 1, 1], [0, 0, np.nan],
+                  [2, 0, 0], [0, -2, 0]], np.float32)
+    y = np.array([[0, 0, 0], [np.nan, 0, 0], [1, 1, 1]], np.float32)
+    return x, y
+
+
+def knn_weights_f64(d2, idx, scale):
+    """softmax(-scale * sqrt(d2)) in float64 over the filled slots (idx >= 0) of every row; 0 in the empty ones and in rows without a
+    neighbour."""
+    d = np.sqrt(np.asarray(d2, np.float64))
+    has = np.asarray(idx) >= 0
+    z = np.where(has, -scale * np.where(has, d, 0.0), -np.inf)
+    m = np.where(has.any(1, keepdims=True), z.max(1, keepdims=True, initial=-np.inf), 0.0)
+    e = np.where(has, np.exp(z - m), 0.0)
+    s = e.sum(1, keepdims=True)
+    return np.where(has, e / np.where(s > 0, s, 1.0), 0.0)

@@ -224,3 +224,96 @@ def test_select_restatement():
     out = AR.select_restate([x, x], [[[0, 0, 0], [1, 1, 1]], [[1, 1, 1], [2, 2, 2]]])
     np.testing.assert_array_equal(out[0], [0, 1])
     np.testing.assert_array_equal(out[1], [1, 2, 4])
+
+
+# ---------------------------------------------------------------- the case builders of tests/test_gpu_anchors_edges.py
+# Each GPU edge test names the launch branch it is there for; these restate the launch code (tests/anchors_restatement.py cites the
+# lines) and fail if a size stops landing in its branch.
+def test_fps_geometry_restated_and_the_classes_of_the_edge_cases():
+    assert AR.fps_geometry(1) == (64, 1) and AR.fps_geometry(65536) == (64, 1) and AR.fps_geometry(65537) == (64, 2)
+    assert AR.fps_geometry(131072) == (64, 2) and AR.fps_geometry(131073) == (64, 4) and AR.fps_geometry(262144) == (64, 4)
+    assert AR.fps_geometry(262145) == (128, 4) and AR.fps_geometry(524288) == (128, 4) and AR.fps_geometry(524289) == (256, 4)
+    assert AR.fps_geometry(MAX_EXAMPLE_POINTS) == (1024, 4)
+    src = open(os.path.join(ROOT, "igs_amd", "csrc", "anchors.hip")).read()
+    for line in ("#define FPS_WAVES 16", "#define FPS_MAX_SLOTS 4", "#define KNNQ_THREADS 256", "#define KNNQ_TILE 2048",
+                 "while ((long long)max_n > (long long)FPS_WAVES * 64 * FPS_MAX_SLOTS * 64 * m) m *= 2;",
+                 "while ((long long)FPS_WAVES * 64 * r < leaves) r *= 2;", "while ((1 << bits) < B) bits++;",
+                 "if (k <= 8) knnq_launch<8>", "else if (k <= 16) knnq_launch<16>", "else if (k <= 32) knnq_launch<32>",
+                 "else knnq_launch<100>"):
+        assert line in src, line
+    seen = set()
+    for name, (side, samples, start, cls) in AR.FPS_CLASS_CASES.items():
+        assert AR.fps_geometry(side ** 3) == cls, name
+        assert 0 < start < side ** 3 and samples < side ** 3
+        assert 3 * (side - 1) ** 2 < 2 ** 24              # every squared distance of the lattice is an exact float32
+        seen.add(cls)
+    assert seen == {(64, 2), (64, 4), (128, 4), (256, 4)}
+    assert AR.fps_geometry(AR.FPS_CERT_R2[0]) == (64, 2)
+    assert AR.fps_geometry(40 ** 3) == (64, 1)            # (what test_gpu_anchors.py's large lattice runs: one slot)
+
+
+def test_fps_batch_builders():
+    xs = AR.fps_batch_case()
+    assert [len(x) for x in xs] == [512, 64, 1000, 27]
+    full = [s == len(x) for s, x in zip(AR.FPS_BATCH_SAMPLES, xs)]
+    assert full == [False, True, False, True]
+    assert all(0 <= s < len(x) for s, x in zip(AR.FPS_BATCH_STARTS, xs)) and AR.FPS_BATCH_STARTS[1] == 63 and AR.FPS_BATCH_STARTS[2] == 999
+    bad = [int((~np.isfinite(x).all(1)).sum()) for x in xs]
+    assert bad == [0, 0, 5, 0] and np.isfinite(xs[2][AR.FPS_BATCH_STARTS[2]]).all()
+    assert AR.FPS_BATCH_SAMPLES[2] <= 1000 - 5            # the non-finite rows are never reached
+    # a fully sampled lattice: a permutation
+    s = AR.fps_restate(xs[3], 27, 0, np.inf)
+    np.testing.assert_array_equal(np.sort(s), np.arange(27))
+    B, side, samples = AR.FPS_MANY
+    assert AR.fps_example_bits(B) == 9 and (AR.fps_example_bits(B) + 7) // 8 == 2 and samples < side ** 3
+    assert AR.fps_example_bits(256) == 8 and AR.fps_example_bits(257) == 9 and AR.fps_example_bits(4) == 2 and AR.fps_example_bits(1) == 0
+    # the 70 000-point example under max_n = 1000: more leaves than the launch's slots hold, while the scratch (sized by N) has its rows
+    LS, R = AR.fps_geometry(1000)
+    assert (LS, R) == (64, 1) and (70000 + LS - 1) // LS > AR.FPS_WAVES * 64 * R
+    # the 100-point example beside the 65^3 lattice: one leaf of 128 rows
+    assert AR.fps_geometry(65 ** 3)[0] == 128 and (100 + 127) // 128 == 1
+
+
+def test_select_builders():
+    for n in (1, 63, 64, 65, 255, 256, 257, 1025, 300000):
+        x, box = AR.select_case(n, seed=n)
+        assert x.shape == (n, 3) and x.dtype == np.float32
+        assert (x[np.isfinite(x)] * 2 == np.round(x[np.isfinite(x)] * 2)).all()              # half-integers
+        if n >= 63:
+            fin = np.isfinite(x).all(1)
+            assert (~fin).sum() >= max(3, n // 100)
+            assert np.isnan(x).any() and (x == np.inf).any() and (x == -np.inf).any()
+            assert ((x[fin] == box[0]).any(1)).any() and ((x[fin] == box[1]).any(1)).any()      # points exactly on both faces
+            assert (x[fin] < box[0]).any() and (x[fin] > box[1]).any()                          # and points outside
+            kept = AR.select_restate([x], [box])[0]
+            assert 0 < kept.size < n
+    assert AR.select_scan_per_thread(300000) == 2 and (300000 + 255) // 256 == 1172
+    assert AR.select_scan_per_thread(262144) == 1 and AR.select_scan_per_thread(1025) == 1
+    xs, boxes = AR.select_batch_case()
+    assert tuple(len(x) for x in xs) == AR.SELECT_BATCH_SIZES == (100, 0, 37, 1, 300)
+    ptr = np.concatenate([[0], np.cumsum(AR.SELECT_BATCH_SIZES)])
+    inside = [p for p in ptr[1:-1] if p % 64 != 0 and p < 256]
+    assert sorted(set(inside)) == [100, 137, 138]         # example boundaries inside waves of the first workgroup
+    want = AR.select_restate(xs, boxes)
+    assert want[0].size == 100 and want[1].size == 0 and want[3].size == 0 and 0 < want[2].size < 37 and 0 < want[4].size < 300
+
+
+def test_knn_builders():
+    assert [AR.knn_slot_class(k) for k in (1, 8, 9, 16, 17, 32, 33, 100)] == [8, 8, 16, 16, 32, 32, 100, 100]
+    x, y, px, py = AR.knn_masked_case()
+    assert list(np.diff(px)) == [2049, 40, 300] and list(np.diff(py)) == [250, 20, 330]
+    assert AR.knn_straddling_workgroups(py) == [True, True, False]
+    assert px[1] - px[0] > AR.KNNQ_TILE                   # example 0 spans two LDS tiles
+    assert 32 < px[2] - px[1] < 100                       # example 1 (40 points): padded slots at k = 100, full rows at 16 and 32
+    assert (x >= 0).all() and (x < 12).all() and (x == np.round(x)).all()
+    assert AR.knn_straddling_workgroups([0, 256, 512]) == [False, False] and AR.knn_straddling_workgroups([0, 255, 512]) == [True, False]
+    # the cut: 99 999^2 rounds below 1e10 in float32, 100 000^2 is 1e10 exactly
+    x, y = AR.knn_cut_case()
+    d = AR.d2_f32(y[0], x[:2])
+    assert d[0] < np.float32(AR.KNN_NONE) and d[1] == np.float32(AR.KNN_NONE) and float(np.float32(1e10)) == 1e10
+    idx, d2 = AR.knn_restate(x, y, 16)
+    assert list(idx[0][:5]) == [8, 9, 3, 5, 0] and (idx[0][5:] == -1).all() and (idx[1] == -1).all()
+    w = AR.knn_weights_f64(d2, idx, 0.001)
+    assert (w[1] == 0).all() and (w[0][5:] == 0).all() and abs(w[0].sum() - 1) < 1e-12 and abs(w[2].sum() - 1) < 1e-12
+    ref = torch.softmax(-0.001 * torch.from_numpy(d2[0, :5]).double().sqrt(), -1).numpy()
+    np.testing.assert_allclose(w[0, :5], ref, rtol=1e-12)

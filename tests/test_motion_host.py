@@ -198,3 +198,106 @@ def test_header_states_the_limits():
         assert s in h
     for name in NAMES:
         assert name + "(" in h
+
+
+# ---------------------------------------------------------------- the case builders of tests/test_gpu_motion_edges.py
+# Each GPU edge test names the launch branch it is there for; these restate the launch code (tests/motion_restatement.py cites the
+# lines) and fail if a size stops landing in its branch.
+def test_launch_geometry_restated_from_the_source():
+    src = open(os.path.join(ROOT, "igs_amd", "csrc", "motion.hip")).read()
+    for line in ("while (c < 512 && (uint64_t)c * 4 * 16 * 256 < E) c *= 2;", "while (((uint64_t)1 << bits) <= (uint64_t)A) bits++;",
+                 "return D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : D <= 512 ? 8 : 16;", "radix_sort_pairs(s, E, ka, kb, va, vb, hist, 0, L.bits, &sk, &sv)"):
+        assert line in src, line
+    common = open(os.path.join(ROOT, "igs_amd", "csrc", "common.h")).read()
+    assert "#define SORT_MAX_BLOCKS 256" in common and "#define SORT_TILE (256 * SORT_ITEMS)" in common and "#define SORT_ITEMS 8" in common
+    assert "for (int lo = bit_lo; lo < bit_hi; lo += 8, pass++)" in open(os.path.join(ROOT, "igs_amd", "csrc", "sort.hip")).read()
+    assert [MR.interp_chunk(e) for e in (1, 1 << 20, (1 << 20) + 1, 1 << 21, (1 << 21) + 1, 1 << 22, (1 << 22) + 1, 1 << 30)] == \
+        [64, 64, 128, 128, 256, 256, 512, 512]
+    assert [MR.interp_index_bits(a) for a in (1, 255, 256, 65535, 65536, MAX_ANCHORS)] == [1, 8, 9, 16, 17, 25]
+    assert [MR.interp_dv(d) for d in (1, 64, 65, 128, 129, 256, 257, 512, 513, 1024)] == [1, 1, 2, 2, 4, 4, 8, 8, 16, 16]
+    assert MR.sort_geometry(1) == (1, 2048) and MR.sort_geometry(2049) == (2, 2048) and MR.sort_geometry(256 * 2048) == (256, 2048)
+    assert MR.sort_geometry(256 * 2048 + 1) == (129, 4096)
+
+
+def test_edge_cases_land_in_the_branches_their_tests_name():
+    # what tests/test_gpu_motion.py already runs: chunk 64 and one or two index passes only
+    assert MR.interp_chunk(150000) == 64 and MR.interp_chunk(15000 * 8) == 64
+    # the shipped backward: chunk 128, a sort capped at 256 blocks whose slices span several sort tiles
+    E = 200000 * 8
+    assert MR.interp_chunk(E) == 128 and (E + MR.SORT_TILE - 1) // MR.SORT_TILE > MR.SORT_MAX_BLOCKS
+    assert MR.sort_geometry(E) == (196, 8192) and MR.interp_index_passes(8192) == 2 and MR.interp_dv(128) == 2
+    # the chunk-length cases
+    for chunk, (N, K, D) in MR.CHUNK_SHAPES.items():
+        assert MR.interp_chunk(N * K) == chunk, chunk
+    assert sorted(MR.CHUNK_SHAPES) == [128, 256, 512]
+    for c in (64, 128, 256, 512):
+        assert {c - 1, c, c + 1} <= set(MR.CHUNK_DEGREES)
+    assert {0, 1, 1025, 150000} <= set(MR.CHUNK_DEGREES)
+    # the index's pass-count boundaries
+    assert [MR.interp_index_passes(a) for a in MR.INDEX_PASS_ANCHORS] == [1, 2, 2, 3]
+    # wide rows: both wide instantiations, at both ends of their ranges
+    assert [MR.interp_dv(d) for d in (257, 512, 513, 1024)] == [8, 8, 16, 16] and MR.INTERP_MAX_D == 1024
+    # the gradient-subset case: every anchor's list has many chunks
+    F, w, col, dout = MR.exact_interp_case(4000, 8, 16, 40, pad=0.02, seed=4)
+    assert int(MR.in_degrees(col, 16).min()) > 10 * MR.interp_chunk(4000 * 8)
+
+
+@pytest.mark.parametrize("chunk", [128, 256, 512])
+def test_exact_case_builder_degrees_and_exactness(chunk):
+    N, K, D = MR.CHUNK_SHAPES[chunk]
+    F, w, col, dout = MR.exact_interp_case(N, K, 300, D, degrees=MR.CHUNK_DEGREES, pad=0.02, seed=chunk)
+    assert col.shape == (N, K) and F.shape == (300, D) and w.shape == (N, K) and dout.shape == (N, D)
+    deg = MR.in_degrees(col, 300)
+    assert deg[:len(MR.CHUNK_DEGREES)].tolist() == list(MR.CHUNK_DEGREES)
+    pad = (col == -1).sum().item() / col.numel()
+    assert 0.01 < pad < 0.03 and int(col.max()) < 300
+    assert (F == F.round()).all() and (dout == dout.round()).all() and F.abs().max() <= 50 and dout.abs().max() <= 4
+    assert set(w.unique().tolist()) == {1.0, 0.5, 0.25}
+    m = MR.exact_margin(F, w, col, dout)
+    assert m < 2 ** 24                                  # 4 * max sum |w g| < 2^24: every partial sum is an exact float32
+    # the float32 evaluation of the restatement, in any order, equals the float64 one
+    out32 = MR.interp_restate(F, w, col)
+    assert torch.equal(out32.double(), MR.interp_restate(F.double(), w.double(), col))
+
+
+def test_exact_case_builder_out_of_range_slots_and_margin_trips():
+    F, w, col, dout = MR.exact_interp_case(3000, 8, 65536, 3, pad=0.05, oob=9, seed=65536)
+    assert (col == 65536 + 7).sum().item() == 9 and 0.03 < (col == -1).float().mean().item() < 0.07
+    big = dout * 2.0 ** 22                              # the condition is a real one: scaled gradients break it
+    assert MR.exact_margin(F, w, col, big) >= 2 ** 24
+
+
+def test_blocked_truth_equals_autograd_of_the_restatement():
+    g = torch.Generator().manual_seed(3)
+    N, K, A, D = 70, 5, 11, 6
+    F = torch.randn(A, D, generator=g).double()
+    w = torch.rand(N, K, generator=g).double()
+    col = torch.randint(-2, A + 2, (N, K), generator=g)
+    dout = torch.randn(N, D, generator=g).double()
+    Fr, wr = F.clone().requires_grad_(True), w.clone().requires_grad_(True)
+    ref = MR.interp_restate(Fr, wr, col)
+    ref.backward(dout)
+    t = MR.interp_truth_blocked(F, w, col, dout, block=16)
+    torch.testing.assert_close(t["out"], ref.detach(), rtol=1e-13, atol=1e-13)
+    torch.testing.assert_close(t["dF"], Fr.grad, rtol=1e-13, atol=1e-13)
+    torch.testing.assert_close(t["dw"], wr.grad, rtol=1e-13, atol=1e-13)
+    bad = (col < 0) | (col >= A)
+    assert (t["dw"][bad] == 0).all() and (t["dw_abs"][bad] == 0).all() and t["deg"] == int(MR.in_degrees(col, A).max())
+    torch.testing.assert_close(t["out_abs"], MR.interp_restate(F.abs(), w.abs(), col), rtol=1e-13, atol=1e-13)
+    tol_F, tol_w = MR.interp_backward_bounds(t, K, D, True)
+    assert (tol_F >= t["deg"] * MR.U * t["dF_abs"]).all() and (tol_F >= MR.U16 * t["dF"].abs()).all() and (tol_w[bad] <= 1e-30).all()
+
+
+def test_ratio_helpers():
+    ref = torch.tensor([[1.0, 2.0]], dtype=torch.float64)
+    assert MR.worst_ratio(ref.float(), ref, torch.zeros_like(ref)) == 0.0                 # a zero bound admits a zero error
+    assert MR.worst_ratio(ref.float() + 1, ref, torch.zeros_like(ref)) == float("inf")
+    assert abs(MR.worst_ratio(ref.float() + 0.5, ref, torch.ones_like(ref)) - 0.5) < 1e-12
+    gb = torch.tensor([[1.0, 100.0], [1e6, 0.0]], dtype=torch.float64)
+    assert MR.deform_grad_ratio(gb.float(), gb, False) == 0.0
+    assert MR.deform_grad_ratio(gb.float() + torch.tensor([[2e-3, 0.0], [0.0, 0.0]]), gb, False) > 1      # 1e-5 of the row's largest
+    ga = gb.clone()
+    ga[1, 0] = float("inf")                             # a float16 row beyond 65504 must hold an inf, and is then left out
+    assert MR.deform_grad_ratio(ga.half(), gb, True) <= 1
+    with pytest.raises(AssertionError):
+        MR.deform_grad_ratio(gb.clamp(max=60000).half(), gb, True)
