@@ -161,6 +161,9 @@ SIGNATURES = {
     "igs_group_norm_tokens_bwd_scratch_bytes": (_sz, [_i, _i, _i, _ll]),
     "igs_group_norm_tokens_bwd": (_i, [_vp, _i, _i, _i, _ll] + [_i, _vp, _ll, _ll] + [_vp, _vp] + [_i, _vp, _ll] + [_i, _vp, _ll, _ll] + [_vp] * 3),
     "igs_tokens_add_residual": (_i, [_vp, _i, _i, _ll] + [_i, _vp, _ll] + [_i, _vp, _ll, _ll] + [_i, _vp, _ll]),
+    # mlp.hip
+    "igs_mlp_heads_pack_elems": (_ll, [_i, _vp, _i, _vp]),
+    "igs_mlp_heads_fwd": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _ll, _vp, _vp, _vp]),
 }
 EXPORTS = list(SIGNATURES)
 

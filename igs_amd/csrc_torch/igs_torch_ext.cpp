@@ -18,6 +18,7 @@
 //   encoder norms       inorm.hip               _encoder.instance_norm_fwd, _encoder.position_add on contiguous [N, C, H, W] tensors
 //   token ops           tokens.hip              _tokens.layer_norm_fwd / _bwd, _tokens.geglu_fwd / _bwd on [N, C] rows with a row stride
 //   transformer ends    gnorm.hip               _gnorm.group_norm_tokens_fwd / _bwd, _gnorm.tokens_add_residual: [B, C, A] in, [B, A, C] out
+//   residual decoder    mlp.hip                 _mlp.mlp_heads_fwd, _mlp.pack_elems: [N, C0] rows with a row stride in, one [N, ch] per head out
 //   deform              motion.hip              motion_deform_fwd / _bwd
 //   Adam                refine_ops.hip          adam_step_multi
 //   losses              refine_ops, loss_ops    l1_mean; ssim_mean
@@ -1080,6 +1081,45 @@ Tensor tokens_add_residual(const Tensor& tokens, const Tensor& residual, bool ou
     return out;
 }
 
+// ---- the residual decoder (mlp.hip) ----
+std::vector<int> mlp_ints(const std::vector<int64_t>& v) { return std::vector<int>(v.begin(), v.end()); }
+int64_t mlp_pack_elems(const std::vector<int64_t>& widths, const std::vector<int64_t>& head_widths)
+{
+    const std::vector<int> w = mlp_ints(widths), hw = mlp_ints(head_widths);
+    return igs_mlp_heads_pack_elems((int)w.size() - 1, w.data(), (int)hw.size(), hw.data());
+}
+// one contiguous [N, head_widths[k]] tensor per head in x's dtype.  x [N, widths[0]] with stride 1 inside a row; wpack, bpack as
+// igs_mlp_heads_fwd takes them (igs_amd/motion.py packs and caches them)
+std::vector<Tensor> mlp_heads_fwd(const Tensor& x, const Tensor& wpack, const Tensor& bpack, const std::vector<int64_t>& widths,
+                                  const std::vector<int64_t>& act_after, const std::vector<int64_t>& head_widths, int64_t act)
+{
+    const char* fn = "mlp_heads_fwd";
+    const int dt = dtype_code(x, fn, "x");
+    if (widths.empty() || act_after.size() + 1 != widths.size()) throw RasterizerError(std::string(fn) + ": widths needs one entry more than act_after");
+    expect(x, fn, "x", x.scalar_type(), {-1, widths[0]});
+    const int64_t N = x.size(0), C0 = x.size(1);
+    const int64_t rs = N > 1 ? x.stride(0) : C0;
+    if ((C0 > 1 && x.stride(1) != 1) || rs < C0) throw RasterizerError(std::string(fn) + ": x must have stride 1 inside a row and a row stride of at least the row length");
+    const int64_t elems = mlp_pack_elems(widths, head_widths);
+    if (elems < 0) throw RasterizerError(std::string(fn) + ": sizes out of range (0..3 hidden Linears, 1..8 heads, every width and the heads' sum in 1..128)");
+    expect(wpack, fn, "wpack", x.scalar_type(), {elems});
+    expect(bpack, fn, "bpack", at::kFloat, {(int64_t)widths.size(), IGS_MLP_MAX_WIDTH});
+    if (!wpack.is_contiguous() || !bpack.is_contiguous()) throw RasterizerError(std::string(fn) + ": wpack and bpack must be contiguous");
+    const GpuCall c(x, fn, "x", {{wpack, "wpack"}, {bpack, "bpack"}});
+    std::vector<Tensor> outs;
+    std::vector<void*> ptrs;
+    for (int64_t ch : head_widths) {
+        outs.push_back(at::empty({N, ch}, x.options()));
+        ptrs.push_back(outs.back().data_ptr());
+    }
+    if (N == 0) return outs;
+    const std::vector<int> w = mlp_ints(widths), aa = mlp_ints(act_after), hw = mlp_ints(head_widths);
+    check(igs_mlp_heads_fwd(c.stream(), N, dt, (int)act, (int)aa.size(), w.data(), aa.data(), (int)hw.size(), hw.data(), x.data_ptr(), rs, wpack.data_ptr(),
+                            bpack.data_ptr<float>(), ptrs.data()),
+          "igs_mlp_heads_fwd");
+    return outs;
+}
+
 // ---- the Gaussian deform (motion.hip) ----
 void deform_checks(const char* fn, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot, int* dt)
 {
@@ -1355,6 +1395,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     def_nogil(gn, "group_norm_tokens_bwd", &group_norm_tokens_bwd, "x"_a, "num_groups"_a, "weight"_a, "stats"_a, "grad_out"_a, "want_x"_a = true,
               "want_weight"_a = true, "want_bias"_a = true);
     def_nogil(gn, "tokens_add_residual", &tokens_add_residual, "tokens"_a, "residual"_a, "out_half"_a = false);
+    // ... and the residual decoder
+    py::module_ ml = m.def_submodule("_mlp", "the residual decoder: MLP and output heads in one launch (mlp.hip)");
+    def_nogil(ml, "mlp_heads_fwd", &mlp_heads_fwd, "x"_a, "wpack"_a, "bpack"_a, "widths"_a, "act_after"_a, "head_widths"_a, "act"_a = 0);
+    ml.def("pack_elems", &mlp_pack_elems, "widths"_a, "head_widths"_a);
     def_nogil(m, "motion_deform_fwd", &motion_deform_fwd, "xyz"_a, "rotation"_a, "mask"_a, "res_xyz"_a, "res_rotation"_a);
     def_nogil(m, "motion_deform_bwd", &motion_deform_bwd, "rotation"_a, "mask"_a, "res_xyz"_a, "res_rotation"_a, "grad_xyz"_a, "grad_rotation"_a,
               "want_xyz"_a = true, "want_rotation"_a = true, "want_res_xyz"_a = true, "want_res_rotation"_a = true);

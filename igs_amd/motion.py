@@ -2,7 +2,11 @@
 
 Per streamed frame and per training step, igs/models/gs.py runs: GS3DRenderer.query_ir_grid's tail (gs.py:812-822), a weighted sum of
 the features of every in-box Gaussian's K nearest anchors, then the decoder MLP, then GaussianModel.deform (gs.py:347-375), which moves
-the masked Gaussians by the decoded residuals.  `query_ir_grid` and `deform` here are those two steps, with autograd.
+the masked Gaussians by the decoded residuals.  `query_ir_grid` and `deform` here are the first and the last step, with autograd.
+
+`mlp_heads` / `decode_residual_feature` / `use_native_decoder` are the step between them: GS3DRenderer.decode_residual_feature
+(gs.py:858-869), the MLP of igs/models/networks.py:60-108 and the per-feature output Linears in one launch (igs_amd/csrc/mlp.hip).
+Forward only, for the streaming path under torch.no_grad(); training keeps the PyTorch lines.
 
 `grid_encoder_lift` / `lift_anchor_features` are the step in front of them: GridEncoder.forward's lift of the 2-D motion features onto the
 anchors (igs/models/grid_encoder.py:66-88 over igs/utils/ops.py:444-477; igs_amd/csrc/lift.hip), with autograd to the features.
@@ -19,7 +23,9 @@ Deviations from the reference lines (INTEGRATION.md lists them):
   - a lifted sample whose pixel coordinate is not finite adds zero; channels-last features are copied to NCHW first;
   - a neighbour slot whose column is -1 (knn_native's padding) or out of range contributes nothing (the reference would index with it);
   - the interpolation backward is deterministic (an inverse index instead of index_put_'s atomics);
-  - float16 residuals are widened to float32 before normalisation (the reference normalises them in float16).
+  - float16 residuals are widened to float32 before normalisation (the reference normalises them in float16);
+  - the float16 decoder accumulates, adds the bias and applies the activation in float32 and rounds each activation to half once (the
+    reference rounds after every Linear and every activation); the decoder has no backward.
 """
 import torch
 
@@ -329,3 +335,214 @@ def deform(gs, res_feat, mask):
     xyz, rotation = deform_xyz_rotation(gs.xyz, gs.rotation, mask, res_feat["xyz"], res_feat["rotation"])
     return {"xyz": xyz, "opacity": gs.opacity.clone(), "rotation": rotation, "scaling": gs.scaling.clone(), "shs": gs.shs.clone(),
             "resi_xyz": res_feat["xyz"].clone(), "resi_rotation": res_feat["rotation"].clone(), "mask": mask}
+
+
+# ---------------------------------------------------------------- the residual decoder (mlp.hip)
+MLP_MAX_WIDTH, MLP_MAX_HIDDEN, MLP_MAX_HEADS = 128, 3, 8        # IGS_MLP_MAX_*
+MLP_ACTIVATIONS = {"silu": 0, "relu": 1}                        # IGS_MLP_ACT_*
+DECODER_MLP, DECODER_HEADS, DECODER_CACHE = "mlp_net", "out_layers", "_igs_decoder_pack"
+
+
+def _tiles(c):
+    return (c + 31) // 32
+
+
+def pack_mlp_tile_order(W):
+    """One Linear's weight W [O, I] in the order mlp.hip's operands want it (include/igs_rast.h, igs_mlp_heads_fwd): a flat tensor of
+    ceil(O / 32) * ceil(I / 32) tiles of 1024 elements, zero where W ends.  Plain tensor ops: works on any device."""
+    O, I = W.shape
+    OT, KT = _tiles(O), _tiles(I)
+    P = W.new_zeros(32 * OT, 32 * KT)
+    P[:O, :I] = W
+    # column c of a 32-channel tile = 8 q + 4 h + p; element e = 4 q + p of lane (r, h)
+    if W.dtype == torch.float16:                 # chunks of 8: [ot, kt, s, h, r, q & 1, p] with q = 2 s + (q & 1)
+        return P.view(OT, 32, KT, 2, 2, 2, 4).permute(0, 2, 3, 5, 1, 4, 6).reshape(-1)
+    return P.view(OT, 32, KT, 4, 2, 4).permute(0, 2, 3, 4, 1, 5).reshape(-1)      # chunks of 4: [ot, kt, q, h, r, p]
+
+
+def pack_mlp(weights, biases, head_weights, head_biases):
+    """(wpack in the weights' dtype, bpack float32 [layers, 128]) for mlp_heads: the hidden Linears, then the heads as one Linear."""
+    Ws = list(weights) + [torch.cat(list(head_weights), 0)]
+    hb = [b if b is not None else w.new_zeros(w.shape[0]) for w, b in zip(head_weights, head_biases)]
+    bs = list(biases) + [torch.cat(hb, 0)]
+    wpack = torch.cat([pack_mlp_tile_order(w.detach()) for w in Ws])
+    bpack = torch.zeros(len(Ws), MLP_MAX_WIDTH, dtype=torch.float32, device=wpack.device)
+    for l, b in enumerate(bs):
+        if b is not None:
+            bpack[l, :b.shape[0]] = b.detach().float()
+    return wpack.contiguous(), bpack
+
+
+def _mlp_checks(fn, x, weights, biases, head_weights, head_biases, activation, act_after):
+    """Every refusal of the decoder that does not need the module; returns (widths, act_after, head_widths)."""
+    weights, biases, head_weights, head_biases = list(weights), list(biases), list(head_weights), list(head_biases)
+    if activation not in MLP_ACTIVATIONS:
+        raise NotImplementedError(f"{fn}: activation must be one of {sorted(MLP_ACTIVATIONS)} (got {activation!r})")
+    if len(biases) != len(weights) or len(head_biases) != len(head_weights):
+        raise ValueError(f"{fn}: one bias (or None) per weight")
+    if len(weights) > MLP_MAX_HIDDEN:
+        raise NotImplementedError(f"{fn}: at most {MLP_MAX_HIDDEN} hidden Linears (got {len(weights)})")
+    if not 1 <= len(head_weights) <= MLP_MAX_HEADS:
+        raise NotImplementedError(f"{fn}: between 1 and {MLP_MAX_HEADS} heads (got {len(head_weights)})")
+    act_after = [1] * len(weights) if act_after is None else [int(bool(a)) for a in act_after]
+    if len(act_after) != len(weights):
+        raise ValueError(f"{fn}: act_after needs one flag per hidden Linear")
+    if x.dim() != 2:
+        raise ValueError(f"{fn}: x must be [N, C] (got {list(x.shape)})")
+    params = [(w, b) for w, b in zip(weights + head_weights, biases + head_biases)]
+    width = x.shape[1]
+    widths = [width]
+    for i, (w, b) in enumerate(params):
+        head = i >= len(weights)
+        if w.dim() != 2 or w.shape[1] != width or (b is not None and tuple(b.shape) != (w.shape[0],)):
+            raise ValueError(f"{fn}: {'head' if head else 'hidden'} Linear {i - len(weights) if head else i} has weight {list(w.shape)}"
+                             f"{'' if b is None else ' and bias ' + str(list(b.shape))} for an input of {width} channels")
+        if not head:
+            width = w.shape[0]
+            widths.append(width)
+    head_widths = [w.shape[0] for w in head_weights]
+    if min(widths + head_widths) < 1 or max(widths) > MLP_MAX_WIDTH or sum(head_widths) > MLP_MAX_WIDTH:
+        raise NotImplementedError(f"{fn}: every width and the heads' sum must be in 1..{MLP_MAX_WIDTH} (widths {widths}, heads {head_widths})")
+    tensors = [t for pair in params for t in pair if t is not None]
+    if x.dtype not in FEATURE_DTYPES:
+        raise NotImplementedError(f"{fn}: x must be float32 or float16 (got {x.dtype})")
+    for t in tensors:
+        if t.dtype != x.dtype:
+            raise NotImplementedError(f"{fn}: x and every parameter must share a dtype (got {x.dtype} and {t.dtype})")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in [x] + tensors):
+        raise NotImplementedError(f"{fn}: forward only -- call it under torch.no_grad(), and train with the PyTorch lines")
+    if not all(t.is_cuda for t in [x] + tensors):
+        raise RuntimeError(f"{fn}: tensors must be on a GPU (no CPU fallback)")
+    return widths, act_after, head_widths
+
+
+def _mlp_launch(x, wpack, bpack, widths, act_after, head_widths, activation):
+    if (x.shape[1] > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()                       # a channel-strided x is copied; a row-strided one is read in place
+    return tuple(_ext()._mlp.mlp_heads_fwd(x, wpack, bpack, widths, act_after, head_widths, MLP_ACTIVATIONS[activation]))
+
+
+def mlp_heads(x, weights, biases, head_weights, head_biases, activation="silu", act_after=None, packed=None):
+    """A tuple of contiguous [N, ch] tensors in x's dtype, one per head: h = x; h = act(h W_l^T + b_l) for every hidden Linear l
+    (act_after[l] false: no activation behind that one; default all true); head k = h Wh_k^T + bh_k.  One launch, forward only.
+
+    x [N, C0] float32 / float16 with any row stride (a channel-strided x is copied first); weights[l] [C_{l+1}, C_l] and head_weights[k]
+    [ch_k, C_L] as nn.Linear keeps them, each bias [out] or None, all in x's dtype; at most 3 hidden Linears and 8 heads, every width and
+    the heads' sum at most 128.  packed = pack_mlp(weights, biases, head_weights, head_biases) skips the packing, which otherwise runs
+    on every call (a handful of small tensor ops); decode_residual_feature keeps it on the module."""
+    fn = "mlp_heads"
+    widths, act_after, head_widths = _mlp_checks(fn, x, weights, biases, head_weights, head_biases, activation, act_after)
+    wpack, bpack = packed if packed is not None else pack_mlp(weights, biases, head_weights, head_biases)
+    return _mlp_launch(x, wpack, bpack, widths, act_after, head_widths, activation)
+
+
+def _decoder_spec(renderer, fn):
+    """(hidden Linears, act_after, activation name, head Linears, keys) of a GS3DRenderer-shaped object, or NotImplementedError."""
+    nn = torch.nn
+    cfg = renderer.cfg
+    keys = list(cfg.feature_channels.keys())
+    heads = list(getattr(renderer, DECODER_HEADS))
+    if len(heads) != len(keys) or not all(isinstance(m, nn.Linear) for m in heads):
+        raise NotImplementedError(f"{fn}: {DECODER_HEADS} must hold one nn.Linear per entry of cfg.feature_channels")
+    linears, act_after, kinds = [], [], set()
+    if cfg.mlp_network_config is not None:
+        mlp = getattr(renderer, DECODER_MLP)
+        oa = getattr(mlp, "output_activation", None)
+        probe = torch.zeros(1)
+        if not (oa is None or isinstance(oa, nn.Identity) or (callable(oa) and oa(probe) is probe)):
+            raise NotImplementedError(f"{fn}: an output_activation other than the identity is not supported")
+        mods = list(mlp.layers)
+        for i, m in enumerate(mods):
+            if i % 2 == 0 and isinstance(m, nn.Linear):
+                linears.append(m)
+                act_after.append(0)
+            elif i % 2 == 1 and isinstance(m, (nn.SiLU, nn.ReLU)):
+                act_after[-1] = 1
+                kinds.add("silu" if isinstance(m, nn.SiLU) else "relu")
+            else:
+                raise NotImplementedError(f"{fn}: the MLP must alternate nn.Linear and nn.SiLU / nn.ReLU (entry {i} is {type(m).__name__})")
+        if not linears:
+            raise NotImplementedError(f"{fn}: the MLP has no Linear")
+    if len(kinds) > 1:
+        raise NotImplementedError(f"{fn}: mixed activations ({sorted(kinds)}) are not supported")
+    if len(linears) > MLP_MAX_HIDDEN:
+        raise NotImplementedError(f"{fn}: at most {MLP_MAX_HIDDEN} Linears in the MLP (got {len(linears)})")
+    if not 1 <= len(heads) <= MLP_MAX_HEADS:
+        raise NotImplementedError(f"{fn}: between 1 and {MLP_MAX_HEADS} output layers (got {len(heads)})")
+    widths = [m.in_features for m in linears + heads[:1]] + [m.out_features for m in linears]
+    if max(widths) > MLP_MAX_WIDTH or sum(m.out_features for m in heads) > MLP_MAX_WIDTH:
+        raise NotImplementedError(f"{fn}: every width and the output layers' sum must be at most {MLP_MAX_WIDTH}")
+    width = linears[0].in_features if linears else heads[0].in_features
+    for m in linears:
+        if m.in_features != width:
+            raise NotImplementedError(f"{fn}: the Linears' widths do not chain")
+        width = m.out_features
+    if any(m.in_features != width for m in heads):
+        raise NotImplementedError(f"{fn}: every output layer must read the MLP's {width} channels")
+    return linears, act_after, (kinds.pop() if kinds else "silu"), heads, keys
+
+
+def _param_key(params):
+    return tuple(None if p is None else (p._version, p.data_ptr(), p.dtype, p.device) for p in params)
+
+
+def _child(m, name):
+    """A submodule by dictionary lookup (nn.Module.__getattr__ is the slow way round), any other attribute as usual."""
+    mods = m.__dict__.get("_modules")
+    return mods[name] if mods is not None and name in mods else getattr(m, name, None)
+
+
+def _structure_key(renderer):
+    """The objects _decoder_spec looks at and the feature keys: the same objects give the same spec (the cache keeps them alive)."""
+    cfg = renderer.cfg
+    heads = _child(renderer, DECODER_HEADS)
+    objs = [heads] + list(heads._modules.values())
+    if cfg.mlp_network_config is not None:
+        mlp = _child(renderer, DECODER_MLP)
+        layers = _child(mlp, "layers")
+        objs += [mlp, layers, _child(mlp, "output_activation")] + list(layers._modules.values())
+    return objs, tuple(cfg.feature_channels)
+
+
+def _same_objects(a, b):
+    return a[1] == b[1] and len(a[0]) == len(b[0]) and all(x is y for x, y in zip(a[0], b[0]))
+
+
+def decode_residual_feature(renderer, residual_feat, bbox=None, radius=None):
+    """GS3DRenderer.decode_residual_feature (gs.py:858-869): {key: [N, ch]} in cfg.feature_channels' order, from renderer.mlp_net.layers
+    (no MLP when cfg.mlp_network_config is None) and renderer.out_layers, in one launch.  Kept on the module: the validated structure,
+    reused while the same module objects are in place, and the packed weights with the checked sizes, rebuilt when a parameter's
+    _version, data_ptr, dtype or device changes; a call that finds both unchanged checks the input only.  Forward only: under enabled grad
+    with anything that requires grad it raises NotImplementedError.  With B > 1 examples the unsplit interpolation buffer can be decoded
+    once and the results split."""
+    fn = "decode_residual_feature"
+    x = residual_feat
+    cache = renderer.__dict__.get(DECODER_CACHE)
+    structure = _structure_key(renderer)
+    if cache is None or not _same_objects(cache["structure"], structure):
+        cache = dict(structure=structure, spec=_decoder_spec(renderer, fn), key=None)
+    linears, act_after, activation, heads, keys = cache["spec"]
+    params = [m._parameters[n] for n in ("weight", "bias") for m in linears + heads]
+    key = _param_key(params)
+    if not (cache["key"] == key and x.dim() == 2 and x.shape[1] == cache["widths"][0] and x.dtype == cache["dtype"] and x.is_cuda
+            and not (torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params)))):
+        n = len(linears)
+        ws, bs, hws, hbs = params[:n], params[len(params) // 2:len(params) // 2 + n], params[n:len(params) // 2], params[len(params) // 2 + n:]
+        widths, act_after, head_widths = _mlp_checks(fn, x, ws, bs, hws, hbs, activation, act_after)          # every refusal is raised here
+        if cache["key"] != key:
+            cache.update(key=key, pack=pack_mlp(ws, bs, hws, hbs))
+        cache.update(widths=widths, act_after=act_after, head_widths=head_widths, dtype=x.dtype)
+        renderer.__dict__[DECODER_CACHE] = cache             # (only after every check has passed: a refusal leaves the module as it was)
+    wpack, bpack = cache["pack"]
+    outs = _mlp_launch(x, wpack, bpack, cache["widths"], cache["act_after"], cache["head_widths"], activation)
+    return dict(zip(keys, outs))
+
+
+def use_native_decoder(renderer):
+    """Binds decode_residual_feature on this GS3DRenderer instance; state_dict() keys and the class are untouched.  Returns the number of
+    Linears taken over (5 for the shipped config).  Raises NotImplementedError, before anything is changed, when the MLP is not nn.Linear
+    and nn.SiLU / nn.ReLU alternating, mixes activations, has an output_activation, more than 3 Linears or a width above 128."""
+    import types
+    linears, _, _, heads, _ = _decoder_spec(renderer, "use_native_decoder")
+    renderer.decode_residual_feature = types.MethodType(decode_residual_feature, renderer)
+    return len(linears) + len(heads)

@@ -884,6 +884,41 @@ int igs_group_norm_tokens_bwd(void* stream, int B, int C, int G, long long A, in
 int igs_tokens_add_residual(void* stream, int B, int C, long long A, int tok_dtype, const void* tok, long long ts, int res_dtype,
                             const void* res, long long r_bs, long long r_cs, int out_dtype, void* out, long long os);
 
+/* The residual decoder of AGM-Net in one launch (mlp.hip): GS3DRenderer.decode_residual_feature (igs/models/gs.py:
+ * 858-869), i.e. the MLP of igs/models/networks.py:60-108 and the per-feature output Linears behind it, per row n of x [N, widths[0]]:
+ *     h0 = x[n];  h_{l+1} = act_l(W_l h_l + b_l) for l = 0 .. n_hidden - 1;  y = W_heads h + b_heads, no activation,
+ * where W_heads, b_heads are the heads' weights and biases one after another, and head k's share of y is written to outs[k], a contiguous
+ * [N, head_widths[k]] tensor.  Forward only.  Runs on `stream`, reads nothing back, allocates nothing, uses no atomics: two runs agree
+ * bit for bit and a row's result does not depend on the other rows.  Each row of x is read once; no intermediate reaches memory.
+ *   - widths[0 .. n_hidden]: the input width and the output width of each hidden Linear; act_after[l] != 0: the activation `act`
+ *     (IGS_MLP_ACT_SILU = v / (1 + exp(-v)), IGS_MLP_ACT_RELU) follows hidden Linear l (the reference's MLP has none behind its last one).
+ *     SiLU is finite for every finite v (below v = -87.3, where exp(-v) leaves float32, the result is below |v| 2^-126 in size); both
+ *     activations keep a NaN, which therefore stays in its own row.
+ *   - x is in `dtype` (IGS_DTYPE_F32 / IGS_DTYPE_F16) with stride 1 inside a row and x_rs elements between rows, so a slice of a wider
+ *     buffer is read in place; the outputs are in `dtype` too.  IGS_DTYPE_F16: v_mfma_f32_32x32x16_f16, float32 accumulators that start
+ *     from the bias, activation in float32, one rounding to half when an activation becomes the next operand and one on store.
+ *     IGS_DTYPE_F32: v_mfma_f32_32x32x2_f32, an exact float32 fma chain, no half value anywhere.
+ *   - wpack: the weights in `dtype`, in the order the kernel's operands want them.  Linear l (the heads' last), W [O, I] row-major as
+ *     nn.Linear keeps it, becomes ceil(O / 32) x ceil(I / 32) tiles of 1024 elements, output tile outermost; tile (ot, kt) is
+ *     [chunk][lane 64][E] with E = 8 (half, 2 chunks) or 4 (float, 4 chunks), and element e = chunk E + j of lane (r = lane & 31,
+ *     h = lane >> 5) is W[32 ot + r][32 kt + (e & 3) + 8 (e >> 2) + 4 h], zero outside W.  igs_mlp_heads_pack_elems gives the element
+ *     count (-1 for sizes out of range).  bpack: float32 [n_hidden + 1][128], the biases zero-padded (an absent bias: zeros).
+ *   - Refused with IGS_RAST_E_INVALID and a message before any HIP call: an unknown dtype or activation code; N < 0 or > IGS_MLP_MAX_ROWS;
+ *     n_hidden outside 0 .. IGS_MLP_MAX_HIDDEN; n_heads outside 1 .. IGS_MLP_MAX_HEADS; a width or head width outside
+ *     1 .. IGS_MLP_MAX_WIDTH, or head widths that add up to more; NULL widths, head_widths or (n_hidden > 0) act_after; a row stride
+ *     below widths[0] or above IGS_TOKENS_MAX_STRIDE; with N > 0 a NULL x, wpack, bpack, outs or outs[k], a pointer not aligned to its
+ *     element size, a wpack not aligned to 16 bytes.  N == 0 returns 0 without a launch.  Four-element loads of x are used when
+ *     widths[0], x_rs and the base pointer allow them, scalar loads otherwise. */
+#define IGS_MLP_MAX_WIDTH 128
+#define IGS_MLP_MAX_HIDDEN 3
+#define IGS_MLP_MAX_HEADS 8
+#define IGS_MLP_MAX_ROWS (1LL << 32)
+#define IGS_MLP_ACT_SILU 0
+#define IGS_MLP_ACT_RELU 1
+long long igs_mlp_heads_pack_elems(int n_hidden, const int* widths, int n_heads, const int* head_widths);
+int igs_mlp_heads_fwd(void* stream, long long N, int dtype, int act, int n_hidden, const int* widths, const int* act_after, int n_heads,
+                      const int* head_widths, const void* x, long long x_rs, const void* wpack, const float* bpack, void* const* outs);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).
