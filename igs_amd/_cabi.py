@@ -164,6 +164,8 @@ SIGNATURES = {
     # mlp.hip
     "igs_mlp_heads_pack_elems": (_ll, [_i, _vp, _i, _vp]),
     "igs_mlp_heads_fwd": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _ll, _vp, _vp, _vp]),
+    "igs_mlp_heads_bwd_scratch_bytes": (_ll, [_ll, _i, _i, _vp, _i, _vp]),
+    "igs_mlp_heads_bwd": (_i, [_vp, _ll, _i, _i, _i, _vp, _vp, _i, _vp] + [_vp, _ll, _vp, _vp, _vp] + [_vp, _vp, _ll] + [_vp, _vp, _vp]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -18,7 +18,8 @@
 //   encoder norms       inorm.hip               _encoder.instance_norm_fwd, _encoder.position_add on contiguous [N, C, H, W] tensors
 //   token ops           tokens.hip              _tokens.layer_norm_fwd / _bwd, _tokens.geglu_fwd / _bwd on [N, C] rows with a row stride
 //   transformer ends    gnorm.hip               _gnorm.group_norm_tokens_fwd / _bwd, _gnorm.tokens_add_residual: [B, C, A] in, [B, A, C] out
-//   residual decoder    mlp.hip                 _mlp.mlp_heads_fwd, _mlp.pack_elems: [N, C0] rows with a row stride in, one [N, ch] per head out
+//   residual decoder    mlp.hip                 _mlp.mlp_heads_fwd, _mlp.pack_elems: [N, C0] rows with a row stride in, one [N, ch] per head out;
+//                                               _mlp.mlp_heads_bwd, _mlp.bwd_scratch_bytes: d x and flat float32 d w / d b from x alone
 //   deform              motion.hip              motion_deform_fwd / _bwd
 //   Adam                refine_ops.hip          adam_step_multi
 //   losses              refine_ops, loss_ops    l1_mean; ssim_mean
@@ -1119,6 +1120,59 @@ std::vector<Tensor> mlp_heads_fwd(const Tensor& x, const Tensor& wpack, const Te
           "igs_mlp_heads_fwd");
     return outs;
 }
+int64_t mlp_bwd_scratch_bytes(int64_t N, bool half, const std::vector<int64_t>& widths, const std::vector<int64_t>& head_widths)
+{
+    const std::vector<int> w = mlp_ints(widths), hw = mlp_ints(head_widths);
+    return igs_mlp_heads_bwd_scratch_bytes(N, half ? IGS_DTYPE_F16 : IGS_DTYPE_F32, (int)w.size() - 1, w.data(), (int)hw.size(), hw.data());
+}
+// (d x [N, widths[0]] in x's dtype, d w, d b float32 and flat as igs_mlp_heads_bwd lays them out), each None unless wanted.  douts[k]:
+// [N, head_widths[k]] contiguous in x's dtype, or None for zeros; wpack_t: the transposed Linears packed like wpack
+std::tuple<OptTensor, OptTensor, OptTensor> mlp_heads_bwd(const Tensor& x, const Tensor& wpack, const Tensor& wpack_t, const Tensor& bpack,
+                                                          const std::vector<int64_t>& widths, const std::vector<int64_t>& act_after,
+                                                          const std::vector<int64_t>& head_widths, int64_t act, const std::vector<OptTensor>& douts,
+                                                          bool want_x, bool want_w, bool want_b)
+{
+    const char* fn = "mlp_heads_bwd";
+    const int dt = dtype_code(x, fn, "x");
+    if (widths.empty() || act_after.size() + 1 != widths.size()) throw RasterizerError(std::string(fn) + ": widths needs one entry more than act_after");
+    expect(x, fn, "x", x.scalar_type(), {-1, widths[0]});
+    const int64_t N = x.size(0), C0 = x.size(1);
+    const int64_t rs = N > 1 ? x.stride(0) : C0;
+    if ((C0 > 1 && x.stride(1) != 1) || rs < C0) throw RasterizerError(std::string(fn) + ": x must have stride 1 inside a row and a row stride of at least the row length");
+    const int64_t elems = mlp_pack_elems(widths, head_widths);
+    if (elems < 0) throw RasterizerError(std::string(fn) + ": sizes out of range (0..3 hidden Linears, 1..8 heads, every width and the heads' sum in 1..128)");
+    expect(wpack, fn, "wpack", x.scalar_type(), {elems});
+    expect(wpack_t, fn, "wpack_t", x.scalar_type(), {elems});
+    expect(bpack, fn, "bpack", at::kFloat, {(int64_t)widths.size(), IGS_MLP_MAX_WIDTH});
+    if (!wpack.is_contiguous() || !wpack_t.is_contiguous() || !bpack.is_contiguous()) throw RasterizerError(std::string(fn) + ": wpack, wpack_t and bpack must be contiguous");
+    if (douts.size() != head_widths.size()) throw RasterizerError(std::string(fn) + ": one upstream gradient (or None) per head");
+    for (size_t k = 0; k < douts.size(); k++)
+        if (douts[k]) {
+            expect(*douts[k], fn, "an upstream gradient", x.scalar_type(), {N, head_widths[k]});
+            if (!douts[k]->is_contiguous()) throw RasterizerError(std::string(fn) + ": the upstream gradients must be contiguous");
+        }
+    const GpuCall c(x, fn, "x", {{wpack, "wpack"}, {wpack_t, "wpack_t"}, {bpack, "bpack"}});
+    for (const OptTensor& g : douts)
+        if (g) same_device(x, fn, {{*g, "an upstream gradient"}});
+    int64_t tw = 0, tb = 0;
+    for (size_t l = 0; l + 1 < widths.size(); l++) { tw += widths[l + 1] * widths[l]; tb += widths[l + 1]; }
+    for (int64_t ch : head_widths) { tw += ch * widths.back(); tb += ch; }
+    OptTensor dx, dw, db;
+    const auto fo = x.options().dtype(at::kFloat);
+    if (want_x) dx = at::empty({N, C0}, x.options());
+    if (want_w) dw = at::empty({tw}, fo);
+    if (want_b) db = at::empty({tb}, fo);
+    if (!(want_x || want_w || want_b)) return {dx, dw, db};
+    const Tensor scratch = at::empty({N == 0 ? 0 : mlp_bwd_scratch_bytes(N, dt == IGS_DTYPE_F16, widths, head_widths)}, x.options().dtype(at::kByte));
+    std::vector<const void*> ptrs;
+    for (const OptTensor& g : douts) ptrs.push_back(ptr_or_null(g));
+    const std::vector<int> w = mlp_ints(widths), aa = mlp_ints(act_after), hw = mlp_ints(head_widths);
+    check(igs_mlp_heads_bwd(c.stream(), N, dt, (int)act, (int)aa.size(), w.data(), aa.data(), (int)hw.size(), hw.data(), x.data_ptr(), rs, wpack.data_ptr(),
+                            wpack_t.data_ptr(), bpack.data_ptr<float>(), ptrs.data(), scratch.data_ptr(), scratch.numel(), ptr_or_null(dx),
+                            ptr_or_null<float>(dw), ptr_or_null<float>(db)),
+          "igs_mlp_heads_bwd");
+    return {dx, dw, db};
+}
 
 // ---- the Gaussian deform (motion.hip) ----
 void deform_checks(const char* fn, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot, int* dt)
@@ -1399,6 +1453,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     py::module_ ml = m.def_submodule("_mlp", "the residual decoder: MLP and output heads in one launch (mlp.hip)");
     def_nogil(ml, "mlp_heads_fwd", &mlp_heads_fwd, "x"_a, "wpack"_a, "bpack"_a, "widths"_a, "act_after"_a, "head_widths"_a, "act"_a = 0);
     ml.def("pack_elems", &mlp_pack_elems, "widths"_a, "head_widths"_a);
+    def_nogil(ml, "mlp_heads_bwd", &mlp_heads_bwd, "x"_a, "wpack"_a, "wpack_t"_a, "bpack"_a, "widths"_a, "act_after"_a, "head_widths"_a, "act"_a, "douts"_a,
+              "want_x"_a = true, "want_w"_a = true, "want_b"_a = true);
+    ml.def("bwd_scratch_bytes", &mlp_bwd_scratch_bytes, "N"_a, "half"_a, "widths"_a, "head_widths"_a);
     def_nogil(m, "motion_deform_fwd", &motion_deform_fwd, "xyz"_a, "rotation"_a, "mask"_a, "res_xyz"_a, "res_rotation"_a);
     def_nogil(m, "motion_deform_bwd", &motion_deform_bwd, "rotation"_a, "mask"_a, "res_xyz"_a, "res_rotation"_a, "grad_xyz"_a, "grad_rotation"_a,
               "want_xyz"_a = true, "want_rotation"_a = true, "want_res_xyz"_a = true, "want_res_rotation"_a = true);

@@ -6,7 +6,8 @@ the masked Gaussians by the decoded residuals.  `query_ir_grid` and `deform` her
 
 `mlp_heads` / `decode_residual_feature` / `use_native_decoder` are the step between them: GS3DRenderer.decode_residual_feature
 (gs.py:858-869), the MLP of igs/models/networks.py:60-108 and the per-feature output Linears in one launch (igs_amd/csrc/mlp.hip).
-Forward only, for the streaming path under torch.no_grad(); training keeps the PyTorch lines.
+These are forward only, for the streaming path under torch.no_grad().  `mlp_heads_autograd` / `decode_residual_feature_train` /
+`use_native_decoder(r, training=True)` add the native backward (igs_mlp_heads_bwd), which recomputes the forward from x.
 
 `grid_encoder_lift` / `lift_anchor_features` are the step in front of them: GridEncoder.forward's lift of the 2-D motion features onto the
 anchors (igs/models/grid_encoder.py:66-88 over igs/utils/ops.py:444-477; igs_amd/csrc/lift.hip), with autograd to the features.
@@ -25,7 +26,8 @@ Deviations from the reference lines (INTEGRATION.md lists them):
   - the interpolation backward is deterministic (an inverse index instead of index_put_'s atomics);
   - float16 residuals are widened to float32 before normalisation (the reference normalises them in float16);
   - the float16 decoder accumulates, adds the bias and applies the activation in float32 and rounds each activation to half once (the
-    reference rounds after every Linear and every activation); the decoder has no backward.
+    reference rounds after every Linear and every activation); its backward recomputes the forward the same way and returns
+    parameter gradients accumulated in float32 and rounded once.
 """
 import torch
 
@@ -341,6 +343,7 @@ def deform(gs, res_feat, mask):
 MLP_MAX_WIDTH, MLP_MAX_HIDDEN, MLP_MAX_HEADS = 128, 3, 8        # IGS_MLP_MAX_*
 MLP_ACTIVATIONS = {"silu": 0, "relu": 1}                        # IGS_MLP_ACT_*
 DECODER_MLP, DECODER_HEADS, DECODER_CACHE = "mlp_net", "out_layers", "_igs_decoder_pack"
+DECODER_TRAIN_CACHE = "_igs_decoder_train_pack"
 
 
 def _tiles(c):
@@ -360,9 +363,13 @@ def pack_mlp_tile_order(W):
     return P.view(OT, 32, KT, 4, 2, 4).permute(0, 2, 3, 4, 1, 5).reshape(-1)      # chunks of 4: [ot, kt, q, h, r, p]
 
 
-def pack_mlp(weights, biases, head_weights, head_biases):
-    """(wpack in the weights' dtype, bpack float32 [layers, 128]) for mlp_heads: the hidden Linears, then the heads as one Linear."""
+def pack_mlp(weights, biases, head_weights, head_biases, transposed=False, dtype=None):
+    """(wpack in the weights' dtype, bpack float32 [layers, 128]) for mlp_heads: the hidden Linears, then the heads as one Linear.
+    transposed=True: (wpack, bpack, wpack_t), wpack_t the same Linears transposed, which the backward's dgrad chain reads
+    (mlp_heads_autograd).  dtype: pack the weights in this dtype instead of their own (float16 under autocast)."""
     Ws = list(weights) + [torch.cat(list(head_weights), 0)]
+    if dtype is not None:
+        Ws = [w.detach().to(dtype) for w in Ws]
     hb = [b if b is not None else w.new_zeros(w.shape[0]) for w, b in zip(head_weights, head_biases)]
     bs = list(biases) + [torch.cat(hb, 0)]
     wpack = torch.cat([pack_mlp_tile_order(w.detach()) for w in Ws])
@@ -370,11 +377,14 @@ def pack_mlp(weights, biases, head_weights, head_biases):
     for l, b in enumerate(bs):
         if b is not None:
             bpack[l, :b.shape[0]] = b.detach().float()
+    if transposed:
+        return wpack.contiguous(), bpack, torch.cat([pack_mlp_tile_order(w.detach().t()) for w in Ws]).contiguous()
     return wpack.contiguous(), bpack
 
 
-def _mlp_checks(fn, x, weights, biases, head_weights, head_biases, activation, act_after):
-    """Every refusal of the decoder that does not need the module; returns (widths, act_after, head_widths)."""
+def _mlp_checks(fn, x, weights, biases, head_weights, head_biases, activation, act_after, train=False, autocast=False):
+    """Every refusal of the decoder that does not need the module; returns (widths, act_after, head_widths).  train: the caller has a
+    backward, so requiring grad is no refusal; autocast: x and the parameters are cast to half, so they need not share a dtype."""
     weights, biases, head_weights, head_biases = list(weights), list(biases), list(head_weights), list(head_biases)
     if activation not in MLP_ACTIVATIONS:
         raise NotImplementedError(f"{fn}: activation must be one of {sorted(MLP_ACTIVATIONS)} (got {activation!r})")
@@ -407,9 +417,9 @@ def _mlp_checks(fn, x, weights, biases, head_weights, head_biases, activation, a
     if x.dtype not in FEATURE_DTYPES:
         raise NotImplementedError(f"{fn}: x must be float32 or float16 (got {x.dtype})")
     for t in tensors:
-        if t.dtype != x.dtype:
+        if t.dtype != x.dtype and not (autocast and t.dtype in FEATURE_DTYPES):
             raise NotImplementedError(f"{fn}: x and every parameter must share a dtype (got {x.dtype} and {t.dtype})")
-    if torch.is_grad_enabled() and any(t.requires_grad for t in [x] + tensors):
+    if not train and torch.is_grad_enabled() and any(t.requires_grad for t in [x] + tensors):
         raise NotImplementedError(f"{fn}: forward only -- call it under torch.no_grad(), and train with the PyTorch lines")
     if not all(t.is_cuda for t in [x] + tensors):
         raise RuntimeError(f"{fn}: tensors must be on a GPU (no CPU fallback)")
@@ -434,6 +444,82 @@ def mlp_heads(x, weights, biases, head_weights, head_biases, activation="silu", 
     widths, act_after, head_widths = _mlp_checks(fn, x, weights, biases, head_weights, head_biases, activation, act_after)
     wpack, bpack = packed if packed is not None else pack_mlp(weights, biases, head_weights, head_biases)
     return _mlp_launch(x, wpack, bpack, widths, act_after, head_widths, activation)
+
+
+class _MlpHeadsFn(torch.autograd.Function):
+    """mlp_heads with the native backward (igs_mlp_heads_bwd).  Saved: x and the three packs; the forward is recomputed from x."""
+
+    @staticmethod
+    def forward(ctx, x, spec, packs, *params):
+        widths, act_after, head_widths, activation = spec
+        wpack, bpack, wpack_t = packs
+        outs = _ext()._mlp.mlp_heads_fwd(x, wpack, bpack, widths, act_after, head_widths, MLP_ACTIVATIONS[activation])
+        ctx.save_for_backward(x, wpack, bpack, wpack_t)
+        ctx.spec = spec
+        ctx.param_meta = [None if p is None else (p.dtype, tuple(p.shape)) for p in params]
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gouts):
+        x, wpack, bpack, wpack_t = ctx.saved_tensors
+        widths, act_after, head_widths, activation = ctx.spec
+        n, nh, meta = len(widths) - 1, len(head_widths), ctx.param_meta
+        need = ctx.needs_input_grad[3:]                      # weights, biases, head weights, head biases, as mlp_heads_autograd lists them
+        is_w = [True] * n + [False] * n + [True] * nh + [False] * nh
+        want_x = ctx.needs_input_grad[0]
+        want_w = any(nd and w for nd, w in zip(need, is_w))
+        want_b = any(nd and not w for nd, w in zip(need, is_w))
+        douts = [None if g is None else g.to(x.dtype).contiguous() for g in gouts]       # (a non-contiguous gradient is copied once)
+        dx, dw, db = _ext()._mlp.mlp_heads_bwd(x, wpack, wpack_t, bpack, widths, act_after, head_widths, MLP_ACTIVATIONS[activation], douts,
+                                               want_x, want_w, want_b)
+        outs_w = [widths[l + 1] for l in range(n)] + list(head_widths)
+        ins_w = list(widths[:n]) + [widths[-1]] * nh
+        gw, gb, wo, bo = [], [], 0, 0
+        for O, I in zip(outs_w, ins_w):
+            gw.append(None if dw is None else dw[wo:wo + O * I].view(O, I))
+            gb.append(None if db is None else db[bo:bo + O])
+            wo, bo = wo + O * I, bo + O
+        flat = gw[:n] + gb[:n] + gw[n:] + gb[n:]
+        grads = [g.to(m[0]) if (nd and m is not None and g is not None) else None for g, nd, m in zip(flat, need, meta)]
+        return (dx, None, None) + tuple(grads)
+
+
+def _autocast_half(fn, x):
+    """True when CUDA autocast to float16 is on for x's device type; bfloat16 autocast is refused."""
+    if not (x.is_cuda and torch.is_autocast_enabled()):
+        return False
+    dt = torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
+    if dt != torch.float16:
+        raise NotImplementedError(f"{fn}: autocast to {dt} is not supported (float16 only)")
+    return True
+
+
+def _mlp_train_launch(x, params, packs, widths, act_after, head_widths, activation):
+    if packs[0].dtype != x.dtype:
+        x = x.to(packs[0].dtype)                  # (autocast; autograd casts the gradient back)
+    if (x.shape[1] > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()                       # a channel-strided x is copied; a row-strided one is read, and saved, in place
+    return _MlpHeadsFn.apply(x, (list(widths), list(act_after), list(head_widths), activation), packs, *params)
+
+
+def mlp_heads_autograd(x, weights, biases, head_weights, head_biases, activation="silu", act_after=None, packed=None):
+    """mlp_heads with a native backward: the same checks, sizes and return value, but gradients reach x and every weight and bias that
+    requires them, in that tensor's dtype (accumulated in float32 and rounded once for half parameters).  Nothing of N rows is kept
+    for the backward but x: the forward is recomputed in chunks (igs_mlp_heads_bwd), deterministically and without float atomics.  A
+    head that took no part in the loss costs nothing; d x is not computed when only parameters require grad, and the parameter
+    gradients are not when only x does.  Under CUDA autocast to float16, x and the packed weights are cast to half and the outputs
+    are half, as eager nn.Linear gives; the gradients of float32 parameters come back float32.  bfloat16 autocast raises
+    NotImplementedError.  packed = pack_mlp(..., transposed=True) skips the packing.  Not twice differentiable."""
+    fn = "mlp_heads_autograd"
+    half = _autocast_half(fn, x)
+    widths, act_after, head_widths = _mlp_checks(fn, x, weights, biases, head_weights, head_biases, activation, act_after, train=True, autocast=half)
+    if packed is None:
+        packed = pack_mlp(weights, biases, head_weights, head_biases, transposed=True, dtype=torch.float16 if half else None)
+    wpack, bpack, wpack_t = packed
+    params = list(weights) + list(biases) + list(head_weights) + list(head_biases)
+    return _mlp_train_launch(x, params, (wpack, bpack, wpack_t), widths, act_after, head_widths, activation)
 
 
 def _decoder_spec(renderer, fn):
@@ -538,11 +624,39 @@ def decode_residual_feature(renderer, residual_feat, bbox=None, radius=None):
     return dict(zip(keys, outs))
 
 
-def use_native_decoder(renderer):
+def decode_residual_feature_train(renderer, residual_feat, bbox=None, radius=None):
+    """decode_residual_feature for a module that is trained.  With grad off, or nothing requiring grad, it is decode_residual_feature
+    (the same cache, the same bits).  Otherwise the outputs carry the native backward of mlp_heads_autograd; the forward and transposed
+    packs are kept on the module under the same rule (rebuilt when a parameter's _version, data_ptr, dtype or device changes, i.e. once
+    per optimiser step), separately for float16 autocast."""
+    fn = "decode_residual_feature_train"
+    x = residual_feat
+    cache = renderer.__dict__.get(DECODER_TRAIN_CACHE)
+    structure = _structure_key(renderer)
+    if cache is None or not _same_objects(cache["structure"], structure):
+        cache = dict(structure=structure, spec=_decoder_spec(renderer, fn), key=None)
+    linears, act_after, activation, heads, keys = cache["spec"]
+    params = [m._parameters[n] for n in ("weight", "bias") for m in linears + heads]
+    if not (torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params))):
+        return decode_residual_feature(renderer, residual_feat, bbox, radius)
+    n, half = len(linears), _autocast_half(fn, x)
+    m = len(params) // 2
+    ws, hws, bs, hbs = params[:n], params[n:m], params[m:m + n], params[m + n:]
+    widths, act_after, head_widths = _mlp_checks(fn, x, ws, bs, hws, hbs, activation, act_after, train=True, autocast=half)
+    key = (_param_key(params), half)
+    if cache["key"] != key:
+        cache.update(key=key, pack=pack_mlp(ws, bs, hws, hbs, transposed=True, dtype=torch.float16 if half else None))
+    renderer.__dict__[DECODER_TRAIN_CACHE] = cache               # (only after every check has passed)
+    outs = _mlp_train_launch(x, ws + bs + hws + hbs, cache["pack"], widths, act_after, head_widths, activation)
+    return dict(zip(keys, outs))
+
+
+def use_native_decoder(renderer, training=False):
     """Binds decode_residual_feature on this GS3DRenderer instance; state_dict() keys and the class are untouched.  Returns the number of
     Linears taken over (5 for the shipped config).  Raises NotImplementedError, before anything is changed, when the MLP is not nn.Linear
-    and nn.SiLU / nn.ReLU alternating, mixes activations, has an output_activation, more than 3 Linears or a width above 128."""
+    and nn.SiLU / nn.ReLU alternating, mixes activations, has an output_activation, more than 3 Linears or a width above 128.
+    training=True binds decode_residual_feature_train instead, which has a backward; the default binds the forward-only method."""
     import types
     linears, _, _, heads, _ = _decoder_spec(renderer, "use_native_decoder")
-    renderer.decode_residual_feature = types.MethodType(decode_residual_feature, renderer)
+    renderer.decode_residual_feature = types.MethodType(decode_residual_feature_train if training else decode_residual_feature, renderer)
     return len(linears) + len(heads)

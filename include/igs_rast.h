@@ -919,6 +919,32 @@ long long igs_mlp_heads_pack_elems(int n_hidden, const int* widths, int n_heads,
 int igs_mlp_heads_fwd(void* stream, long long N, int dtype, int act, int n_hidden, const int* widths, const int* act_after, int n_heads,
                       const int* head_widths, const void* x, long long x_rs, const void* wpack, const float* bpack, void* const* outs);
 
+/* The residual decoder's backward (mlp.hip).  The forward is recomputed from x: between igs_mlp_heads_fwd, which is
+ * also the training forward, and this call nothing of N rows has to be kept but x.  From the heads' upstream gradients
+ *     dh_L = Wh^T dY,  dWh = dY^T h_L,  dbh = sum_rows dY;   for l = L-1 .. 0:  dz_l = dh_{l+1} act'(z_l) (dh_{l+1} where act_after[l] == 0),
+ *     dW_l = dz_l^T h_l,  db_l = sum_rows dz_l,  dh_l = W_l^T dz_l;   dx = dh_0.
+ * ReLU' is 0 at z <= 0 and keeps a NaN; SiLU' = s (1 + z (1 - s)), s = sigmoid(z), on the forward's clamped exponent: finite for every
+ * finite z.  Runs on `stream`, reads nothing back, allocates nothing, uses no float atomics: every sum has a fixed order (the rows of a
+ * slice of 256, chunk after chunk, then the slices), two runs agree bit for bit, and a row's dx does not depend on the other rows.
+ *   - sizes, dtype, act, act_after, x, x_rs, wpack, bpack as igs_mlp_heads_fwd takes them.  wpack_t: every Linear's TRANSPOSE packed the
+ *     same way (W^T [I, O] in place of W [O, I]; the same element count per Linear, so the same offsets).  The products use the forward's
+ *     matrix instructions (float16: float32 accumulation, operands rounded to half once; float32: exact fma chains).
+ *   - douts[k]: d outs[k], [N, head_widths[k]] contiguous in `dtype`, or NULL for zeros.  dx: [N, widths[0]] contiguous in `dtype`, or NULL
+ *     if not wanted.  dw: float32 whatever the dtype, every Linear's [O, I] row-major as nn.Linear keeps it, layer after layer, then the
+ *     heads concatenated along the output; db: float32, every Linear's outputs concatenated in the same order; each NULL if not wanted.
+ *     Every element of a non-NULL output is written.  With all three NULL nothing is launched.
+ *   - scratch: igs_mlp_heads_bwd_scratch_bytes(N, ...) bytes (-1 for sizes out of range), 16-byte aligned, not initialised by the caller.
+ *     It holds the pre-activations and their gradients of one chunk of 16384 rows as float32 and the slices' partial sums, so it does
+ *     not grow with N above 16384.  The launches: two per chunk (rows, weight gradients) and one reduction.
+ *   - Refused with IGS_RAST_E_INVALID and a message before any HIP call: what igs_mlp_heads_fwd refuses about codes, sizes, N, act_after
+ *     and the row stride; a dw or db not aligned to 4 bytes; with N > 0 a NULL x, wpack, wpack_t, bpack, douts or scratch, an x, douts[k]
+ *     or dx not aligned to its element size, a wpack, wpack_t or scratch not aligned to 16 bytes, a scratch_bytes below the needed size.
+ *     N == 0 zero-fills dw and db where given and launches nothing else. */
+long long igs_mlp_heads_bwd_scratch_bytes(long long N, int dtype, int n_hidden, const int* widths, int n_heads, const int* head_widths);
+int igs_mlp_heads_bwd(void* stream, long long N, int dtype, int act, int n_hidden, const int* widths, const int* act_after, int n_heads,
+                      const int* head_widths, const void* x, long long x_rs, const void* wpack, const void* wpack_t, const float* bpack,
+                      const void* const* douts, void* scratch, long long scratch_bytes, void* dx, float* dw, float* db);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).
