@@ -23,6 +23,7 @@
 //   deform              motion.hip              motion_deform_fwd / _bwd
 //   Adam                refine_ops.hip          adam_step_multi
 //   losses              refine_ops, loss_ops    l1_mean; ssim_mean
+//   training loss       ssim_batch.hip          _loss.ssim_batch on [N, C, H, W] float32 batches
 //   module                                      names, defaults, GIL release
 //
 // A new op's glue follows one order: argument checks (dtype, shape, ranges) -> GpuCall on its anchor tensor ("no CPU fallback", device
@@ -1353,6 +1354,43 @@ std::tuple<Tensor, Tensor> ssim_mean(const Tensor& a, const Tensor& b)
     return { mean, grad };               // grad = d(mean SSIM)/da
 }
 
+// ---- the AGM-Net training loss (ssim_batch.hip) ----
+// (means [N + 1], l1_means [N + 1] | None, grad [N, C, H, W] | None, ssim_map [N, C, H, W] | None) of two [N, C, H, W] float32 batches
+// (igs_ssim_batch_fwd_bwd; loss_utils.py:17-18,33-63, main.py:252-265): means[n] = mean SSIM of image n, means[N] = their mean;
+// grad[n] = c_ssim * d means[n] / d a + c_l1 * d l1_means[n] / d a.  The scratch is this call's own, from the caching allocator (the
+// stream-ordered free keeps it alive for the launches; under capture it belongs to the graph's pool)
+int64_t ssim_batch_scratch_bytes(int64_t W, int64_t H, int64_t N, int64_t C, bool want_grad)
+{
+    if (W > INT_MAX || H > INT_MAX || N > INT_MAX || C > INT_MAX) return -1;
+    return igs_ssim_batch_scratch_bytes((int)W, (int)H, (int)N, (int)C, want_grad ? 1 : 0);
+}
+std::tuple<Tensor, OptTensor, OptTensor, OptTensor> ssim_batch(const Tensor& a, const Tensor& b, double c_ssim, double c_l1, bool want_grad,
+                                                                bool want_map, bool want_l1)
+{
+    const char* fn = "ssim_batch";
+    expect(a, fn, "a", at::kFloat, {-1, -1, -1, -1});
+    expect(b, fn, "b", at::kFloat, {a.size(0), a.size(1), a.size(2), a.size(3)});
+    const int64_t N = a.size(0), C = a.size(1), H = a.size(2), W = a.size(3);
+    const int64_t bytes = ssim_batch_scratch_bytes(W, H, N, C, want_grad);
+    if (bytes < 0)
+        throw RasterizerError(std::string(fn) + ": sizes out of range for " + c10::str(a.sizes()) + " (every size >= 1, N * C <= " +
+                              std::to_string(IGS_SSIM_BATCH_MAX_PLANES) + ", 8 * N * C * ceil(ceil(H / 32) / 8) * ceil(W / 32) < 2^31)");
+    const GpuCall c(a, fn, "a", {{b, "b"}});
+    const auto fo = a.options();
+    Tensor means = at::empty({N + 1}, fo);
+    OptTensor l1_means, grad, map;
+    if (want_l1) l1_means = at::empty({N + 1}, fo);
+    if (want_grad) grad = at::empty({N, C, H, W}, fo);
+    if (want_map) map = at::empty({N, C, H, W}, fo);
+    const Tensor scratch = at::empty({bytes}, a.options().dtype(at::kByte));
+    const Tensor x = a.contiguous(), y = b.contiguous();
+    check(igs_ssim_batch_fwd_bwd(c.stream(), (int)W, (int)H, (int)N, (int)C, x.data_ptr<float>(), y.data_ptr<float>(), (float)c_ssim, (float)c_l1,
+                                 scratch.data_ptr(), means.data_ptr<float>(), ptr_or_null<float>(l1_means), ptr_or_null<float>(grad),
+                                 ptr_or_null<float>(map)),
+          "igs_ssim_batch_fwd_bwd");
+    return {means, l1_means, grad, map};
+}
+
 // ---- the module ----
 // m.def for a function that runs with the GIL released: every function that reaches a kernel (host threads drive streams side by side)
 using namespace pybind11::literals;      // "name"_a = py::arg("name")
@@ -1456,6 +1494,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     def_nogil(ml, "mlp_heads_bwd", &mlp_heads_bwd, "x"_a, "wpack"_a, "wpack_t"_a, "bpack"_a, "widths"_a, "act_after"_a, "head_widths"_a, "act"_a, "douts"_a,
               "want_x"_a = true, "want_w"_a = true, "want_b"_a = true);
     ml.def("bwd_scratch_bytes", &mlp_bwd_scratch_bytes, "N"_a, "half"_a, "widths"_a, "head_widths"_a);
+    py::module_ ls = m.def_submodule("_loss", "SSIM and L1 of a batch of images: the AGM-Net training loss (ssim_batch.hip)");
+    def_nogil(ls, "ssim_batch", &ssim_batch, "a"_a, "b"_a, "c_ssim"_a, "c_l1"_a, "want_grad"_a, "want_map"_a, "want_l1"_a);
+
     def_nogil(m, "motion_deform_fwd", &motion_deform_fwd, "xyz"_a, "rotation"_a, "mask"_a, "res_xyz"_a, "res_rotation"_a);
     def_nogil(m, "motion_deform_bwd", &motion_deform_bwd, "rotation"_a, "mask"_a, "res_xyz"_a, "res_rotation"_a, "grad_xyz"_a, "grad_rotation"_a,
               "want_xyz"_a = true, "want_rotation"_a = true, "want_res_xyz"_a = true, "want_res_rotation"_a = true);

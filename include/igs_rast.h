@@ -447,6 +447,28 @@ int igs_ssim_l1_loss_fwd_bwd_cached(void* stream, int width, int height, const f
 int igs_ssim_mean_fwd_bwd(void* stream, int width, int height, const float* pred, const float* gt, void* scratch, float* grad,
                           float* mean_out);
 
+/* SSIM and L1 of a BATCH of images, forward + backward: the AGM-Net training loss (igs/utils/loss_utils.py:17-18,33-63; main.py:252-265;
+ * ssim_batch.hip).  pred, gt: [images][channels][H][W] float32, contiguous (4-byte alignment is enough).
+ *   means    [images + 1]: mean SSIM of every image over its channels * H * W elements, then the mean of those, added in index order.
+ *   l1_means [images + 1] (NULL allowed): the same for |pred - gt|.
+ *   grad     (NULL = forward only: the derivative maps are neither written nor read and the gradient launch is skipped; a wanted
+ *            l1_means then comes from the first launch): [images][channels][H][W], every element written,
+ *              grad[n] = c_ssim * d(mean SSIM of image n)/d pred + c_l1 * d(mean |pred - gt| of image n)/d pred.
+ *   ssim_map (NULL allowed): [images][channels][H][W], the SSIM value at every pixel.
+ *   scratch  igs_ssim_batch_scratch_bytes(width, height, images, channels, grad != NULL) bytes, 256-byte aligned; need not be initialised.
+ * Three launches with a gradient, two without; no host synchronisation and no allocation, so the call can be captured into a graph.
+ * Every workgroup leaves its tile's sums in scratch and one workgroup of the last launch adds them per image in an order that depends on
+ * (channels, width, height) alone: no atomics, two runs agree bit for bit, and an image's mean, map and gradient have the same bits alone
+ * and at any position of any batch.  The forward-only instances give the means and the map of the gradient instances bit for bit.
+ *   - Refused with IGS_RAST_E_INVALID and a message before any HIP call: a non-positive width, height, images or channels; images * channels
+ *     above IGS_SSIM_BATCH_MAX_PLANES; a grid 8 * images * channels * ceil(ceil(H / 32) / 8) * ceil(W / 32) that does not fit in 31 bits;
+ *     a NULL pred, gt, scratch or means.  igs_ssim_batch_scratch_bytes returns -1 for the sizes the call would refuse; without want_grad it
+ *     holds the tile sums only (no derivative maps). */
+#define IGS_SSIM_BATCH_MAX_PLANES (1 << 16)
+long long igs_ssim_batch_scratch_bytes(int width, int height, int images, int channels, int want_grad);
+int igs_ssim_batch_fwd_bwd(void* stream, int width, int height, int images, int channels, const float* pred, const float* gt,
+                           float c_ssim, float c_l1, void* scratch, float* means, float* l1_means, float* grad, float* ssim_map);
+
 /* RaDe-GS depth-normal consistency regulariser, value and gradients in one launch
  * (submodules/RaDe-GS/utils/graphics_utils.py:97-126, train.py:143-160):
  *   loss = weight * ((1 - depth_ratio) * mean(1 - normal . n(depth)) + depth_ratio * mean(1 - normal . n(mdepth))),
