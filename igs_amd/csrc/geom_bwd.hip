@@ -203,7 +203,10 @@ sh_grad_views_kernel(int P, int D, int M, int V, const float* __restrict__ means
         for (int k = 0; k < 16; k++) {
             if (k < used && k < M) {
                 float t0 = b[k] * g.x, t1 = b[k] * g.y, t2 = b[k] * g.z;
-                if (clamp > 0.f) { t0 = fminf(fmaxf(t0, -clamp), clamp); t1 = fminf(fmaxf(t1, -clamp), clamp); t2 = fminf(fmaxf(t2, -clamp), clamp); }
+                if (clamp > 0.f) {                    // comparisons as in sh_grad1: a NaN stays a NaN (fminf / fmaxf would return the bound)
+                    t0 = t0 < -clamp ? -clamp : (t0 > clamp ? clamp : t0); t1 = t1 < -clamp ? -clamp : (t1 > clamp ? clamp : t1);
+                    t2 = t2 < -clamp ? -clamp : (t2 > clamp ? clamp : t2);
+                }
                 acc[3 * k] += t0; acc[3 * k + 1] += t1; acc[3 * k + 2] += t2;
             }
         }

@@ -407,7 +407,9 @@ size_t igs_refine_mask_args_size(void);       /* sizeof(igs_refine_mask_args) of
  * 3-float colour gradients of all views (`color_grad_out` of igs_refine_step: 12 bytes per Gaussian and view instead of a
  * 192-byte SH gradient in an all-reduce) and rebuilds the sum itself, views in the order given -- identical bits on every rank.
  *   campos [n_views][3] in HOST memory (read before the call returns; n_views <= 64), color_grads [n_views][P][3] and means3D on the
- *   device, dL_dsh [P][M][3] (overwritten), clamp_grads as in igs_refine_step. */
+ *   device, dL_dsh [P][M][3] (overwritten), clamp_grads as in igs_refine_step.  A view whose three colour gradients of a Gaussian are
+ *   zero (either sign) does not see it; rows at or beyond (D + 1)^2 and Gaussians no view sees are +0; a NaN colour gradient makes
+ *   that Gaussian's rows NaN, through the clamp too (as torch.clamp), and touches no other Gaussian. */
 int igs_sh_grad_from_view_colors(void* stream, int P, int D, int M, int n_views, const float* means3D, const float* campos,
                                  const float* color_grads, float clamp_grads, float* dL_dsh);
 /* The same sum applied directly as the Adam update of the SH coefficients (torch.optim.Adam semantics as igs_adam_step_groups:

@@ -469,14 +469,20 @@ def reference_adam(init, lrs, grads):
     return ps, opt
 
 
+# check_adam's bars as (rtol, atol factor): the atol factor multiplies lr for the parameter and the largest |reference| entry for a moment
+# (tests/exchange_restatement.py::adam_allowance reads them from here)
+ADAM_BARS = dict(param=(2e-6, 2e-4), exp_avg=(2e-5, 2e-6), exp_avg_sq=(2e-5, 1e-6))
+
+
 def check_adam(p, m, v, ref_p, ref_st, lr, what):
     """test_gpu_dropin.py::test_multi_tensor_adam_matches_torch_adam's bars (a step moves a parameter by ~lr)."""
     p, m, v = (t.detach().cpu().double() for t in (p, m, v))
-    torch.testing.assert_close(p, ref_p.detach(), rtol=2e-6, atol=2e-4 * lr, msg=lambda s: "%s param: %s" % (what, s))
+    bp, bm, bv = ADAM_BARS["param"], ADAM_BARS["exp_avg"], ADAM_BARS["exp_avg_sq"]
+    torch.testing.assert_close(p, ref_p.detach(), rtol=bp[0], atol=bp[1] * lr, msg=lambda s: "%s param: %s" % (what, s))
     if m.numel():
-        torch.testing.assert_close(m, ref_st["exp_avg"], rtol=2e-5, atol=2e-6 * float(ref_st["exp_avg"].abs().max()),
+        torch.testing.assert_close(m, ref_st["exp_avg"], rtol=bm[0], atol=bm[1] * float(ref_st["exp_avg"].abs().max()),
                                    msg=lambda s: "%s exp_avg: %s" % (what, s))
-        torch.testing.assert_close(v, ref_st["exp_avg_sq"], rtol=2e-5, atol=1e-6 * float(ref_st["exp_avg_sq"].abs().max()),
+        torch.testing.assert_close(v, ref_st["exp_avg_sq"], rtol=bv[0], atol=bv[1] * float(ref_st["exp_avg_sq"].abs().max()),
                                    msg=lambda s: "%s exp_avg_sq: %s" % (what, s))
 
 
