@@ -174,8 +174,7 @@ __device__ __forceinline__ void blend_bwd_tile(const BlendBwdArgs& a, const uint
             gp1 = d1 > 0.f ? a.l1_scale : (d1 < 0.f ? -a.l1_scale : 0.f);
             gp2 = d2 > 0.f ? a.l1_scale : (d2 < 0.f ? -a.l1_scale : 0.f);
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+        acc = wave_sum_lane0(acc);      // (the pairing of the __shfl_down tree: lane 0's sum is the same float)
         if (lane == 0 && acc != 0.f) atomicAdd(&a.l1_loss[16 * ((tile * 4 + wid) & 63)], acc);
     }
     float gc0 = 0, gc1 = 0, gc2 = 0, gm0 = 0, gm1 = 0, gm2 = 0, g_t = 0, g_mt = 0, gn0 = 0, gn1 = 0, gn2 = 0;
@@ -221,9 +220,7 @@ __device__ __forceinline__ void blend_bwd_tile(const BlendBwdArgs& a, const uint
     // nothing behind the deepest last_contributor of the tile is ever touched: start there
     int my_wave_max;                               // ... and this wave's own deepest one (wave-uniform): rows behind it are skipped
     {
-        int m = last_contributor;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off, 64));
+        const int m = wave_max_lane0(last_contributor);      // (lane 0 alone uses it)
         if (lane == 0) wave_max[wid] = m;
         my_wave_max = __builtin_amdgcn_readfirstlane(m);
     }
@@ -283,10 +280,10 @@ __device__ __forceinline__ void blend_bwd_tile(const BlendBwdArgs& a, const uint
                 __builtin_amdgcn_wave_barrier();      // ... and the next splat's column writes must stay behind these row reads
                 float tot;
                 if constexpr (ADJ) {
-                    // (s_nop 1: a DPP operand needs two wait states behind the vector instruction that wrote it; s_nop is free)
-                    float t1;
-                    asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=v"(t1) : "v"(part));
-                    asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "=v"(tot) : "v"(t1));
+                    // (as builtins, not asm statements: the compiler knows the two wait states a DPP operand needs behind the vector
+                    //  instruction that wrote it, and fills them with the row's address arithmetic where it can instead of s_nop)
+                    const float t1 = part + __uint_as_float(dpp_read<0xb1>(__float_as_uint(part)));      // quad_perm:[1,0,3,2]
+                    tot = t1 + __uint_as_float(dpp_read<0x4e>(__float_as_uint(t1)));                        // quad_perm:[2,3,0,1]
                 } else {
                     // the LPR partials of a row sit 64 / LPR lanes apart: v_permlane32_swap / v_permlane16_swap (gfx950) fold them in the
                     // vector ALU -- no trip through the LDS crossbar (ds_bpermute: 6 LDS cycles each, and a round trip of latency)
@@ -324,8 +321,11 @@ __device__ __forceinline__ void blend_bwd_tile(const BlendBwdArgs& a, const uint
                 const float G = __expf(power);
                 const float alpha0 = fminf(0.99f, op * G);
                 const bool valid = (j > j_first) && !(power > 0.0f) && !(alpha0 < 1.0f / 255.0f);
-                if (__ballot(valid) == 0ull) return;
+                if (__builtin_expect(__ballot(valid) == 0ull, 0)) return;      // (1.2 % of the rows: the row's fall-through path is the valid one)
 
+                // (the suffix recurrence first: it is the last reader of last_alpha and Dprev, so this row's alpha and D can be formed in
+                //  the very registers that carry them to the next row -- behind it they were formed elsewhere and copied, two v_mov a row)
+                const float Snew = last_alpha * Dprev + (1.f - last_alpha) * S;
                 uint32_t gid;
                 if constexpr (GEO) { q2 = R.q2(); col0 = q1.z; col1 = q1.w; col2 = q2.x; gid = chunk_id[j]; }
                 else { const float4 c4 = R.r[2]; col0 = c4.x; col1 = c4.y; col2 = c4.z; gid = __float_as_uint(c4.w); }
@@ -360,7 +360,6 @@ __device__ __forceinline__ void blend_bwd_tile(const BlendBwdArgs& a, const uint
                 }
                 if constexpr (NORMAL) D += q3.w * gn0 + q5.z * gn1 + q5.w * gn2;
 
-                const float Snew = last_alpha * Dprev + (1.f - last_alpha) * S;
                 const float dL_dopa = (D - Snew) * T + (-T_final * inv_one_m) * bg_dot_e;
                 S = Snew; Dprev = D; last_alpha = alpha;
                 if constexpr (MASK) {

@@ -67,6 +67,42 @@ __device__ __forceinline__ uint32_t quad_reach_mask(float4 q0, float4 q1, float 
     return m;
 }
 
+// Six-step reduction trees over the 64 lanes of a wave whose result is wanted in LANE 0 ONLY, in the vector ALU: v_permlane32_swap /
+// v_permlane16_swap (gfx950) for the steps of 32 and 16 lanes, DPP row shifts and quad permutes below a row -- no ds_bpermute_b32
+// (24 cycles each through the LDS crossbar, tools/ubench; twelve of them per wave and tile were more than one whole splat row).
+// The pairing is that of `for (off = 32; off > 0; off >>= 1) x = op(x, __shfl_down(x, off))`: after the step `off` lane i < off holds
+// op(x[i], x[i + off]), so lane 0 ends with the same float, bit for bit.  Lanes other than 0 end with values of no meaning.
+// DPP controls: row_shl:n = 0x100 + n (lane i reads lane i + n of its row of 16), quad_perm:[2,3,0,1] = 0x4e, quad_perm:[1,0,3,2] = 0xb1;
+// a lane whose source lies outside its row reads 0 (bound_ctrl) -- such lanes are never ones lane 0's tree depends on.
+template <int CTRL> __device__ __forceinline__ uint32_t dpp_read(uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
+}
+__device__ __forceinline__ float wave_sum_lane0(float x)
+{
+    const auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    x = __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
+    const auto s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    x = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
+    x += __uint_as_float(dpp_read<0x108>(__float_as_uint(x)));
+    x += __uint_as_float(dpp_read<0x104>(__float_as_uint(x)));
+    x += __uint_as_float(dpp_read<0x4e>(__float_as_uint(x)));
+    x += __uint_as_float(dpp_read<0xb1>(__float_as_uint(x)));
+    return x;
+}
+__device__ __forceinline__ int wave_max_lane0(int m)      // m >= 0 (a lane reading outside its row takes part with 0)
+{
+    const auto s32 = __builtin_amdgcn_permlane32_swap((uint32_t)m, (uint32_t)m, false, false);
+    m = max((int)s32[0], (int)s32[1]);
+    const auto s16 = __builtin_amdgcn_permlane16_swap((uint32_t)m, (uint32_t)m, false, false);
+    m = max((int)s16[0], (int)s16[1]);
+    m = max(m, (int)dpp_read<0x108>((uint32_t)m));
+    m = max(m, (int)dpp_read<0x104>((uint32_t)m));
+    m = max(m, (int)dpp_read<0x4e>((uint32_t)m));
+    m = max(m, (int)dpp_read<0xb1>((uint32_t)m));
+    return m;
+}
+
 // wave-uniform copy of a 64-bit value (readfirstlane returns a SIGNED int: widen through uint32_t, not int)
 __device__ __forceinline__ uint64_t uniform64(uint64_t v)
 {

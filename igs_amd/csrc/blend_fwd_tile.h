@@ -51,6 +51,14 @@ __device__ __forceinline__ void blend_fwd_tile(const BlendFwdArgs& a, const uint
     float C0 = 0, C1 = 0, C2 = 0, weight = 0;
     float Co0 = 0, Co1 = 0, Co2 = 0, mC0 = 0, mC1 = 0, mC2 = 0, Depth = 0, mDepth = 0, N0 = 0, N1 = 0, N2 = 0;
 
+    // Two constants of the row loop that are no inline constants, defined HERE through asm statements the compiler cannot look into:
+    // as plain literals both were re-materialised in every row (a v_mov_b32 for the record size of the v_mul_u32_u24 below, an
+    // s_mov_b32 for the 1e-4 of a VOP3 compare) -- two of the row's 70 issue slots.  The values are the same bits.
+    uint32_t rec_bytes = 0;
+    if constexpr (NQ * 16 > 64) asm volatile("v_mov_b32 %0, %1" : "=v"(rec_bytes) : "n"(NQ * 16));
+    float t_min;
+    asm volatile("s_mov_b32 %0, 0x38d1b717" : "=s"(t_min));      // 0.0001f
+
     if (tid < 4) wave_done[tid] = 0;
     for (int i = 0; i < rounds; i++) {
         wg_barrier();                                           // previous chunk consumed, wave_done published
@@ -93,7 +101,7 @@ __device__ __forceinline__ void blend_fwd_tile(const BlendFwdArgs& a, const uint
                     // was nine scalar instructions per row.)
                     const float alpha_e = (!(power > 0.0f) && !(alpha < 1.0f / 255.0f)) ? alpha : 0.0f;
                     const float test_T = Tl * (1.0f - alpha_e);
-                    const bool alive = !(test_T < 0.0001f);
+                    const bool alive = !(test_T < t_min);
                     const float aT = alive ? alpha_e * Tl : 0.0f;
                     const bool contrib = aT > 0.0f;
                     const uint32_t contributor = (uint32_t)(i * FWD_CHUNK + 1) + (uint32_t)slot;
@@ -132,7 +140,7 @@ __device__ __forceinline__ void blend_fwd_tile(const BlendFwdArgs& a, const uint
                     const int j = sw * 64 + jj;
                     uint32_t addr;                                           // LDS byte offset of the record: ONE vector multiply (s_mul + v_mov otherwise)
                     if constexpr (NQ * 16 <= 64) asm("v_mul_u32_u24 %0, %1, %2" : "=v"(addr) : "s"(j), "n"(NQ * 16));
-                    else asm("v_mul_u32_u24 %0, %1, %2" : "=v"(addr) : "s"(j), "v"(NQ * 16));
+                    else asm("v_mul_u32_u24 %0, %1, %2" : "=v"(addr) : "s"(j), "v"(rec_bytes));      // (96 is no inline constant: from a register)
                     blend_row((const float4*)((const char*)chunk + addr), (uint32_t)j);
                 }
                 // "has every pixel of the quad saturated?" is asked once per 64 staged splats, not per row: the ballot
