@@ -11,12 +11,16 @@
 
 __device__ __forceinline__ bool near0(float x) { return fabsf(x) <= 0.0000001f; }
 
+// The reference's two arms (|a| > |b|: |a| sqrt(1 + (|b|/|a|)^2); otherwise 0 if |b| is near zero, else |b| sqrt(1 + (|a|/|b|)^2)) are one
+// expression on the larger and the smaller magnitude, so they are written once with selects: as two branches a wave whose lanes disagree
+// walks both, each with its IEEE divide and square root, three times per QL sweep.  Same operations on the same operands: same bits.
 __device__ __forceinline__ float hyp(float a, float b) {   // auxiliary.h:200-214
-    float absa = fabsf(a), absb = fabsf(b);
-    if (absa > absb) { absb /= absa; absb *= absb; return absa * sqrtf(1.0f + absb); }
-    if (near0(absb)) return 0.0f;
-    absa /= absb; absa *= absa;
-    return absb * sqrtf(1.0f + absa);
+    const float absa = fabsf(a), absb = fabsf(b);
+    const bool a_big = absa > absb;
+    const float big = a_big ? absa : absb, small = a_big ? absb : absa;
+    float q = small / big; q *= q;
+    const float r = big * sqrtf(1.0f + q);
+    return (!a_big && near0(absb)) ? 0.0f : r;          // (0 / 0 only where this select discards it)
 }
 
 // 3x3 symmetric eigen-decomposition: Householder tridiagonalisation + implicit-shift QL, absolute 1e-7 thresholds,

@@ -81,6 +81,7 @@ preprocess_body(const FwdParams& p, const uint32_t blk, float* __restrict__ rec,
     uint32_t my_tiles = 0;
     int rect_x0 = 0, rect_y0 = 0, rect_w = 1;
     uint32_t my_dkey = 0;
+    bool my_seen = false;             // radii[idx] > 0: the only Gaussians whose accumulator row anybody reads
     if (BIN && p.zero_stats && blk == 0 && threadIdx.x < 4) p.zero_stats[threadIdx.x] = 0u;      // (nothing reads them before the tile sort)
     if (idx < p.P) {
         int radius = 0;
@@ -172,6 +173,7 @@ preprocess_body(const FwdParams& p, const uint32_t blk, float* __restrict__ rec,
                 rgb = make_float3(p.colors_precomp[3 * idx], p.colors_precomp[3 * idx + 1], p.colors_precomp[3 * idx + 2]);
             }
             radius = (int)my_radius;
+            my_seen = radius > 0;
             my_tiles = (uint32_t)((y1 - y0) * (x1 - x0));
             rect_x0 = x0; rect_y0 = y0; rect_w = x1 - x0;
             dkey = __float_as_uint(p_view.z);
@@ -205,8 +207,12 @@ preprocess_body(const FwdParams& p, const uint32_t blk, float* __restrict__ rec,
     if (BIN && p.zero_gacc) {
         // refine step: this kernel is latency-bound and leaves the memory pipes idle -- zero-fill the backward's accumulator
         // line of this Gaussian (and the loss shards) here instead of in a 25 MB fill of its own.  AFTER the wave's loads: issued at
-        // the top, the stores sat in front of them in the memory pipeline (position loads back after 4.8 us instead of 1.0)
-        if (idx < p.P && idx >= p.zero_gacc_first) {          // (masked refine step: rows exist for the trainable Gaussians only)
+        // the top, the stores sat in front of them in the memory pipeline (position loads back after 4.8 us instead of 1.0).
+        // Only the rows of the Gaussians this view sees: the blend kernels add to the rows of Gaussians in a tile list, geom_bwd and
+        // extract_view_colors read a row under `radii[idx] > 0`, and the workspace's contents are undefined on entry anyway.  A view
+        // culls ~60 % of the Gaussians, in Morton order by whole waves, and the stores of those waves stood in front of the parameter
+        // loads of the waves behind them (profiles/front_end_split.txt)
+        if (my_seen && idx >= p.zero_gacc_first) {            // (masked refine step: rows exist for the trainable Gaussians only)
             float4* Z4 = (float4*)(p.zero_gacc + (size_t)(idx - p.zero_gacc_first) * p.zero_gacc_stride);
             const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll

@@ -45,6 +45,11 @@ def main():
             v = (tt[ok, k] - t0) * 0.01        # us
             if len(v):
                 print("  mark %d %-52s n=%5d  median %6.2f  p90 %6.2f  last %6.2f us" % (k, NAMES[k], len(v), np.median(v), np.percentile(v, 90), v.max()))
+        # the EWA (+ eigen-solver) segment of each wave on its own: mark 2 minus mark 1, whenever the wave started
+        ok = (tt[:, 1] >= tt[:, 0]) & (tt[:, 2] >= tt[:, 1]) & (tt[:, 2] >= t0)
+        if ok.any():
+            seg = (tt[ok, 2] - tt[ok, 1]) * 0.01
+            print("  mark 2 - mark 1, per wave %-34s n=%5d  median %6.2f  p90 %6.2f  longest %6.2f us" % ("", len(seg), np.median(seg), np.percentile(seg, 90), seg.max()))
     print("launch span (first start to last stamp): %.2f us" % ((t[t >= t0].max() - t0) * 0.01))
 
 
