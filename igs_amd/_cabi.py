@@ -169,6 +169,9 @@ SIGNATURES = {
     # ssim_batch.hip
     "igs_ssim_batch_scratch_bytes": (_ll, [_i] * 5),
     "igs_ssim_batch_fwd_bwd": (_i, [_vp] + [_i] * 4 + [_vp, _vp, _f, _f] + [_vp] * 5),
+    # densify.hip
+    "igs_densify_plan_scratch_bytes": (_sz, [_i]),
+    "igs_densify_plan": (_i, [_vp, _i] + [_vp] * 7 + [_f] * 4 + [_ll, _i] + [_vp] * 7),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -17,10 +17,11 @@ class DensifyConfig:
     """configs/demo.yaml:57-62 + the literals of infer_batch.py:308-321."""
 
     def __init__(self, until_iter=100, from_iter=0, interval=20, grad_threshold=0.00015, min_opacity=0.005, max_num=150000,
-                 percent_dense=0.01, extent=1.0, max_screen_size=None, control_max=True):
+                 percent_dense=0.01, extent=1.0, max_screen_size=None, control_max=True, native=False):
         self.until_iter, self.from_iter, self.interval = until_iter, from_iter, interval
         self.grad_threshold, self.min_opacity, self.max_num = grad_threshold, min_opacity, max_num
         self.percent_dense, self.extent, self.max_screen_size, self.control_max = percent_dense, extent, max_screen_size, control_max
+        self.native = native          # the decision by igs_densify_plan (plan_native) instead of the PyTorch plan
 
 
 class DensifyState:
@@ -33,6 +34,7 @@ class DensifyState:
         self.grad_accum = torch.zeros(P, dtype=torch.float32, device=device)
         self.denom = torch.zeros(P, dtype=torch.float32, device=device)
         self.max_radii = torch.zeros(P, dtype=torch.float32, device=device)
+        self.plan_bufs = None         # plan_native: scratch and output buffers for these P Gaussians, allocated by its first call
 
     def add(self, dL_dmean2D, radii):
         """infer_batch.py:311-312: max_radii2D update + add_densification_stats for the Gaussians with radii > 0."""
@@ -126,12 +128,73 @@ def plan(xyz, rotation, opacity_logit, log_scale, state, cfg, generator=None):
                 n_clone=n_c, n_split=n_s, n_pruned=int((~keep).sum()) - n_s)
 
 
+class _PlanBuffers:
+    """Scratch and outputs of igs_densify_plan for P Gaussians (capacity 2 P rows: a Gaussian is cloned or split, never both)."""
+
+    def __init__(self, P, device, scratch_bytes):
+        self.P = P
+        self.scratch = torch.empty(max(int(scratch_bytes), 1), dtype=torch.uint8, device=device)
+        self.rows = torch.empty((3, 2 * P), dtype=torch.int32, device=device)           # src, fresh, ovr
+        self.children = torch.empty((2, 2 * P, 3), dtype=torch.float32, device=device)  # ovr_xyz, ovr_scale
+        self.counts = torch.zeros(4, dtype=torch.int32, device=device)
+
+
+def plan_native(xyz, rotation, opacity_logit, log_scale, state, cfg, generator=None, normals=None):
+    """`plan` as a few HIP launches (igs_densify_plan) and ONE device-to-host copy, of the four counts.  Same dict, same rows in the
+    same order; child c of Gaussian i is sampled from normals[i, c] ([P, 2, 3] standard-normal draws, drawn here from `generator` when
+    not given: the same distribution as `plan`'s torch.normal over the split sources, other draws).  Ties at the max-points cut go to
+    the lowest index.  The arrays are views of the state's buffers (DensifyState.plan_bufs, sized for P): the next call on the same
+    state overwrites them.  There is no CPU fallback."""
+    P = xyz.shape[0]
+    ins = dict(xyz=(xyz, (P, 3)), rotation=(rotation, (P, 4)), opacity_logit=(opacity_logit, None), log_scale=(log_scale, (P, 3)),
+               grad_accum=(state.grad_accum, None), denom=(state.denom, None))
+    if normals is not None:
+        ins["normals"] = (normals, (P, 2, 3))
+    for name, (t, shape) in ins.items():
+        if not t.is_cuda:
+            raise RuntimeError("plan_native: %s is a CPU tensor; the native plan runs on the GPU only (densify.plan is the PyTorch one)" % name)
+        if t.dtype != torch.float32:
+            raise NotImplementedError("plan_native: %s is %s, only float32 is implemented" % (name, t.dtype))
+        if t.device != xyz.device:
+            raise RuntimeError("plan_native: %s is on %s, xyz on %s" % (name, t.device, xyz.device))
+        if (tuple(t.shape) != shape) if shape is not None else (t.numel() != P):
+            raise ValueError("plan_native: %s has shape %s for P = %d" % (name, tuple(t.shape), P))
+    dev = xyz.device
+    L = _cabi.lib()
+    if P == 0:
+        zi, zf = torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros((0, 3), dtype=torch.float32, device=dev)
+        return dict(src=zi, fresh=zi.clone(), ovr=zi.clone(), ovr_xyz=zf, ovr_scale=zf.clone(), n_clone=0, n_split=0, n_pruned=0)
+    bufs = getattr(state, "plan_bufs", None)
+    if bufs is None or bufs.P != P or bufs.scratch.device != dev:
+        nbytes = L.igs_densify_plan_scratch_bytes(P)
+        if nbytes == 0:
+            raise RuntimeError("igs_densify_plan: P = %d out of range" % P)
+        bufs = _PlanBuffers(P, dev, nbytes)
+        if hasattr(state, "plan_bufs"):
+            state.plan_bufs = bufs
+    with torch.cuda.device(dev):
+        if normals is None:
+            normals = torch.randn((P, 2, 3), generator=generator, device=dev)
+        t = [v.contiguous() for v in (xyz, rotation, opacity_logit, log_scale, state.grad_accum, state.denom, normals)]
+        world = 0.1 * cfg.extent if cfg.max_screen_size else 0.0
+        rc = L.igs_densify_plan(torch.cuda.current_stream(dev).cuda_stream, P, *[v.data_ptr() for v in t], cfg.grad_threshold,
+                                cfg.min_opacity, cfg.percent_dense * cfg.extent, world, int(cfg.max_num) - P, int(bool(cfg.control_max)),
+                                bufs.scratch.data_ptr(), bufs.rows[0].data_ptr(), bufs.rows[1].data_ptr(), bufs.rows[2].data_ptr(),
+                                bufs.children[0].data_ptr(), bufs.children[1].data_ptr(), bufs.counts.data_ptr())
+        if rc != 0:
+            raise RuntimeError("igs_densify_plan failed: %d (%s)" % (rc, _cabi.last_error()))
+        P_new, n_c, n_s, n_p = bufs.counts.tolist()          # the one host wait of the event
+    return dict(src=bufs.rows[0, :P_new], fresh=bufs.rows[1, :P_new], ovr=bufs.rows[2, :P_new], ovr_xyz=bufs.children[0, :2 * n_s],
+                ovr_scale=bufs.children[1, :2 * n_s], n_clone=n_c, n_split=n_s, n_pruned=n_p)
+
+
 def densify_and_prune(params, state, cfg, generator=None):
-    """Applies `plan` to a GaussianParams store in place (new flat param / exp_avg / exp_avg_sq buffers, statistics reset).
-    Returns the plan (for logging / tests)."""
+    """Applies `plan` (`plan_native` with cfg.native) to a GaussianParams store in place (new flat param / exp_avg / exp_avg_sq
+    buffers, statistics reset).  Returns the plan (for logging / tests)."""
     L = _cabi.lib()
     lv = params.leaves
-    pl = plan(lv["xyz"].detach(), lv["rotation"].detach(), lv["opacity"].detach(), lv["scaling"].detach(), state, cfg, generator)
+    plan_fn = plan_native if cfg.native else plan
+    pl = plan_fn(lv["xyz"].detach(), lv["rotation"].detach(), lv["opacity"].detach(), lv["scaling"].detach(), state, cfg, generator)
     P_new = int(pl["src"].numel())
     dev = params.device
     per = sum(k for _, k in GROUPS)

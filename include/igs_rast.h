@@ -975,11 +975,39 @@ int igs_mlp_heads_bwd(void* stream, long long N, int dtype, int act, int n_hidde
  * igs_densify_remap: rebuilds the flat optimiser state (param / exp_avg / exp_avg_sq, five groups at off_*[5] = xyz, rotation,
  *   shs, opacity, scaling) after clone / split / prune in one pass: new Gaussian i copies old Gaussian src[i]; fresh[i] != 0
  *   zeroes its Adam moments; ovr[i] >= 0 takes position and log-scale from row ovr[i] of ovr_xyz / ovr_scale (split children).
- *   The selection itself (masks, top-k, sampling) is host logic: igs_amd/densify.py. */
+ *   The selection itself (masks, top-k, sampling) is host logic (igs_amd/densify.py: plan) or igs_densify_plan below. */
 int igs_densify_stats(void* stream, int P, const float* dL_dmean2D, const int* radii, float* grad_accum, float* denom, float* max_radii);
 int igs_densify_remap(void* stream, int P_new, int M, const int* src, const int* fresh, const int* ovr, const float* ovr_xyz,
                       const float* ovr_scale, const float* param_old, const float* exp_avg_old, const float* exp_avg_sq_old,
                       const size_t* off_old, float* param_new, float* exp_avg_new, float* exp_avg_sq_new, const size_t* off_new);
+
+/* igs_densify_plan (densify.hip): the densify-and-prune decision on the device -- what igs_amd/densify.py: plan computes with PyTorch
+ * (gaussian_model.py:586-663), as the gather plan igs_densify_remap executes.  All inputs are float32 device arrays of the P current
+ * Gaussians: the raw leaves xyz [P,3], rotation [P,4] (w, x, y, z; normalised here), opacity_logit [P], log_scale [P,3], the statistics
+ * grad_accum [P] and denom [P], and normals [P,2,3], the standard-normal draw of child c of Gaussian i at [i][c] (NULL: zeros, for calls
+ * in which nothing can split).
+ *   - g = grad_accum / denom; a NaN (0/0) and a negative value count as 0, +inf stays.  Candidate: g >= grad_threshold.
+ *   - control_max != 0 and more than max_num_add candidates: only the max_num_add candidates with the largest g stay, ties at the cut
+ *     going to the lowest index (torch.topk leaves them unspecified); none stay for max_num_add <= 0.
+ *   - big = max_c exp(log_scale[c]) > split_scale_limit (= percent_dense * extent).  A candidate that is not big is cloned (the row is kept
+ *     and copied), a big one is split: the original leaves and two children take its place.  Child c of the j-th split source (ascending
+ *     index) is row c * n_split + j of ovr_xyz / ovr_scale:  ovr_xyz = R(q / |q|) (normals[i][c] * exp(log_scale)) + xyz,
+ *     ovr_scale = log(exp(log_scale) / 1.6).  All 2 n_split rows are written.
+ *   - A row is pruned when sigmoid(opacity_logit) of its source < min_opacity, and, with world_scale_limit > 0 (= 0.1 * extent), when its
+ *     own largest scale (the child's for children) exceeds that limit.
+ *   - Output: rows 0 .. P_new - 1 of src / fresh / ovr (capacity 2 P each; ovr_xyz / ovr_scale: [2 P, 3]) in the order of `plan`: the
+ *     surviving originals by index, the surviving clones by index, the surviving children with c = 0, then those with c = 1.
+ *     src = source row, fresh = 1 for clones and children, ovr = the child's row of ovr_xyz / ovr_scale, else -1.
+ *     counts (device int[4]) = {P_new, n_clone, n_split, n_pruned}; n_pruned counts the removed rows other than the split originals.
+ *   - scratch: igs_densify_plan_scratch_bytes(P) bytes (0 for P out of range: 0 <= P <= 2^28), not initialised by the caller.
+ *   - 9 launches with control_max, 4 without; no host wait, no atomics that decide an order: two calls give identical bits.
+ *   - Refused with IGS_RAST_E_INVALID and a message before any HIP call: P out of range, a grad_threshold that is not finite and > 0,
+ *     with P > 0 a NULL pointer other than normals.  P == 0 returns 0, launches nothing and writes nothing. */
+size_t igs_densify_plan_scratch_bytes(int P);
+int igs_densify_plan(void* stream, int P, const float* xyz, const float* rotation, const float* opacity_logit, const float* log_scale,
+                     const float* grad_accum, const float* denom, const float* normals, float grad_threshold, float min_opacity,
+                     float split_scale_limit, float world_scale_limit, long long max_num_add, int control_max, void* scratch,
+                     int* src, int* fresh, int* ovr, float* ovr_xyz, float* ovr_scale, int* counts);
 
 /* Fused activations applied outside the rasterizer (igs/models/gaussian_model.py:90-127): opacity = sigmoid(logit),
  * scale = exp(log_scale), rotation = F.normalize(rot) (eps 1e-12); and their backward. */
