@@ -212,12 +212,23 @@ preprocess_body(const FwdParams& p, const uint32_t blk, float* __restrict__ rec,
         // extract_view_colors read a row under `radii[idx] > 0`, and the workspace's contents are undefined on entry anyway.  A view
         // culls ~60 % of the Gaussians, in Morton order by whole waves, and the stores of those waves stood in front of the parameter
         // loads of the waves behind them (profiles/front_end_split.txt)
-        if (my_seen && idx >= p.zero_gacc_first) {            // (masked refine step: rows exist for the trainable Gaussians only)
-            float4* Z4 = (float4*)(p.zero_gacc + (size_t)(idx - p.zero_gacc_first) * p.zero_gacc_stride);
+        // WHO FILLS WHEN: this role, on every path that has a zero_gacc (slab and radix binning, every attempt of a redone frame), after
+        // its loads and before its binning; nobody else.  HOW: the 64 rows of a wave are ONE span of 64 x stride doubles, and the wave
+        // stores it coalesced -- lane l of store k writes the 16-byte unit 64 k + l (two doubles) if the row that unit belongs to is a
+        // seen one; a row is owned by stride / 2 neighbouring lanes.  stride / 2 store instructions of 1 KB of consecutive addresses
+        // each, where one row per lane (64 stores of 16 B, 128 / 256 bytes apart, per instruction: ~0.7 M partial-line write requests a
+        // view) stood in front of the role's own parameter loads and kept its last wave 7-8 us longer (profiles/front_end_fill.txt).  As extra workgroups of the tile
+        // sort the same stores cost that launch what they save here (measured there too; not built).
+        const unsigned long long seen = __ballot(my_seen && idx >= p.zero_gacc_first);      // (masked refine step: rows exist for the trainable Gaussians only)
+        if (seen) {
+            const uint32_t lane_ = threadIdx.x & 63, lpr = (uint32_t)p.zero_gacc_stride / 2u;      // lanes per row (8 or 16)
+            const long long row0 = (long long)blk * 256 + (threadIdx.x & ~63u) - p.zero_gacc_first;      // (< 0 where the wave straddles the first row: those rows' bits are clear)
+            float4* span = (float4*)(p.zero_gacc + row0 * p.zero_gacc_stride);
             const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int k = 0; k < GACC_F / 2; k++)            // (16 bytes = two doubles per store)
-                if (2 * k < p.zero_gacc_stride) Z4[k] = z;
+            for (uint32_t k = 0; k < lpr; k++) {
+                const uint32_t u = 64u * k + lane_;                // its row, u / lpr, is one of the wave's 64
+                if ((seen >> (u / lpr)) & 1ull) span[u] = z;
+            }
         }
         if (blk == 0 && threadIdx.x < 64) {
             p.zero_loss[16 * threadIdx.x] = 0.f;
