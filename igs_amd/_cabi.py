@@ -138,6 +138,9 @@ SIGNATURES = {
     "igs_modln_bwd_scratch_bytes": (_sz, [_i] * 4),
     "igs_modln_fwd": (_i, [_vp] + [_i] * 5 + [_vp] + [_ll] * 4 + [_i] + [_vp] * 3 + [_f] + [_vp] * 3),
     "igs_modln_bwd": (_i, [_vp] + [_i] * 5 + [_vp] + [_ll] * 4 + [_i] + [_vp] * 11),
+    # cond_fused.hip
+    "igs_condition3d_pack_elems": (_ll, [_i] * 3),
+    "igs_condition3d_fwd": (_i, [_vp] + [_i] * 8 + [_vp] + [_ll] * 4 + [_vp] * 2 + [_i] + [_vp] * 4 + [_f] + [_vp]),
     # attn.hip
     "igs_attn_bwd_scratch_bytes": (_sz, [_i] * 6),
     "igs_attn_fwd": (_i, [_vp] + [_i] * 6 + ([_vp] + [_ll] * 3) * 3 + [_f] + [_vp] + [_ll] * 3 + [_vp]),

@@ -25,13 +25,11 @@
 // per SIMD at up to 256 registers, so that one workgroup computes while the other stages its next layer, and so that the rows are dealt
 // in trips of 128 (this kernel is bound by the matrix pipe: a SIMD's share of the tiles is what its time is made of).  A workgroup loops
 // over trips of 32 rows per wave; the grid is at most what the chip holds at once.
-#include "attn_common.h"
+#include "mlp_common.h"                   // MlpIn, mlp_mm, mlp_silu, MLP_TILE, mlp_tiles, mlp_cus
 #include "host_api.h"
 
-#define MLP_CUS 256                        // the compute units of an MI355X, where the device cannot be asked (mlp_cus)
 // GROUPS_PER_CU: the workgroups a compute unit holds at once; more than that would only stage the weights again
 template <typename T> struct MlpCfg { enum { WAVES = AttnCfg<T>::HALF ? 16 : 4, THREADS = 64 * WAVES, TRIP_ROWS = 32 * WAVES, GROUPS_PER_CU = AttnCfg<T>::HALF ? 1 : 2 }; };
-#define MLP_TILE 1024                      // elements of one packed 32x32 weight tile
 #define MLP_MAX_LINEARS (IGS_MLP_MAX_HIDDEN + 1)
 
 struct MlpArgs {
@@ -48,52 +46,6 @@ struct MlpArgs {
     void* out[IGS_MLP_MAX_HEADS];
 };
 
-// the activations of 32 rows as the next product's B operand: element e of 32-channel tile k is channel 32 k + attn_row(e, h)
-template <typename T> struct MlpIn;
-template <> struct MlpIn<float> {
-    float v[4][16];
-    __device__ __forceinline__ void set(int k, int e, float f) { v[k][e] = f; }
-};
-template <> struct MlpIn<_Float16> {
-    attn_h8 v[4][2];
-    __device__ __forceinline__ void set(int k, int e, float f) { v[k][e >> 3][e & 7] = (_Float16)f; }     // the one rounding to half
-};
-
-// o += W tile x the activations' tile k
-__device__ __forceinline__ attn_acc mlp_mm(const _Float16* tile, int lane, const MlpIn<_Float16>& in, int k, attn_acc o)
-{
-#pragma unroll
-    for (int s = 0; s < 2; s++) o = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const attn_h8*)(tile + (s * 64 + lane) * 8), in.v[k][s], o, 0, 0, 0);
-    return o;
-}
-__device__ __forceinline__ attn_acc mlp_mm(const float* tile, int lane, const MlpIn<float>& in, int k, attn_acc o)
-{
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-        const attn_f4 w = *(const attn_f4*)(tile + (g * 64 + lane) * 4);
-#pragma unroll
-        for (int u = 0; u < 4; u++) o = __builtin_amdgcn_mfma_f32_32x32x2f32(w[u], in.v[k][4 * g + u], o, 0, 0, 0);
-    }
-    return o;
-}
-
-// v sigmoid(v).  exp(-v) = exp2(t) (1 + tl ln 2) with t + tl = -v log2(e) to about 2^-48 relative: the product's rounding error comes back
-// through the fma, so the argument's error does not grow with |v|.  v_exp_f32 and v_rcp_f32 are within 1 ulp each; with the rounding of
-// 1 + e and of the last product the result is within 6 u (1 + small) of v sigmoid(v), u = 2^-24 (tests/decoder_restatement.py takes a = 8).
-// sigmoid is taken of v held to [-128, 128] (beyond, it is 0 or 1 to float32 anyway) and the exponent is held at 126, so that t, tl, e,
-// its correction and 1 + e stay finite for every v: below v = -87.3 the result is v / (1 + 2^126 (1 + tl ln 2)), within |v| 2^-126 of the
-// true value (which is smaller still), never inf * c + inf = NaN; above 128 exp2 underflows to 0 and the result is v.  The last product
-// takes v itself, so an infinity stays one on the positive side (-inf gives -inf * tiny = -inf where PyTorch gives NaN) and a NaN a NaN.
-__device__ __forceinline__ float mlp_silu(float v)
-{
-    const float L = -1.4426950408889634f, Ll = -1.9259629911266175e-8f;      // -log2(e) = L + Ll
-    const float c = __builtin_amdgcn_fmed3f(v, -128.f, 128.f);
-    const float t = c * L;
-    const float tl = fmaf(c, L, -t) + c * Ll;
-    float e = attn_exp2(t > 126.f ? 126.f : t);
-    e = fmaf(e, tl * 0.6931471805599453f, e);
-    return v * __builtin_amdgcn_rcpf(1.f + e);
-}
 // max(v, 0) that keeps a NaN, as torch.relu does
 __device__ __forceinline__ float mlp_relu(float v) { return v < 0.f ? 0.f : v; }
 
@@ -583,22 +535,6 @@ __global__ __launch_bounds__(256) void mlp_bwd_reduce_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------------------------------------------
 // the entry points (the contract is in include/igs_rast.h)
 // ---------------------------------------------------------------------------------------------------------------------------------
-static int mlp_tiles(int c) { return (c + 31) / 32; }
-
-// the compute units of the current device (a partition in the CPX modes has fewer than the whole chip), asked once per device
-static int mlp_cus()
-{
-    static int cus[64];
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return MLP_CUS;
-    if (cus[d] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n < 1) return MLP_CUS;
-        cus[d] = n;
-    }
-    return cus[d];
-}
-
 // the sizes of a decoder, or what is wrong with them
 static const char* mlp_size_error(int n_hidden, const int* widths, int n_heads, const int* head_widths, int* head_sum)
 {

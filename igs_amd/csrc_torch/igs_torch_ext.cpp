@@ -13,6 +13,7 @@
 //   interpolation       motion.hip              motion_interp_fwd / _index / _bwd
 //   lifting             lift.hip                motion_lift_fwd / _bwd
 //   condition3D         cond.hip                cond_ray_fwd, modln_fwd / _bwd
+//                       cond_fused.hip          _cond.condition3d_fwd, _cond.pack_elems: the forward in one launch, ModLN's MLP included
 //   attention           attn.hip                attn_fwd / _bwd on [B, H, A, 64] views of any acceptable strides
 //   window attention    wattn.hip               _window.window_attn_fwd / _bwd on [B, h w, 128] views of any acceptable strides
 //   encoder norms       inorm.hip               _encoder.instance_norm_fwd, _encoder.position_add on contiguous [N, C, H, W] tensors
@@ -674,6 +675,44 @@ std::tuple<OptTensor, OptTensor, OptTensor, OptTensor> modln_bwd(const Tensor& x
                         gc.data_ptr<float>(), ptr_or_null(dx), ptr_or_null(dmod), ptr_or_null<float>(dw), ptr_or_null<float>(db),
                         ptr_or_null(scratch)), "igs_modln_bwd");
     return {dx, dmod, dw, db};
+}
+
+// ---- condition3D in one launch (cond_fused.hip) ----
+int64_t cond_fused_pack_elems(int64_t C, int64_t hidden, bool half)
+{
+    return igs_condition3d_pack_elems((int)C, (int)hidden, half ? IGS_DTYPE_F16 : IGS_DTYPE_F32);
+}
+// out [N, C, H, W] float32 contiguous.  x [N, C, H, W] float32 / float16 with contiguous H x W planes, rays [N, H, W, 6] and depth
+// [N, Hd, Wd] float32, wpack (float32 or float16: the MLP instance) and bpack [3, 128] as igs_condition3d_fwd takes them
+// (igs_amd/motion.py packs and caches them), weight, bias [C] float32: the LayerNorm's
+Tensor condition3d_fwd(const Tensor& x, const Tensor& rays, const Tensor& depth, const Tensor& wpack, const Tensor& bpack, int64_t hidden,
+                       const Tensor& weight, const Tensor& bias, double eps)
+{
+    const char* fn = "condition3d_fwd";
+    const int xdt = dtype_code(x, fn, "x"), mdt = dtype_code(wpack, fn, "wpack");
+    if (x.dim() != 4) throw RasterizerError(std::string(fn) + ": x must have shape [N, C, H, W] (got " + c10::str(x.sizes()) + ")");
+    const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+    expect(rays, fn, "rays", at::kFloat, {N, H, W, 6});
+    expect(depth, fn, "depth", at::kFloat, {N, -1, -1});
+    expect(weight, fn, "weight", at::kFloat, {C});
+    expect(bias, fn, "bias", at::kFloat, {C});
+    const int64_t Hd = depth.size(1), Wd = depth.size(2);
+    if (H < 1 || W < 1 || Hd < 1 || Wd < 1 || H > IGS_COND_MAX_HW || W > IGS_COND_MAX_HW || Hd > IGS_COND_MAX_HW || Wd > IGS_COND_MAX_HW ||
+        N * H * W > IGS_COND_MAX_PIXELS)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (1 <= H, W, Hd, Wd <= 8192, N * H * W <= 2^24)");
+    const int64_t elems = C >= 1 && C <= INT_MAX && hidden >= 1 && hidden <= INT_MAX ? igs_condition3d_pack_elems((int)C, (int)hidden, mdt) : -1;
+    if (elems < 0) throw RasterizerError(std::string(fn) + ": C and hidden must be in 1..128 (got " + std::to_string(C) + ", " + std::to_string(hidden) + ")");
+    expect(wpack, fn, "wpack", wpack.scalar_type(), {elems});
+    expect(bpack, fn, "bpack", at::kFloat, {3, IGS_COND_MLP_MAX_WIDTH});
+    if (!wpack.is_contiguous() || !bpack.is_contiguous()) throw RasterizerError(std::string(fn) + ": wpack and bpack must be contiguous");
+    const GpuCall c(x, fn, "x", {{rays, "rays"}, {depth, "depth"}, {wpack, "wpack"}, {bpack, "bpack"}, {weight, "weight"}, {bias, "bias"}});
+    Tensor out = at::empty({N, C, H, W}, x.options().dtype(at::kFloat));
+    if (N == 0) return out;
+    const Tensor rc = rays.contiguous(), dc = depth.contiguous(), wc = weight.contiguous(), bc = bias.contiguous();
+    check(igs_condition3d_fwd(c.stream(), (int)N, (int)C, (int)hidden, (int)H, (int)W, (int)Hd, (int)Wd, xdt, x.data_ptr(), x.stride(0), x.stride(1),
+                              x.stride(2), x.stride(3), rc.data_ptr<float>(), dc.data_ptr<float>(), mdt, wpack.data_ptr(), bpack.data_ptr<float>(),
+                              wc.data_ptr<float>(), bc.data_ptr<float>(), (float)eps, out.data_ptr<float>()), "igs_condition3d_fwd");
+    return out;
 }
 
 // ---- fused attention for the anchor transformer (attn.hip; contract in include/igs_rast.h) ----
@@ -1488,6 +1527,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
               "want_weight"_a = true, "want_bias"_a = true);
     def_nogil(gn, "tokens_add_residual", &tokens_add_residual, "tokens"_a, "residual"_a, "out_half"_a = false);
     // ... and the residual decoder
+    py::module_ cf = m.def_submodule("_cond", "condition3D's forward in one launch, ModLN's MLP included (cond_fused.hip)");
+    def_nogil(cf, "condition3d_fwd", &condition3d_fwd, "x"_a, "rays"_a, "depth"_a, "wpack"_a, "bpack"_a, "hidden"_a, "weight"_a, "bias"_a, "eps"_a = 1e-6);
+    def_nogil(cf, "pack_elems", &cond_fused_pack_elems, "C"_a, "hidden"_a, "half"_a = false);
     py::module_ ml = m.def_submodule("_mlp", "the residual decoder: MLP and output heads in one launch (mlp.hip)");
     def_nogil(ml, "mlp_heads_fwd", &mlp_heads_fwd, "x"_a, "wpack"_a, "bpack"_a, "widths"_a, "act_after"_a, "head_widths"_a, "act"_a = 0);
     ml.def("pack_elems", &mlp_pack_elems, "widths"_a, "head_widths"_a);

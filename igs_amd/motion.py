@@ -14,7 +14,8 @@ anchors (igs/models/grid_encoder.py:66-88 over igs/utils/ops.py:444-477; igs_amd
 
 `ray_condition` / `modln` / `condition3d` are the step in front of the lift: IGS.condition3D (igs/IGS.py:185-210 with ray_to_plucker,
 rsh_cart_3 and ModLN; igs_amd/csrc/cond.hip).  The ray embedding and the fused LayerNorm + adaLN modulation are native, ModLN's small MLP
-between them stays PyTorch.
+between them stays PyTorch: the path with autograd.  `condition3d_fused` / `use_native_condition3d` are the same stage's forward in one
+launch, the MLP on the matrix cores included (igs_amd/csrc/cond_fused.hip): forward only, for the streaming path under torch.no_grad().
 
 Deviations from the reference lines (INTEGRATION.md lists them):
   - condition3d returns the reference's shape, dtype and values NCHW-contiguous, where the reference returns a channels-last-strided
@@ -289,6 +290,151 @@ def condition3d(motion_feature, rays, depth, modln_module):
     cond = ray_condition(rays, depth, motion_feature.shape[-2:])
     mod = modln_module.mlp(cond)
     return modln(motion_feature, mod, norm.weight, norm.bias, norm.eps)
+
+
+# ---------------------------------------------------------------- condition3D in one launch (cond_fused.hip)
+COND_CH, COND_MLP_MAX_WIDTH = 33, 128                           # IGS_COND_MLP_MAX_WIDTH
+COND_FUSED_MAX_STRIDE = 1 << 27                                 # IGS_COND_FUSED_MAX_STRIDE
+COND_FUSED_CACHE = "_igs_condition3d_pack"
+MODLN_NAME = "ModLN"                                            # IGS.ModLN (IGS.py:91-95)
+# What use_native_condition3d sends to the fused kernel: per MLP dtype the largest N * H * W it takes (None: no limit, 0: never).
+# DESIGN.md 15.7 has the measurements this follows: the fused forward is the faster one in every measured case.
+COND_FUSED_MAX_PIXELS = {torch.float32: None, torch.float16: None}
+
+
+def _cond_mlp_spec(fn, modln_module, C):
+    """(Linear(33, hidden), Linear(hidden, 2C)) of a ModLN-shaped module, or NotImplementedError."""
+    nn = torch.nn
+    mlp = getattr(modln_module, "mlp", None)
+    mods = list(mlp) if isinstance(mlp, nn.Sequential) else []
+    if len(mods) != 3 or not (isinstance(mods[0], nn.Linear) and isinstance(mods[1], nn.SiLU) and isinstance(mods[2], nn.Linear)):
+        raise NotImplementedError(f"{fn}: .mlp must be nn.Sequential(Linear(33, hidden), SiLU, Linear(hidden, 2C))")
+    l0, l2 = mods[0], mods[2]
+    if l0.in_features != COND_CH or l2.in_features != l0.out_features or l2.out_features != 2 * C:
+        raise NotImplementedError(f"{fn}: .mlp must map 33 -> hidden -> 2C = {2 * C} (got {l0.in_features} -> {l0.out_features}, "
+                                  f"{l2.in_features} -> {l2.out_features})")
+    if not (1 <= C <= COND_MLP_MAX_WIDTH and 1 <= l0.out_features <= COND_MLP_MAX_WIDTH):
+        raise NotImplementedError(f"{fn}: C and hidden must be in 1..{COND_MLP_MAX_WIDTH} (got {C}, {l0.out_features})")
+    return l0, l2
+
+
+def _cond_params(modln_module):
+    mlp, norm = modln_module.mlp, modln_module.norm
+    return [mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias, norm.weight, norm.bias]
+
+
+def pack_condition_mlp(mlp, dtype=torch.float32):
+    """(wpack in `dtype`, bpack float32 [3, 128]) as igs_condition3d_fwd takes them (include/igs_rast.h), from
+    mlp = nn.Sequential(Linear(33, hidden), SiLU, Linear(hidden, 2C)): W1, W2[:C] (shift) and W2[C:] (scale), each in
+    pack_mlp_tile_order, one after another; the biases b1, b2[:C], b2[C:] zero-padded (an absent bias: zeros).  Plain tensor ops."""
+    l0, l2 = mlp[0], mlp[2]
+    hidden, C = l0.out_features, l2.out_features // 2
+    W1, W2 = l0.weight.detach().to(dtype), l2.weight.detach().to(dtype)
+    wpack = torch.cat([pack_mlp_tile_order(W1), pack_mlp_tile_order(W2[:C]), pack_mlp_tile_order(W2[C:])]).contiguous()
+    bpack = torch.zeros(3, COND_MLP_MAX_WIDTH, dtype=torch.float32, device=wpack.device)
+    if l0.bias is not None:
+        bpack[0, :hidden] = l0.bias.detach().float()
+    if l2.bias is not None:
+        bpack[1, :C] = l2.bias.detach().float()[:C]
+        bpack[2, :C] = l2.bias.detach().float()[C:]
+    return wpack, bpack
+
+
+def condition3d_fused(motion_feature, rays, depth, modln_module, packed=None, mlp_dtype=None):
+    """condition3d's result in one launch, forward only: the ray / depth condition, ModLN's MLP and the modulated LayerNorm per pixel,
+    with neither cond, the hidden activations nor mod stored (igs_condition3d_fwd, cond_fused.hip).  motion_feature [B*V, C, H, W] float32
+    / float16 (plane-contiguous NCHW is read in place, anything else is copied), rays [B, V, H, W, 6], depth [B, V, Hd, Wd] float32;
+    out float32, NCHW-contiguous.  modln_module: .norm as condition3d takes it, .mlp = nn.Sequential(Linear(33, hidden), SiLU,
+    Linear(hidden, 2C)) with C, hidden <= 128.  mlp_dtype: torch.float32 (an exact float32 fma chain) or torch.float16 (half operands,
+    float32 accumulation; mod is not rounded to half); default float16 under autocast to half, float32 otherwise.  packed:
+    pack_condition_mlp(modln_module.mlp, mlp_dtype), packed here when absent.  The argument checks are condition3d's; another .mlp
+    structure, C or hidden out of range, or anything that requires grad under enabled grad raise NotImplementedError."""
+    fn = "condition3d_fused"
+    if motion_feature.dim() != 4:
+        raise ValueError(f"{fn}: motion_feature must be [B*V, C, H, W] (got {list(motion_feature.shape)})")
+    norm = modln_module.norm
+    N, C, H, W = motion_feature.shape
+    if tuple(norm.normalized_shape) != (C,):
+        raise ValueError(f"{fn}: the module normalises {tuple(norm.normalized_shape)}, motion_feature has C = {C}")
+    if norm.weight is None or norm.bias is None:
+        raise NotImplementedError(f"{fn}: LayerNorm without affine parameters is not supported")
+    if rays.dim() != 5 or rays.shape[-1] != 6:
+        raise ValueError(f"{fn}: rays must be [B, V, H, W, 6] (got {list(rays.shape)})")
+    if rays.shape[0] * rays.shape[1] != N:
+        raise ValueError(f"{fn}: rays {list(rays.shape)} do not match {N} views")
+    if depth.dim() != 4 or tuple(depth.shape[:2]) != tuple(rays.shape[:2]):
+        raise ValueError(f"{fn}: depth must be [B, V, Hd, Wd] with B, V = {list(rays.shape[:2])} (got {list(depth.shape)})")
+    if tuple(rays.shape[2:4]) != (H, W):
+        raise ValueError(f"{fn}: rays are at {list(rays.shape[2:4])}, the feature resolution is {[H, W]}")
+    if rays.dtype != torch.float32 or depth.dtype != torch.float32:
+        raise NotImplementedError(f"{fn}: rays and depth must be float32 (got {rays.dtype}, {depth.dtype})")
+    if motion_feature.dtype not in FEATURE_DTYPES:
+        raise NotImplementedError(f"{fn}: motion_feature must be float32 or float16 (got {motion_feature.dtype})")
+    if norm.weight.dtype != torch.float32 or norm.bias.dtype != torch.float32:
+        raise NotImplementedError(f"{fn}: the LayerNorm's weight and bias must be float32 (got {norm.weight.dtype}, {norm.bias.dtype})")
+    l0, _ = _cond_mlp_spec(fn, modln_module, C)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [motion_feature, rays, depth] + _cond_params(modln_module)):
+        raise NotImplementedError(f"{fn}: forward only -- call it under torch.no_grad(), and train with condition3d")
+    if not (motion_feature.is_cuda and rays.is_cuda and depth.is_cuda):
+        raise RuntimeError(f"{fn}: tensors must be on a GPU (no CPU fallback)")
+    if mlp_dtype is None:
+        mlp_dtype = torch.float16 if _autocast_half(fn, motion_feature) else torch.float32
+    if mlp_dtype not in FEATURE_DTYPES:
+        raise NotImplementedError(f"{fn}: mlp_dtype must be float32 or float16 (got {mlp_dtype})")
+    wpack, bpack = pack_condition_mlp(modln_module.mlp, mlp_dtype) if packed is None else packed
+    if wpack.dtype != mlp_dtype:
+        raise ValueError(f"{fn}: packed holds {wpack.dtype} weights, mlp_dtype is {mlp_dtype}")
+    x = motion_feature
+    if not _plane_contiguous(x) or (C > 1 and x.stride(1) > COND_FUSED_MAX_STRIDE):
+        x = x.contiguous()
+    return _ext()._cond.condition3d_fwd(x, rays.reshape(N, *rays.shape[2:]), depth.reshape(N, *depth.shape[2:]), wpack, bpack, l0.out_features,
+                                  norm.weight.detach(), norm.bias.detach(), float(norm.eps))
+
+
+def _condition3d_bound(self, motion_feature, rays, depth):
+    """IGS.condition3D as use_native_condition3d binds it: the fused forward when nothing needs a gradient and the module qualifies,
+    condition3d (ray_condition -> the PyTorch MLP -> modln, with autograd) otherwise."""
+    fn = "condition3D"
+    module = _child(self, MODLN_NAME)
+    try:
+        params = _cond_params(module)
+    except (AttributeError, IndexError, TypeError):
+        return condition3d(motion_feature, rays, depth, module)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [motion_feature, rays, depth] + params):
+        return condition3d(motion_feature, rays, depth, module)
+    try:
+        _cond_mlp_spec(fn, module, motion_feature.shape[1] if motion_feature.dim() == 4 else -1)
+    except NotImplementedError:
+        return condition3d(motion_feature, rays, depth, module)
+    dtype = torch.float16 if _autocast_half(fn, motion_feature) else torch.float32
+    limit = COND_FUSED_MAX_PIXELS[dtype]
+    if limit is not None and motion_feature.numel() // max(motion_feature.shape[1], 1) > limit:
+        return condition3d(motion_feature, rays, depth, module)
+    key = (_param_key(params[:4]), dtype)
+    cache = module.__dict__.get(COND_FUSED_CACHE)
+    if cache is None or cache["key"] != key:
+        cache = dict(key=key, pack=pack_condition_mlp(module.mlp, dtype))
+        module.__dict__[COND_FUSED_CACHE] = cache
+    return condition3d_fused(motion_feature, rays, depth, module, packed=cache["pack"], mlp_dtype=dtype)
+
+
+def use_native_condition3d(model):
+    """Binds condition3D(motion_feature, rays, depth) on this IGS-shaped instance (IGS.py:185-210) and returns the instance; the class and
+    state_dict() keys are untouched.  A call under torch.no_grad() (or with nothing that requires grad) on a module whose .ModLN.mlp is
+    Linear(33, hidden) . SiLU . Linear(hidden, 2C) with C, hidden <= 128 takes condition3d_fused -- float16 weights under autocast to half,
+    float32 otherwise, within COND_FUSED_MAX_PIXELS -- and every other call is condition3d, exactly today's training path.  The packed
+    weights are kept on the ModLN module and rebuilt when a parameter's _version, data_ptr, dtype or device changes.  Raises
+    NotImplementedError, before anything is changed, for cfg.local_ray true or cfg.use_condition3d false."""
+    import types
+    cfg = model.cfg
+    if getattr(cfg, "local_ray", False):
+        raise NotImplementedError("use_native_condition3d: local_ray True (the 4-channel condition) is not supported")
+    if not getattr(cfg, "use_condition3d", True):
+        raise NotImplementedError("use_native_condition3d: cfg.use_condition3d is False: the model has no ModLN to bind")
+    if _child(model, MODLN_NAME) is None:
+        raise NotImplementedError(f"use_native_condition3d: the model has no {MODLN_NAME} module")
+    model.condition3D = types.MethodType(_condition3d_bound, model)
+    return model
 
 
 class _Deform(torch.autograd.Function):

@@ -720,6 +720,39 @@ int igs_modln_bwd(void* stream, int N, int C, int H, int W, int x_dtype, const v
                   long long xs_w, int mod_dtype, const void* mod, const float* weight, const float* bias, const float* mean, const float* rstd,
                   const float* gout, void* dx, void* dmod, float* dweight, float* dbias, void* scratch);
 
+/* IGS.condition3D's forward in one launch (cond_fused.hip).  Per pixel of x [N, C, H, W]:
+ *     cond = the 33 channels of igs_ray_condition_fwd, bit for bit (the two kernels share the statements)
+ *     h    = SiLU(W1 cond + b1)                     W1 [hidden, 33]          (ModLN.mlp[0], SiLU = v / (1 + exp(-v)) as igs_mlp_heads_fwd's)
+ *     mod  = W2 h + b2                              W2 [2 C, hidden]         (ModLN.mlp[2]); shift = mod[:C], scale = mod[C:]
+ *     out  = ((x - mu) r weight + bias) (1 + scale) + shift                  mu, r as igs_modln_fwd defines them
+ * Neither cond, h nor mod is stored.  Forward only: no saved statistics, no backward.  Runs on `stream`, reads nothing back, allocates
+ * nothing, uses no atomics: two runs agree bit for bit, and a pixel's result depends on no other pixel, not on the grid and not on N.
+ *   - x in x_dtype (IGS_DTYPE_F32 / IGS_DTYPE_F16, widened on load) under igs_modln_fwd's stride rule (every H x W plane contiguous; xs_n,
+ *     xs_c free); rays [N, H, W, 6], depth [N, Hd, Wd] float32 contiguous as igs_ray_condition_fwd takes them; weight, bias [C] float32 (the
+ *     LayerNorm's); out [N, C, H, W] float32 contiguous.
+ *   - mlp_dtype selects the MLP instance, independently of x_dtype.  IGS_DTYPE_F32: v_mfma_f32_32x32x2_f32 over the first 32 condition
+ *     channels and one fma per hidden channel for the depth channel, an exact float32 fma chain of 34 terms that starts from the bias, then
+ *     v_mfma_f32_32x32x2_f32 for W2; no reduced-precision value anywhere.  IGS_DTYPE_F16: v_mfma_f32_32x32x16_f16, float32 accumulators that
+ *     start from the bias, SiLU in float32; cond and h are rounded to half once each as the next product's operand (a condition value
+ *     beyond the half range becomes inf), mod is NOT rounded: it goes from the accumulators into the float32 modulation.
+ *   - wpack, in mlp_dtype: three Linears, each in igs_mlp_heads_fwd's tile order (ceil(O / 32) x ceil(I / 32) tiles of 1024 elements, output
+ *     tile outermost, tile (ot, kt) = [chunk][lane 64][E], E = 8 (half) or 4 (float), element e = chunk E + j of lane (r, h) =
+ *     W[32 ot + r][32 kt + (e & 3) + 8 (e >> 2) + 4 h], zero outside W), one after another: W1 [hidden, 33] (two k tiles per output tile),
+ *     W2[:C] [C, hidden], W2[C:] [C, hidden].  igs_condition3d_pack_elems(C, hidden, mlp_dtype) = (2 ht + 2 ct ht) 1024 with
+ *     ht = ceil(hidden / 32), ct = ceil(C / 32) is the element count (-1: C or hidden outside 1 .. IGS_COND_MLP_MAX_WIDTH, or an unknown
+ *     dtype code).  bpack: float32 [3][128] = b1, b2[:C], b2[C:], zero-padded.
+ *   - Refused with IGS_RAST_E_INVALID and a message before any HIP call: N, H, W, Hd, Wd outside igs_ray_condition_fwd's limits; C or
+ *     hidden outside 1 .. IGS_COND_MLP_MAX_WIDTH; an unknown dtype code; a stride pattern igs_modln_fwd refuses; xs_c above
+ *     IGS_COND_FUSED_MAX_STRIDE (the kernel adds a lane's channel and pixel offset in 32 bits); eps < 0 or NaN; with N > 0
+ *     a NULL pointer, a pointer not aligned to its element, a wpack not aligned to 16 bytes.  N == 0 returns 0 without a launch.
+ * One persistent workgroup of 8 waves per compute unit keeps the weights in LDS (float32: 147 KB); a wave owns 32 pixels of one image. */
+#define IGS_COND_MLP_MAX_WIDTH 128
+#define IGS_COND_FUSED_MAX_STRIDE (1LL << 27)
+long long igs_condition3d_pack_elems(int C, int hidden, int mlp_dtype);
+int igs_condition3d_fwd(void* stream, int N, int C, int hidden, int H, int W, int Hd, int Wd, int x_dtype, const void* x, long long xs_n,
+                        long long xs_c, long long xs_h, long long xs_w, const float* rays, const float* depth, int mlp_dtype, const void* wpack,
+                        const float* bpack, const float* weight, const float* bias, float eps, float* out);
+
 /* Fused attention for the anchor transformer (attn.hip): out = softmax(scale * Q K^T) V in one pass over the keys, the
  * self-attention of GridEncoder.conv's Transformer1D (igs/models/transformers.py:673-907: 8 heads of 64 channels over 8192 anchors, no mask,
  * no dropout).  The score matrix is never stored.  Everything runs on `stream`, reads nothing back and allocates nothing.
