@@ -100,7 +100,7 @@ SIGNATURES = {
     "igs_l1_mean_fwd_bwd": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "igs_ply_to_params": (_i, [_vp, _i, _vp, _i, _vp, _i, _i] + [_vp] * 5),
     "igs_params_to_ply": (_i, [_vp, _i, _i] + [_vp] * 6),
-    # the fused refine step (api.hip) and the N > 1 exchange (geom_bwd.hip)
+    # the fused refine step (api.hip) and the N > 1 exchange (sh_exchange.hip)
     "igs_refine_step": (_i, [C.POINTER(RefineStepArgs)]),
     "igs_refine_step_args_size": (_sz, []),
     "igs_refine_step_masked": (_i, [C.POINTER(RefineStepArgs), C.POINTER(RefineMaskArgs)]),

@@ -264,6 +264,12 @@ __device__ __forceinline__ void adam_update(float& p, float& m, float& v, float 
     v = b2 * v + (1.f - b2) * g * g;
     p -= lr * m / (sqrtf(v) * inv_sqrt_bc2 + eps);
 }
+// ... on one float4 item of a parameter span, by the one-item update `upd`: adam_update, or one with its contractions pinned
+template <class F>
+__device__ __forceinline__ void adam_update4(F upd, float4& p, float4& m, float4& v, const float4& g, float lr, float b1, float b2, float eps, float inv_sqrt_bc2) {
+    upd(p.x, m.x, v.x, g.x, lr, b1, b2, eps, inv_sqrt_bc2); upd(p.y, m.y, v.y, g.y, lr, b1, b2, eps, inv_sqrt_bc2);
+    upd(p.z, m.z, v.z, g.z, lr, b1, b2, eps, inv_sqrt_bc2); upd(p.w, m.w, v.w, g.w, lr, b1, b2, eps, inv_sqrt_bc2);
+}
 struct M3 { float m[3][3]; };     // standard row-major [row][col]
 
 // The helpers below feed discrete decisions of the per-Gaussian stage (near-plane cull, radius, tile rectangle, depth key):

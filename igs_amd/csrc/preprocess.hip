@@ -1,15 +1,8 @@
 // preprocess.hip -- per-Gaussian forward stage (one thread per Gaussian), gfx950.
 // Replaces FORWARD::preprocess / preprocessCUDA (DGR/cuda_rasterizer/forward.cu:307-423), checkFrustum
 // (rasterizer_impl.cu:54-66) and the tiles_touched reduction that the reference does with cub::DeviceScan.
-#include "geom_math.h"
+#include "sh_math.h"       // (the SH constants; geom_math.h)
 #include <type_traits>
-
-__constant__ float SH_C0 = 0.28209479177387814f;
-__constant__ float SH_C1 = 0.4886025119029199f;
-__constant__ float SH_C2[5] = { 1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f, -1.0925484305920792f,
-                                0.5462742152960396f };
-__constant__ float SH_C3[7] = { -0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
-                                -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f };
 
 // SH -> RGB (forward.cu:23-74).  sh points at this Gaussian's [M][3] coefficients.
 __device__ __forceinline__ float3 sh_to_rgb(int deg, const float* __restrict__ sh, float3 dir, uint32_t& clamped) {

@@ -1,4 +1,4 @@
-"""Float64 restatement of the N > 1 colour exchange (igs_amd/csrc/geom_bwd.hip: sh_grad_views_kernel<ADAM>, behind
+"""Float64 restatement of the N > 1 colour exchange (igs_amd/csrc/sh_exchange.hip: sh_grad_views_kernel<ADAM>, behind
 igs_sh_grad_from_view_colors, igs_adam_sh_from_view_colors and igs_adam_exchange_step), the bounds a float32 evaluation is held to,
 the launch geometry restated, and the seeded cases of tests/test_exchange_host.py (CPU) and tests/test_gpu_exchange_edges.py (MI355X).
 

@@ -36,9 +36,10 @@ def kernel_metadata(code_object):
     return kernels
 
 
-def test_colour_only_geom_bwd_fits_the_bench_grid_in_one_round():
+def geom_bwd_instances():
+    """{kernel symbol: metadata} of every geom_bwd_kernel instance in the built library"""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
-    from igs_amd import build, _cabi
+    from igs_amd import build
     build.build()
     import audit_barriers as A
     tmp, cos = A.code_objects(build.LIB)
@@ -46,10 +47,25 @@ def test_colour_only_geom_bwd_fits_the_bench_grid_in_one_round():
         found = {}
         for co in cos:
             for name, md in kernel_metadata(co).items():
-                if COLOUR_ONLY.match(name):
+                if name.startswith("_Z15geom_bwd_kernelI"):
                     found[name] = md
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
+    return found
+
+
+def test_no_geom_bwd_instance_uses_scratch():
+    """The kernel's phases hand their values on in small structs: none of them may end up in private memory (a runtime-indexed local
+    array would), in any instance: unfused, and fused general / colour-only with and without frozen groups."""
+    found = geom_bwd_instances()
+    assert len(found) == 5, sorted(found)
+    for name, md in found.items():
+        assert int(md[".private_segment_fixed_size"]) == 0, (name, "scratch bytes per lane", md[".private_segment_fixed_size"])
+
+
+def test_colour_only_geom_bwd_fits_the_bench_grid_in_one_round():
+    from igs_amd import _cabi
+    found = {name: md for name, md in geom_bwd_instances().items() if COLOUR_ONLY.match(name)}
     assert len(found) == 2, sorted(found)            # the unmasked and the masked (PARTIAL) instance
     fn = _cabi.lib().igs_geom_bwd_adam_dyn_lds
     fn.restype, fn.argtypes = ctypes.c_size_t, [ctypes.c_int]

@@ -1,5 +1,5 @@
 """The N > 1 colour exchange on the MI355X -- igs_sh_grad_from_view_colors, igs_adam_sh_from_view_colors, igs_adam_exchange_step (both
-instances of sh_grad_views_kernel in igs_amd/csrc/geom_bwd.hip) and the two writers of igs_refine_step's `color_grad_out` -- at the
+instances of sh_grad_views_kernel in igs_amd/csrc/sh_exchange.hip) and the two writers of igs_refine_step's `color_grad_out` -- at the
 sizes, alignments and view counts where the kernels branch, against the float64 restatement of tests/exchange_restatement.py.
 
 Every element is compared.  The allowances are derived, never measured: `rebuild_allowance` (K(V) 2^-24 sum_v B_k |g_v|, K(V) = 25 +
