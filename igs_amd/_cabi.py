@@ -109,7 +109,7 @@ SIGNATURES = {
     "igs_sh_grad_from_view_colors": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp]),
     "igs_adam_sh_from_view_colors": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f]),
     "igs_adam_exchange_step": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp] + [_sz] * 5 + [_f] * 10),
-    # sort.hip
+    # radix_sort.hip (Morton order), tile_sort.hip (debug)
     "igs_morton_order_scratch_bytes": (_sz, [_i]),
     "igs_morton_order": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
     "igs_debug_tile_sort": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i]),

@@ -138,7 +138,7 @@ static hipError_t launch_bbox_select(hipStream_t s, int B, int N, const float* x
     uint32_t* blocksum = (uint32_t*)align_ptr((const char*)scratch);
     const int nb = (N + 255) / 256;
     hipLaunchKernelGGL(select_count_kernel, dim3(nb), dim3(256), 0, s, N, B, xyz, ptr, box, blocksum, count);
-    e = launch_scan_blocksums(s, nb, blocksum);
+    e = launch_exclusive_scan(s, nb, blocksum);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(select_scatter_kernel, dim3(nb), dim3(256), 0, s, N, B, xyz, ptr, box, (const uint32_t*)blocksum, out_xyz, out_idx);
     return hipGetLastError();
@@ -160,7 +160,8 @@ static void fps_geometry(int max_n, int* LS, int* R)
 }
 
 struct FpsLayout {
-    size_t lohi, part, ka, kb, va, vb, hist1, hist2, rowoff, rows, ord, leaf, total;
+    size_t lohi, part, rowoff, rows, ord, leaf, total;
+    RadixOffsets sort;                 // two rounds: two adjacent histogram blocks
     int LS, R;
     long long nrows, nleaves;
     FpsLayout(int B, int N, int max_n) {
@@ -169,16 +170,10 @@ struct FpsLayout {
         nrows = (long long)n + (long long)B * (LS - 1);          // every example padded to whole leaves
         nrows = (nrows + LS - 1) / LS * LS;
         nleaves = nrows / LS;
-        const size_t hist = (size_t)SORT_MAX_PASSES * 256 * SORT_MAX_BLOCKS * 4;
         size_t o = 0;
         lohi = o;   o += 256;
         part = o;   o += align_up((size_t)KNN_BBOX_PARTS * 8 * 4, 256);
-        ka = o;     o += align_up(n * 4, 256);
-        kb = o;     o += align_up(n * 4, 256);
-        va = o;     o += align_up(n * 4, 256);
-        vb = o;     o += align_up(n * 4, 256);
-        hist1 = o;  o += align_up(hist, 256);                    // the two sorts' histogram tables, adjacent: one zero-fill
-        hist2 = o;  o += align_up(hist, 256);
+        sort = radix_layout_append(o, n, 2);
         rowoff = o; o += align_up(((size_t)B + 1) * 4, 256);
         rows = o;   o += align_up((size_t)nrows * 16, 256);
         ord = o;    o += align_up((size_t)nrows * 4, 256);
@@ -196,7 +191,7 @@ fps_keys_morton_kernel(int N, const float* __restrict__ xyz, const float* __rest
     if (i >= N) return;
     const uint32_t k = (uint32_t)(knn_key(xyz, (uint32_t)i, lohi) >> 33);
     keys[i] = k; vals[i] = (uint32_t)i;
-    atomicAdd(&hist0[((uint32_t)i / per_block) * 256 + (k & 255u)], 1u);
+    radix_count_first(hist0, (uint32_t)i, per_block, k);
 }
 // round 2: the example of every point, in round-1 order (stable: Morton order inside each example)
 __global__ void __launch_bounds__(256)
@@ -204,19 +199,14 @@ fps_keys_example_kernel(int N, int B, const int* __restrict__ ptr, const uint32_
                         uint32_t* __restrict__ vals, uint32_t* __restrict__ hist0, uint32_t per_block)
 {
     // few distinct keys per block: counted in LDS first (one global add per digit), as knn.hip's high-bit round
-    __shared__ uint32_t h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
     const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s < N) {
+    radix_count_first_lds(hist0, per_block, [&](uint32_t& k) {
+        if (s >= N) return false;
         const uint32_t v = order[s];
-        const uint32_t k = (uint32_t)example_of(ptr, B, (int)v);
+        k = (uint32_t)example_of(ptr, B, (int)v);
         keys[s] = k; vals[s] = v;
-        atomicAdd(&h[k & 255u], 1u);
-    }
-    __syncthreads();
-    const uint32_t c = h[threadIdx.x];
-    if (c) atomicAdd(&hist0[(blockIdx.x * 256u / per_block) * 256 + threadIdx.x], c);     // (per_block is a multiple of 256)
+        return true;
+    });
 }
 // leaf-aligned row offsets of the examples (one thread: B is small beside N)
 __global__ void __launch_bounds__(64)
@@ -394,37 +384,33 @@ static hipError_t launch_fps(hipStream_t s, int B, int N, int max_n, const float
     char* base = align_ptr((const char*)scratch);
     float* lohi = (float*)(base + F.lohi);
     float* part = (float*)(base + F.part);
-    uint32_t *ka = (uint32_t*)(base + F.ka), *kb = (uint32_t*)(base + F.kb), *va = (uint32_t*)(base + F.va), *vb = (uint32_t*)(base + F.vb);
-    uint32_t *hist1 = (uint32_t*)(base + F.hist1), *hist2 = (uint32_t*)(base + F.hist2);
+    RadixBufs r1 = F.sort.at(base);                  // Morton bits, then (r2) the example
     int* rowoff = (int*)(base + F.rowoff);
     float4* rows = (float4*)(base + F.rows);
     uint32_t* ord = (uint32_t*)(base + F.ord);
     float4* leaf = (float4*)(base + F.leaf);
 
-    hipError_t e = zero_fill_async(s, hist1, F.rowoff - F.hist1);
+    hipError_t e = radix_sort_begin(s, (uint32_t)N, r1, 2);
     if (e != hipSuccess) return e;
+    const RadixBufs r2 = r1.second_round(30);
     hipLaunchKernelGGL(fps_rowoff_kernel, dim3(1), dim3(64), 0, s, B, F.LS, ptr, rowoff);
-    const uint32_t* perm = va;
+    const uint32_t* perm = r1.va;
     if (N > 0) {
         e = launch_knn_bbox(s, N, xyz, part, lohi);
         if (e != hipSuccess) return e;
-        uint32_t nb, per;
-        sort_geometry((uint32_t)N, &nb, &per);
         const dim3 g256((N + 255) / 256);
-        hipLaunchKernelGGL(fps_keys_morton_kernel, g256, dim3(256), 0, s, N, xyz, (const float*)lohi, ka, va, hist1, per);
-        uint32_t *sk = nullptr, *sv = nullptr;
-        e = radix_sort_pairs(s, (uint32_t)N, ka, kb, va, vb, hist1, 0, 30, &sk, &sv);
+        hipLaunchKernelGGL(fps_keys_morton_kernel, g256, dim3(256), 0, s, N, xyz, (const float*)lohi, r1.ka, r1.va, r1.hist, r1.per_block);
+        e = radix_sort_pairs(s, (uint32_t)N, r1, 0, 30);
         if (e != hipSuccess) return e;
+        perm = r1.sorted_vals(30);
         if (B > 1) {
             int bits = 0;
             while ((1 << bits) < B) bits++;
-            uint32_t* k2 = (sk == ka) ? kb : ka;
-            uint32_t* v2 = (sv == va) ? vb : va;
-            hipLaunchKernelGGL(fps_keys_example_kernel, g256, dim3(256), 0, s, N, B, ptr, (const uint32_t*)sv, k2, v2, hist2, per);
-            e = radix_sort_pairs(s, (uint32_t)N, k2, sk, v2, sv, hist2, 0, bits, &sk, &sv);
+            hipLaunchKernelGGL(fps_keys_example_kernel, g256, dim3(256), 0, s, N, B, ptr, perm, r2.ka, r2.va, r2.hist, r2.per_block);
+            e = radix_sort_pairs(s, (uint32_t)N, r2, 0, bits);
             if (e != hipSuccess) return e;
+            perm = r2.sorted_vals(bits);
         }
-        perm = sv;
         hipLaunchKernelGGL(fps_rows_kernel, dim3((unsigned)((F.nrows + 255) / 256)), dim3(256), 0, s, (int)F.nrows, N, B, init_d2, xyz, ptr,
                            (const int*)rowoff, perm, rows, ord);
         hipLaunchKernelGGL(fps_leaf_kernel, dim3((unsigned)((F.nleaves + 3) / 4)), dim3(256), 0, s, (int)F.nleaves, B, F.LS,

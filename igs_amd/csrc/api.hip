@@ -310,14 +310,12 @@ static int bin_radix(Frame& f, Binned& b)
     const hipStream_t s = f.in.s; const int debug = f.in.debug; const int P = f.in.P;
     const size_t counter_bytes = (COUNTER_SHARDS + 1) * COUNTER_SHARD_STRIDE * 4;
     uint32_t *counters = f.gbuf(f.GL.counters), *tiles = f.gbuf(f.GL.tiles), *ghist = f.gbuf(f.GL.hist), *blocksum = f.gbuf(f.GL.blocksum);
-    uint32_t *keys_a = f.gbuf(f.GL.keys_a), *keys_b = f.gbuf(f.GL.keys_b), *vals_a = f.gbuf(f.GL.vals_a), *vals_b = f.gbuf(f.GL.vals_b);
+    RadixBufs dsort{f.gbuf(f.GL.keys_a), f.gbuf(f.GL.keys_b), f.gbuf(f.GL.vals_a), f.gbuf(f.GL.vals_b), ghist};      // the depth sort
     HIP_TRY(hipMemsetAsync(counters, 0, counter_bytes, s), "memset counters");
 
-    uint32_t dnb = 0, dper = 0;
-    sort_geometry((uint32_t)P, &dnb, &dper);
-    HIP_TRY(hipMemsetAsync(ghist, 0, (size_t)256 * SORT_MAX_BLOCKS * 4, s), "memset depth-sort histogram 0");
+    HIP_TRY(radix_sort_begin(s, (uint32_t)P, dsort), "zero depth-sort histogram 0");
     prof_mark(s, ST_GAP);
-    HIP_TRY(launch_preprocess_fwd(s, f.fp, f.rec(), tiles, keys_a, vals_a, f.in.radii, counters, ghist, dper, nullptr, nullptr, 0, f.ex.count),
+    HIP_TRY(launch_preprocess_fwd(s, f.fp, f.rec(), tiles, dsort.ka, dsort.va, f.in.radii, counters, ghist, dsort.per_block, nullptr, nullptr, 0, f.ex.count),
             "preprocess_fwd launch");
     DBG_SYNC("preprocess_fwd");
     prof_mark(s, ST_PREPROCESS);
@@ -326,13 +324,13 @@ static int bin_radix(Frame& f, Binned& b)
     HIP_TRY(hipEventRecord(g_slot.ev, s), "event record");
     prof_mark(s, ST_GAP);
 
-    uint32_t *dk = nullptr, *order = nullptr;
-    HIP_TRY(radix_sort_pairs(s, (uint32_t)P, keys_a, keys_b, vals_a, vals_b, ghist, 0, 32, &dk, &order), "depth sort launch");
+    HIP_TRY(radix_sort_pairs(s, (uint32_t)P, dsort, 0, 32), "depth sort launch");
+    const uint32_t* order = dsort.sorted_vals(32);
     DBG_SYNC("depth sort");
     prof_mark(s, ST_DEPTH_SORT);
     const int nblk = (P + 255) / 256;
     HIP_TRY(launch_count_sorted(s, P, order, tiles, blocksum), "count_sorted launch");
-    HIP_TRY(launch_scan_blocksums(s, nblk, blocksum), "scan_blocksums launch");
+    HIP_TRY(launch_exclusive_scan(s, nblk, blocksum), "exclusive scan launch");
     DBG_SYNC("scan");
     prof_mark(s, ST_SCAN);
 
@@ -356,25 +354,19 @@ static int bin_radix(Frame& f, Binned& b)
     prof_mark(s, ST_GAP);
     if (R == 0) return 0;
     const int bits = ceil_log2((uint32_t)f.Tn);
-    const int passes = (bits + 7) / 8;
     // arrange the ping-pong so that the sorted ids land in point_list
-    uint32_t *ka, *kb, *va, *vb;
-    if (passes % 2 == 0) { ka = bkeys_a; va = point_list; kb = bkeys_b; vb = bvals_b; }
-    else                 { ka = bkeys_b; va = bvals_b;   kb = bkeys_a; vb = point_list; }
-    uint32_t tnb = 0, tper = 0;
-    sort_geometry(R, &tnb, &tper);
-    HIP_TRY(hipMemsetAsync(bhist, 0, (size_t)256 * SORT_MAX_BLOCKS * 4, s), "memset tile-sort histogram 0");
+    RadixBufs tsort = radix_lands_in_b(bits) ? RadixBufs{bkeys_b, bkeys_a, bvals_b, point_list, bhist}
+                                             : RadixBufs{bkeys_a, bkeys_b, point_list, bvals_b, bhist};
+    HIP_TRY(radix_sort_begin(s, R, tsort), "zero tile-sort histogram 0");
     const uint32_t mask0 = bits >= 8 ? 255u : ((1u << bits) - 1u);
-    HIP_TRY(launch_emit_instances(s, P, f.gx, f.gy, order, tiles, blocksum, f.rec(), f.in.radii, ka, va, passes ? bhist : nullptr, tper, mask0),
-            "emit launch");
+    HIP_TRY(launch_emit_instances(s, P, f.gx, f.gy, order, tiles, blocksum, f.rec(), f.in.radii, tsort.ka, tsort.va, bits ? bhist : nullptr,
+                                  tsort.per_block, mask0), "emit launch");
     DBG_SYNC("emit");
     prof_mark(s, ST_EMIT);
-    uint32_t *sk = nullptr, *sv = nullptr;
-    HIP_TRY(radix_sort_pairs(s, R, ka, kb, va, vb, bhist, 0, bits, &sk, &sv), "tile sort launch");
+    HIP_TRY(radix_sort_pairs(s, R, tsort, 0, bits), "tile sort launch");
     DBG_SYNC("tile sort");
     prof_mark(s, ST_TILE_SORT);
-    if (sv != point_list) return fail(IGS_RAST_E_INVALID, "internal: sort ping-pong mismatch");
-    HIP_TRY(launch_tile_ranges(s, R, sk, ranges), "tile_ranges launch");
+    HIP_TRY(launch_tile_ranges(s, R, tsort.sorted_keys(bits), ranges), "tile_ranges launch");
     DBG_SYNC("tile_ranges");
     prof_mark(s, ST_RANGES);
     return 0;

@@ -55,7 +55,7 @@ blend_step_kernel(const BlendFwdArgs f, const BlendBwdArgs b)
     }
     uint32_t tile;
     BTL(0, wall_clock64());
-    // Dispatch order: tile_sort's extra workgroup wrote it (sort.hip: build_step_order -- the plain XCD-aware order with the light tiles
+    // Dispatch order: tile_sort's extra workgroup wrote it (tile_sort.hip: build_step_order -- the plain XCD-aware order with the light tiles
     // last); without it (dense scenes, huge images) the plain order.  Every reordering that needed a launch or empty workgroups of its
     // own cost more than the drain it removes (profiles/r03_blend_order_ab.txt).
     if (f.step_order) {

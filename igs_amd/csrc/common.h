@@ -43,10 +43,7 @@ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; 
 
 #define COUNTER_SHARDS 64                  // instance-count shards (counters[16*(1+s)]); counters[1] = prefilter flag
 #define COUNTER_SHARD_STRIDE 16            // uint32 per shard = one 64-byte line
-#define SORT_ITEMS 8                       // elements per thread per sort sub-tile
-#define SORT_TILE (256 * SORT_ITEMS)       // 2048 elements per block sub-tile
-#define SORT_MAX_PASSES 5                  // histogram tables kept per sort (32-bit keys: 4 passes)
-#define SORT_MAX_BLOCKS 256                // one block per CU
+#include "radix_sort.h"
 
 struct GeomLayout {          // sizes in bytes, offsets from a 256-byte aligned base
     size_t rec, tiles, keys_a, keys_b, vals_a, vals_b, hist, blocksum, counters, planes, total;
@@ -54,11 +51,8 @@ struct GeomLayout {          // sizes in bytes, offsets from a 256-byte aligned 
         size_t o = 0;
         rec = o;      o += align_up(P * REC_F * 4, 256);
         tiles = o;    o += align_up(P * 4, 256);
-        keys_a = o;   o += align_up(P * 4, 256);
-        keys_b = o;   o += align_up(P * 4, 256);
-        vals_a = o;   o += align_up(P * 4, 256);     // after the depth sort: Gaussian ids in depth order
-        vals_b = o;   o += align_up(P * 4, 256);
-        hist = o;     o += align_up((size_t)SORT_MAX_PASSES * 256 * SORT_MAX_BLOCKS * 4, 256);
+        const RadixOffsets r = radix_layout_append(o, P);   // the depth sort (radix binning): after it, vals_a = Gaussian ids in depth order
+        keys_a = r.ka; keys_b = r.kb; vals_a = r.va; vals_b = r.vb; hist = r.hist;
         blocksum = o; o += align_up((P / 256 + 2) * 4, 256);   // per-256 block instance counts / offsets (depth order)
         counters = o; o += align_up((COUNTER_SHARDS + 1) * COUNTER_SHARD_STRIDE * 4, 256);   // [1] prefilter flag, [16*(1+s)] count shard s
         planes = o;   o += align_up(P * 12 * 4, 256);          // PlaneCache (geom_math.h): Sigma^-1 per visible Gaussian, kept on request for the backward
@@ -69,11 +63,9 @@ struct BinLayout {
     size_t point_list, keys_a, keys_b, vals_b, hist, total;
     __host__ explicit BinLayout(size_t R) {
         size_t o = 0;
-        point_list = o; o += align_up(R * 4, 256);   // final sorted Gaussian ids (kept for backward)
-        keys_a = o;     o += align_up(R * 4, 256);
-        keys_b = o;     o += align_up(R * 4, 256);
-        vals_b = o;     o += align_up(R * 4, 256);
-        hist = o;       o += align_up((size_t)SORT_MAX_PASSES * 256 * SORT_MAX_BLOCKS * 4, 256);
+        // the tile sort's regions; the FIRST is the point list (final sorted ids, kept for the backward, where SlabLayout has it too)
+        const RadixOffsets r = radix_layout_append(o, R);
+        point_list = r.ka; keys_a = r.kb; keys_b = r.va; vals_b = r.vb; hist = r.hist;
         total = o + 256;
     }
 };
@@ -131,7 +123,6 @@ struct FwdParams {
 hipError_t launch_preprocess_fwd(hipStream_t s, const FwdParams& p, float* rec, uint32_t* tiles, uint32_t* depth_keys,
                                  uint32_t* ident, int* radii, uint32_t* counters, uint32_t* hist0, uint32_t per_block,
                                  uint32_t* tile_count, uint64_t* pairs, uint32_t slab, int* count = nullptr);
-void sort_geometry(uint32_t n, uint32_t* nb, uint32_t* per);
 hipError_t launch_tile_sort(hipStream_t s, uint32_t T, uint32_t* tile_count, const uint64_t* pairs, uint32_t* point_list,
                             uint32_t* ranges, uint32_t slab, uint32_t* stats, uint32_t* counters, uint32_t P,
                             uint32_t* step_order = nullptr, uint32_t gx = 0, uint32_t gy = 0);
@@ -139,13 +130,8 @@ hipError_t launch_compact_lists(hipStream_t s, uint32_t T, const uint32_t* range
                                 uint32_t* list_out, uint32_t out_capacity);
 hipError_t launch_mark_visible(hipStream_t s, int P, const float* means3D, const float* view, uint8_t* present);
 
-// stable LSD radix sort of (key,value) pairs on key bits [bit_lo, bit_hi); result ends in *out_keys/*out_vals
-// (ping-pong between a and b).  `hist` holds SORT_MAX_PASSES tables of 256*SORT_MAX_BLOCKS uint32, zeroed by the caller
-// except table 0, which the producer of keys_a filled with the first pass's per-block digit counts.
-hipError_t radix_sort_pairs(hipStream_t s, uint32_t n, uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a, uint32_t* vals_b,
-                            uint32_t* hist, int bit_lo, int bit_hi, uint32_t** out_keys, uint32_t** out_vals);
+// radix binning, the fallback (bin_radix.hip); the stable radix sort itself: radix_sort.h
 hipError_t launch_count_sorted(hipStream_t s, int P, const uint32_t* order, const uint32_t* tiles, uint32_t* blocksum);
-hipError_t launch_scan_blocksums(hipStream_t s, int nblocks, uint32_t* blocksum);
 hipError_t launch_emit_instances(hipStream_t s, int P, int gx, int gy, const uint32_t* order, const uint32_t* tiles,
                                  const uint32_t* blocksum, const float* rec, const int* radii, uint32_t* tile_keys,
                                  uint32_t* vals, uint32_t* hist0, uint32_t per_block, uint32_t mask0);
@@ -343,10 +329,10 @@ __device__ __forceinline__ bool tile_for_block(uint32_t b, uint32_t gx, uint32_t
     return row < gy;
 }
 static inline uint32_t tile_grid_blocks(uint32_t gx, uint32_t gy) { return 8u * ((gy + 7u) / 8u) * gx; }
-// The fused blend kernel's dispatch order (sort.hip: build_step_order): usable when tile_sort's one-wave-per-tile kernel runs (slabs
+// The fused blend kernel's dispatch order (tile_sort.hip: build_step_order): usable when tile_sort's one-wave-per-tile kernel runs (slabs
 // of at most 1024 slots) and an XCD group has at most 64 * STEP_ORDER_CHUNKS workgroups.
 #define STEP_ORDER_CHUNKS 16
-// slabs up to this size: every tile is sorted by one wave in registers and no second launch follows (sort.hip: launch_tile_sort) -- the
+// slabs up to this size: every tile is sorted by one wave in registers and no second launch follows (tile_sort.hip: launch_tile_sort) -- the
 // only configuration in which the tile sort also writes the fused blend kernel's dispatch order, so both places read THIS constant
 #ifndef TILE_SORT_WAVE_ALONE
 #define TILE_SORT_WAVE_ALONE 1024

@@ -52,11 +52,11 @@ __global__ void __launch_bounds__(256)
 plan_classify_kernel(int P, const float* __restrict__ opacity_logit, const float* __restrict__ log_scale,
                      const float* __restrict__ grad_accum, const float* __restrict__ denom, float grad_threshold, float min_opacity,
                      float split_scale_limit, float world_scale_limit, uint32_t* __restrict__ key, uint8_t* __restrict__ flags,
-                     uint32_t* __restrict__ hist0)
+                     uint32_t* __restrict__ sel_hist0)
 {
     __shared__ uint32_t h[256];
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (hist0) { h[threadIdx.x] = 0u; __syncthreads(); }
+    if (sel_hist0) { h[threadIdx.x] = 0u; __syncthreads(); }
     if (i < P) {
         float g = grad_accum[i] / denom[i];
         if (!(g > 0.f)) g = 0.f;                                   // 0/0, and the negative values the statistics cannot take
@@ -73,11 +73,11 @@ plan_classify_kernel(int P, const float* __restrict__ opacity_logit, const float
         if (!(world_scale_limit > 0.f && cmax > world_scale_limit)) f |= DP_CHILD_OK;
         key[i] = k;
         flags[i] = (uint8_t)f;
-        if (hist0 && k) atomicAdd(&h[k >> 24], 1u);
+        if (sel_hist0 && k) atomicAdd(&h[k >> 24], 1u);
     }
-    if (hist0) {
+    if (sel_hist0) {
         __syncthreads();
-        if (h[threadIdx.x]) atomicAdd(&hist0[threadIdx.x], h[threadIdx.x]);
+        if (h[threadIdx.x]) atomicAdd(&sel_hist0[threadIdx.x], h[threadIdx.x]);
     }
 }
 
@@ -315,7 +315,7 @@ extern "C" int igs_densify_plan(void* stream, int P, const float* xyz, const flo
     hipLaunchKernelGGL(plan_count_kernel, grid, block, 0, s, P, L.nb, (const uint32_t*)key, flags, (const uint32_t*)hist, max_num_add,
                        (const uint32_t*)tie, seg);
     HIP_TRY(hipGetLastError(), "densify plan: count launches");
-    HIP_TRY(launch_scan_blocksums(s, 6 * L.nb + 1, seg), "densify plan: scan launch");
+    HIP_TRY(launch_exclusive_scan(s, 6 * L.nb + 1, seg), "densify plan: scan launch");
     hipLaunchKernelGGL(plan_emit_kernel, grid, block, 0, s, P, L.nb, xyz, rotation, log_scale, normals, (const uint8_t*)flags,
                        (const uint32_t*)seg, src, fresh, ovr, ovr_xyz, ovr_scale, counts);
     HIP_TRY(hipGetLastError(), "densify plan: emit launch");

@@ -31,21 +31,16 @@ static_assert(KNN_K == 3, "knn_insert keeps exactly three values");
 
 // scratch layout (offsets from a 256-byte aligned base)
 struct KnnLayout {
-    size_t lohi, part, ka, kb, va, vb, hist1, hist2, pts, leaf, node, total;
+    size_t lohi, part, pts, leaf, node, total;
+    RadixOffsets sort;                 // two rounds: two adjacent histogram blocks
     int L, Nn;
     explicit KnnLayout(int P) {
         const size_t n = (size_t)(P > 0 ? P : 0);
         L = (int)((n + 63) / 64); Nn = (L + 63) / 64;
-        const size_t hist = (size_t)SORT_MAX_PASSES * 256 * SORT_MAX_BLOCKS * 4;
         size_t o = 0;
         lohi = o;  o += 256;
         part = o;  o += align_up((size_t)KNN_BBOX_PARTS * 8 * 4, 256);
-        ka = o;    o += align_up(n * 4, 256);
-        kb = o;    o += align_up(n * 4, 256);
-        va = o;    o += align_up(n * 4, 256);
-        vb = o;    o += align_up(n * 4, 256);
-        hist1 = o; o += align_up(hist, 256);         // the two sorts' histogram tables, adjacent: one zero-fill
-        hist2 = o; o += align_up(hist, 256);
+        sort = radix_layout_append(o, n, 2);
         pts = o;   o += align_up((size_t)L * 64 * 16, 256);
         leaf = o;  o += align_up((size_t)L * 32, 256);
         node = o;  o += align_up((size_t)Nn * 32, 256);
@@ -106,7 +101,7 @@ knn_keys_lo_kernel(int P, const float* __restrict__ xyz, const float* __restrict
     if (i >= P) return;
     const uint32_t k = (uint32_t)knn_key(xyz, (uint32_t)i, lohi);
     keys[i] = k; vals[i] = (uint32_t)i;
-    atomicAdd(&hist0[((uint32_t)i / per_block) * 256 + (k & 255u)], 1u);
+    radix_count_first(hist0, (uint32_t)i, per_block, k);
 }
 // round 2: key bits [32, 63) of the points in round-1 order
 __global__ void __launch_bounds__(256)
@@ -114,19 +109,14 @@ knn_keys_hi_kernel(int P, const float* __restrict__ xyz, const float* __restrict
                    uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ hist0, uint32_t per_block)
 {
     // the high key bits are coarse: a block's keys share few digits, so they are counted in LDS first (one global add per digit)
-    __shared__ uint32_t h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
     const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s < P) {
+    radix_count_first_lds(hist0, per_block, [&](uint32_t& k) {
+        if (s >= P) return false;
         const uint32_t v = order[s];
-        const uint32_t k = (uint32_t)(knn_key(xyz, v, lohi) >> 32);
+        k = (uint32_t)(knn_key(xyz, v, lohi) >> 32);
         keys[s] = k; vals[s] = v;
-        atomicAdd(&h[k & 255u], 1u);
-    }
-    __syncthreads();
-    const uint32_t c = h[threadIdx.x];
-    if (c) atomicAdd(&hist0[(blockIdx.x * 256u / per_block) * 256 + threadIdx.x], c);     // (per_block is a multiple of 256)
+        return true;
+    });
 }
 
 // ---- phase 3: sorted points and leaf boxes (one wave per leaf) ----
@@ -270,36 +260,31 @@ static hipError_t launch_knn_mean_dist2(hipStream_t s, int P, const float* xyz, 
     char* b = align_ptr((const char*)scratch);
     float* lohi = (float*)(b + K.lohi);
     float* part = (float*)(b + K.part);
-    uint32_t *ka = (uint32_t*)(b + K.ka), *kb = (uint32_t*)(b + K.kb), *va = (uint32_t*)(b + K.va), *vb = (uint32_t*)(b + K.vb);
-    uint32_t *hist1 = (uint32_t*)(b + K.hist1), *hist2 = (uint32_t*)(b + K.hist2);
+    RadixBufs r1 = K.sort.at(b);                      // low 32 key bits, then (r2) the high 31
     float4 *pts = (float4*)(b + K.pts), *leafbox = (float4*)(b + K.leaf), *nodebox = (float4*)(b + K.node);
 
-    hipError_t e = zero_fill_async(s, hist1, K.pts - K.hist1);
+    hipError_t e = radix_sort_begin(s, (uint32_t)P, r1, 2);
     if (e != hipSuccess) return e;
+    const RadixBufs r2 = r1.second_round(32);
     int parts = (P + 63) / 64;
     if (parts > KNN_BBOX_PARTS) parts = KNN_BBOX_PARTS;
     hipLaunchKernelGGL(knn_bbox_partial_kernel, dim3(parts), dim3(64), 0, s, P, xyz, part);
     hipLaunchKernelGGL(knn_bbox_final_kernel, dim3(1), dim3(64), 0, s, parts, (const float*)part, lohi);
-
-    uint32_t nb, per;
-    sort_geometry((uint32_t)P, &nb, &per);
     const dim3 g256((P + 255) / 256);
-    hipLaunchKernelGGL(knn_keys_lo_kernel, g256, dim3(256), 0, s, P, xyz, (const float*)lohi, ka, va, hist1, per);
-    uint32_t *sk = nullptr, *sv = nullptr;
-    e = radix_sort_pairs(s, (uint32_t)P, ka, kb, va, vb, hist1, 0, 32, &sk, &sv);
+    hipLaunchKernelGGL(knn_keys_lo_kernel, g256, dim3(256), 0, s, P, xyz, (const float*)lohi, r1.ka, r1.va, r1.hist, r1.per_block);
+    e = radix_sort_pairs(s, (uint32_t)P, r1, 0, 32);
     if (e != hipSuccess) return e;
-    // round 2 writes into the pair round 1 did not end in
-    uint32_t* k2 = (sk == ka) ? kb : ka;
-    uint32_t* v2 = (sv == va) ? vb : va;
-    hipLaunchKernelGGL(knn_keys_hi_kernel, g256, dim3(256), 0, s, P, xyz, (const float*)lohi, (const uint32_t*)sv, k2, v2, hist2, per);
-    e = radix_sort_pairs(s, (uint32_t)P, k2, sk, v2, sv, hist2, 0, 3 * KNN_BITS - 32, &sk, &sv);
+    hipLaunchKernelGGL(knn_keys_hi_kernel, g256, dim3(256), 0, s, P, xyz, (const float*)lohi, (const uint32_t*)r1.sorted_vals(32), r2.ka, r2.va,
+                       r2.hist, r2.per_block);
+    e = radix_sort_pairs(s, (uint32_t)P, r2, 0, 3 * KNN_BITS - 32);
     if (e != hipSuccess) return e;
+    const uint32_t* sv = r2.sorted_vals(3 * KNN_BITS - 32);
 
     const dim3 gl((K.L + 3) / 4), gn((K.Nn + 3) / 4);
-    hipLaunchKernelGGL(knn_gather_kernel, gl, dim3(256), 0, s, P, K.L, xyz, (const uint32_t*)sv, pts, leafbox);
+    hipLaunchKernelGGL(knn_gather_kernel, gl, dim3(256), 0, s, P, K.L, xyz, sv, pts, leafbox);
     hipLaunchKernelGGL(knn_node_kernel, gn, dim3(256), 0, s, K.L, K.Nn, (const float4*)leafbox, nodebox);
     hipLaunchKernelGGL(knn_query_kernel, gl, dim3(256), 0, s, P, K.L, K.Nn, (const float4*)pts, (const float4*)leafbox,
-                       (const float4*)nodebox, (const uint32_t*)sv, out);
+                       (const float4*)nodebox, sv, out);
     return hipGetLastError();
 }
 // the entry points (the contract is in include/igs_rast.h)

@@ -34,28 +34,23 @@ __device__ __forceinline__ float lift_weight(int q, float tx, float ty)
 }
 
 struct LiftLayout {            // offsets from a 256-byte aligned base; the index part only when `backward`
-    size_t cell, tx, ty, ka, kb, va, vb, hist, start, total;
+    size_t cell, tx, ty, start, total;
+    RadixOffsets sort = {};    // edges by pixel (backward only)
     uint64_t S, E, NPIX;
     int bits;
-    bool sorted_in_b;
     LiftLayout(int B, int V, int A, int H, int W, bool backward) {
         S = (uint64_t)B * V * A;
         E = 4 * S;
         NPIX = (uint64_t)B * V * H * W;
         bits = 1;
         while (((uint64_t)1 << bits) <= NPIX) bits++;              // keys 0 .. NPIX (NPIX = a corner outside the map)
-        sorted_in_b = (((bits + 7) / 8) & 1) != 0;
         size_t o = 0;
         cell = o; o += align_up(S * 4, 256);
         tx = o;   o += align_up(S * 4, 256);
         ty = o;   o += align_up(S * 4, 256);
-        ka = kb = va = vb = hist = start = o;
+        start = o;
         if (backward) {
-            ka = o;    o += align_up(E * 4, 256);
-            kb = o;    o += align_up(E * 4, 256);
-            va = o;    o += align_up(E * 4, 256);
-            vb = o;    o += align_up(E * 4, 256);
-            hist = o;  o += align_up((size_t)SORT_MAX_PASSES * 256 * SORT_MAX_BLOCKS * 4, 256);
+            sort = radix_layout_append(o, E);
             start = o; o += align_up((NPIX + 1) * 4, 256);        // start[p]: first sorted edge of pixel p; start[NPIX] = valid edges
         }
         total = o + 256;
@@ -211,7 +206,7 @@ lift_keys_kernel(uint32_t E, int A, int H, int W, uint32_t NPIX, const uint32_t*
         if (x >= 0 && x < W && y >= 0 && y < H) k = (s / (uint32_t)A) * (uint32_t)(H * W) + (uint32_t)(y * W + x);
     }
     keys[e] = k; vals[e] = e;
-    atomicAdd(&hist0[(e / per_block) * 256 + (k & 255u)], 1u);
+    radix_count_first(hist0, e, per_block, k);
 }
 
 // start[p] = the first sorted position whose key is >= p, for p = 0 .. NPIX: a lower bound per pixel.  (motion.hip's boundary walk fills
@@ -292,24 +287,21 @@ static hipError_t launch_lift_bwd(hipStream_t s, int B, int V, int A, int C, int
     char* base = align_ptr((const char*)scratch);
     uint32_t* cell = (uint32_t*)(base + L.cell);
     float *tx = (float*)(base + L.tx), *ty = (float*)(base + L.ty);
-    uint32_t *ka = (uint32_t*)(base + L.ka), *kb = (uint32_t*)(base + L.kb), *va = (uint32_t*)(base + L.va), *vb = (uint32_t*)(base + L.vb);
-    uint32_t* hist = (uint32_t*)(base + L.hist);
+    RadixBufs r = L.sort.at(base);
     uint32_t* start = (uint32_t*)(base + L.start);
     const uint32_t S = (uint32_t)L.S, E = (uint32_t)L.E, NPIX = (uint32_t)L.NPIX;
-    hipError_t e = zero_fill_async(s, hist, (size_t)SORT_MAX_PASSES * 256 * SORT_MAX_BLOCKS * 4);
+    hipError_t e = radix_sort_begin(s, E, r);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(lift_project_kernel, dim3((S + 255) / 256), dim3(256), 0, s, V, A, H, W, S, points, w2c, intr, cell, tx, ty);
-    uint32_t nb, per;
-    sort_geometry(E, &nb, &per);
-    hipLaunchKernelGGL(lift_keys_kernel, dim3((E + 255) / 256), dim3(256), 0, s, E, A, H, W, NPIX, (const uint32_t*)cell, ka, va, hist, per);
-    uint32_t *sk = nullptr, *sv = nullptr;
-    e = radix_sort_pairs(s, E, ka, kb, va, vb, hist, 0, L.bits, &sk, &sv);
+    hipLaunchKernelGGL(lift_keys_kernel, dim3((E + 255) / 256), dim3(256), 0, s, E, A, H, W, NPIX, (const uint32_t*)cell, r.ka, r.va, r.hist, r.per_block);
+    e = radix_sort_pairs(s, E, r, 0, L.bits);
     if (e != hipSuccess) return e;
-    if (sv != (L.sorted_in_b ? vb : va)) return hipErrorUnknown;
-    hipLaunchKernelGGL(lift_start_kernel, dim3(NPIX / 256 + 1), dim3(256), 0, s, E, NPIX, (const uint32_t*)sk, start);
-    uint32_t* ea = L.sorted_in_b ? ka : kb;                            // the sort's other pair of buffers is free now
-    float* ew = (float*)(L.sorted_in_b ? va : vb);
-    hipLaunchKernelGGL(lift_edge_kernel, dim3((E + 255) / 256), dim3(256), 0, s, E, A, (const uint32_t*)sv, (const float*)tx, (const float*)ty, ea, ew);
+    hipLaunchKernelGGL(lift_start_kernel, dim3(NPIX / 256 + 1), dim3(256), 0, s, E, NPIX, (const uint32_t*)r.sorted_keys(L.bits), start);
+    const bool in_b = radix_lands_in_b(L.bits);
+    uint32_t* ea = in_b ? r.ka : r.kb;                                 // the sort's other pair of buffers is free now
+    float* ew = (float*)(in_b ? r.va : r.vb);
+    hipLaunchKernelGGL(lift_edge_kernel, dim3((E + 255) / 256), dim3(256), 0, s, E, A, (const uint32_t*)r.sorted_vals(L.bits), (const float*)tx,
+                       (const float*)ty, ea, ew);
     const int ncg = (C + LIFT_BWD_CH - 1) / LIFT_BWD_CH;
     const int use_lds = (size_t)A * LIFT_BWD_CH <= LIFT_LDS_FLOATS ? 1 : 0;
     const size_t lds = use_lds ? (size_t)A * LIFT_BWD_CH * 4 : 0;

@@ -29,24 +29,19 @@ static uint32_t interp_chunk(uint64_t E)
 }
 
 struct InterpLayout {          // the inverse index and the backward's partial sums, offsets from a 256-byte aligned base
-    size_t ka, kb, va, vb, hist, start, choff, part, total;
+    RadixOffsets sort;         // edges by anchor: the result is where radix_lands_in_b(bits) says, for the index build and the backward alike
+    size_t start, choff, part, total;
     uint64_t E, max_chunks;
     uint32_t chunk;
     int bits;
-    bool sorted_in_b;          // the radix sort's result landed in (kb, vb): an odd number of passes
     InterpLayout(int N, int K, int A, int D) {
         E = (uint64_t)N * (uint64_t)K;
         chunk = interp_chunk(E);
         max_chunks = (E + chunk - 1) / chunk + (uint64_t)A;         // every anchor adds at most one partly filled chunk
         bits = 1;
         while (((uint64_t)1 << bits) <= (uint64_t)A) bits++;       // keys 0..A (A = an empty or out-of-range slot)
-        sorted_in_b = (((bits + 7) / 8) & 1) != 0;
         size_t o = 0;
-        ka = o;    o += align_up(E * 4, 256);
-        kb = o;    o += align_up(E * 4, 256);
-        va = o;    o += align_up(E * 4, 256);
-        vb = o;    o += align_up(E * 4, 256);
-        hist = o;  o += align_up((size_t)SORT_MAX_PASSES * 256 * SORT_MAX_BLOCKS * 4, 256);
+        sort = radix_layout_append(o, E);
         start = o; o += align_up(((size_t)A + 1) * 4, 256);         // start[a]: first sorted position of anchor a; start[A] = valid edges
         choff = o; o += align_up(((size_t)A + 1) * 4, 256);         // exclusive scan of the chunks per anchor; choff[A] = all chunks
         part = o;  o += align_up((size_t)max_chunks * (size_t)D * 4, 256);
@@ -138,7 +133,7 @@ interp_keys_kernel(uint32_t E, int A, const int64_t* __restrict__ col, uint32_t*
     const int64_t a = col[e];
     const uint32_t k = (a >= 0 && a < A) ? (uint32_t)a : (uint32_t)A;
     keys[e] = k; vals[e] = e;
-    atomicAdd(&hist0[(e / per_block) * 256 + (k & 255u)], 1u);        // the first radix pass's per-block digit counts
+    radix_count_first(hist0, e, per_block, k);
 }
 
 // start[a] for every a in (key[i - 1], key[i]]; the last position also closes (key[E - 1], A] with E
@@ -166,23 +161,18 @@ static hipError_t launch_interp_index(hipStream_t s, int N, int K, int A, int D,
 {
     const InterpLayout L(N, K, A, D);
     char* base = align_ptr((const char*)scratch);
-    uint32_t *ka = (uint32_t*)(base + L.ka), *kb = (uint32_t*)(base + L.kb), *va = (uint32_t*)(base + L.va), *vb = (uint32_t*)(base + L.vb);
-    uint32_t* hist = (uint32_t*)(base + L.hist);
+    RadixBufs r = L.sort.at(base);
     uint32_t* start = (uint32_t*)(base + L.start);
     uint32_t* choff = (uint32_t*)(base + L.choff);
     const uint32_t E = (uint32_t)L.E;
-    hipError_t e = zero_fill_async(s, hist, (size_t)SORT_MAX_PASSES * 256 * SORT_MAX_BLOCKS * 4);
+    hipError_t e = radix_sort_begin(s, E, r);
     if (e != hipSuccess) return e;
-    uint32_t nb, per;
-    sort_geometry(E, &nb, &per);
-    hipLaunchKernelGGL(interp_keys_kernel, dim3((E + 255) / 256), dim3(256), 0, s, E, A, col, ka, va, hist, per);
-    uint32_t *sk = nullptr, *sv = nullptr;
-    e = radix_sort_pairs(s, E, ka, kb, va, vb, hist, 0, L.bits, &sk, &sv);
+    hipLaunchKernelGGL(interp_keys_kernel, dim3((E + 255) / 256), dim3(256), 0, s, E, A, col, r.ka, r.va, r.hist, r.per_block);
+    e = radix_sort_pairs(s, E, r, 0, L.bits);
     if (e != hipSuccess) return e;
-    if (sv != (L.sorted_in_b ? vb : va)) return hipErrorUnknown;         // (the backward finds the result by the same rule)
-    hipLaunchKernelGGL(interp_start_kernel, dim3((E + 255) / 256), dim3(256), 0, s, E, A, (const uint32_t*)sk, start);
+    hipLaunchKernelGGL(interp_start_kernel, dim3((E + 255) / 256), dim3(256), 0, s, E, A, (const uint32_t*)r.sorted_keys(L.bits), start);
     hipLaunchKernelGGL(interp_nchunks_kernel, dim3((unsigned)((A + 1 + 255) / 256)), dim3(256), 0, s, A, L.chunk, (const uint32_t*)start, choff);
-    return launch_scan_blocksums(s, A + 1, choff);
+    return launch_exclusive_scan(s, A + 1, choff);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -277,7 +267,7 @@ static hipError_t interp_bwd_t(hipStream_t s, int N, int K, int D, int A, const 
 {
     const InterpLayout L(N, K, A, D);
     char* base = align_ptr((const char*)scratch);
-    const uint32_t* perm = (const uint32_t*)(base + (L.sorted_in_b ? L.vb : L.va));
+    const uint32_t* perm = L.sort.at(base).sorted_vals(L.bits);
     const uint32_t* start = (const uint32_t*)(base + L.start);
     const uint32_t* choff = (const uint32_t*)(base + L.choff);
     float* part = (float*)(base + L.part);

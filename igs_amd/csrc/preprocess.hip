@@ -194,7 +194,7 @@ preprocess_body(const FwdParams& p, const uint32_t blk, float* __restrict__ rec,
         if (BIN && hist0) {                                          // radix binning: keys + first-pass histogram of the depth sort
             depth_keys[idx] = dkey;
             ident[idx] = (uint32_t)idx;
-            atomicAdd(&hist0[((uint32_t)idx / per_block) * 256u + (dkey & 255u)], 1u);
+            radix_count_first(hist0, (uint32_t)idx, per_block, dkey);
         }
     }
     if (BIN && p.zero_gacc) {

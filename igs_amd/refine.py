@@ -193,7 +193,7 @@ class GaussianParams:
             sub = xyz[lo:hi]
             lohi = torch.cat([sub.min(dim=0).values, sub.max(dim=0).values]).contiguous()      # stays on the device: no host read-back
             with torch.cuda.device(self.device):
-                # keys, identity and the stable radix sort are the library's own (sort.hip); same order as torch.argsort(code, stable=True)
+                # keys, identity and the stable radix sort are the library's own (radix_sort.hip); same order as torch.argsort(code, stable=True)
                 rc = Lb.igs_morton_order(torch.cuda.current_stream(self.device).cuda_stream, hi - lo, sub.data_ptr(), lohi.data_ptr(), bits,
                                          self._morton_scratch.data_ptr(), perm[lo:hi].data_ptr())
             if rc != 0:

@@ -135,9 +135,9 @@ FPS_WAVES = 16                 # anchors.hip:20
 FPS_MAX_SLOTS = 4              # anchors.hip:21
 KNNQ_THREADS = 256             # anchors.hip:22  queries per kNN workgroup
 KNNQ_TILE = 2048               # anchors.hip:23  x points per LDS tile
-KNN_SLOT_CLASSES = (8, 16, 32, 100)       # anchors.hip:526-529  launch_knn_query's instantiations
+KNN_SLOT_CLASSES = (8, 16, 32, 100)       # anchors.hip:512-515  launch_knn_query's instantiations
 SELECT_BLOCK = 256             # anchors.hip:139  points per select workgroup (one block sum each)
-SCAN_THREADS = 1024            # sort.hip:34-40  the single-block scan: ceil(n / 1024) entries per thread
+SCAN_THREADS = 1024            # radix_sort.hip:19-25  the single-block scan: ceil(n / 1024) entries per thread
 
 
 def fps_geometry(max_n):
@@ -153,7 +153,7 @@ def fps_geometry(max_n):
 
 
 def fps_example_bits(B):
-    """anchors.hip:418-420: bits of the example-keyed sort round (none for B = 1); ceil(bits / 8) radix passes."""
+    """anchors.hip:406-408: bits of the example-keyed sort round (none for B = 1); ceil(bits / 8) radix passes."""
     if B <= 1:
         return 0
     bits = 0
@@ -163,12 +163,12 @@ def fps_example_bits(B):
 
 
 def knn_slot_class(k):
-    """anchors.hip:526-529: the register slots K of the instantiation that serves k."""
+    """anchors.hip:512-515: the register slots K of the instantiation that serves k."""
     return next(c for c in KNN_SLOT_CLASSES if k <= c)
 
 
 def knn_straddling_workgroups(ptr_y):
-    """Per kNN workgroup (256 consecutive queries, anchors.hip:453-459): True where its first and last query lie in different
+    """Per kNN workgroup (256 consecutive queries, anchors.hip:439-445): True where its first and last query lie in different
     examples -- the workgroups the masked instantiation serves."""
     ptr_y = np.asarray(ptr_y)
     ny = int(ptr_y[-1])
@@ -180,7 +180,7 @@ def knn_straddling_workgroups(ptr_y):
 
 
 def select_scan_per_thread(n):
-    """Entries per thread of the single-block scan over the select's block sums (anchors.hip:139-141, sort.hip:40)."""
+    """Entries per thread of the single-block scan over the select's block sums (anchors.hip:139-141, radix_sort.hip:25)."""
     nb = (n + SELECT_BLOCK - 1) // SELECT_BLOCK
     return (nb + SCAN_THREADS - 1) // SCAN_THREADS
 

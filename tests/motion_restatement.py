@@ -65,10 +65,10 @@ def deform_restate(gs, res_feat, mask):
             "resi_rotation": res_feat["rotation"].clone(), "mask": mask, "resi_xyz": res_feat["xyz"].clone()}
 
 
-# ---------------------------------------------------------------- launch geometry, restated from motion.hip / sort.hip (lines cited)
+# ---------------------------------------------------------------- launch geometry, restated from motion.hip / radix_sort.hip / radix_sort.h (lines cited)
 INTERP_MAX_D = 1024            # IGS_INTERP_MAX_D (include/igs_rast.h)
-SORT_TILE = 2048               # common.h:47
-SORT_MAX_BLOCKS = 256          # common.h:49
+SORT_TILE = 2048               # radix_sort.h:15
+SORT_MAX_BLOCKS = 256          # radix_sort.h:17
 
 
 def interp_chunk(E):
@@ -91,13 +91,20 @@ def interp_index_passes(A):
     return (interp_index_bits(A) + 7) // 8
 
 
+def radix_lands_in_b(bits):
+    """radix_sort.h:25 radix_lands_in_b: a radix sort over `bits` key bits, 8 per pass, swaps its buffer pairs once per pass, so it ends
+    in the second pair (kb, vb) after an odd number of passes and in the first (ka, va) after an even number (none included)."""
+    return ((bits + 7) // 8) % 2 == 1
+
+
 def interp_dv(D):
-    """motion.hip:104 interp_dv: floats per lane of the row / chunk kernel instantiation that serves D."""
+    """motion.hip:99 interp_dv: floats per lane of the row / chunk kernel instantiation that serves D."""
     return 1 if D <= 64 else 2 if D <= 128 else 4 if D <= 256 else 8 if D <= 512 else 16
 
 
 def sort_geometry(n):
-    """sort.hip:20-31 sort_geometry: (blocks, elements per block) of one radix sort of n pairs."""
+    """radix_sort.hip:8-16 sort_per_block and the block count radix_sort_pairs takes from it: (blocks, elements per block) of one radix
+    sort of n pairs."""
     nb = min((n + SORT_TILE - 1) // SORT_TILE, SORT_MAX_BLOCKS) or 1
     per = (n + nb - 1) // nb
     per = (per + SORT_TILE - 1) // SORT_TILE * SORT_TILE or SORT_TILE

@@ -953,27 +953,44 @@ def test_morton_order_equals_stable_argsort_of_the_codes(dev):
     """igs_morton_order (the library's own keys + stable LSD radix sort: no PyTorch / rocPRIM sort on the stream path) against
     torch.argsort(code, stable=True) of the same 30-bit Morton codes, incl. many equal keys (4 bits per axis) and P not a multiple of
     anything."""
-    from igs_amd import _cabi
-    L = _cabi.lib()
     gen = torch.Generator().manual_seed(5)
     for P, bits in ((1, 10), (777, 10), (200003, 10), (50000, 4)):
-        xyz = (torch.randn(P, 3, generator=gen) * 3.0).to(dev).contiguous()
-        lo, hi = xyz.min(dim=0).values, xyz.max(dim=0).values
-        q = ((xyz - lo) / (hi - lo).clamp(min=1e-12) * (2 ** bits - 1)).long().clamp(0, 2 ** bits - 1)
+        _check_morton_order(dev, gen, P, bits)
 
-        def spread(v):
-            v = (v | (v << 16)) & 0x30000FF
-            v = (v | (v << 8)) & 0x300F00F
-            v = (v | (v << 4)) & 0x30C30C3
-            return (v | (v << 2)) & 0x9249249
-        code = spread(q[:, 0]) | (spread(q[:, 1]) << 1) | (spread(q[:, 2]) << 2)
-        want = torch.argsort(code, stable=True).to(torch.int32)
-        perm = torch.empty(P, dtype=torch.int32, device=dev)
-        scratch = torch.empty(L.igs_morton_order_scratch_bytes(P), dtype=torch.uint8, device=dev)
-        lohi = torch.cat([lo, hi]).contiguous()
-        assert L.igs_morton_order(torch.cuda.current_stream(dev).cuda_stream, P, xyz.data_ptr(), lohi.data_ptr(), bits, scratch.data_ptr(),
-                                  perm.data_ptr()) == 0
-        assert torch.equal(perm, want), (P, bits)
+
+def _check_morton_order(dev, gen, P, bits):
+    """One igs_morton_order call on P random points at `bits` bits per axis against torch.argsort(code, stable=True) of the codes."""
+    from igs_amd import _cabi
+    L = _cabi.lib()
+    xyz = (torch.randn(P, 3, generator=gen) * 3.0).to(dev).contiguous()
+    lo, hi = xyz.min(dim=0).values, xyz.max(dim=0).values
+    q = ((xyz - lo) / (hi - lo).clamp(min=1e-12) * (2 ** bits - 1)).long().clamp(0, 2 ** bits - 1)
+
+    def spread(v):
+        v = (v | (v << 16)) & 0x30000FF
+        v = (v | (v << 8)) & 0x300F00F
+        v = (v | (v << 4)) & 0x30C30C3
+        return (v | (v << 2)) & 0x9249249
+    code = spread(q[:, 0]) | (spread(q[:, 1]) << 1) | (spread(q[:, 2]) << 2)
+    want = torch.argsort(code, stable=True).to(torch.int32)
+    perm = torch.empty(P, dtype=torch.int32, device=dev)
+    scratch = torch.empty(L.igs_morton_order_scratch_bytes(P), dtype=torch.uint8, device=dev)
+    lohi = torch.cat([lo, hi]).contiguous()
+    assert L.igs_morton_order(torch.cuda.current_stream(dev).cuda_stream, P, xyz.data_ptr(), lohi.data_ptr(), bits, scratch.data_ptr(),
+                              perm.data_ptr()) == 0
+    assert torch.equal(perm, want), (P, bits)
+
+
+def test_morton_order_at_every_pass_count_and_sort_tile_edge(dev):
+    """The radix sort under igs_morton_order where its protocol has edges (csrc/radix_sort.h): 3 * bits = 3 .. 27 key bits are 1, 1, 2, 2,
+    3, 3 and 4 passes, so the result is read from each buffer pair; P sits either side of one and of two 2048-element sort tiles; 1 and
+    2 bits per axis leave 8 and 64 distinct keys, so nearly every comparison is a tie that only a stable sort orders as
+    torch.argsort(code, stable=True) does.  Last, the capped geometry: 256 * 2048 + 1 pairs sort in 129 blocks of 4096."""
+    gen = torch.Generator().manual_seed(11)
+    for P in (2047, 2048, 2049, 4097):
+        for bits in (1, 2, 3, 5, 6, 8, 9):
+            _check_morton_order(dev, gen, P, bits)
+    _check_morton_order(dev, gen, 256 * 2048 + 1, 10)
 
 
 def test_spatial_sort_keeps_results_and_aggregated_binning_is_exact(dev):

@@ -206,11 +206,11 @@ def test_header_states_the_limits():
 def test_launch_geometry_restated_from_the_source():
     src = open(os.path.join(ROOT, "igs_amd", "csrc", "motion.hip")).read()
     for line in ("while (c < 512 && (uint64_t)c * 4 * 16 * 256 < E) c *= 2;", "while (((uint64_t)1 << bits) <= (uint64_t)A) bits++;",
-                 "return D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : D <= 512 ? 8 : 16;", "radix_sort_pairs(s, E, ka, kb, va, vb, hist, 0, L.bits, &sk, &sv)"):
+                 "return D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : D <= 512 ? 8 : 16;", "radix_sort_pairs(s, E, r, 0, L.bits)"):
         assert line in src, line
-    common = open(os.path.join(ROOT, "igs_amd", "csrc", "common.h")).read()
-    assert "#define SORT_MAX_BLOCKS 256" in common and "#define SORT_TILE (256 * SORT_ITEMS)" in common and "#define SORT_ITEMS 8" in common
-    assert "for (int lo = bit_lo; lo < bit_hi; lo += 8, pass++)" in open(os.path.join(ROOT, "igs_amd", "csrc", "sort.hip")).read()
+    header = open(os.path.join(ROOT, "igs_amd", "csrc", "radix_sort.h")).read()
+    assert "#define SORT_MAX_BLOCKS 256" in header and "#define SORT_TILE (256 * SORT_ITEMS)" in header and "#define SORT_ITEMS 8" in header
+    assert "for (int lo = bit_lo; lo < bit_hi; lo += 8, pass++)" in open(os.path.join(ROOT, "igs_amd", "csrc", "radix_sort.hip")).read()
     assert [MR.interp_chunk(e) for e in (1, 1 << 20, (1 << 20) + 1, 1 << 21, (1 << 21) + 1, 1 << 22, (1 << 22) + 1, 1 << 30)] == \
         [64, 64, 128, 128, 256, 256, 512, 512]
     assert [MR.interp_index_bits(a) for a in (1, 255, 256, 65535, 65536, MAX_ANCHORS)] == [1, 8, 9, 16, 17, 25]

@@ -1,6 +1,6 @@
 """Where does tile_sort spend its time?  Debug build only:
     IGS_EXTRA_FLAGS=-DSORT_TIMELINE python -c "import igs_amd.build as b; b.build()" && python tools/debug/sort_timeline.py
-Every workgroup (= tile) stamps the 100 MHz clock at its start, after the count, and when its sorted list is written (sort.hip, STL)."""
+Every workgroup (= tile) stamps the 100 MHz clock at its start, after the count, and when its sorted list is written (tile_sort.hip, STL)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
