@@ -70,6 +70,11 @@ SIGNATURES = {
     "igs_rast_backward_workspace_bytes": (_sz, [_i]),
     "igs_rast_backward": (_i, ([_vp, _i, _i, _i, _i, _vp, _i, _i] + [_vp] * 5 + [_f, _vp, _vp, _vp, _vp, _vp, _f, _f, _f]
                                + [_vp] * 5 + [_vp] * 7 + [_vp] + [_vp] * 8 + [_i, _i, _i])),
+    # V views of one Gaussian set: the two lists above with V behind the stream, [V] user / buffer / count arrays, and num_rendered [V]
+    "igs_rast_views_max": (_i, []),
+    "igs_rast_forward_views": (_i, [_vp, _i] + _FORWARD[1:-3] + [_vp, _i, _i, _i]),
+    "igs_rast_backward_views": (_i, ([_vp, _i, _i, _i, _i, _vp, _vp, _i, _i] + [_vp] * 5 + [_f, _vp, _vp, _vp, _vp, _vp, _f, _f, _f]
+                                     + [_vp] * 5 + [_vp] * 7 + [_vp] + [_vp] * 8 + [_i, _i, _i])),
     "igs_rast_mark_visible": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "igs_rast_debug_dump": (_i, [_vp, _i, _i, _i, _i] + [_vp] * 8),
     "igs_rast_next_backward_options": (None, [_i, _f]),

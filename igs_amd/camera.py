@@ -77,6 +77,30 @@ class Camera:
         return self
 
 
+def render_views(gs_fields, c2ws, FOV, resolution, background, sh_degree, clamp=True, means2D=None, scale_modifier=1.0):
+    """The view loop of GS3DRenderer.forward_single_batch (igs/models/gs.py:839-847) as one call: renders the activated Gaussians
+    `gs_fields` (a mapping with means3D [P,3], opacities [P,1], scales [P,3], rotations [P,4] and shs [P,M,3] or colors_precomp [P,3]) from
+    every camera of `c2ws` [V,4,4] with the settings of forward_single_view (gs.py:591-610: kernel_size 0, require_coord and
+    require_depth, no prefilter; `clamp` = the rade_clamp package, as there) and returns what the loop stacks (gs.py:849-854):
+    images_pred [V,3,H,W], depth_pred [V,1,H,W] (the expected depth) and bg_color [V,3].  The cameras are built by Camera.from_c2w, one by
+    one as the loop builds them.  `means2D` [V,P,3], if given, receives the per-view screen-space gradient."""
+    from . import rasterizer as R
+    cams = [Camera.from_c2w(c2w, FOV, resolution) for c2w in c2ws]
+    if not cams:
+        raise ValueError("render_views: no cameras")
+    E = torch.Tensor([])
+    settings = R.GaussianRasterizationSettings(
+        image_height=cams[0].height, image_width=cams[0].width, tanfovx=cams[0].tanfovx, tanfovy=cams[0].tanfovy, kernel_size=0.0,
+        bg=background, scale_modifier=scale_modifier, viewmatrix=E, projmatrix=E, sh_degree=sh_degree, campos=E, prefiltered=False,
+        require_depth=True, require_coord=True, debug=False)
+    shs, colors = gs_fields.get("shs"), gs_fields.get("colors_precomp")
+    out = R.rasterize_views(gs_fields["means3D"], E if shs is None else shs, E if colors is None else colors, gs_fields["opacities"],
+                            gs_fields["scales"], gs_fields["rotations"], E, settings,
+                            torch.stack([c.world_view_transform for c in cams]), torch.stack([c.full_proj_transform.float() for c in cams]),
+                            torch.stack([c.camera_center for c in cams]), means2D=means2D, clamp=clamp)
+    return {"images_pred": out[0], "depth_pred": out[4], "bg_color": background.unsqueeze(0).expand(len(cams), -1)}
+
+
 def look_at_c2w(eye, target, up=(0.0, -1.0, 0.0)):
     """OpenCV/COLMAP-style camera-to-world (x right, y down, z forward)."""
     eye = torch.as_tensor(eye, dtype=torch.float32)

@@ -32,11 +32,14 @@ static const bool g_trace_launches = getenv("IGS_TRACE_LAUNCHES") != nullptr;
 
 // pinned status slot + event: one per host thread AND device, kept until the thread ends (a blend kernel still running on the
 // device used before may yet post into its slot, so switching devices never frees one)
-struct HostSlot { uint32_t* pinned = nullptr; uint32_t* pinned_dev = nullptr; hipEvent_t ev = nullptr; };
+// Slot 0 (`pinned`) is the single-view entry points'; the multi-view forward (igs_rast_forward_views) posts view v's status into slot
+// 1 + v of `views`, one 64-byte line each, allocated by the first such call.
+struct HostSlot { uint32_t* pinned = nullptr; uint32_t* pinned_dev = nullptr; hipEvent_t ev = nullptr; uint32_t* views = nullptr; uint32_t* views_dev = nullptr; };
 #define IGS_MAX_DEVICES 64
+#define VIEW_SLOT_WORDS 16
 struct HostSlots {
     HostSlot slot[IGS_MAX_DEVICES];
-    ~HostSlots() { for (auto& h : slot) if (h.pinned) { (void)hipHostFree(h.pinned); (void)hipEventDestroy(h.ev); } }
+    ~HostSlots() { for (auto& h : slot) { if (h.pinned) { (void)hipHostFree(h.pinned); (void)hipEventDestroy(h.ev); } if (h.views) (void)hipHostFree(h.views); } }
 };
 static thread_local HostSlots g_slots;
 static thread_local HostSlot g_slot;                // the current device's slot (a copy of the table entry)
@@ -57,6 +60,24 @@ static int ensure_slot()
     g_slot = h;
     return 0;
 }
+// ... and the current device's view slots 1 .. IGS_VIEWS_MAX
+static int ensure_view_slots()
+{
+    if (int rc = ensure_slot()) return rc;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev), "hipGetDevice");
+    HostSlot& h = g_slots.slot[dev];
+    if (!h.views) {
+        HIP_TRY(hipHostMalloc((void**)&h.views, IGS_VIEWS_MAX * VIEW_SLOT_WORDS * 4, hipHostMallocDefault), "hipHostMalloc");
+        HIP_TRY(hipHostGetDevicePointer((void**)&h.views_dev, h.views, 0), "hipHostGetDevicePointer");
+        memset(h.views, 0, IGS_VIEWS_MAX * VIEW_SLOT_WORDS * 4);
+    }
+    g_slot = h;
+    return 0;
+}
+// status slot k of the current device as the host and as the device address it (k = 0: the single-view slot)
+static uint32_t* slot_host(int k) { return k ? g_slot.views + (size_t)(k - 1) * VIEW_SLOT_WORDS : g_slot.pinned; }
+static uint32_t* slot_dev(int k) { return k ? g_slot.views_dev + (size_t)(k - 1) * VIEW_SLOT_WORDS : g_slot.pinned_dev; }
 
 static double now_s() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
 static double wait_limit_s()
@@ -71,16 +92,16 @@ static double wait_limit_s()
 // a ~6 us bubble per step, and the first workgroup posts at the START of the kernel, so the host is released earlier too.
 // Bounded: a stream that reports an error, a stream that drains without the post, or IGS_RAST_WAIT_TIMEOUT_S (default 10)
 // seconds of wall clock without it all end the wait with IGS_RAST_E_HIP.
-static int wait_status(hipStream_t s)
+static int wait_status(hipStream_t s, const uint32_t* pinned, uint32_t want)
 {
-    volatile uint32_t* seq = (volatile uint32_t*)&g_slot.pinned[3];
+    volatile uint32_t* seq = (volatile uint32_t*)&pinned[3];
     double t0 = 0.0;
     for (long spins = 0;; spins++) {
-        if (__atomic_load_n(seq, __ATOMIC_ACQUIRE) == g_host_seq) return 0;
+        if (__atomic_load_n(seq, __ATOMIC_ACQUIRE) == want) return 0;
         if ((spins & 0x3FFF) == 0x3FFF) {
             const hipError_t q = hipStreamQuery(s);
             if (q != hipSuccess && q != hipErrorNotReady) return fail(IGS_RAST_E_HIP, "stream error while waiting for the frame status", q);
-            if (q == hipSuccess && __atomic_load_n(seq, __ATOMIC_ACQUIRE) != g_host_seq)
+            if (q == hipSuccess && __atomic_load_n(seq, __ATOMIC_ACQUIRE) != want)
                 return fail(IGS_RAST_E_HIP, "the frame status was never posted");
             const double t = now_s();
             if (t0 == 0.0) t0 = t;
@@ -215,6 +236,7 @@ struct FwdExtra {
     // igs_rast_count_gaussians: vanilla preprocess (dilated conic, raw opacity) and the counting colour-only blend (blend_count.hip);
     // the per-Gaussian pixel counts land here (zeroed by the preprocess of every attempt, so a redone frame counts once)
     int* count = nullptr;
+    int status_slot = 0;                // igs_rast_forward_views: the pinned slot view v's blend kernel posts into (1 + v)
 };
 // where the last slab-binned forward left its device-side validity words (refine step guards)
 struct LastFwd { const uint32_t* overflow = nullptr; const uint32_t* prefilter = nullptr; };
@@ -385,10 +407,10 @@ static int launch_blend(const Frame& f, const Binned& b)
     ba.accum_coord = (float*)f.ibuf(f.IL.accum_coord); ba.accum_depth = (float*)f.ibuf(f.IL.accum_depth);
     ba.normal_length = (float*)f.ibuf(f.IL.normal_length);
     ba.stats_src = b.slab_stats; ba.flag_src = b.slab_stats ? b.slab_stats + 2 : f.gbuf(f.GL.counters) + 1;
-    ba.host_dst = b.pending ? g_slot.pinned_dev : nullptr;
+    ba.host_dst = b.pending ? slot_dev(ex.status_slot) : nullptr;
     ba.tile_order = f.ibuf(f.IL.tile_order);          // built on the side for the backward (both binning paths)
     ba.skip_bwd_state = ex.skip_bwd_state ? 1 : 0;
-    if (b.pending) { g_host_seq = g_host_seq + 1 ? g_host_seq + 1 : 1; g_slot.pinned[3] = 0; }
+    if (b.pending) { g_host_seq = g_host_seq + 1 ? g_host_seq + 1 : 1; slot_host(ex.status_slot)[3] = 0; }
     ba.host_seq = g_host_seq;
     if (b.pending && ex.no_latch) g_nowait_seq = g_host_seq;
     g_status_stream = s;
@@ -418,10 +440,11 @@ static int launch_blend(const Frame& f, const Binned& b)
 struct FrameStatus { uint32_t R, overflow, prefilter; };
 static FrameStatus read_status(const uint32_t* p) { return { __atomic_load_n(&p[0], __ATOMIC_ACQUIRE), __atomic_load_n(&p[1], __ATOMIC_ACQUIRE), p[2] }; }
 // waits for the status of the current slab-binned frame and checks it: returns R or an error; *overflow as posted
-static int collect_status(hipStream_t s, uint32_t* overflow)
+static int collect_status(hipStream_t s, uint32_t* overflow, int slot = 0, uint32_t seq = g_host_seq)
 {
-    if (int rc = wait_status(s)) return rc;
-    const FrameStatus st = read_status(g_slot.pinned);
+    const uint32_t* pinned = slot_host(slot);
+    if (int rc = wait_status(s, pinned, seq)) return rc;
+    const FrameStatus st = read_status(pinned);
     *overflow = st.overflow;
     if (st.prefilter) return fail(IGS_RAST_E_PREFILTER, "Point is filtered although prefiltered is set. This shouldn't happen!");
     if (st.R > 0x7FFFFFFFu) return fail(IGS_RAST_E_INVALID, "instance count overflows int");
@@ -591,6 +614,107 @@ static int last_status(int* num_rendered, unsigned* overflow, unsigned* prefilte
 }
 extern "C" int igs_rast_last_status(int* num_rendered, unsigned* overflow, unsigned* prefilter) { return last_status(num_rendered, overflow, prefilter, true); }
 extern "C" int igs_rast_last_posted_status(int* num_rendered, unsigned* overflow, unsigned* prefilter) { return last_status(num_rendered, overflow, prefilter, false); }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// V views of one Gaussian set (the view loop of GS3DRenderer.forward_single_batch, igs/models/gs.py:839-847, each pass of which is
+// one RasterizeGaussiansCUDA, rasterize_points.cu:35-133): all V slab-binned pipelines are enqueued, view v posting into status
+// slot 1 + v, before the host looks at the first status -- one host wait per call.  A view whose slabs overflowed is redone alone
+// through forward_impl (slot 0) once every status is in and the slab hint has been raised to fit the largest of them.
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int igs_rast_views_max(void) { return IGS_VIEWS_MAX; }
+
+// view v's FwdIn: the shared arguments, camera v, scratch set v and slice v of every output
+static FwdIn view_fwd_in(const FwdIn& in, int v, void* const* geometry_user, void* const* binning_user, void* const* image_user)
+{
+    FwdIn f = in;
+    const size_t HW = (size_t)in.width * in.height;
+    f.geometry_user = geometry_user[v]; f.binning_user = binning_user[v]; f.image_user = image_user[v];
+    f.viewmatrix = in.viewmatrix + 16 * v; f.projmatrix = in.projmatrix + 16 * v; f.cam_pos = in.cam_pos + 3 * v;
+    f.out_color = in.out_color + 3 * HW * v; f.out_coord = in.out_coord + 3 * HW * v; f.out_mcoord = in.out_mcoord + 3 * HW * v;
+    f.out_depth = in.out_depth + HW * v; f.out_mdepth = in.out_mdepth + HW * v; f.out_alpha = in.out_alpha + HW * v;
+    f.out_normal = in.out_normal + 3 * HW * v; f.radii = in.radii + (size_t)in.P * v;
+    return f;
+}
+
+extern "C" int igs_rast_forward_views(
+    void* stream, int V, igs_rast_alloc_fn geometry_buffer, void* const* geometry_user, igs_rast_alloc_fn binning_buffer, void* const* binning_user,
+    igs_rast_alloc_fn image_buffer, void* const* image_user, int P, int D, int M, const float* background, int width, int height,
+    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
+    float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+    const float* cam_pos, float tan_fovx, float tan_fovy, float kernel_size, int prefiltered, float* out_color, float* out_coord,
+    float* out_mcoord, float* out_depth, float* out_mdepth, float* out_alpha, float* out_normal, int* radii, int* num_rendered,
+    int require_coord, int require_depth, int debug)
+{
+    const char* fn = "igs_rast_forward_views";
+    if (V < 1 || V > IGS_VIEWS_MAX) return fail_in(fn, "V must be 1 .. igs_rast_views_max()");
+    if (P < 0 || width <= 0 || height <= 0) return fail_in(fn, "bad sizes");
+    if (!num_rendered) return fail_in(fn, "NULL num_rendered");
+    for (int v = 0; v < V; v++) num_rendered[v] = 0;
+    if (P == 0) return 0;
+    if (!viewmatrix || !projmatrix || !cam_pos) return fail_in(fn, "NULL camera array");
+    if (!geometry_buffer || !binning_buffer || !image_buffer || !geometry_user || !binning_user || !image_user)
+        return fail_in(fn, "NULL scratch callback or per-view user array");
+    if (!out_color || !out_coord || !out_mcoord || !out_depth || !out_mdepth || !out_alpha || !out_normal || !radii) return fail_in(fn, "NULL output");
+    if (M > 16) return fail_in(fn, "more than 16 SH coefficients per channel are not supported");
+    if (g_pending.active) return fail_in(fn, "an asynchronous forward is pending on this thread; call igs_rast_forward_finish() first");
+    const hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return fail_in(fn, "the stream is capturing: capture of the multi-view forward is not supported (capture single views with igs_rast_forward_nowait)");
+    const FwdIn in{ s, geometry_buffer, nullptr, binning_buffer, nullptr, image_buffer, nullptr, P, D, M, background, width, height, means3D,
+                    shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx,
+                    tan_fovy, kernel_size, prefiltered, out_color, out_coord, out_mcoord, out_depth, out_mdepth, out_alpha, out_normal, radii,
+                    require_coord, require_depth, debug };
+    const bool hint_clean = g_hint_clean; g_hint_clean = false;      // (igs_rast_hint_scratch_clean: here a promise about all V image buffers)
+    FwdIn vin[IGS_VIEWS_MAX];
+    for (int v = 0; v < V; v++) vin[v] = view_fwd_in(in, v, geometry_user, binning_user, image_user);
+    const uint64_t slab = g_hint.slab ? g_hint.slab : 1024;
+    const uint64_t Tn = (uint64_t)((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE);
+    if (radix_forced() || Tn * slab > 0x7FFFFFFFull || Tn * slab * 12 > SLAB_MAX_BYTES) {
+        // the global sort reads its instance count back in the middle of every frame: one view after the other
+        for (int v = 0; v < V; v++) {
+            prof_new_frame();
+            const int R = forward_impl(vin[v], FwdExtra(), radix_forced());
+            if (R < 0) return R;
+            num_rendered[v] = R;
+        }
+        return 0;
+    }
+    // forward_impl's argument checks on view 0 (the views differ in pointers offset from the same bases), without launching anything
+    if (!means3D || !opacities || !background) return fail_in(fn, "NULL required input");
+    if (!colors_precomp && !shs) return fail_in(fn, "neither shs nor colors_precomp");
+    if (!cov3D_precomp && (!scales || !rotations)) return fail_in(fn, "neither scales/rotations nor cov3D_precomp");
+    if (!colors_precomp && (M < (D + 1) * (D + 1) || D < 0 || D > 3)) return fail_in(fn, "SH degree / coefficient count mismatch");
+    if (int rc = ensure_view_slots()) return rc;
+    uint32_t seq[IGS_VIEWS_MAX];
+    for (int v = 0; v < V; v++) {
+        prof_new_frame();
+        FwdExtra ex; ex.status_slot = 1 + v; ex.scratch_clean = hint_clean;
+        Frame f(vin[v], ex);
+        if (int rc = carve_frame(f)) return rc;
+        Binned b;
+        if (int rc = bin_slab(f, (uint32_t)slab, b)) return rc;
+        if (int rc = launch_blend(f, b)) return rc;
+        seq[v] = g_host_seq;
+    }
+    uint32_t overflow[IGS_VIEWS_MAX], worst = 0;
+    for (int v = 0; v < V; v++) {
+        const int R = collect_status(s, &overflow[v], 1 + v, seq[v]);
+        if (R < 0) return R;
+        num_rendered[v] = R;
+        if (overflow[v] > worst) worst = overflow[v];
+        if (g_prof.on && !overflow[v]) { g_prof.r_sum += (double)R; g_prof.calls++; }
+    }
+    if (!worst) return 0;
+    g_hint.slab = slab_hint_for(worst);              // raised once, to what the densest tile of any view needs
+    for (int v = 0; v < V; v++) {
+        if (!overflow[v]) continue;
+        const int R = forward_impl(vin[v], FwdExtra(), false);
+        if (R < 0) return R;
+        num_rendered[v] = R;
+    }
+    return 0;
+}
 
 extern "C" void igs_rast_set_slab_hint(unsigned slots_per_tile) { g_hint.slab = slots_per_tile > TILE_SORT_BIG ? TILE_SORT_BIG : slots_per_tile; }
 extern "C" unsigned igs_rast_get_slab_hint(void) { return g_hint.slab; }
@@ -815,6 +939,103 @@ extern "C" int igs_rast_backward(
                     dL_dpixel_normals, workspace, dL_dmean2D, dL_dcolor, dL_dopacity, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
                     require_coord, require_depth, debug };
     return backward_impl(in, nullptr);
+}
+
+// The backward of igs_rast_forward_views (V times RasterizeGaussiansBackwardCUDA, rasterize_points.cu:135-246, and the AccumulateGrad
+// adds of gs.py:839-847's loop): every view's blend backward into its own accumulator rows, then ONE per-Gaussian kernel that sums
+// over the views (geom_bwd.hip: geom_bwd_views_kernel).  Nothing between the launches involves the host.
+extern "C" int igs_rast_backward_views(
+    void* stream, int V, int P, int D, int M, const int* R, const float* background, int width, int height,
+    const float* means3D, const float* shs, const float* colors_precomp, const float* alphas,
+    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+    const float* viewmatrix, const float* projmatrix, const float* campos,
+    float tan_fovx, float tan_fovy, float kernel_size, const int* radii, const float* normalmap,
+    const char* const* geom_buffer, const char* const* binning_buffer, const char* const* image_buffer,
+    const float* dL_dpix, const float* dL_dpix_coord, const float* dL_dpix_mcoord, const float* dL_dpix_depth,
+    const float* dL_dpix_mdepth, const float* dL_dalphas, const float* dL_dpixel_normals,
+    void* workspace,
+    float* dL_dmean2D, float* dL_dcolor, float* dL_dopacity, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+    float* dL_dscale, float* dL_drot, int require_coord, int require_depth, int debug)
+{
+    const char* fn = "igs_rast_backward_views";
+    const hipStream_t s = (hipStream_t)stream;
+    if (V < 1 || V > IGS_VIEWS_MAX) return fail_in(fn, "V must be 1 .. igs_rast_views_max()");
+    if (P < 0 || width <= 0 || height <= 0) return fail_in(fn, "bad sizes");
+    if (P == 0) return 0;
+    if (!viewmatrix || !projmatrix || !campos) return fail_in(fn, "NULL camera array");
+    if (!R || !geom_buffer || !binning_buffer || !image_buffer || !workspace) return fail_in(fn, "NULL per-view scratch");
+    for (int v = 0; v < V; v++) {
+        if (R[v] < 0) return fail_in(fn, "negative instance count");
+        if (!geom_buffer[v] || !image_buffer[v] || (!binning_buffer[v] && R[v] > 0)) return fail_in(fn, "NULL per-view scratch");
+    }
+    if (!means3D || !alphas || !background || !radii || !normalmap) return fail_in(fn, "NULL required input");
+    if (!dL_dcolor || !dL_dopacity || !dL_dmean3D || !dL_dcov3D || !dL_dscale || !dL_drot || (shs && M > 0 && !dL_dsh)) return fail_in(fn, "NULL output");
+    if (M > 16) return fail_in(fn, "more than 16 SH coefficients per channel are not supported");
+    if ((uint64_t)P * GACC_F * 8 >= (1ull << 32)) return fail_in(fn, "more than 16 million Gaussians are not supported");
+    const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
+    const size_t Tn = (size_t)gx * gy, HW = (size_t)width * height;
+    const GeomLayout GL(P);
+    const ImgLayout IL(HW, Tn);
+    const float fy = height / (2.0f * tan_fovy), fx = width / (2.0f * tan_fovx);
+    const size_t ws_view = igs_rast_backward_workspace_bytes(P);
+
+    const float clamp_next = g_next_clamp; g_next_clamp = 0.f;       // (one-shot, consumed here even if the call fails later)
+    NanSlot* nan = nullptr;
+    if (int rc = take_nan_request(&nan)) return rc;
+    // one layout for the call, as backward_impl picks it for a view: an upstream gradient is present for all views or for none
+    const bool will_compact = !(require_coord && (dL_dpix_coord || dL_dpix_mcoord)) && !(require_depth && (dL_dpix_depth || dL_dpix_mdepth))
+                              && !((require_coord || require_depth) && dL_dpixel_normals);
+    GeomBwdViews w;
+    w.V = V; w.views = viewmatrix; w.projs = projmatrix; w.campos = campos; w.radii = radii; w.dL_dmean2D = dL_dmean2D;
+    int inst_last = -1;
+    prof_mark(s, ST_GAP);
+    for (int v = 0; v < V; v++) {
+        const char* gbase = align_ptr(geom_buffer[v]);
+        const char* ibase = align_ptr(image_buffer[v]);
+        const char* bbase = binning_buffer[v] ? align_ptr(binning_buffer[v]) : nullptr;
+        double* gacc = (double*)align_ptr((const char*)workspace + ws_view * v);
+        HIP_TRY(zero_fill_async(s, gacc, (size_t)P * (will_compact ? GACC_COMPACT_F : GACC_F) * 8), "zero gacc");
+        auto img = [&](const float* p, size_t c) { return p ? p + c * HW * v : nullptr; };
+        BlendBwdArgs ba;
+        ba.W = width; ba.H = height; ba.gx = gx; ba.gy = gy; ba.fx = fx; ba.fy = fy; ba.bg = background;
+        ba.ranges = (const uint32_t*)(ibase + IL.ranges);
+        ba.point_list = bbase ? (const uint32_t*)(bbase + BinLayout(R[v]).point_list) : nullptr;
+        ba.rec = (const float*)(gbase + GL.rec); ba.colors_precomp = colors_precomp;
+        ba.alphas = alphas + HW * v; ba.normalmap = normalmap + 3 * HW * v;
+        ba.accum_coord = (const float*)(ibase + IL.accum_coord); ba.accum_depth = (const float*)(ibase + IL.accum_depth);
+        ba.normal_length = (const float*)(ibase + IL.normal_length); ba.n_contrib = (const uint32_t*)(ibase + IL.n_contrib);
+        ba.dL_dpix = img(dL_dpix, 3); ba.dL_dcoord = img(dL_dpix_coord, 3); ba.dL_dmcoord = img(dL_dpix_mcoord, 3); ba.dL_ddepth = img(dL_dpix_depth, 1);
+        ba.dL_dmdepth = img(dL_dpix_mdepth, 1); ba.dL_dalpha = img(dL_dalphas, 1); ba.dL_dnormal = img(dL_dpixel_normals, 3);
+        ba.gacc = gacc;
+        ba.l1_gt = nullptr; ba.l1_color = nullptr; ba.l1_scale = 0.f; ba.l1_loss = nullptr;
+        ba.want_absgrad = dL_dmean2D ? 1 : 0;
+        ba.tile_order = (const uint32_t*)(ibase + IL.tile_order);
+        if (R[v] > 0) {
+            bool gacc_compact = will_compact;
+            HIP_TRY(launch_blend_bwd(s, ba, require_coord != 0, require_depth != 0, &gacc_compact, &inst_last), "blend_bwd launch");
+            if (gacc_compact != will_compact) return fail(IGS_RAST_E_INVALID, "internal: accumulator layout mismatch");
+            DBG_SYNC("blend_bwd");
+        }
+        w.rec[v] = ba.rec; w.gacc[v] = gacc;
+    }
+    __atomic_store_n(&g_last_bwd_instance, inst_last, __ATOMIC_RELAXED);
+    prof_mark(s, ST_BLEND_BWD);
+    GeomBwdArgs ga;
+    ga.P = P; ga.D = D; ga.M = shs ? M : 0; ga.W = width; ga.H = height;
+    ga.means3D = means3D; ga.shs = shs; ga.scales = scales; ga.rotations = rotations; ga.cov3D_precomp = cov3D_precomp;
+    ga.radii = nullptr; ga.scale_modifier = scale_modifier; ga.tan_fovx = tan_fovx; ga.tan_fovy = tan_fovy;
+    ga.fx = fx; ga.fy = fy; ga.kernel_size = kernel_size;
+    ga.view = nullptr; ga.proj = nullptr; ga.campos = nullptr; ga.rec = nullptr; ga.gacc = nullptr; ga.gacc_compact = will_compact ? 1 : 0;
+    ga.dL_dmean2D = nullptr; ga.dL_dcolor = dL_dcolor; ga.dL_dopacity = dL_dopacity; ga.dL_dmean3D = dL_dmean3D;
+    ga.dL_dcov3D = dL_dcov3D; ga.dL_dsh = dL_dsh; ga.dL_dscale = dL_dscale; ga.dL_drot = dL_drot;
+    ga.clamp = clamp_next;
+    NanTicket* ticket = nullptr;
+    if (nan) { if (int rc = next_nan_ticket(*nan, ga, &ticket)) return rc; }
+    HIP_TRY(launch_geom_bwd_views(s, ga, w), "geom_bwd_views launch");
+    if (ticket) { HIP_TRY(hipEventRecord(ticket->ev, s), "record NaN-report event"); nan->pending = true; }
+    DBG_SYNC("geom_bwd_views");
+    prof_mark(s, ST_GEOM_BWD);
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -194,6 +194,17 @@ struct GeomBwdArgs {
     const float* plane_cache = nullptr; uint32_t plane_tag = 0;      // what the forward of this frame kept (NULL = nothing: run the eigen-solver)
 };
 hipError_t launch_geom_bwd(hipStream_t s, const GeomBwdArgs& a);
+// V views of one Gaussian set (igs_rast_backward_views): what differs per view.  GeomBwdArgs carries what the views share and the summed
+// outputs; its view / proj / campos / radii / rec / gacc / dL_dmean2D are not looked at.
+#define IGS_VIEWS_MAX 16
+struct GeomBwdViews {
+    int V;
+    const float *views, *projs, *campos;      // [V][16], [V][16], [V][3] on the device
+    const int* radii;                         // [V][P]
+    float* dL_dmean2D;                        // [V][P][3] or NULL
+    const float* rec[IGS_VIEWS_MAX]; const double* gacc[IGS_VIEWS_MAX];      // every view's records and accumulator rows
+};
+hipError_t launch_geom_bwd_views(hipStream_t s, const GeomBwdArgs& a, const GeomBwdViews& w);
 
 // Single-GPU refine step: the per-Gaussian backward continues through the activations (sigmoid / exp / normalize) and applies
 // the Adam update in place, so no gradient array ever reaches HBM.  means3D / shs / scales / rotations of GeomBwdArgs then

@@ -5,6 +5,7 @@
 // Input is the 128-byte raw-moment accumulator line written by blend_bwd.hip; every output element is written
 // (zeros for culled Gaussians), so the caller needs no memsets.
 // The kernel (geom_bwd_kernel, below its phases) is a sequence of phases, each a function of its own here (the plane-fit backward: two, and a tail).
+// geom_bwd_views_kernel, further down, runs the same phases once per view of a multi-view call and writes the sum (igs_rast_backward_views).
 //
 // Quirks of the reference reproduced on purpose:
 //  * computeCov2DCUDA is handed dL_dconic in its `conic_opacity` parameter (rasterizer_impl.cu:569), so what it calls
@@ -796,6 +797,154 @@ hipError_t launch_geom_bwd_adam(hipStream_t s, const GeomBwdArgs& a, const Refin
         else                hipLaunchKernelGGL((geom_bwd_kernel<true, NT, false, true>), dim3(blocks), dim3(NT), lds, s, g);
     } else if (a.gacc_compact) hipLaunchKernelGGL((geom_bwd_kernel<true, NT, true>), dim3(blocks), dim3(NT), lds, s, g);
     else                       hipLaunchKernelGGL((geom_bwd_kernel<true, NT, false>), dim3(blocks), dim3(NT), lds, s, g);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// V views of one Gaussian set in one launch (igs_rast_backward_views): the sum over the views of what geom_bwd_kernel<false> writes
+// for each of them (gs.py:839-847 renders the same Gaussians once per camera and leaves the sum to autograd's AccumulateGrad).
+// ---------------------------------------------------------------------------------------------
+// the plane fit's tail as a function, for the view loop below (geom_bwd_kernel keeps it in its body: see plane_fit_planes)
+__device__ __forceinline__ void plane_fit_tail(const Cov2DCtx& c, const Moments& mo, const UvProducts& p2, const PlaneFitMid& mid, PlaneFitGrads& pf)
+{
+    const float u = c.txtz, v = c.tytz;
+    const float3 t = c.t, m = mid.m, NiT_dpa = mid.NiT_dpa; const float nl = pf.nl;
+    const float c0x = mo.c0x, c0y = mo.c0y, c1x = mo.c1x, c1y = mo.c1y;
+    const float dpx = mid.dpx, dpy = mid.dpy, dL_dnl = mid.dL_dnl, tmp = mid.tmp, clamp_vb = mid.clamp_vb;
+    M3 Cd;
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) Cd.m[r][q] = c.Cinv.m[r][q] / clamp_vb;
+    const float3 dL_duvh = m * (2 * (-tmp)) + m3_vec(Cd, NiT_dpa);
+    const float DI01 = dpx * m.y, DI10 = dpy * m.x, DI11 = dpy * m.y, DI02 = dpx * m.z, DI00 = dpx * m.x, DI12 = dpy * m.z;
+    pf.dL_du = dL_dnl * 2 * u + dL_duvh.x + (DI10 + DI01) * (-v) + 2 * DI11 * u - DI02 + (c0y * t.y + c1x * t.y + c1y * (-2 * t.x)) / nl;
+    pf.dL_dv = dL_dnl * 2 * v + dL_duvh.y + (DI10 + DI01) * (-u) + 2 * DI00 * v - DI12 + (c0x * (-2 * t.y) + c0y * t.x + c1x * t.x) / nl;
+}
+// one visible Gaussian's gradients under the camera and the rows of `a`: the phases in geom_bwd_kernel's order, dL_dsh left out
+__device__ __forceinline__ void view_grads(const GeomBwdArgs& a, int idx, GaussGrads& o)
+{
+    Moments mo;
+    PlaneCacheEntry pce;
+    load_moments<false>(a, idx, mo, o, pce);
+    Cov2DCtx c;
+    cov2d_ctx(c, mo.mean, mo.cov3D, a.view, a.fx, a.fy, a.tan_fovx, a.tan_fovy, a.kernel_size, mo.need_planes, &pce, a.plane_tag);
+    PlaneFitGrads pf;
+    const float u = c.txtz, v = c.tytz;
+    const UvProducts p2 = { u * u, v * v, u * v };
+    if (!c.degenerate) {
+        PlaneFitMid mid;
+        plane_fit_planes(c, mo, p2, pf, mid);
+        plane_fit_sigma(c, p2, mid, pf.dVs);
+        plane_fit_tail(c, mo, p2, mid, pf);
+    }
+    ConicGrads cg;
+    conic_backward(c, mo, pf, a.kernel_size, cg, o);
+    mean_backward(a, c, mo, pf, p2, cg, o);
+    if (a.shs) {
+        const float3 dir_orig = mo.mean - make_float3(a.campos[0], a.campos[1], a.campos[2]);
+        o.mean = o.mean + sh_backward<false>(a.D, a.M, a.shs + (size_t)idx * a.M * 3, dir_orig, mo.clamped, o.color, nullptr);
+    }
+    if (a.scales) cov3d_backward<false>(a, idx, o);
+}
+
+struct GBVArgs { GeomBwdArgs a; GeomBwdViews w; };
+
+// One thread per Gaussian, two loops over the views in index order, each adding into registers; every output row is written once and no
+// atomics are involved, so the result depends on the inputs and the view order alone.  A Gaussian that no view sees keeps the +0 its
+// sums start from.
+//  loop 1: the seven small gradients.  A view's gradients are clamped (clamp variant) before they are added: two single-view calls of
+//          the clamp package clamp each view's tensors and autograd adds them afterwards.  dL_dmean2D is per view and is not summed.
+//  loop 2: dL_dsh = sum_v basis(direction_v) x masked colour gradient_v, with sh_exchange.hip's convention (b_k * g_c, clamp, add; rows
+//          at or beyond (D + 1)^2 stay +0).  It reads three moments and the clamp mask of every view again: 28 bytes per view, against
+//          48 more live registers in loop 1.  The two loops' registers overlap instead of adding up: loop 1 holds the general
+//          instance's body and 20 sums, loop 2 holds 48 sums and little else.
+// The view loop has nothing to hoist but the Gaussian's own mean, scale and rotation -- the cameras are uniform (SGPRs) and the rows
+// are a view's own -- which is what kept it clear of the grid-stride loop's register blow-up recorded at geom_bwd_kernel.
+template <int NT>
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(GEOM_WAVES_PER_EU)))
+geom_bwd_views_kernel(const GBVArgs args)
+{
+    const GeomBwdArgs& a = args.a;
+    const GeomBwdViews& w = args.w;
+    const int idx = blockIdx.x * NT + threadIdx.x;
+    if (idx >= a.P) return;
+    GaussGrads sum;
+    bool found_nan = false;
+    for (int v = 0; v < w.V; v++) {
+        GaussGrads o;
+        if (w.radii[(size_t)v * a.P + idx] > 0) {
+            GeomBwdArgs av = a;
+            av.view = w.views + 16 * v; av.proj = w.projs + 16 * v; av.campos = w.campos + 3 * v;
+            av.rec = w.rec[v]; av.gacc = w.gacc[v];
+            view_grads(av, idx, o);
+        }
+        if (w.dL_dmean2D) {
+            float* m2d = w.dL_dmean2D + ((size_t)v * a.P + idx) * 3;
+            m2d[0] = o.m2d.x; m2d[1] = o.m2d.y; m2d[2] = o.m2d.z;
+        }
+        if (a.nan_host) found_nan |= (o.m2d.x != o.m2d.x) | (o.m2d.y != o.m2d.y) | (o.m2d.z != o.m2d.z);
+        if (a.clamp > 0.f) clamp_grads(o, a.clamp);
+        sum.color = sum.color + o.color; sum.mean = sum.mean + o.mean; sum.scale = sum.scale + o.scale;
+        sum.opacity += o.opacity;
+#pragma unroll
+        for (int k = 0; k < 6; k++) sum.cov[k] += o.cov[k];
+        sum.rot = make_float4(sum.rot.x + o.rot.x, sum.rot.y + o.rot.y, sum.rot.z + o.rot.z, sum.rot.w + o.rot.w);
+    }
+    found_nan |= write_grads(a, idx, sum);
+    if (a.M) {
+        float acc[48];
+#pragma unroll
+        for (int k = 0; k < 48; k++) acc[k] = 0.f;
+        const float3 mean = make_float3(a.means3D[3 * idx], a.means3D[3 * idx + 1], a.means3D[3 * idx + 2]);
+        const int used = min((a.D + 1) * (a.D + 1), a.M);
+        const int stride = a.gacc_compact ? GACC_COMPACT_F : GACC_F;
+        for (int v = 0; v < w.V; v++) {
+            if (w.radii[(size_t)v * a.P + idx] <= 0) continue;
+            const double* gr = w.gacc[v] + (size_t)idx * stride;
+            const uint32_t clamped = __float_as_uint(w.rec[v][(size_t)idx * REC_F + 30]);      // record word 7.z (preprocess.hip)
+            const float3 g = make_float3((clamped & 1u) ? 0.f : (float)gr[0], (clamped & 2u) ? 0.f : (float)gr[1], (clamped & 4u) ? 0.f : (float)gr[2]);
+            const float3 dir = mean - make_float3(w.campos[3 * v], w.campos[3 * v + 1], w.campos[3 * v + 2]);
+            const float len = sqrtf(dot3(dir, dir));
+            const float x = dir.x / len, y = dir.y / len, z = dir.z / len;
+            float b[16];
+#pragma unroll
+            for (int k = 0; k < 16; k++) b[k] = 0.f;
+            sh_basis(a.D, x, y, z, [&](int k, float bk) { b[k] = bk; });
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                if (k < used) {
+                    float t0 = b[k] * g.x, t1 = b[k] * g.y, t2 = b[k] * g.z;
+                    if (a.clamp > 0.f) { t0 = clamp_keep_nan(t0, a.clamp); t1 = clamp_keep_nan(t1, a.clamp); t2 = clamp_keep_nan(t2, a.clamp); }
+                    acc[3 * k] += t0; acc[3 * k + 1] += t1; acc[3 * k + 2] += t2;
+                }
+            }
+        }
+        if (a.nan_host) {
+#pragma unroll
+            for (int k = 0; k < 48; k++) found_nan |= acc[k] != acc[k];
+        }
+        float* dst = a.dL_dsh + (size_t)idx * a.M * 3;
+        if (a.M == 16 && (((uintptr_t)a.dL_dsh) & 15) == 0) {
+#pragma unroll
+            for (int k = 0; k < 12; k++) ((float4*)dst)[k] = make_float4(acc[4 * k], acc[4 * k + 1], acc[4 * k + 2], acc[4 * k + 3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; k++)
+                if (k < a.M) { dst[3 * k] = acc[3 * k]; dst[3 * k + 1] = acc[3 * k + 1]; dst[3 * k + 2] = acc[3 * k + 2]; }
+        }
+    }
+    if (a.nan_host && found_nan) __atomic_store_n(a.nan_host, a.nan_seq, __ATOMIC_RELAXED);      // (as geom_bwd_kernel reports)
+}
+#ifndef GEOM_VIEWS_THREADS
+#define GEOM_VIEWS_THREADS 128
+#endif
+hipError_t launch_geom_bwd_views(hipStream_t s, const GeomBwdArgs& a, const GeomBwdViews& w)
+{
+    if (a.M > 16 || w.V < 1 || w.V > IGS_VIEWS_MAX) return hipErrorInvalidValue;
+    GBVArgs g; g.a = a; g.w = w;
+    constexpr int NT = GEOM_VIEWS_THREADS;
+    hipLaunchKernelGGL((geom_bwd_views_kernel<NT>), dim3((a.P + NT - 1) / NT), dim3(NT), 0, s, g);
     return hipGetLastError();
 }
 

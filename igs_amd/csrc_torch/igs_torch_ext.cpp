@@ -8,6 +8,7 @@
 //                                               four functions of the reference's pybind module (DGR/ext.cpp:15-20, DGR/rasterize_points.cu:
 //                                               35-267; DGR = submodules/RaDe-GS/submodules/diff-gaussian-rasterization); count_gaussians of
 //                                               the compress package (compress-diff-gaussian-rasterization rasterize_points.cu:130-217)
+//   multi-view          api.hip, geom_bwd.hip   ViewsCall; _views.rasterize_views, _views.rasterize_views_backward: V cameras on one Gaussian set, one C call each
 //   simple_knn          knn.hip                 distCUDA2
 //   anchor graph        anchors.hip             anchors_bbox_select, anchors_fps, anchors_knn (fixed output shapes, no host synchronisation)
 //   interpolation       motion.hip              motion_interp_fwd / _index / _bwd
@@ -370,6 +371,162 @@ template <class... A> struct BackwardFns<BwdResult(int64_t, double, A...)> {
         return std::make_tuple(r.grads, r.nan, r.nan_word, r.nan_seq);
     }
 };
+
+// ---- V views of one Gaussian set (api.hip: igs_rast_forward_views / igs_rast_backward_views; no reference counterpart as one call: the
+// view loop of igs/models/gs.py:839-847 over RasterizeGaussiansCUDA / RasterizeGaussiansBackwardCUDA, DGR/rasterize_points.cu:35-246) ----
+// what the two functions check alike: float32 everywhere, V cameras, V scratch sets, P rows in every per-Gaussian input
+struct ViewsCall : GpuCall {
+    int64_t V, P;
+    static const Tensor& checked(const char* fn, const Tensor& means3D, const Tensor& viewmatrices, const Tensor& projmatrices, const Tensor& camposes,
+                                 size_t n_scratch, std::initializer_list<Named> per_gaussian, std::initializer_list<Named> floats)
+    {
+        const std::string f(fn);
+        if (means3D.dim() != 2 || means3D.size(1) != 3) throw RasterizerError(f + ": means3D must have dimensions (num_points, 3)");
+        const int64_t V = viewmatrices.dim() >= 1 ? viewmatrices.size(0) : 0, P = means3D.size(0);
+        if (V < 1 || V > igs_rast_views_max())
+            throw RasterizerError(f + ": " + std::to_string(V) + " views; one call takes 1 .. " + std::to_string(igs_rast_views_max()));
+        if (viewmatrices.numel() != 16 * V || projmatrices.numel() != 16 * V || projmatrices.size(0) != V || camposes.numel() != 3 * V || camposes.size(0) != V)
+            throw RasterizerError(f + ": viewmatrices / projmatrices / camposes must be [V, 4, 4], [V, 4, 4], [V, 3] with the same V");
+        if ((int64_t)n_scratch != V) throw RasterizerError(f + ": " + std::to_string(n_scratch) + " scratch sets for " + std::to_string(V) + " views");
+        for (const Named& o : per_gaussian)
+            if (o.t.numel() && o.t.size(0) != P) throw RasterizerError(f + ": " + o.name + " has " + std::to_string(o.t.size(0)) + " rows, means3D " + std::to_string(P));
+        for (const Named& o : floats)
+            if (o.t.defined() && o.t.numel() && o.t.scalar_type() != at::kFloat)
+                throw RasterizerError(f + ": " + o.name + " must be float32 (got " + c10::toString(o.t.scalar_type()) + ")");
+        return means3D;
+    }
+    ViewsCall(const char* fn, const Tensor& means3D, const Tensor& viewmatrices, const Tensor& projmatrices, const Tensor& camposes, size_t n_scratch,
+              std::initializer_list<Named> per_gaussian, std::initializer_list<Named> floats)
+        : GpuCall(checked(fn, means3D, viewmatrices, projmatrices, camposes, n_scratch, per_gaussian, floats), RASTERIZER_ON_CPU),
+          V(viewmatrices.size(0)), P(means3D.size(0)) {}
+};
+using ScratchSets = std::vector<std::shared_ptr<ScratchSet>>;
+using ViewsFwdTuple = std::tuple<std::vector<int64_t>, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
+
+// _C._views.rasterize_views: rasterize_gaussians' arguments with [V, 4, 4] / [V, 4, 4] / [V, 3] cameras and one scratch set per view.
+// Returns (num_rendered [V], color, coord, mcoord, alpha, normal, depth, mdepth -- each [V, c, H, W] -- and radii [V, P]).
+ViewsFwdTuple rasterize_views(
+    const Tensor& background, const Tensor& means3D, const Tensor& colors, const Tensor& opacity, const Tensor& scales,
+    const Tensor& rotations, double scale_modifier, const Tensor& cov3D_precomp, const Tensor& viewmatrices, const Tensor& projmatrices,
+    double tan_fovx, double tan_fovy, double kernel_size, int64_t image_height, int64_t image_width, const Tensor& sh, int64_t degree,
+    const Tensor& camposes, bool prefiltered, bool require_coord, bool require_depth, bool debug, const ScratchSets& scratch, bool scratch_clean)
+{
+    const char* fn = "rasterize_views";
+    const ViewsCall c(fn, means3D, viewmatrices, projmatrices, camposes, scratch.size(),
+                      { {colors, "colors_precomp"}, {opacity, "opacities"}, {scales, "scales"}, {rotations, "rotations"}, {cov3D_precomp, "cov3D_precomp"}, {sh, "shs"} },
+                      { {background, "bg"}, {means3D, "means3D"}, {colors, "colors_precomp"}, {opacity, "opacities"}, {scales, "scales"}, {rotations, "rotations"},
+                        {cov3D_precomp, "cov3D_precomp"}, {sh, "shs"}, {viewmatrices, "viewmatrices"}, {projmatrices, "projmatrices"}, {camposes, "camposes"} });
+    const int64_t V = c.V, P = c.P, H = image_height, W = image_width;
+    if (H <= 0 || W <= 0) throw RasterizerError("image_height and image_width must be positive");
+    for (const auto& ss : scratch)
+        if (!ss || ss->device != c.dev) throw RasterizerError("rasterize_views: every scratch set must live on " + c.dev.str());
+    auto fopt = at::TensorOptions().dtype(at::kFloat).device(c.dev);
+    // one allocation for the seven image stacks ([V][c][H][W] each, as the C call writes them); every pixel is written when P > 0
+    Tensor imgs = P > 0 ? at::empty({15 * V * H * W}, fopt) : at::zeros({15 * V * H * W}, fopt);
+    Tensor radii = P > 0 ? at::empty({V, P}, fopt.dtype(at::kInt)) : at::zeros({V, 0}, fopt.dtype(at::kInt));
+    const int64_t HW = H * W;
+    auto stack = [&](int64_t first, int64_t ch) { return imgs.narrow(0, first * V * HW, ch * V * HW).view({V, ch, H, W}); };
+    Tensor color = stack(0, 3), coord = stack(3, 3), mcoord = stack(6, 3), depth = stack(9, 1), mdepth = stack(10, 1), alpha = stack(11, 1),
+           normal = stack(12, 3);
+    std::vector<int64_t> rendered((size_t)V, 0);
+    if (P != 0) {
+        In m3(means3D, c.dev, "means3D"), col(colors, c.dev, "colors_precomp"), op(opacity, c.dev, "opacities"), sc(scales, c.dev, "scales"),
+           rot(rotations, c.dev, "rotations"), cov(cov3D_precomp, c.dev, "cov3D_precomp"), shs(sh, c.dev, "shs"), bg(background, c.dev, "bg"),
+           view(viewmatrices, c.dev, "viewmatrices"), proj(projmatrices, c.dev, "projmatrices"), cam(camposes, c.dev, "camposes");
+        const int64_t M = shs.p ? shs.keep.size(1) : 0;
+        std::vector<void*> ug, ub, ui;
+        for (const auto& ss : scratch) { ug.push_back(&ss->g_geom); ub.push_back(&ss->g_binning); ui.push_back(&ss->g_img); }
+        std::vector<int> nr((size_t)V, 0);
+        if (scratch_clean) igs_rast_hint_scratch_clean(1);
+        check(igs_rast_forward_views(c.stream(), (int)V, grow_cb, ug.data(), grow_cb, ub.data(), grow_cb, ui.data(), (int)P, (int)degree, (int)M, bg.p,
+                                     (int)W, (int)H, m3.p, shs.p, col.p, op.p, sc.p, (float)scale_modifier, rot.p, cov.p, view.p, proj.p, cam.p,
+                                     (float)tan_fovx, (float)tan_fovy, (float)kernel_size, prefiltered ? 1 : 0, color.data_ptr<float>(),
+                                     coord.data_ptr<float>(), mcoord.data_ptr<float>(), depth.data_ptr<float>(), mdepth.data_ptr<float>(),
+                                     alpha.data_ptr<float>(), normal.data_ptr<float>(), radii.data_ptr<int>(), nr.data(), require_coord ? 1 : 0,
+                                     require_depth ? 1 : 0, debug ? 1 : 0),
+              "igs_rast_forward_views");
+        for (int64_t v = 0; v < V; v++) rendered[(size_t)v] = nr[(size_t)v];
+    }
+    return ViewsFwdTuple(rendered, color, coord, mcoord, alpha, normal, depth, mdepth, radii);
+}
+
+// _C._views.rasterize_views_backward: the upstream gradients are [V, c, H, W] stacks or None (= zeros for every view); `scratch` and `R` are the
+// forward's sets and counts.  Returns ((dL_dmeans2D [V, P, 3] or an empty tensor, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh,
+// dL_dscales, dL_drotations -- summed over the views), nan flag, verdict word, sequence number) as rasterize_gaussians_backward_ex does.
+std::tuple<BwdTuple, int64_t, int64_t, int64_t> rasterize_views_backward(
+    const Tensor& background, const Tensor& means3D, const Tensor& radii, const Tensor& colors, const Tensor& scales, const Tensor& rotations,
+    double scale_modifier, const Tensor& cov3D_precomp, const Tensor& viewmatrices, const Tensor& projmatrices, double tan_fovx, double tan_fovy,
+    double kernel_size, const OptTensor& dL_dout_color, const OptTensor& dL_dout_coord, const OptTensor& dL_dout_mcoord,
+    const OptTensor& dL_dout_depth, const OptTensor& dL_dout_mdepth, const OptTensor& dL_dout_alpha, const OptTensor& dL_dout_normal,
+    const Tensor& normalmap, const Tensor& sh, int64_t degree, const Tensor& camposes, const ScratchSets& scratch, const std::vector<int64_t>& R,
+    const Tensor& alphas, bool require_coord, bool require_depth, bool debug, bool want_means2D, int64_t nan_report, double clamp)
+{
+    const char* fn = "rasterize_views_backward";
+    const ViewsCall c(fn, means3D, viewmatrices, projmatrices, camposes, scratch.size(),
+                      { {colors, "colors_precomp"}, {scales, "scales"}, {rotations, "rotations"}, {cov3D_precomp, "cov3D_precomp"}, {sh, "shs"} },
+                      { {background, "bg"}, {means3D, "means3D"}, {colors, "colors_precomp"}, {scales, "scales"}, {rotations, "rotations"},
+                        {cov3D_precomp, "cov3D_precomp"}, {sh, "shs"}, {viewmatrices, "viewmatrices"}, {projmatrices, "projmatrices"}, {camposes, "camposes"},
+                        {normalmap, "normalmap"}, {alphas, "alphas"} });
+    const c10::Device& dev = c.dev;
+    const int64_t V = c.V, P = c.P;
+    if ((int64_t)R.size() != V) throw RasterizerError("rasterize_views_backward: R must hold one instance count per view");
+    if (alphas.dim() != 4 || alphas.size(0) != V || normalmap.dim() != 4 || normalmap.size(0) != V)
+        throw RasterizerError("rasterize_views_backward: alphas / normalmap must be the forward's [V, c, H, W] stacks");
+    if (P > 0 && (radii.dim() != 2 || radii.size(0) != V || radii.size(1) != P || radii.scalar_type() != at::kInt))
+        throw RasterizerError("rasterize_views_backward: radii must be int32 [V, P]");
+    const int64_t H = alphas.size(-2), W = alphas.size(-1);
+    const int64_t ch[7] = { 3, 3, 3, 1, 1, 1, 3 };
+    const OptTensor* ups[7] = { &dL_dout_color, &dL_dout_coord, &dL_dout_mcoord, &dL_dout_depth, &dL_dout_mdepth, &dL_dout_alpha, &dL_dout_normal };
+    for (int k = 0; k < 7; k++)
+        if (ups[k]->has_value() && (*ups[k])->defined() && (*ups[k])->numel() != V * ch[k] * H * W)
+            throw RasterizerError("rasterize_views_backward: an upstream gradient is not a [V, c, H, W] stack of the forward's size");
+    In shs(sh, dev, "shs");
+    const int64_t M = shs.p ? shs.keep.size(1) : 0;
+    auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
+    Tensor dL_dsh = P > 0 ? at::empty({P, M, 3}, fopt) : at::zeros({P, M, 3}, fopt);
+    Tensor block = P > 0 ? at::empty({20 * P}, fopt) : at::zeros({0}, fopt);
+    Tensor dL_dmeans2D = (want_means2D && P > 0) ? at::empty({V, P, 3}, fopt) : at::zeros({want_means2D ? V : 0, want_means2D ? P : 0, 3}, fopt);
+    int64_t o = 0;
+    auto carve = [&](int64_t k) { Tensor t = block.narrow(0, o, k * P).view({P, k}); o += k * P; return t; };
+    Tensor dL_dcolors = carve(3), dL_dopacity = carve(1), dL_dmeans3D = carve(3), dL_dscales = carve(3), dL_drotations = carve(4), dL_dcov3D = carve(6);
+    int64_t nan = 0, nan_word = 0, nan_seq = 0;
+    if (P != 0) {
+        In m3(means3D, dev, "means3D"), col(colors, dev, "colors_precomp"), sc(scales, dev, "scales"), rot(rotations, dev, "rotations"),
+           cov(cov3D_precomp, dev, "cov3D_precomp"), bg(background, dev, "bg"), view(viewmatrices, dev, "viewmatrices"),
+           proj(projmatrices, dev, "projmatrices"), cam(camposes, dev, "camposes"), al(alphas, dev, "alphas"), nm(normalmap, dev, "normalmap");
+        In g0(dL_dout_color, dev, "grad"), g1(dL_dout_coord, dev, "grad"), g2(dL_dout_mcoord, dev, "grad"), g3(dL_dout_depth, dev, "grad"),
+           g4(dL_dout_mdepth, dev, "grad"), g5(dL_dout_alpha, dev, "grad"), g6(dL_dout_normal, dev, "grad");
+        Tensor radii_c = radii.contiguous();
+        Tensor ws = at::empty({V * (int64_t)igs_rast_backward_workspace_bytes((int)P)}, at::TensorOptions().dtype(at::kByte).device(dev));
+        std::vector<const char*> pg, pb, pi; std::vector<int> nr;
+        auto bp = [](const Tensor& t) { return t.numel() ? (const char*)t.data_ptr() : nullptr; };
+        for (int64_t v = 0; v < V; v++) {
+            const auto& ss = scratch[(size_t)v];
+            if (!ss || ss->device != dev) throw RasterizerError("rasterize_views_backward: every scratch set must live on " + dev.str());
+            pg.push_back(bp(ss->geom)); pb.push_back(bp(ss->binning)); pi.push_back(bp(ss->img));
+            nr.push_back((int)std::min<int64_t>(R[(size_t)v], INT_MAX));
+        }
+        if (nan_report || clamp > 0.0) igs_rast_next_backward_options(nan_report ? 1 : 0, (float)clamp);
+        check(igs_rast_backward_views(
+                  c.stream(), (int)V, (int)P, (int)degree, (int)M, nr.data(), bg.p, (int)W, (int)H, m3.p, shs.p, col.p, al.p, sc.p, (float)scale_modifier,
+                  rot.p, cov.p, view.p, proj.p, cam.p, (float)tan_fovx, (float)tan_fovy, (float)kernel_size, radii_c.data_ptr<int>(), nm.p, pg.data(),
+                  pb.data(), pi.data(), g0.p, g1.p, g2.p, g3.p, g4.p, g5.p, g6.p, ws.data_ptr(), want_means2D ? dL_dmeans2D.data_ptr<float>() : nullptr,
+                  dL_dcolors.data_ptr<float>(), dL_dopacity.data_ptr<float>(), dL_dmeans3D.data_ptr<float>(), dL_dcov3D.data_ptr<float>(),
+                  M > 0 ? dL_dsh.data_ptr<float>() : nullptr, dL_dscales.data_ptr<float>(), dL_drotations.data_ptr<float>(), require_coord ? 1 : 0,
+                  require_depth ? 1 : 0, debug ? 1 : 0),
+              "igs_rast_backward_views");
+        if (nan_report == 1) {
+            const int v = igs_rast_nan_report_wait();
+            check(v, "igs_rast_nan_report_wait");
+            nan = v;
+        } else if (nan_report == 2) {
+            const void* word = nullptr; unsigned seq = 0;
+            check(igs_rast_nan_report_handle(&word, &seq), "igs_rast_nan_report_handle");
+            nan_word = (int64_t)(uintptr_t)word; nan_seq = (int64_t)seq;
+        }
+    }
+    return std::make_tuple(BwdTuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations), nan, nan_word, nan_seq);
+}
 
 // _C.mark_visible (DGR/rasterize_points.cu:248-267)
 Tensor mark_visible(const Tensor& means3D, const Tensor& viewmatrix, const Tensor& projmatrix)
@@ -1481,6 +1638,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
         check(v, "igs_rast_nan_report_wait_at");
         return v != 0;
     }, "word"_a, "seq"_a);
+    py::module_ vw = m.def_submodule("_views", "V views of one Gaussian set in one call (api.hip, geom_bwd.hip)");
+    def_nogil(vw, "rasterize_views", &rasterize_views, "background"_a, "means3D"_a, "colors"_a, "opacity"_a, "scales"_a, "rotations"_a,
+              "scale_modifier"_a, "cov3D_precomp"_a, "viewmatrices"_a, "projmatrices"_a, "tan_fovx"_a, "tan_fovy"_a, "kernel_size"_a, "image_height"_a,
+              "image_width"_a, "sh"_a, "degree"_a, "camposes"_a, "prefiltered"_a, "require_coord"_a, "require_depth"_a, "debug"_a, py::kw_only(),
+              "scratch"_a, "scratch_clean"_a = false);
+    def_nogil(vw, "rasterize_views_backward", &rasterize_views_backward, "background"_a, "means3D"_a, "radii"_a, "colors"_a, "scales"_a, "rotations"_a,
+              "scale_modifier"_a, "cov3D_precomp"_a, "viewmatrices"_a, "projmatrices"_a, "tan_fovx"_a, "tan_fovy"_a, "kernel_size"_a, "dL_dout_color"_a,
+              "dL_dout_coord"_a, "dL_dout_mcoord"_a, "dL_dout_depth"_a, "dL_dout_mdepth"_a, "dL_dout_alpha"_a, "dL_dout_normal"_a, "normalmap"_a, "sh"_a,
+              "degree"_a, "camposes"_a, "scratch"_a, "R"_a, "alphas"_a, "require_coord"_a, "require_depth"_a, "debug"_a, py::kw_only(),
+              "want_means2D"_a = true, "nan_report"_a = 0, "clamp"_a = 0.0);
+    vw.def("views_max", []() { return igs_rast_views_max(); });
     def_nogil(m, "count_gaussians", &count_gaussians, "background"_a, "means3D"_a, "colors"_a, "opacity"_a, "scales"_a, "rotations"_a,
               "scale_modifier"_a, "cov3D_precomp"_a, "viewmatrix"_a, "projmatrix"_a, "tan_fovx"_a, "tan_fovy"_a, "image_height"_a, "image_width"_a,
               "sh"_a, "degree"_a, "campos"_a, "prefiltered"_a, "debug"_a, "f_count"_a, py::kw_only(), "scratch"_a = std::shared_ptr<ScratchSet>());

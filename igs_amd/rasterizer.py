@@ -69,9 +69,9 @@ class _ScratchPool:
             return lst.pop()
         return ScratchSet(key[3], True)
 
-    def release(self, key, item):
+    def release(self, key, item, keep=None):
         lst = self.free.setdefault(key, [])
-        if len(lst) < self.KEEP:
+        if len(lst) < (keep or self.KEEP):          # (`keep`: a multi-view call leases V sets at once)
             lst.append(item)
         if len(self.free) > 8:            # sizes come and go (densification): forget the oldest keys
             for k in list(self.free)[:-8]:
@@ -139,10 +139,11 @@ class _Lease:
     must be memory the GRAPH owns -- it is allocated fresh while capturing (from the graph's private memory pool, which the
     graph keeps reserved for as long as it lives) and never handed to `_POOL`, where an eager call with the same key would
     share it and a pool eviction would let the allocator recycle it under later replays."""
-    __slots__ = ("key", "item", "pooled", "scope", "baked")
+    __slots__ = ("key", "item", "pooled", "scope", "baked", "keep")
 
-    def __init__(self, key, capturing):
+    def __init__(self, key, capturing, keep=None):
         self.key = key
+        self.keep = keep
         self.scope = getattr(_TLS, "scope", None)
         self.baked = None
         if self.scope is not None:
@@ -166,7 +167,7 @@ class _Lease:
     def __del__(self):
         try:
             if self.pooled:
-                _POOL.release(self.key, self.item)
+                _POOL.release(self.key, self.item, self.keep)
         except Exception:  # noqa: BLE001  (interpreter shutdown)
             pass
 
@@ -426,3 +427,134 @@ def _make_api(fn_cls):
 
 rasterize_gaussians_autograd, GaussianRasterizer = _make_api(_RasterizeGaussians)
 rasterize_gaussians_autograd_clamp, GaussianRasterizerClamp = _make_api(_RasterizeGaussiansClamp)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# V views of one Gaussian set in one call: the view loop of GS3DRenderer.forward_single_batch (igs/models/gs.py:839-847) as ONE autograd
+# node over igs_rast_forward_views / igs_rast_backward_views.  The loop's V nodes each wait for their instance count, write a full set
+# of gradients and, from the second view on, have autograd add them up; here there is one host wait and one set of summed gradients.
+# ---------------------------------------------------------------------------------------------------------------
+def views_max():
+    """The largest V `rasterize_views` accepts (igs_rast_views_max)."""
+    return _C._views.views_max()
+
+
+def _check_views(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices, projmatrices, camposes, means2D):
+    """The refusals of `rasterize_views`, before any GPU work: ValueError for dtypes and shapes, then RuntimeError for CPU tensors."""
+    named = dict(means3D=means3D, sh=sh, colors_precomp=colors_precomp, opacities=opacities, scales=scales, rotations=rotations,
+                 cov3Ds_precomp=cov3Ds_precomp, viewmatrices=viewmatrices, projmatrices=projmatrices, camposes=camposes)
+    if means2D is not None:
+        named["means2D"] = means2D
+    for n, t in named.items():
+        if t.numel() and t.dtype != torch.float32:
+            raise ValueError("rasterize_views: %s must be float32 (got %s)" % (n, t.dtype))
+    if means3D.dim() != 2 or means3D.size(1) != 3:
+        raise ValueError("rasterize_views: means3D must have dimensions (num_points, 3)")
+    V, P = (viewmatrices.size(0) if viewmatrices.dim() else 0), means3D.size(0)
+    if not 1 <= V <= views_max():
+        raise ValueError("rasterize_views: %d views; one call takes 1 .. %d" % (V, views_max()))
+    if tuple(viewmatrices.shape) != (V, 4, 4) or tuple(projmatrices.shape) != (V, 4, 4) or tuple(camposes.shape) != (V, 3):
+        raise ValueError("rasterize_views: viewmatrices / projmatrices / camposes must be [V, 4, 4], [V, 4, 4], [V, 3] with the same V (got %s, %s, %s)"
+                         % (tuple(viewmatrices.shape), tuple(projmatrices.shape), tuple(camposes.shape)))
+    for n in ("sh", "colors_precomp", "opacities", "scales", "rotations", "cov3Ds_precomp"):
+        if named[n].numel() and named[n].size(0) != P:
+            raise ValueError("rasterize_views: %s has %d rows, means3D %d" % (n, named[n].size(0), P))
+    if means2D is not None and tuple(means2D.shape) != (V, P, 3):
+        raise ValueError("rasterize_views: means2D must be [V, P, 3] = %s (got %s)" % ((V, P, 3), tuple(means2D.shape)))
+    for n, t in named.items():
+        if t.numel() and not t.is_cuda:
+            raise RasterizerError("rasterize_views: %s must be on a GPU (no CPU fallback)" % n)
+    if torch.cuda.is_current_stream_capturing():
+        raise RasterizerError("rasterize_views: capture into a graph is not supported; capture single views (rasterize_gaussians_autograd)")
+    return V, P
+
+
+def _views_forward(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices, projmatrices, camposes):
+    """The forward call with V pooled scratch sets; returns (leases, _C._views.rasterize_views' tuple)."""
+    V, dev = viewmatrices.size(0), means3D.device
+    key = (means3D.size(0), int(rs.image_height), int(rs.image_width), dev, torch._C._cuda_getCurrentRawStream(dev.index))
+    leases = [_Lease(key, False, keep=views_max()) for _ in range(V)]
+    out = _C._views.rasterize_views(rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, viewmatrices,
+                             projmatrices, rs.tanfovx, rs.tanfovy, rs.kernel_size, rs.image_height, rs.image_width, sh, rs.sh_degree, camposes,
+                             rs.prefiltered, rs.require_coord, rs.require_depth, rs.debug, scratch=[l.item for l in leases], scratch_clean=True)
+    return leases, out
+
+
+def _make_views_function(clamp_grads):
+    clamp_value = 15.0 if clamp_grads else 0.0
+
+    class _RasterizeViews(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices, projmatrices,
+                    camposes, raster_settings):
+            ctx.set_materialize_grads(False)      # (an output outside the loss arrives as None: the C ABI reads NULL as zeros, for every view)
+            leases, out = _views_forward(raster_settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                         viewmatrices, projmatrices, camposes)
+            num_rendered, color, coord, mcoord, alpha, normal, depth, mdepth, radii = out
+            ctx.raster_settings, ctx.num_rendered = raster_settings, num_rendered
+            ctx.leases = leases               # the V scratch sets go back to the pool when this context dies
+            ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, normal, radii, sh, alpha, viewmatrices,
+                                  projmatrices, camposes)
+            ctx.mark_non_differentiable(radii)
+            return color, radii, coord, mcoord, depth, mdepth, alpha, normal
+
+        @staticmethod
+        def backward(ctx, grad_color, grad_radii, grad_coord, grad_mcoord, grad_depth, grad_mdepth, grad_alpha, grad_normal):
+            rs = ctx.raster_settings
+            (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, normal, radii, sh, alpha, viewmatrices, projmatrices,
+             camposes) = ctx.saved_tensors
+            nan_report = 0
+            if NAN_CHECKS:
+                nan_report = 2 if NAN_CHECKS_AT_END_OF_PASS else 1
+            out, has_nan, word, seq = _C._views.rasterize_views_backward(
+                rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, viewmatrices, projmatrices,
+                rs.tanfovx, rs.tanfovy, rs.kernel_size, grad_color, grad_coord, grad_mcoord, grad_depth, grad_mdepth, grad_alpha, grad_normal,
+                normal, sh, rs.sh_degree, camposes, [l.item for l in ctx.leases], ctx.num_rendered, alpha, rs.require_coord, rs.require_depth,
+                rs.debug, want_means2D=bool(ctx.needs_input_grad[1]), nan_report=nan_report, clamp=clamp_value)
+            grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales, grad_rotations = out
+            assert not has_nan
+            if nan_report == 2 and word:          # raised from the end of the backward pass, as the single-view Function does
+                def _verdict(word=word, seq=seq):
+                    assert not _C.nan_report_wait(word, seq)
+                try:
+                    torch.autograd.Variable._execution_engine.queue_callback(_verdict)
+                except Exception:  # noqa: BLE001  (no engine pass to attach to: wait here)
+                    _verdict()
+            return (grad_means3D, grad_means2D if ctx.needs_input_grad[1] else None, grad_sh if sh.numel() else None,
+                    grad_colors_precomp if colors_precomp.numel() else None, grad_opacities, grad_scales if scales.numel() else None,
+                    grad_rotations if rotations.numel() else None, grad_cov3Ds_precomp if cov3Ds_precomp.numel() else None,
+                    None, None, None, None)
+
+    return _RasterizeViews
+
+
+_RasterizeViews = _make_views_function(False)
+_RasterizeViewsClamp = _make_views_function(True)
+
+
+def rasterize_views(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, viewmatrices, projmatrices,
+                    camposes, means2D=None, clamp=False):
+    """V views of one Gaussian set: what V calls of `rasterize_gaussians_autograd[_clamp]` with cameras (viewmatrices[v], projmatrices[v],
+    camposes[v]) return, stacked -- (color [V,3,H,W], radii [V,P], coord, mcoord, depth, mdepth, alpha, normal), every view bit for bit --
+    and, in backward, the SUM of their gradients, formed by one per-Gaussian kernel (views in index order; with `clamp` every view's
+    gradients are clamped to +-15 before the sum, as the clamp package's V backward passes do).
+
+    `settings` is a GaussianRasterizationSettings whose viewmatrix / projmatrix / campos are ignored; image size, field of view,
+    background, SH degree, kernel size and the require_* flags are shared by the views.  Absent inputs are empty tensors, as for
+    `rasterize_gaussians_autograd`.  `means2D`, if given, is [V, P, 3] and receives the per-view screen-space gradient (the
+    densification statistics take it per view).  Refused before any GPU work: CPU tensors (RuntimeError); V outside 1 .. views_max(),
+    mismatching V or P, non-float32 inputs (ValueError); a capturing stream (RasterizerError)."""
+    _check_views(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices, projmatrices, camposes, means2D)
+    diff = (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in diff)):
+        # nothing to differentiate: no autograd node, nothing saved, the scratch sets go back to the pool at once
+        with torch.no_grad():
+            _, out = _views_forward(settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices,
+                                    projmatrices, camposes)
+        _, color, coord, mcoord, alpha, normal, depth, mdepth, radii = out
+        return color, radii, coord, mcoord, depth, mdepth, alpha, normal
+    if means2D is None:
+        means2D = torch.Tensor([])
+    fn = _RasterizeViewsClamp if clamp else _RasterizeViews
+    return fn.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices, projmatrices, camposes,
+                    settings)

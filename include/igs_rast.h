@@ -233,6 +233,68 @@ int igs_rast_backward(
     int require_coord, int require_depth,
     int debug);
 
+/* ---- V views of one Gaussian set in one call (no reference counterpart as ONE call: it replaces the view loop of
+ * GS3DRenderer.forward_single_batch, igs/models/gs.py:839-847, every pass of which is one RasterizeGaussiansCUDA /
+ * RasterizeGaussiansBackwardCUDA, rasterize_points.cu:35-246, and the AccumulateGrad adds autograd runs from the second view on) ----
+ *
+ * igs_rast_views_max(): the largest V one call accepts (16).
+ *
+ * igs_rast_forward_views: the argument list of igs_rast_forward with
+ *   viewmatrix [V][16], projmatrix [V][16], cam_pos [V][3]       device arrays, one camera per view;
+ *   out_color .. out_normal [V][c][H][W], radii [V][P]           view v's slice is what igs_rast_forward writes for camera v, bit for bit;
+ *   geometry_user / binning_user / image_user [V]                HOST arrays of `user` words: view v's scratch is requested as
+ *                                                                geometry_buffer(geometry_user[v], bytes) and so on -- one callback per
+ *                                                                kind, V distinct buffers, which igs_rast_backward_views takes back;
+ *   num_rendered [V]                                             HOST array: view v's instance count.
+ * Shared by all views: image size, tan_fovx/y, background, scale_modifier, kernel_size, SH degree (M <= 16), prefiltered, require_*.
+ * All V pipelines are enqueued before the host looks at a status, view v posting into status slot 1 + v of the calling thread (slot 0
+ * stays the single-view entry points'): one host wait per call.  A view whose per-tile slabs overflowed is redone alone once every
+ * status is in; the slab hint is raised once, to what the densest tile of any view needs; the other views' results stand.  With
+ * IGS_BINNING=radix (or slabs beyond the scratch limits) the views run one after the other through the global sort.
+ * igs_rast_hint_scratch_clean before the call is a promise about all V image buffers.
+ * Returns 0 or a negative IGS_RAST_E_* code.  IGS_RAST_E_INVALID before any HIP call: V < 1 or V > igs_rast_views_max(), bad sizes, a
+ * NULL camera array, a NULL callback or user array, a NULL output or num_rendered.  P == 0 launches nothing, zeroes num_rendered and
+ * returns 0.  On a capturing stream: IGS_RAST_E_INVALID (capture single views with igs_rast_forward_nowait).
+ *
+ * igs_rast_backward_views: the argument list of igs_rast_backward with
+ *   R [V]                                                        HOST array: num_rendered of igs_rast_forward_views;
+ *   viewmatrix / projmatrix / campos, radii [V][P]               as above;
+ *   alphas [V][1][H][W], normalmap [V][3][H][W]                  the forward's out_alpha / out_normal;
+ *   geom_buffer / binning_buffer / image_buffer [V]              HOST arrays of the V views' scratch addresses;
+ *   dL_dpix .. dL_dpixel_normals [V][c][H][W]                    any may be NULL = zeros for ALL views;
+ *   workspace                                                    V x igs_rast_backward_workspace_bytes(P) bytes, view v's part at v x that;
+ *   dL_dmean2D [V][P][3] or NULL                                 per view (the densification statistics take it per view); NULL skips it;
+ *   dL_dcolor .. dL_drot                                         ONE set: the sum over the views, views added in index order.
+ * The V blend backwards (the existing kernels) are enqueued, then one per-Gaussian kernel forms every view's gradients and adds them
+ * in registers: no float atomics, every row written once, +0 everywhere for a Gaussian no view sees.  With clamp_grads
+ * (igs_rast_next_backward_options) each VIEW's dL_dmean3D, dL_dsh, dL_dopacity, dL_dscale, dL_drot are clamped before they are added,
+ * which is what V single-view calls of the clamp package followed by autograd's adds compute.  nan_report: one word for the whole call.
+ * Returns 0 or a negative code; IGS_RAST_E_INVALID before any HIP call as above, and for a NULL entry of the per-view scratch arrays. */
+int igs_rast_views_max(void);
+int igs_rast_forward_views(
+    void* stream, int V,
+    igs_rast_alloc_fn geometry_buffer, void* const* geometry_user, igs_rast_alloc_fn binning_buffer, void* const* binning_user,
+    igs_rast_alloc_fn image_buffer, void* const* image_user,
+    int P, int D, int M, const float* background, int width, int height,
+    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
+    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+    const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+    float tan_fovx, float tan_fovy, float kernel_size, int prefiltered,
+    float* out_color, float* out_coord, float* out_mcoord, float* out_depth, float* out_mdepth, float* out_alpha,
+    float* out_normal, int* radii, int* num_rendered, int require_coord, int require_depth, int debug);
+int igs_rast_backward_views(
+    void* stream, int V, int P, int D, int M, const int* R, const float* background, int width, int height,
+    const float* means3D, const float* shs, const float* colors_precomp, const float* alphas,
+    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+    const float* viewmatrix, const float* projmatrix, const float* campos,
+    float tan_fovx, float tan_fovy, float kernel_size, const int* radii, const float* normalmap,
+    const char* const* geom_buffer, const char* const* binning_buffer, const char* const* image_buffer,
+    const float* dL_dpix, const float* dL_dpix_coord, const float* dL_dpix_mcoord, const float* dL_dpix_depth,
+    const float* dL_dpix_mdepth, const float* dL_dalphas, const float* dL_dpixel_normals,
+    void* workspace,
+    float* dL_dmean2D, float* dL_dcolor, float* dL_dopacity, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+    float* dL_dscale, float* dL_drot, int require_coord, int require_depth, int debug);
+
 int igs_rast_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix,
                           const float* projmatrix, uint8_t* present /* [P], 0/1 */);
 
