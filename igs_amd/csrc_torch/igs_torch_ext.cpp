@@ -15,6 +15,7 @@
 //   lifting             lift.hip                motion_lift_fwd / _bwd
 //   condition3D         cond.hip                cond_ray_fwd, modln_fwd / _bwd
 //                       cond_fused.hip          _cond.condition3d_fwd, _cond.pack_elems: the forward in one launch, ModLN's MLP included
+//   upsample + conv     upconv.hip              _upconv.upconv_fwd, _upconv.pack_elems: 2x bilinear upsample and 3x3 convolution in one launch
 //   attention           attn.hip                attn_fwd / _bwd on [B, H, A, 64] views of any acceptable strides
 //   window attention    wattn.hip               _window.window_attn_fwd / _bwd on [B, h w, 128] views of any acceptable strides
 //   encoder norms       inorm.hip               _encoder.instance_norm_fwd, _encoder.position_add on contiguous [N, C, H, W] tensors
@@ -872,6 +873,35 @@ Tensor condition3d_fwd(const Tensor& x, const Tensor& rays, const Tensor& depth,
     return out;
 }
 
+// ---- 2x bilinear upsample + 3x3 convolution in one launch (upconv.hip) ----
+int64_t upconv_pack_elems(int64_t Cin, int64_t Cout, bool half)
+{
+    if (Cin < 1 || Cin > INT_MAX || Cout < 1 || Cout > INT_MAX) return -1;
+    return igs_upconv_pack_elems((int)Cin, (int)Cout, half ? IGS_DTYPE_F16 : IGS_DTYPE_F32);
+}
+// out [N, Cout, 2H, 2W] contiguous in wpack's dtype (the compute dtype).  x [N, Cin, H, W] float32 / float16 with contiguous H x W planes,
+// wpack and bpack [128] as igs_upconv_fwd takes them (igs_amd/motion.py packs and caches them)
+Tensor upconv_fwd(const Tensor& x, const Tensor& wpack, const Tensor& bpack, int64_t Cout)
+{
+    const char* fn = "upconv_fwd";
+    const int xdt = dtype_code(x, fn, "x"), cdt = dtype_code(wpack, fn, "wpack");
+    if (x.dim() != 4) throw RasterizerError(std::string(fn) + ": x must have shape [N, Cin, H, W] (got " + c10::str(x.sizes()) + ")");
+    const int64_t N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+    if (H < 1 || W < 1 || H > IGS_UPCONV_MAX_HW || W > IGS_UPCONV_MAX_HW || N * H * W > IGS_UPCONV_MAX_PIXELS)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (1 <= H, W <= 4096, N * H * W <= 2^22)");
+    const int64_t elems = upconv_pack_elems(Cin, Cout, cdt == IGS_DTYPE_F16);
+    if (elems < 0) throw RasterizerError(std::string(fn) + ": Cin and Cout must be in 1..128 (got " + std::to_string(Cin) + ", " + std::to_string(Cout) + ")");
+    expect(wpack, fn, "wpack", wpack.scalar_type(), {elems});
+    expect(bpack, fn, "bpack", at::kFloat, {IGS_UPCONV_MAX_WIDTH});
+    if (!wpack.is_contiguous() || !bpack.is_contiguous()) throw RasterizerError(std::string(fn) + ": wpack and bpack must be contiguous");
+    const GpuCall c(x, fn, "x", {{wpack, "wpack"}, {bpack, "bpack"}});
+    Tensor out = at::empty({N, Cout, 2 * H, 2 * W}, x.options().dtype(wpack.scalar_type()));
+    if (N == 0) return out;
+    check(igs_upconv_fwd(c.stream(), (int)N, (int)Cin, (int)Cout, (int)H, (int)W, xdt, x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), x.stride(3),
+                         cdt, wpack.data_ptr(), bpack.data_ptr<float>(), out.data_ptr()), "igs_upconv_fwd");
+    return out;
+}
+
 // ---- fused attention for the anchor transformer (attn.hip; contract in include/igs_rast.h) ----
 struct AttnSizes { int64_t B, H, Aq, Ak; int dt; };
 void attn_view_check(const char* fn, const Tensor& t, const char* name, const Tensor& like, int64_t B, int64_t H, int64_t A)
@@ -1698,6 +1728,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     py::module_ cf = m.def_submodule("_cond", "condition3D's forward in one launch, ModLN's MLP included (cond_fused.hip)");
     def_nogil(cf, "condition3d_fwd", &condition3d_fwd, "x"_a, "rays"_a, "depth"_a, "wpack"_a, "bpack"_a, "hidden"_a, "weight"_a, "bias"_a, "eps"_a = 1e-6);
     def_nogil(cf, "pack_elems", &cond_fused_pack_elems, "C"_a, "hidden"_a, "half"_a = false);
+    py::module_ uc = m.def_submodule("_upconv", "2x bilinear upsample + 3x3 convolution in one launch (upconv.hip)");
+    def_nogil(uc, "upconv_fwd", &upconv_fwd, "x"_a, "wpack"_a, "bpack"_a, "Cout"_a);
+    def_nogil(uc, "pack_elems", &upconv_pack_elems, "Cin"_a, "Cout"_a, "half"_a = false);
     py::module_ ml = m.def_submodule("_mlp", "the residual decoder: MLP and output heads in one launch (mlp.hip)");
     def_nogil(ml, "mlp_heads_fwd", &mlp_heads_fwd, "x"_a, "wpack"_a, "bpack"_a, "widths"_a, "act_after"_a, "head_widths"_a, "act"_a = 0);
     ml.def("pack_elems", &mlp_pack_elems, "widths"_a, "head_widths"_a);

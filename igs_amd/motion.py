@@ -17,6 +17,10 @@ rsh_cart_3 and ModLN; igs_amd/csrc/cond.hip).  The ray embedding and the fused L
 between them stays PyTorch: the path with autograd.  `condition3d_fused` / `use_native_condition3d` are the same stage's forward in one
 launch, the MLP on the matrix cores included (igs_amd/csrc/cond_fused.hip): forward only, for the streaming path under torch.no_grad().
 
+`upsample_conv` / `pack_upsample_conv` are the step in front of condition3D: the 2x bilinear upsample and the 3x3 convolution of the
+motion features (igs/IGS.py:132-134, up_sample True) in one launch on the matrix cores, the upsampled map never stored
+(igs_amd/csrc/upconv.hip): forward only; a call that needs a gradient is the eager two lines.
+
 Deviations from the reference lines (INTEGRATION.md lists them):
   - condition3d returns the reference's shape, dtype and values NCHW-contiguous, where the reference returns a channels-last-strided
     view of a [N, H, W, C] tensor: its only consumer, grid_encoder_lift, then reads it in place instead of copying it;
@@ -435,6 +439,89 @@ def use_native_condition3d(model):
         raise NotImplementedError(f"use_native_condition3d: the model has no {MODLN_NAME} module")
     model.condition3D = types.MethodType(_condition3d_bound, model)
     return model
+
+
+# ---------------------------------------------------------------- 2x bilinear upsample + 3x3 convolution in one launch (upconv.hip)
+UPCONV_MAX_WIDTH, UPCONV_MAX_HW, UPCONV_MAX_PIXELS = 128, 4096, 1 << 22      # IGS_UPCONV_MAX_*
+UPCONV_CACHE = "_igs_upconv_pack"
+# Per compute dtype, whether upsample_conv's no-grad call takes the native kernel (True) or the eager two lines (False).
+# DESIGN.md 25 has the measurements this follows.
+UPCONV_NATIVE = {torch.float32: True, torch.float16: True}
+
+
+def _upconv_spec(fn, conv):
+    """(Cin, Cout) of nn.Conv2d(Cin, Cout, 3, stride=1, padding=1) with widths <= 128, or NotImplementedError."""
+    if not isinstance(conv, torch.nn.Conv2d):
+        raise NotImplementedError(f"{fn}: conv must be an nn.Conv2d (got {type(conv).__name__})")
+    if (tuple(conv.kernel_size), tuple(conv.stride), conv.padding, tuple(conv.dilation), conv.groups, conv.padding_mode) != \
+            ((3, 3), (1, 1), (1, 1), (1, 1), 1, "zeros"):
+        raise NotImplementedError(f"{fn}: conv must be Conv2d(Cin, Cout, 3, stride=1, padding=1, dilation=1, groups=1, padding_mode='zeros') "
+                                  f"(got {conv})")
+    if not (1 <= conv.in_channels <= UPCONV_MAX_WIDTH and 1 <= conv.out_channels <= UPCONV_MAX_WIDTH):
+        raise NotImplementedError(f"{fn}: Cin and Cout must be in 1..{UPCONV_MAX_WIDTH} (got {conv.in_channels}, {conv.out_channels})")
+    return conv.in_channels, conv.out_channels
+
+
+def pack_upsample_conv(conv, dtype=torch.float32):
+    """(wpack in `dtype`, bpack float32 [128]) as igs_upconv_fwd takes them (include/igs_rast.h) from conv = nn.Conv2d(Cin, Cout, 3,
+    padding=1): the 9 taps weight[:, :, dy, dx], dy outermost, each a Linear [Cout, Cin] in pack_mlp_tile_order, one after another;
+    the bias zero-padded (an absent bias: zeros).  Plain tensor ops."""
+    W = conv.weight.detach().to(dtype)
+    wpack = torch.cat([pack_mlp_tile_order(W[:, :, dy, dx]) for dy in range(3) for dx in range(3)]).contiguous()
+    bpack = torch.zeros(UPCONV_MAX_WIDTH, dtype=torch.float32, device=wpack.device)
+    if conv.bias is not None:
+        bpack[:W.shape[0]] = conv.bias.detach().float()
+    return wpack, bpack
+
+
+def upsample_conv(x, conv, packed=None, conv_dtype=None):
+    """conv(F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=False)) for conv = nn.Conv2d(Cin, Cout, 3, stride=1,
+    padding=1), the motion features' step between the transformer and condition3D (IGS.py:132-134), in one launch without storing the
+    upsampled map (igs_upconv_fwd, upconv.hip).  x [N, Cin, H, W] float32 / float16 (plane-contiguous NCHW, slices of n and c included,
+    is read in place; channels-last and anything else is copied first); out [N, Cout, 2H, 2W] NCHW-contiguous in conv_dtype:
+    torch.float32 (float32 interpolation, one float32 fma chain per output) or torch.float16 (the upsampled value and the weights in
+    half, float32 accumulation, one rounding of the result); default float16 under autocast to half, float32 otherwise -- the dtype
+    the eager convolution returns.  The packed weights (pack_upsample_conv) are kept on the module and rebuilt when weight's or bias's
+    _version, data_ptr, dtype or device changes; `packed` overrides them.
+
+    With grad enabled and x or a parameter of conv requiring it the result is the eager two lines, with autograd: there is no native
+    backward.  So it is, for the default conv_dtype, where UPCONV_NATIVE[conv_dtype] is False (an explicit conv_dtype always takes the
+    kernel).  Another Conv2d configuration or a width above 128 raises
+    NotImplementedError, as do bfloat16 / float64; a CPU tensor raises RuntimeError (no CPU fallback); a wrong rank ValueError."""
+    fn = "upsample_conv"
+    Cin, Cout = _upconv_spec(fn, conv)
+    if x.dim() != 4 or x.shape[1] != Cin:
+        raise ValueError(f"{fn}: x must be [N, {Cin}, H, W] (got {list(x.shape)})")
+    params = [conv.weight, conv.bias]
+    if x.dtype not in FEATURE_DTYPES or any(p is not None and p.dtype not in FEATURE_DTYPES for p in params):
+        raise NotImplementedError(f"{fn}: x and conv's parameters must be float32 or float16 (got {x.dtype}, {conv.weight.dtype})")
+    if conv_dtype is not None and conv_dtype not in FEATURE_DTYPES:
+        raise NotImplementedError(f"{fn}: conv_dtype must be float32 or float16 (got {conv_dtype})")
+    if torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params)):
+        return conv(torch.nn.functional.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False))
+    if not (x.is_cuda and all(p is None or p.is_cuda for p in params)):
+        raise RuntimeError(f"{fn}: tensors must be on a GPU (no CPU fallback)")
+    routed = conv_dtype is None                  # the default dtype goes where UPCONV_NATIVE sends it; an explicit one is always native
+    if routed:
+        conv_dtype = torch.float16 if _autocast_half(fn, x) else torch.float32
+    N, _, H, W = x.shape
+    if not (1 <= H <= UPCONV_MAX_HW and 1 <= W <= UPCONV_MAX_HW and N * H * W <= UPCONV_MAX_PIXELS):
+        raise NotImplementedError(f"{fn}: sizes out of range (1 <= H, W <= {UPCONV_MAX_HW}, N * H * W <= 2^22; got {list(x.shape)})")
+    if routed and not UPCONV_NATIVE[conv_dtype]:
+        return conv(torch.nn.functional.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False))
+    if packed is None:
+        key = (_param_key(params), conv_dtype)
+        cache = conv.__dict__.get(UPCONV_CACHE)
+        if cache is None or cache["key"] != key:
+            cache = dict(key=key, pack=pack_upsample_conv(conv, conv_dtype))
+            conv.__dict__[UPCONV_CACHE] = cache
+        packed = cache["pack"]
+    wpack, bpack = packed
+    if wpack.dtype != conv_dtype:
+        raise ValueError(f"{fn}: packed holds {wpack.dtype} weights, conv_dtype is {conv_dtype}")
+    if not _plane_contiguous(x) or x.stride(0) < 0 or x.stride(1) < 0:
+        x = x.contiguous()
+    return _ext()._upconv.upconv_fwd(x, wpack, bpack, Cout)
 
 
 class _Deform(torch.autograd.Function):

@@ -815,6 +815,37 @@ int igs_condition3d_fwd(void* stream, int N, int C, int hidden, int H, int W, in
                         long long xs_c, long long xs_h, long long xs_w, const float* rays, const float* depth, int mlp_dtype, const void* wpack,
                         const float* bpack, const float* weight, const float* bias, float eps, float* out);
 
+/* The 2x bilinear upsample and the 3x3 convolution of the motion features in one launch (upconv.hip; DESIGN.md section 25;
+ * igs/IGS.py:132-134 with up_sample True).  For x [N, Cin, H, W]:
+ *     up[n, c, Y, X]  = the bilinear sample of x[n, c] at ((Y + 0.5) / 2 - 0.5, (X + 0.5) / 2 - 0.5), the source clamped at 0 and the
+ *                       neighbour index at H - 1 / W - 1 (F.interpolate(scale_factor=2, mode='bilinear', align_corners=False)) for
+ *                       0 <= Y < 2 H, 0 <= X < 2 W, and ZERO outside: the convolution pads at the upsampled resolution
+ *     out[n, o, Y, X] = bias[o] + sum_{c, dy, dx} weight[o, c, dy, dx] up[n, c, Y + dy - 1, X + dx - 1]          out [N, Cout, 2 H, 2 W]
+ * up is never stored.  Forward only.  Runs on `stream`, reads nothing back, allocates nothing, uses no atomics; every output element is
+ * written by one lane: two runs agree bit for bit, and an image's result does not depend on N or on its place in the batch.
+ *   - x in x_dtype (IGS_DTYPE_F32 / IGS_DTYPE_F16, widened on load), every H x W plane contiguous (xs_w == 1, xs_h == W); xs_n and xs_c,
+ *     in elements, are free (>= 0), so slices of n and c of a larger buffer are read in place.  Channels-last is refused.
+ *   - conv_dtype selects the instance, independently of x_dtype, and is the dtype of wpack and of out (NCHW contiguous).
+ *     IGS_DTYPE_F32: the interpolation in float32 (two fma per axis), then v_mfma_f32_32x32x2_f32: one float32 fma chain per output that
+ *     starts from the bias and runs over the 9 Cin products in a fixed order (input tile, tap, channel).  IGS_DTYPE_F16: the float32
+ *     upsampled value is rounded once to half, the weights are half, v_mfma_f32_32x32x16_f16 accumulates in float32 from the float32 bias,
+ *     and the result is rounded once to half.
+ *   - wpack: 9 Linears [Cout, Cin], tap dy * 3 + dx = weight[:, :, dy, dx], each in igs_mlp_heads_fwd's tile order (see
+ *     igs_condition3d_fwd), one after another: tile ((tap * ot) + o) * kt + k.  igs_upconv_pack_elems(Cin, Cout, conv_dtype) =
+ *     9 ot kt 1024 with ot = ceil(Cout / 32), kt = ceil(Cin / 32) is the element count (-1: a width outside 1 .. IGS_UPCONV_MAX_WIDTH or
+ *     an unknown dtype code).  bpack: float32 [128], the bias zero-padded.
+ *   - Refused with IGS_RAST_E_INVALID and a message before any HIP call: Cin or Cout outside 1 .. IGS_UPCONV_MAX_WIDTH; H or W outside
+ *     1 .. IGS_UPCONV_MAX_HW; N < 0 or N * H * W above IGS_UPCONV_MAX_PIXELS; an unknown dtype code; a stride pattern other than the one
+ *     above; with N > 0 a NULL pointer, x or out not aligned to its element, wpack or bpack not aligned to 16 bytes.  N == 0 returns 0
+ *     without a launch.
+ * A workgroup owns an 8 x 32 output tile of one image and all output channels; the weights stream from L2. */
+#define IGS_UPCONV_MAX_WIDTH 128
+#define IGS_UPCONV_MAX_HW 4096
+#define IGS_UPCONV_MAX_PIXELS (1 << 22)
+long long igs_upconv_pack_elems(int Cin, int Cout, int conv_dtype);
+int igs_upconv_fwd(void* stream, int N, int Cin, int Cout, int H, int W, int x_dtype, const void* x, long long xs_n, long long xs_c,
+                   long long xs_h, long long xs_w, int conv_dtype, const void* wpack, const float* bpack, void* out);
+
 /* Fused attention for the anchor transformer (attn.hip): out = softmax(scale * Q K^T) V in one pass over the keys, the
  * self-attention of GridEncoder.conv's Transformer1D (igs/models/transformers.py:673-907: 8 heads of 64 channels over 8192 anchors, no mask,
  * no dropout).  The score matrix is never stored.  Everything runs on `stream`, reads nothing back and allocates nothing.
