@@ -204,6 +204,25 @@ def test_allowance_rejects_three_wrong_variants():
     assert r["one_pass"] > 1.0 and r["unbiased"] > 1.0 and r["no_eps"] > 1.0, r
 
 
+@pytest.mark.parametrize("n", [4097, 16384, 65536])
+def test_allowance_rejects_the_wrong_variants_at_the_larger_resident_planes(n):
+    """The same three variants on planes of the workgroup shapes that the GPU test reaches with 4097 .. 16385 and `max` elements: the
+    comparison there is not vacuous either.  "unbiased" changes rstd by the factor sqrt(n / (n - 1)), 1 / (2 n) relative, so an element of
+    |x_hat| = h moves by h / (2 n) against an allowance of 4 * 2^-24 * (2 h + 1) on a plane of mean 0: with h about 4 that is some 230 x the
+    allowance at 4097, 57 x at 16384 and 14 x at 65536 (printed below), so all three variants stay separable up to the resident limit
+    and all three are asserted; the ratio falls below 1 only near n = 10^6, on the streamed path."""
+    g = torch.Generator().manual_seed(5 + n)
+    x = (torch.randn(2, 1, n, generator=g, dtype=torch.float64) + 1e3).float()              # mean 1e3, std 1
+    y = torch.randn(2, 1, n, generator=g, dtype=torch.float64).float()                      # mean 0, std 1
+    z = (torch.randn(2, 1, n, generator=g, dtype=torch.float64) * 1e-3).float()             # std 1e-3
+    r = {"right": max(_ratio(ER.emulate(t)[None], t.double()[None]) for t in (x, y, z))}
+    for t, kind in ((x, "one_pass"), (y, "unbiased"), (z, "no_eps")):
+        r[kind] = _ratio(ER.emulate(t, variant=kind)[None], t.double()[None])
+    print(n, "max |err| / allowance:", r)
+    assert r["right"] <= 1.0, r
+    assert r["one_pass"] > 1.0 and r["unbiased"] > 1.0 and r["no_eps"] > 1.0, r
+
+
 # ---------------------------------------------------------------- the Python layer
 def test_python_refusals_on_the_cpu():
     from igs_amd import backbone as BB

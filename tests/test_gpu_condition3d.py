@@ -137,7 +137,12 @@ def test_modln_half(x_dtype, mod_dtype):
 
 
 @pytest.mark.parametrize("shape", [(3, 1, 9, 7), (2, 7, 12, 10), (2, 129, 17, 16), (1, 1024, 9, 8), (2, 1024, 3, 5), (5, 16, 33, 1), (1, 244, 8, 24),
-                                   (1, 248, 8, 24), (2, 480, 4, 20), (1, 64, 1, 1)])
+                                   (1, 248, 8, 24), (2, 480, 4, 20), (1, 64, 1, 1)] + [
+    # the last and the first C of every tile size that modln_tile_log2 (cond.hip) picks from the 64 KB of LDS: the forward holds 64 pixels
+    # up to C = 240, 32 up to 477, 16 up to 929, then 8; the backward (two operand tiles) 32 up to 238, 16 up to 464, 8 up to 880, then 4.
+    # 72 and 35 pixels: more than one tile with a part tile at every size, the four-element and the scalar form
+    (1, 238, 9, 8), (1, 239, 5, 7), (1, 240, 9, 8), (1, 241, 5, 7), (1, 464, 9, 8), (1, 465, 5, 7), (1, 477, 5, 7), (1, 478, 9, 8),
+    (1, 880, 9, 8), (1, 881, 5, 7), (1, 929, 5, 7), (1, 930, 9, 8)])
 def test_modln_odd_sizes(shape):
     N, C, H, W = shape
     x, mod, w, b, gout = _modln_case(N, C, H, W, seed=sum(shape))

@@ -85,7 +85,7 @@ def test_shipped_widths_on_a_small_image(x_dtype, mlp_dtype):
     _check(_x(B * V, C, H, W, 2, x_dtype), rays, depth, _module(C, seed=3), mlp_dtype, "x %s mlp %s" % (x_dtype, mlp_dtype))
 
 
-@pytest.mark.parametrize("C,hidden", [(7, 5), (33, 65), (96, 32), (128, 1)])
+@pytest.mark.parametrize("C,hidden", [(7, 5), (33, 65), (96, 32), (128, 1), (65, 48)])         # (65, 48): the one count of hidden tiles, 2, not above
 @pytest.mark.parametrize("H,W", [(1, 1), (5, 13), (33, 2)])
 @pytest.mark.parametrize("mlp_dtype", [F32, F16])
 def test_widths_off_the_tile_grid(C, hidden, H, W, mlp_dtype):

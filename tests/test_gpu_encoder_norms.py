@@ -12,7 +12,9 @@ one allocation and is pre-filled with NaN.
 
 Recorded on one MI355X: worst |err| / allowance 0.35 in float32 and 0.99 in float16 (the output's own rounding) for
 the norm modes, 0.35 / 0.998 for the position add.  Stand-in encoder, max |error| against the float64 run of the same weights (allowed:
-4 x the unpatched error): [2, 3, 32, 32] unpatched PyTorch float32 4.8e-6, patched 5.9e-6; [2, 3, 40, 24] 5.7e-6 and 4.6e-6."""
+4 x the unpatched error): [2, 3, 32, 32] unpatched PyTorch float32 4.8e-6, patched 5.9e-6; [2, 3, 40, 24] 5.7e-6 and 4.6e-6.
+CLASS_PLANES (every workgroup shape of the resident path at both ends): 0.22 in float32 (0.08 with the normalised
+skip) and 0.992 in float16."""
 import types
 
 import pytest
@@ -26,6 +28,27 @@ DTYPES = [torch.float32, torch.float16]
 CODE = {torch.float32: 0, torch.float16: 1}
 SHAPES = [(1, 2), (1, 3), (7, 9), (8, 8), (5, 13), (15, 17), (64, 64)]
 EDGES = ("max-1", "max", "max+1", "2max+3")                          # planes of resident_max - 1, ... elements, as (1, hw)
+# Every workgroup shape of the resident path (launch_inorm in igs_amd/csrc/inorm.hip) at its smallest and its largest plane and at an odd
+# size inside: (threads, vectors per thread) of the plain / relu / relu-add-relu modes | of the normalised-skip mode.  SHAPES above stays
+# in (64, 4) except (64, 64), EDGES holds the top of the two largest shapes ("max-1" is their odd inside size, "max+1" the streamed
+# kernel).  These follow EDGES in the parametrisation, so the offset from the 16-byte grid alternates down the list: the capacities 1024,
+# 4096 and 16384 fall on offset 0 (every vector slot of the shape in use), (128, 128) on offset 1.
+CLASS_PLANES = [
+    (1, 1024),                                                       # (64, 4) | (64, 4): the largest
+    (1, 1023),                                                       # (64, 4) | (64, 4): odd, one below
+    (1, 1025),                                                       # (256, 4) | (256, 4): the smallest
+    (1, 4095),                                                       # (256, 4) | (256, 4): odd, inside
+    (1, 4096),                                                       # (256, 4) | (256, 4): the largest, on the grid
+    (1, 4097),                                                       # (256, 16) | (1024, 4): the smallest
+    (1, 9001),                                                       # (256, 16) | (1024, 4): odd, inside
+    (1, 16383),                                                      # (256, 16) | (1024, 4): odd, one below the largest
+    (1, 16384),                                                      # (256, 16) | (1024, 4): the largest
+    (128, 128),                                                      # (256, 16) | (1024, 4): the quarter-resolution plane of a 512 x 512 input
+    (1, 16385),                                                      # (1024, 16) | (1024, 8): the smallest
+]
+ALL_SHAPES = SHAPES + list(EDGES) + CLASS_PLANES                     # (appended: the seeds and offsets of the earlier cases stay)
+INSIDE_NEW = [(1, 9001)]                                             # one plane from the (256, 16) and the (1024, 4) shape: the same size
+CLASS_IDS = lambda s: "%dx%d" % s if s in CLASS_PLANES else None     # noqa: E731  (the earlier cases keep the ids they had)
 BAND = 64                                                            # sentinel elements on either side of out
 SENTINEL = 12345.0
 
@@ -95,10 +118,10 @@ def _compare(out, x, skip, mode, label, eps=1e-5, planes=None):
 # ---------------------------------------------------------------- every mode, dtype and plane size against float64
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("mode", ER.MODES)
-@pytest.mark.parametrize("shape", SHAPES + list(EDGES))
+@pytest.mark.parametrize("shape", ALL_SHAPES, ids=CLASS_IDS)
 def test_modes_against_float64(shape, mode, dtype):
     hw = _hw(shape, dtype, mode)
-    index = (SHAPES + list(EDGES)).index(shape)
+    index = ALL_SHAPES.index(shape)
     for planes in (1, 3) + ((700,) if shape == (8, 8) else ()):
         seed = 9 * index + planes + mode
         offset = (index + planes) % 2                                # half of the cases start one element past the 16-byte grid
@@ -132,7 +155,7 @@ def test_operands_on_different_offsets_take_the_scalar_form():
 # ---------------------------------------------------------------- aliasing and determinism, on both paths
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("mode", ER.MODES)
-@pytest.mark.parametrize("shape", [(7, 9), (64, 64), "max", "max+1"])
+@pytest.mark.parametrize("shape", [(7, 9), (64, 64), "max", "max+1"] + INSIDE_NEW, ids=CLASS_IDS)
 def test_out_is_x_and_a_second_run_give_the_same_bits(shape, mode, dtype):
     hw = _hw(shape, dtype, mode)
     x, skip = _inputs(3, hw, dtype, mode, seed=21, offset=1)
@@ -165,7 +188,7 @@ def test_out_is_x_and_a_second_run_give_the_same_bits(shape, mode, dtype):
 # ---------------------------------------------------------------- non-finite planes
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("mode", ER.MODES)
-@pytest.mark.parametrize("shape", [(7, 9), (64, 64), "max", "max+1"])
+@pytest.mark.parametrize("shape", [(7, 9), (64, 64), "max", "max+1"] + INSIDE_NEW, ids=CLASS_IDS)
 def test_a_non_finite_plane_is_all_nan_and_its_neighbours_are_untouched(shape, mode, dtype):
     hw = _hw(shape, dtype, mode)
     x, skip = _inputs(4, hw, dtype, mode, seed=31)

@@ -189,10 +189,14 @@ def _backward(feat, pts, c2w, intr, gout):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
 def test_backward_against_float64_twice(dtype):
-    for (B, V, C, H, W, A) in ((1, 4, 128, 128, 128, 8192), (2, 3, 7, 136, 200, 9000)):  # (A > 8192: d out read from global memory)
+    # (A > 8192: d out read from global memory; 8192 is the last A that stages it in LDS, 8193 the first that does not)
+    for (B, V, C, H, W, A) in ((1, 4, 128, 128, 128, 8192), (2, 3, 7, 136, 200, 9000), (1, 2, 3, 24, 20, 8193)):
         feat, pts, c2w, w2c = _case(B=B, V=V, C=C, H=H, W=W, A=A, seed=11 + C, dtype=dtype)
         intr = _intr(B * V, H, W)
         gout = torch.randn(B, A, C, generator=torch.Generator().manual_seed(1)).to(DEV)
+        with torch.no_grad():                                                            # (the banded forward of either dtype: 136 x 200)
+            from igs_amd.motion import lift_anchor_features
+            _check_forward(lift_anchor_features(feat, pts, c2w, intr), feat, pts, w2c, intr, reject=False)
         d1 = _backward(feat, pts, c2w, intr, gout)
         d2 = _backward(feat, pts, c2w, intr, gout)
         assert d1.dtype == dtype and d1.shape == feat.shape

@@ -99,6 +99,26 @@ def test_backward_against_float64():
         assert ((dw.double() - w64.grad).abs() <= tol_w.reshape(w.shape)).all(), (N, K, D, B)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16], ids=["float32", "float16"])
+@pytest.mark.parametrize("D", [64, 65, 128, 129, 256, 257, 512, 513, 1024])
+def test_every_lane_group_count_at_both_ends_forward_and_backward(D, dtype):
+    """interp_dv (motion.hip) gives a lane 1, 2, 4, 8 or 16 features for D up to 64, 128, 256, 512 and 1024: the row kernel and the chunk
+    kernel of every count at the smallest and the largest D it serves (1 is above), in both feature dtypes, against the same bounds as the
+    tests above.  Few rows and anchors: what changes with D is the lane mapping, not the lists."""
+    N, K, A, B = 300, 8, 40, 2
+    F, w, col = _case(N, K, A, D, B=B, seed=D + 7, dtype=dtype, pad=0.05)
+    dF, dw, dout = _backward_pair(F, w, col, seed=D)
+    from igs_amd.motion import interpolate_anchor_features
+    out = interpolate_anchor_features(F, w, col)
+    truth = MR.interp_truth_blocked(F.detach(), w.detach(), col, dout)
+    tol_F, tol_w = MR.interp_backward_bounds(truth, K, D, dtype == torch.float16)
+    assert out.shape == (N, D) and dF.dtype == dtype and dF.shape == F.shape and dw.shape == w.shape
+    ratios = (MR.worst_ratio(out, truth["out"], _fwd_bound(F, w, col)), MR.worst_ratio(dF.reshape(-1, D), truth["dF"], tol_F),
+              MR.worst_ratio(dw.reshape(N, K), truth["dw"], tol_w))
+    print("D %d (%d per lane) %s: max |err| / bound forward %.3f, dF %.3f, dw %.3f" % ((D, MR.interp_dv(D), str(dtype)[6:]) + ratios))
+    assert max(ratios) <= 1.0, ratios
+
+
 def test_bit_equality_on_exact_inputs():
     """Integer features, power-of-two weights: every product and partial sum is exact in float32."""
     from igs_amd.motion import interpolate_anchor_features

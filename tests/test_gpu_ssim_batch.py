@@ -104,6 +104,8 @@ def test_every_output_matches_float64(dev, shape):
         assert same_bits(m0, means) and same_bits(l0, l1m) and (not want_map or same_bits(s0, smap))
     m0, l0, _, _ = E._loss.ssim_batch(a, b, 1.0, 0.0, False, False, False)
     assert l0 is None and same_bits(m0, means)
+    m0, l0, g0, s0 = E._loss.ssim_batch(a, b, 1.0, 0.0, False, True, False)      # the map without the L1 means: what ssim() asks for under no_grad
+    assert l0 is None and g0 is None and same_bits(m0, means) and same_bits(s0, smap)
 
 
 # ---- igs_amd.losses.ssim ----------------------------------------------------------------------------------------------------------

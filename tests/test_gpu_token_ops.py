@@ -18,7 +18,9 @@ Recorded on one MI355X: worst |err| / allowance for Layer
 float32 and 0.994 / 0.987 in float16 (the output's own rounding); for GEGLU 0.18 forward, 0.23 backward in float32 and 0.997 / 0.996 in
 float16.  Stand-ins, relative error against the float64 run: layer unpatched 6.8e-7 to 9.5e-7, patched 6.9e-7 to 1.07e-6; block (two heads) 1.70e-6 and
 1.86e-6; under float16 autocast layer 1.06e-3 to 1.71e-3 on both sides, block 1.76e-3 unpatched and 1.29e-3 patched; with the native window
-attention 8.1e-7 / 1.04e-6, with the native anchor attention (eight heads of 64) 1.30e-6."""
+attention 8.1e-7 / 1.04e-6, with the native anchor attention (eight heads of 64) 1.30e-6.  The LayerNorm rows at the capacities of the
+lane shapes, their neighbours and the widths off the grid of four: 0.50 forward, 0.11 dx, 0.11 dweight, 0.19 dbias
+in float32 and 0.998 / 0.984 in float16."""
 import copy
 
 import pytest
@@ -90,6 +92,19 @@ LN_CASES = [
     (257, 512, F16, F32, "alias", F32, 0, 1, True), (3, 512, F32, F32, "none", F32, 0, 0, False),
     (3, 1024, F32, F32, "alias", F32, 0, 0, True), (67, 1024, F16, F16, "own", F16, 16, 0, True), (257, 1024, F32, F32, "none", F32, 0, 1, True),
     (4200, 132, F32, F32, "own", F32, 0, 0, True),                                              # more row groups than workgroups in the backward
+    # the capacity of each (lanes per row, groups per lane) shape of LN_LAUNCH in igs_amd/csrc/tokens.hip and the first width of the next
+    # one, each in the four-element form and (a stride extra off the grid of four, or offset 1) in the scalar form of the same shape:
+    # 64 fills (16, 1), 68 opens (16, 2); 256 fills (64, 1), 260 opens (64, 2); 516 opens (64, 4)   (128 | 132, 512 and 1024 are above)
+    (3, 64, F32, F32, "own", F32, 0, 0, True), (67, 64, F16, F16, "alias", F16, 4, 1, True), (257, 64, F16, F32, "none", F32, 0, 0, False),
+    (67, 68, F32, F32, "alias", F32, 0, 0, True), (3, 68, F16, F16, "own", F16, 1, 0, True),
+    (3, 256, F16, F16, "own", F16, 0, 0, True), (67, 256, F32, F32, "alias", F32, 0, 1, True), (257, 256, F32, F32, "none", F32, 256, 0, True),
+    (67, 260, F32, F32, "own", F32, 0, 0, True), (3, 260, F16, F32, "alias", F32, 2, 0, True),
+    (3, 516, F32, F32, "alias", F32, 0, 0, True), (67, 516, F16, F16, "own", F16, 4, 1, True), (257, 516, F16, F32, "none", F32, 0, 0, True),
+    # widths that are no multiple of four take the scalar form whatever the addresses, with a last group that is partly outside the row: the
+    # first width of each scalar shape (1, 65, 129, 257, 513) and the last widths of the smallest and the largest one (63, 1023)
+    (3, 1, F32, F32, "own", F32, 0, 0, True), (67, 63, F16, F16, "none", F16, 0, 0, True), (67, 65, F32, F32, "none", F32, 0, 0, True),
+    (3, 129, F16, F16, "own", F16, 0, 0, True), (67, 257, F32, F32, "alias", F32, 0, 0, True), (3, 513, F32, F32, "own", F32, 3, 0, False),
+    (67, 1023, F16, F32, "none", F32, 0, 1, True),
 ]
 
 

@@ -2,7 +2,11 @@
 restatement and its derived bound (tests/upconv_restatement.py).  Every element is compared; every float test prints its worst
 |error| / bound.  The shapes are the smallest at which the kernel can still go wrong: widths off the 32-channel tile grid, a single
 pixel, one-row and one-column maps where both clamps and both paddings meet, maps that are partial in and span several 8 x 32 output
-tiles in both directions (the kernel's tile is no larger than 32 x 32, so no map beyond those)."""
+tiles in both directions (the kernel's tile is no larger than 32 x 32, so no map beyond those).
+
+Recorded on one MI355X for the widths that run every count of output tiles at both ends of its range (7 -> 33,
+128 -> 64, 65 -> 48, 5 -> 96, 40 -> 97): worst |error| / bound 0.072 with a float32 and 0.285 with a float16 convolution; with a
+float16 x (65 -> 48, 7 -> 5) 0.017 and 0.214."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -68,22 +72,28 @@ def test_not_vacuous_on_the_gpu(conv_dtype):
 @pytest.mark.parametrize("conv_dtype", [F32, F16], ids=IDS)
 @pytest.mark.parametrize("x_dtype", [F32, F16], ids=IDS)
 def test_strided_views_are_read_in_place_and_channels_last_is_copied(x_dtype, conv_dtype):
+    """The only test that hands the kernel a float16 x below the shipped width, so it runs one width of each other count of output tiles
+    (3, 2, 1: igs_upconv_fwd's switch) and compares the contiguous result with float64 before the views are held against it."""
     from igs_amd.motion import upsample_conv
-    case = (33, 65, 2, 9, 7)
-    out, x, _, _, dconv = _run(case, x_dtype, conv_dtype)
-    x = x.to(x_dtype)
-    big = torch.full((4, 40, 9, 7), float("nan"), dtype=x_dtype, device=DEV)     # what the kernel must not touch is NaN
-    big[1:3, 5:38] = x.to(DEV)
-    view = big[1:3, 5:38]
-    assert not view.is_contiguous()
-    with torch.no_grad():
-        assert torch.equal(upsample_conv(view, dconv, conv_dtype=conv_dtype), out)
-        step = torch.full((4, 33, 9, 7), float("nan"), dtype=x_dtype, device=DEV)
-        step[::2] = x.to(DEV)
-        assert torch.equal(upsample_conv(step[::2], dconv, conv_dtype=conv_dtype), out)
-        cl = x.to(DEV).contiguous(memory_format=torch.channels_last)
-        assert not cl.is_contiguous()
-        assert torch.equal(upsample_conv(cl, dconv, conv_dtype=conv_dtype), out)
+    for ci, co in ((33, 65), (65, 48), (7, 5)):
+        case = (ci, co, 2, 9, 7)
+        out, x, _, r, dconv = _run(case, x_dtype, conv_dtype)
+        ratio = UR.worst(out, r["out64"], r["bound"])
+        print("%s x %s conv %s: max |out - out64| / bound %.4f" % (case, x_dtype, conv_dtype, ratio))
+        assert ratio <= 1.0, case
+        x = x.to(x_dtype)
+        big = torch.full((4, ci + 7, 9, 7), float("nan"), dtype=x_dtype, device=DEV)     # what the kernel must not touch is NaN
+        big[1:3, 5:5 + ci] = x.to(DEV)
+        view = big[1:3, 5:5 + ci]
+        assert not view.is_contiguous()
+        with torch.no_grad():
+            assert torch.equal(upsample_conv(view, dconv, conv_dtype=conv_dtype), out)
+            step = torch.full((4, ci, 9, 7), float("nan"), dtype=x_dtype, device=DEV)
+            step[::2] = x.to(DEV)
+            assert torch.equal(upsample_conv(step[::2], dconv, conv_dtype=conv_dtype), out)
+            cl = x.to(DEV).contiguous(memory_format=torch.channels_last)
+            assert not cl.is_contiguous()
+            assert torch.equal(upsample_conv(cl, dconv, conv_dtype=conv_dtype), out)
 
 
 @pytest.mark.parametrize("conv_dtype", [F32, F16], ids=IDS)

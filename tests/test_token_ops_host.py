@@ -239,7 +239,7 @@ def _ln_ratio(y, x, w=None, b=None, eps=1e-5):
     return ((y.double() - ref).abs() / TR.layer_norm_forward_bound(x, w, b, eps)).max().item()
 
 
-@pytest.mark.parametrize("C", [4, 12, 128, 132, 512, 1024])
+@pytest.mark.parametrize("C", [4, 12, 128, 132, 512, 1024] + [64, 68, 256, 260, 516] + [1, 63, 65, 129, 257, 513, 1023])   # (every width of LN_CASES)
 def test_layer_norm_allowance_accepts_the_kernel_arithmetic_and_pytorch_float32(C):
     """On the GPU tests' inputs (every pair of mean and std): the float32 emulation of the kernel's arithmetic and PyTorch's own float32
     layer_norm on the CPU, forward and backward, stay inside the allowance."""

@@ -21,7 +21,9 @@ import torch.nn.functional as F
 
 U24, U11 = 2.0 ** -24, 2.0 ** -11
 SHIPPED = (128, 128, 2, 5, 7)                                    # Cin, Cout, N, H, W
-WIDTHS = ((7, 5), (33, 65), (96, 32), (128, 1), (1, 128))
+# (Cin, Cout).  igs_upconv_fwd picks the kernel by ceil(Cout / 32) output tiles: 1, 3, 1, 1, 4, then the two-tile kernel at the bottom, the
+# top and the inside of its range 33 .. 64, under one, four and three input tiles, then the last Cout of three tiles and the first of four
+WIDTHS = ((7, 5), (33, 65), (96, 32), (128, 1), (1, 128), (7, 33), (128, 64), (65, 48), (5, 96), (40, 97))
 MAPS = ((1, 1), (1, 9), (9, 1), (17, 3), (33, 18))
 CASES = [SHIPPED] + [(ci, co, 2, h, w) for ci, co in WIDTHS for h, w in MAPS]
 VARIANTS = ("align_corners", "nearest", "flipped_taps", "transposed_taps", "replicate_padding", "low_resolution_zero_padding")
