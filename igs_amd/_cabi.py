@@ -149,6 +149,9 @@ SIGNATURES = {
     # upconv.hip
     "igs_upconv_pack_elems": (_ll, [_i] * 3),
     "igs_upconv_fwd": (_i, [_vp] + [_i] * 6 + [_vp] + [_ll] * 4 + [_i] + [_vp] * 3),
+    # upconv_bwd.hip
+    "igs_upconv_bwd_scratch_bytes": (_ll, [_i] * 6),
+    "igs_upconv_bwd": (_i, [_vp] + [_i] * 6 + [_vp] + [_ll] * 4 + [_i] + [_vp] * 3 + [_ll] + [_vp] * 3),
     # attn.hip
     "igs_attn_bwd_scratch_bytes": (_sz, [_i] * 6),
     "igs_attn_fwd": (_i, [_vp] + [_i] * 6 + ([_vp] + [_ll] * 3) * 3 + [_f] + [_vp] + [_ll] * 3 + [_vp]),

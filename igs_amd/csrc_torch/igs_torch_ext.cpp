@@ -16,6 +16,7 @@
 //   condition3D         cond.hip                cond_ray_fwd, modln_fwd / _bwd
 //                       cond_fused.hip          _cond.condition3d_fwd, _cond.pack_elems: the forward in one launch, ModLN's MLP included
 //   upsample + conv     upconv.hip              _upconv.upconv_fwd, _upconv.pack_elems: 2x bilinear upsample and 3x3 convolution in one launch
+//                       upconv_bwd.hip          _upconv.upconv_bwd: its backward, d x / d weight / d bias from x and d out
 //   attention           attn.hip                attn_fwd / _bwd on [B, H, A, 64] views of any acceptable strides
 //   window attention    wattn.hip               _window.window_attn_fwd / _bwd on [B, h w, 128] views of any acceptable strides
 //   encoder norms       inorm.hip               _encoder.instance_norm_fwd, _encoder.position_add on contiguous [N, C, H, W] tensors
@@ -901,6 +902,35 @@ Tensor upconv_fwd(const Tensor& x, const Tensor& wpack, const Tensor& bpack, int
                          cdt, wpack.data_ptr(), bpack.data_ptr<float>(), out.data_ptr()), "igs_upconv_fwd");
     return out;
 }
+// (d x [N, Cin, H, W] in x's dtype, d weight [Cout, Cin, 3, 3] and d bias [Cout] float32), each None unless wanted.  dout [N, Cout, 2H, 2W]
+// contiguous in wpack_t's dtype (the compute dtype); wpack_t: the transposed, flipped convolution packed like wpack (igs_upconv_bwd)
+std::tuple<OptTensor, OptTensor, OptTensor> upconv_bwd(const Tensor& x, const Tensor& wpack_t, const Tensor& dout, bool want_x, bool want_w, bool want_b)
+{
+    const char* fn = "upconv_bwd";
+    const int xdt = dtype_code(x, fn, "x"), cdt = dtype_code(wpack_t, fn, "wpack_t");
+    if (x.dim() != 4) throw RasterizerError(std::string(fn) + ": x must have shape [N, Cin, H, W] (got " + c10::str(x.sizes()) + ")");
+    if (dout.dim() != 4) throw RasterizerError(std::string(fn) + ": dout must have shape [N, Cout, 2H, 2W] (got " + c10::str(dout.sizes()) + ")");
+    const int64_t N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3), Cout = dout.size(1);
+    if (H < 1 || W < 1 || H > IGS_UPCONV_MAX_HW || W > IGS_UPCONV_MAX_HW || N * H * W > IGS_UPCONV_MAX_PIXELS)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (1 <= H, W <= 4096, N * H * W <= 2^22)");
+    const int64_t elems = upconv_pack_elems(Cout, Cin, cdt == IGS_DTYPE_F16);
+    if (elems < 0) throw RasterizerError(std::string(fn) + ": Cin and Cout must be in 1..128 (got " + std::to_string(Cin) + ", " + std::to_string(Cout) + ")");
+    expect(wpack_t, fn, "wpack_t", wpack_t.scalar_type(), {elems});
+    expect(dout, fn, "dout", wpack_t.scalar_type(), {N, Cout, 2 * H, 2 * W});
+    if (!wpack_t.is_contiguous() || !dout.is_contiguous()) throw RasterizerError(std::string(fn) + ": wpack_t and dout must be contiguous");
+    const GpuCall c(x, fn, "x", {{wpack_t, "wpack_t"}, {dout, "dout"}});
+    OptTensor dx, dw, db;
+    const auto fo = x.options().dtype(at::kFloat);
+    if (want_x) dx = at::empty({N, Cin, H, W}, x.options());
+    if (want_w) dw = at::empty({Cout, Cin, 3, 3}, fo);
+    if (want_b) db = at::empty({Cout}, fo);
+    if (!(want_x || want_w || want_b)) return {dx, dw, db};
+    const Tensor scratch = at::empty({igs_upconv_bwd_scratch_bytes((int)N, (int)Cin, (int)Cout, (int)H, (int)W, cdt)}, x.options().dtype(at::kByte));
+    check(igs_upconv_bwd(c.stream(), (int)N, (int)Cin, (int)Cout, (int)H, (int)W, xdt, x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), x.stride(3),
+                         cdt, wpack_t.data_ptr(), dout.data_ptr(), scratch.data_ptr(), scratch.numel(), ptr_or_null(dx), ptr_or_null<float>(dw),
+                         ptr_or_null<float>(db)), "igs_upconv_bwd");
+    return {dx, dw, db};
+}
 
 // ---- fused attention for the anchor transformer (attn.hip; contract in include/igs_rast.h) ----
 struct AttnSizes { int64_t B, H, Aq, Ak; int dt; };
@@ -1730,6 +1760,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     def_nogil(cf, "pack_elems", &cond_fused_pack_elems, "C"_a, "hidden"_a, "half"_a = false);
     py::module_ uc = m.def_submodule("_upconv", "2x bilinear upsample + 3x3 convolution in one launch (upconv.hip)");
     def_nogil(uc, "upconv_fwd", &upconv_fwd, "x"_a, "wpack"_a, "bpack"_a, "Cout"_a);
+    def_nogil(uc, "upconv_bwd", &upconv_bwd, "x"_a, "wpack_t"_a, "dout"_a, "want_x"_a, "want_w"_a, "want_b"_a);
     def_nogil(uc, "pack_elems", &upconv_pack_elems, "Cin"_a, "Cout"_a, "half"_a = false);
     py::module_ ml = m.def_submodule("_mlp", "the residual decoder: MLP and output heads in one launch (mlp.hip)");
     def_nogil(ml, "mlp_heads_fwd", &mlp_heads_fwd, "x"_a, "wpack"_a, "bpack"_a, "widths"_a, "act_after"_a, "head_widths"_a, "act"_a = 0);

@@ -19,7 +19,9 @@ launch, the MLP on the matrix cores included (igs_amd/csrc/cond_fused.hip): forw
 
 `upsample_conv` / `pack_upsample_conv` are the step in front of condition3D: the 2x bilinear upsample and the 3x3 convolution of the
 motion features (igs/IGS.py:132-134, up_sample True) in one launch on the matrix cores, the upsampled map never stored
-(igs_amd/csrc/upconv.hip): forward only; a call that needs a gradient is the eager two lines.
+(igs_amd/csrc/upconv.hip): forward only; a call that needs a gradient is the eager two lines.  `upsample_conv_autograd` is the same step
+for training: the native forward with the native backward (igs_upconv_bwd, igs_amd/csrc/upconv_bwd.hip), which recomputes the upsampled map
+from x and stores neither it nor its gradient.
 
 Deviations from the reference lines (INTEGRATION.md lists them):
   - condition3d returns the reference's shape, dtype and values NCHW-contiguous, where the reference returns a channels-last-strided
@@ -447,6 +449,10 @@ UPCONV_CACHE = "_igs_upconv_pack"
 # Per compute dtype, whether upsample_conv's no-grad call takes the native kernel (True) or the eager two lines (False).
 # DESIGN.md 25 has the measurements this follows.
 UPCONV_NATIVE = {torch.float32: True, torch.float16: True}
+UPCONV_TRAIN_CACHE = "_igs_upconv_train_pack"
+# Per compute dtype, whether upsample_conv_autograd's default-dtype call that needs a gradient takes the native forward + backward (True)
+# or the eager two lines (False).  DESIGN.md 25 has the measurements this follows.
+UPCONV_BWD_NATIVE = {torch.float32: False, torch.float16: True}
 
 
 def _upconv_spec(fn, conv):
@@ -462,15 +468,46 @@ def _upconv_spec(fn, conv):
     return conv.in_channels, conv.out_channels
 
 
-def pack_upsample_conv(conv, dtype=torch.float32):
+def _pack_taps(W):
+    """The 9 taps W[:, :, dy, dx] of W [O, I, 3, 3], dy outermost, each in pack_mlp_tile_order, one after another -- as two copies instead
+    of nine packs and a cat (the training path packs every step)."""
+    O, I = W.shape[:2]
+    OT, KT = _tiles(O), _tiles(I)
+    P = W.permute(2, 3, 0, 1).reshape(9, O, I)
+    if (O, I) != (32 * OT, 32 * KT):
+        Z = W.new_zeros(9, 32 * OT, 32 * KT)
+        Z[:, :O, :I] = P
+        P = Z
+    if W.dtype == torch.float16:                 # pack_mlp_tile_order's two permutations behind a leading tap index
+        return P.view(9, OT, 32, KT, 2, 2, 2, 4).permute(0, 1, 3, 4, 6, 2, 5, 7).reshape(-1)
+    return P.view(9, OT, 32, KT, 4, 2, 4).permute(0, 1, 3, 4, 5, 2, 6).reshape(-1)
+
+
+def _upconv_args(fn, x, conv, conv_dtype):
+    """(Cin, Cout, [weight, bias]) after the checks upsample_conv and upsample_conv_autograd share."""
+    Cin, Cout = _upconv_spec(fn, conv)
+    if x.dim() != 4 or x.shape[1] != Cin:
+        raise ValueError(f"{fn}: x must be [N, {Cin}, H, W] (got {list(x.shape)})")
+    params = [conv.weight, conv.bias]
+    if x.dtype not in FEATURE_DTYPES or any(p is not None and p.dtype not in FEATURE_DTYPES for p in params):
+        raise NotImplementedError(f"{fn}: x and conv's parameters must be float32 or float16 (got {x.dtype}, {conv.weight.dtype})")
+    if conv_dtype is not None and conv_dtype not in FEATURE_DTYPES:
+        raise NotImplementedError(f"{fn}: conv_dtype must be float32 or float16 (got {conv_dtype})")
+    return Cin, Cout, params
+
+
+def pack_upsample_conv(conv, dtype=torch.float32, transposed=False):
     """(wpack in `dtype`, bpack float32 [128]) as igs_upconv_fwd takes them (include/igs_rast.h) from conv = nn.Conv2d(Cin, Cout, 3,
     padding=1): the 9 taps weight[:, :, dy, dx], dy outermost, each a Linear [Cout, Cin] in pack_mlp_tile_order, one after another;
-    the bias zero-padded (an absent bias: zeros).  Plain tensor ops."""
+    the bias zero-padded (an absent bias: zeros).  transposed=True: (wpack, bpack, wpack_t), wpack_t the same layout of the [Cin, Cout, 3, 3]
+    convolution weight_t[c, o, dy, dx] = weight[o, c, 2 - dy, 2 - dx] that igs_upconv_bwd takes.  Plain tensor ops."""
     W = conv.weight.detach().to(dtype)
-    wpack = torch.cat([pack_mlp_tile_order(W[:, :, dy, dx]) for dy in range(3) for dx in range(3)]).contiguous()
+    wpack = _pack_taps(W)
     bpack = torch.zeros(UPCONV_MAX_WIDTH, dtype=torch.float32, device=wpack.device)
     if conv.bias is not None:
         bpack[:W.shape[0]] = conv.bias.detach().float()
+    if transposed:
+        return wpack, bpack, _pack_taps(W.flip(2, 3).transpose(0, 1))
     return wpack, bpack
 
 
@@ -489,14 +526,7 @@ def upsample_conv(x, conv, packed=None, conv_dtype=None):
     kernel).  Another Conv2d configuration or a width above 128 raises
     NotImplementedError, as do bfloat16 / float64; a CPU tensor raises RuntimeError (no CPU fallback); a wrong rank ValueError."""
     fn = "upsample_conv"
-    Cin, Cout = _upconv_spec(fn, conv)
-    if x.dim() != 4 or x.shape[1] != Cin:
-        raise ValueError(f"{fn}: x must be [N, {Cin}, H, W] (got {list(x.shape)})")
-    params = [conv.weight, conv.bias]
-    if x.dtype not in FEATURE_DTYPES or any(p is not None and p.dtype not in FEATURE_DTYPES for p in params):
-        raise NotImplementedError(f"{fn}: x and conv's parameters must be float32 or float16 (got {x.dtype}, {conv.weight.dtype})")
-    if conv_dtype is not None and conv_dtype not in FEATURE_DTYPES:
-        raise NotImplementedError(f"{fn}: conv_dtype must be float32 or float16 (got {conv_dtype})")
+    Cin, Cout, params = _upconv_args(fn, x, conv, conv_dtype)
     if torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params)):
         return conv(torch.nn.functional.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False))
     if not (x.is_cuda and all(p is None or p.is_cuda for p in params)):
@@ -522,6 +552,78 @@ def upsample_conv(x, conv, packed=None, conv_dtype=None):
     if not _plane_contiguous(x) or x.stride(0) < 0 or x.stride(1) < 0:
         x = x.contiguous()
     return _ext()._upconv.upconv_fwd(x, wpack, bpack, Cout)
+
+
+class _UpsampleConv(torch.autograd.Function):
+    """igs_upconv_fwd with igs_upconv_bwd behind it.  Saves x as it was handed over (not a copy, not the upsampled map) and wpack_t."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, wpack, bpack, wpack_t):
+        ctx.save_for_backward(x, wpack_t)
+        ctx.param_dtypes = (weight.dtype, None if bias is None else bias.dtype)
+        return _ext()._upconv.upconv_fwd(_upconv_readable(x), wpack, bpack, weight.shape[0])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, wpack_t = ctx.saved_tensors
+        want_x, want_w, want_b = ctx.needs_input_grad[:3]
+        if g.dtype != wpack_t.dtype:
+            g = g.to(wpack_t.dtype)
+        if not g.is_contiguous():
+            g = g.contiguous()                   # (the one copy of a strided d out)
+        dx, dw, db = _ext()._upconv.upconv_bwd(_upconv_readable(x), wpack_t, g, want_x, want_w, want_b)
+        wdt, bdt = ctx.param_dtypes              # accumulated in float32, cast once
+        if dw is not None and dw.dtype != wdt:
+            dw = dw.to(wdt)
+        if db is not None and db.dtype != bdt:
+            db = db.to(bdt)
+        return dx, dw, db, None, None, None
+
+
+def _upconv_readable(x):
+    """x where the kernels read it in place (plane-contiguous NCHW, slices of n and c included), a contiguous copy otherwise."""
+    return x.contiguous() if not _plane_contiguous(x) or x.stride(0) < 0 or x.stride(1) < 0 else x
+
+
+def upsample_conv_autograd(x, conv, packed=None, conv_dtype=None):
+    """upsample_conv for training: the same checks, sizes, dtypes and value, and a native backward.  When grad is disabled or neither x
+    nor a parameter of conv requires it this IS upsample_conv(x, conv, packed, conv_dtype).  Otherwise the forward is igs_upconv_fwd and
+    the backward igs_upconv_bwd (upconv_bwd.hip): dx in x's dtype, weight.grad and bias.grad accumulated in float32 and cast once to the
+    parameters' dtype; x itself and the transposed pack are saved, the upsampled map is recomputed.  Once differentiable, deterministic.
+    Under CUDA autocast to float16 the compute dtype and the output are half (bfloat16 autocast raises).  A conv without a bias works.
+    `packed`, if given, is pack_upsample_conv(conv, conv_dtype, transposed=True); otherwise the three packs are kept on the module under
+    UPCONV_TRAIN_CACHE and rebuilt when weight's or bias's _version, data_ptr, dtype or device changes (every optimiser step).
+
+    The default conv_dtype goes where UPCONV_BWD_NATIVE[conv_dtype] sends it: False is the eager two lines with autograd (an explicit
+    conv_dtype always takes the kernels).  Refusals as upsample_conv's; there is no CPU fallback."""
+    fn = "upsample_conv_autograd"
+    Cin, Cout, params = _upconv_args(fn, x, conv, conv_dtype)
+    if not (torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params))):
+        return upsample_conv(x, conv, packed=None if packed is None else tuple(packed[:2]), conv_dtype=conv_dtype)
+    if not (x.is_cuda and all(p is None or p.is_cuda for p in params)):
+        raise RuntimeError(f"{fn}: tensors must be on a GPU (no CPU fallback)")
+    routed = conv_dtype is None
+    if routed:
+        conv_dtype = torch.float16 if _autocast_half(fn, x) else torch.float32
+    N, _, H, W = x.shape
+    if not (1 <= H <= UPCONV_MAX_HW and 1 <= W <= UPCONV_MAX_HW and N * H * W <= UPCONV_MAX_PIXELS):
+        raise NotImplementedError(f"{fn}: sizes out of range (1 <= H, W <= {UPCONV_MAX_HW}, N * H * W <= 2^22; got {list(x.shape)})")
+    if routed and not UPCONV_BWD_NATIVE[conv_dtype]:
+        return conv(torch.nn.functional.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False))
+    if packed is None:
+        key = (_param_key(params), conv_dtype)
+        cache = conv.__dict__.get(UPCONV_TRAIN_CACHE)
+        if cache is None or cache["key"] != key:
+            cache = dict(key=key, pack=pack_upsample_conv(conv, conv_dtype, transposed=True))
+            conv.__dict__[UPCONV_TRAIN_CACHE] = cache
+        packed = cache["pack"]
+    if len(packed) != 3:
+        raise ValueError(f"{fn}: packed must be pack_upsample_conv(conv, conv_dtype, transposed=True)")
+    wpack, bpack, wpack_t = packed
+    if wpack.dtype != conv_dtype or wpack_t.dtype != conv_dtype:
+        raise ValueError(f"{fn}: packed holds {wpack.dtype} weights, conv_dtype is {conv_dtype}")
+    return _UpsampleConv.apply(x, conv.weight, conv.bias, wpack, bpack, wpack_t)
 
 
 class _Deform(torch.autograd.Function):

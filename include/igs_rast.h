@@ -846,6 +846,43 @@ long long igs_upconv_pack_elems(int Cin, int Cout, int conv_dtype);
 int igs_upconv_fwd(void* stream, int N, int Cin, int Cout, int H, int W, int x_dtype, const void* x, long long xs_n, long long xs_c,
                    long long xs_h, long long xs_w, int conv_dtype, const void* wpack, const float* bpack, void* out);
 
+/* The backward of igs_upconv_fwd (upconv_bwd.hip).  With g = dout = d out [N, Cout, 2 H, 2 W]:
+ *     db[o]             = sum_{n, Y, X} g[n, o, Y, X]
+ *     dw[o, c, dy, dx]  = sum_{n, Y, X} g[n, o, Y, X] up[n, c, Y + dy - 1, X + dx - 1]        up as igs_upconv_fwd defines it, zero outside
+ *     dup[n, c, y, x]   = sum_{o, dy, dx} weight[o, c, dy, dx] g[n, o, y - dy + 1, x - dx + 1]  g zero outside the map
+ *     dx                = U^T dup: low-resolution row i gathers the upsampled rows 2 i - 1 .. 2 i + 2 with 1/4, 3/4, 3/4, 1/4, columns
+ *                         likewise, and what the forward's clamp folded onto the first / last row or column comes back to it
+ * up is recomputed from x and dup lives in registers and LDS: neither reaches memory.  Runs on `stream`, reads nothing back, allocates
+ * nothing, uses no atomics; every sum has a fixed order and every output element is written by one lane: two runs agree bit for bit, and
+ * an image's dx does not depend on N or on its place in the batch.
+ *   - x, xs_*, x_dtype as igs_upconv_fwd takes them; x is read only for dw and may be NULL when dw is NULL.  dout: contiguous, in
+ *     conv_dtype.  dx [N, Cin, H, W] contiguous in x_dtype; dw float32 [Cout, Cin, 3, 3] row-major; db float32 [Cout].  Each of dx, dw, db
+ *     may be NULL (not wanted): no work is launched for a NULL output, nothing at all with all three NULL.  Every element of a non-NULL
+ *     output is written.  N == 0 zero-fills dw and db where given and launches nothing else.
+ *   - wpack_t, in conv_dtype: igs_upconv_fwd's layout of the convolution weight_t[c, o, dy, dx] = weight[o, c, 2 - dy, 2 - dx], a
+ *     [Cin, Cout, 3, 3] convolution: tile ((tap * kt) + k) * ot + o with kt = ceil(Cin / 32) now the output tiles;
+ *     igs_upconv_pack_elems(Cout, Cin, conv_dtype) elements.
+ *   - IGS_DTYPE_F32: v_mfma_f32_32x32x2_f32 in both product phases.  A dx element is one float32 fma chain over the 9 Cout products (output
+ *     tile of Cout, tap, channel) per dup value and at most 8 more fma of the gather (4 per column pass, 4 for the rows; the weights and
+ *     their products are exact).  dw and db are float32 sums over the N 4 H W pixels in a fixed order: a slice's pixels in order in one
+ *     chain per lane half, the two halves added by the matrix instruction, then the slices in order.  IGS_DTYPE_F16:
+ *     v_mfma_f32_32x32x16_f16; wpack_t and dout are half as given, the recomputed upsampled value is rounded to half once exactly as
+ *     the forward rounds it, all sums are float32, dx is rounded once where x_dtype is half.
+ *   - scratch: igs_upconv_bwd_scratch_bytes(N, Cin, Cout, H, W, conv_dtype) bytes (-1: sizes out of range or an unknown dtype code),
+ *     16-byte aligned: the float32 partial dw and db of the slices the 4 x 32 pixel tiles of the batch are cut into, at most
+ *     IGS_UPCONV_BWD_SLICES of them, so it does not grow with N beyond that: min(tiles, IGS_UPCONV_BWD_SLICES) *
+ *     (9 ot kt 1024 + 128) * 4 with tiles = N ceil(2 H / 4) ceil(2 W / 32).  Needed (and checked) whatever is wanted.
+ *   - Refused with IGS_RAST_E_INVALID and a message before any HIP call: everything igs_upconv_fwd refuses about sizes, dtype codes and
+ *     strides; with N > 0 a NULL wpack_t, dout or scratch; a NULL x with a non-NULL dw; x, dx or dout not aligned to its element; dw or db
+ *     not aligned to 4 bytes; wpack_t or scratch not aligned to 16 bytes; scratch_bytes below the needed size.
+ * dgrad: a workgroup owns a 3 x 15 low-resolution tile of one image (8 x 32 dup pixels, the forward's product shape).  wgrad: a
+ * workgroup owns 32 input channels and one slice of the pixel tiles; a second launch adds the slices in order. */
+#define IGS_UPCONV_BWD_SLICES 64
+long long igs_upconv_bwd_scratch_bytes(int N, int Cin, int Cout, int H, int W, int conv_dtype);
+int igs_upconv_bwd(void* stream, int N, int Cin, int Cout, int H, int W, int x_dtype, const void* x, long long xs_n, long long xs_c,
+                   long long xs_h, long long xs_w, int conv_dtype, const void* wpack_t, const void* dout, void* scratch,
+                   long long scratch_bytes, void* dx, float* dw, float* db);
+
 /* Fused attention for the anchor transformer (attn.hip): out = softmax(scale * Q K^T) V in one pass over the keys, the
  * self-attention of GridEncoder.conv's Transformer1D (igs/models/transformers.py:673-907: 8 heads of 64 channels over 8192 anchors, no mask,
  * no dropout).  The score matrix is never stored.  Everything runs on `stream`, reads nothing back and allocates nothing.
