@@ -1,5 +1,5 @@
 // elem_common.h -- the small device helpers that every kernel file shares: the workgroup barrier, the float32 / float16 element access
-// (typed, or by a runtime dtype code), the lane-sum butterfly and the tail of the corrected two-pass statistics.  Device only; nothing
+// (typed, or by a runtime dtype code), the exact GELU's Phi, the lane-sum butterfly and the tail of the corrected two-pass statistics.  Device only; nothing
 // of the rasterizer is included.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,6 +50,9 @@ __device__ __forceinline__ float ld(TokPtr t, size_t i) { return t.half ? ld((co
 __device__ __forceinline__ float4 ld4(TokPtr t, size_t i) { return t.half ? ld4((const _Float16*)t.p + i) : ld4((const float*)t.p + i); }
 __device__ __forceinline__ void st(TokPtr t, size_t i, float v) { if (t.half) st((_Float16*)t.p + i, v); else st((float*)t.p + i, v); }
 __device__ __forceinline__ void st4(TokPtr t, size_t i, float4 v) { if (t.half) st4((_Float16*)t.p + i, v); else st4((float*)t.p + i, v); }
+
+// Phi(g) = 0.5 (1 + erf(g / sqrt 2)): the exact GELU is g Phi(g) (tokens.hip's GEGLU and its backward, ffn.hip's feed-forward)
+__device__ __forceinline__ float gelu_cdf(float g) { return 0.5f * (1.f + erff(g * 0.70710678118654752f)); }
 
 // The sums of N values over every group of LANES neighbouring lanes of a wave (a power of two), the same bits in every lane of the
 // group: an xor butterfly, largest offset first, whose two operands commute.  A fixed order: the same result on every run.

@@ -273,7 +273,6 @@ static hipError_t launch_ln_bwd(hipStream_t s, long long N, int C, int x_dtype, 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // (2) GEGLU
 // ---------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float geglu_cdf(float g) { return 0.5f * (1.f + erff(g * 0.70710678118654752f)); }
 __device__ __forceinline__ float geglu_pdf(float g) { return 0.3989422804014327f * expf(-0.5f * g * g); }
 
 // thread i takes the V columns (i mod dv) V .. of row i / dv, dv = D / V
@@ -288,17 +287,17 @@ geglu_fwd_kernel(uint32_t total, uint32_t dv, int D, const T* __restrict__ p, si
     T* o = out + (size_t)n * D + d;
     if (V == 4) {
         const float4 h = ld4(row), g = ld4(row + D);
-        st4(o, make_float4(h.x * (g.x * geglu_cdf(g.x)), h.y * (g.y * geglu_cdf(g.y)), h.z * (g.z * geglu_cdf(g.z)), h.w * (g.w * geglu_cdf(g.w))));
+        st4(o, make_float4(h.x * (g.x * gelu_cdf(g.x)), h.y * (g.y * gelu_cdf(g.y)), h.z * (g.z * gelu_cdf(g.z)), h.w * (g.w * gelu_cdf(g.w))));
     } else {
         const float h = ld(row), g = ld(row + D);
-        st(o, h * (g * geglu_cdf(g)));
+        st(o, h * (g * gelu_cdf(g)));
     }
 }
 
 // d h = dout gelu(g), d g = dout h (Phi(g) + g phi(g))
 __device__ __forceinline__ void geglu_grad(float h, float g, float u, float& dh, float& dg)
 {
-    const float cdf = geglu_cdf(g);
+    const float cdf = gelu_cdf(g);
     dh = u * (g * cdf);
     dg = (u * h) * fmaf(g, geglu_pdf(g), cdf);
 }

@@ -24,6 +24,7 @@
 //   transformer ends    gnorm.hip               _gnorm.group_norm_tokens_fwd / _bwd, _gnorm.tokens_add_residual: [B, C, A] in, [B, A, C] out
 //   residual decoder    mlp.hip                 _mlp.mlp_heads_fwd, _mlp.pack_elems: [N, C0] rows with a row stride in, one [N, ch] per head out;
 //                                               _mlp.mlp_heads_bwd, _mlp.bwd_scratch_bytes: d x and flat float32 d w / d b from x alone
+//   layer tail          ffn.hip                 _ffn.layer_tail_fwd, _ffn.pack_elems: merge, LayerNorms and FFN of a unimatch TransformerLayer on [T, 128] rows
 //   deform              motion.hip              motion_deform_fwd / _bwd
 //   Adam                refine_ops.hip          adam_step_multi
 //   losses              refine_ops, loss_ops    l1_mean; ssim_mean
@@ -1431,6 +1432,44 @@ std::tuple<OptTensor, OptTensor, OptTensor> mlp_heads_bwd(const Tensor& x, const
     return {dx, dw, db};
 }
 
+// ---- the tail of a unimatch TransformerLayer in one launch (ffn.hip; contract in include/igs_rast.h) ----
+int64_t layer_tail_pack_elems(int64_t hidden, bool has_ffn) { return igs_layer_tail_pack_elems((int)std::min<int64_t>(hidden, INT_MAX), has_ffn ? 1 : 0); }
+// out [T, 128] contiguous, float16 when out_half, else float32.  attn_out, source: [T, 128] rows (token_rows_check), float32 / float16 each;
+// wpack in the compute dtype as igs_layer_tail_fwd takes it (igs_amd/tokens.py packs and caches it); hidden == 0: no FFN, and ln2_* absent
+Tensor layer_tail_fwd(const Tensor& attn_out, const Tensor& source, const Tensor& wpack, int64_t hidden, const Tensor& ln1_w, const Tensor& ln1_b,
+                      double eps1, const OptTensor& ln2_w, const OptTensor& ln2_b, double eps2, bool out_half)
+{
+    const char* fn = "layer_tail_fwd";
+    const int adt = token_rows_check(fn, attn_out, "attn_out"), sdt = token_rows_check(fn, source, "source");
+    const int cdt = dtype_code(wpack, fn, "wpack");
+    const int64_t T = attn_out.size(0);
+    if (attn_out.size(1) != 128 || source.sizes() != attn_out.sizes())
+        throw RasterizerError(std::string(fn) + ": attn_out and source must both be [T, 128] (got " + c10::str(attn_out.sizes()) + " and " + c10::str(source.sizes()) + ")");
+    const bool has_ffn = hidden != 0;
+    const int64_t elems = layer_tail_pack_elems(hidden, has_ffn);
+    if (hidden < 0 || elems < 0 || T > IGS_LAYER_TAIL_MAX_ROWS)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (hidden a multiple of 32 in 32.." + std::to_string(IGS_LAYER_TAIL_MAX_HIDDEN) + ", T <= 2^24)");
+    expect(wpack, fn, "wpack", wpack.scalar_type(), {elems});
+    if (!wpack.is_contiguous()) throw RasterizerError(std::string(fn) + ": wpack must be contiguous");
+    expect(ln1_w, fn, "ln1_w", at::kFloat, {128});
+    expect(ln1_b, fn, "ln1_b", at::kFloat, {128});
+    if (has_ffn != (ln2_w.has_value() && ln2_b.has_value())) throw RasterizerError(std::string(fn) + ": ln2_w and ln2_b go with the FFN (both or neither)");
+    token_param_check(fn, ln2_w, "ln2_w", 128);
+    token_param_check(fn, ln2_b, "ln2_b", 128);
+    const GpuCall c(attn_out, fn, "attn_out", {{source, "source"}, {wpack, "wpack"}, {ln1_w, "ln1_w"}, {ln1_b, "ln1_b"}});
+    if (has_ffn) same_device(attn_out, fn, {{*ln2_w, "ln2_w"}, {*ln2_b, "ln2_b"}});
+    Tensor out = at::empty({T, 128}, attn_out.options().dtype(out_half ? at::kHalf : at::kFloat));
+    if (T == 0) return out;
+    const Tensor w1 = ln1_w.contiguous(), b1 = ln1_b.contiguous();
+    OptTensor w2, b2;
+    if (has_ffn) { w2 = ln2_w->contiguous(); b2 = ln2_b->contiguous(); }
+    check(igs_layer_tail_fwd(c.stream(), T, cdt, has_ffn ? 1 : 0, (int)hidden, attn_out.data_ptr(), adt, token_row_stride(attn_out), source.data_ptr(), sdt,
+                             token_row_stride(source), wpack.data_ptr(), w1.data_ptr<float>(), b1.data_ptr<float>(), (float)eps1, ptr_or_null<float>(w2),
+                             ptr_or_null<float>(b2), (float)eps2, out.data_ptr(), out_half ? IGS_DTYPE_F16 : IGS_DTYPE_F32, 128),
+          "igs_layer_tail_fwd");
+    return out;
+}
+
 // ---- the Gaussian deform (motion.hip) ----
 void deform_checks(const char* fn, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot, int* dt)
 {
@@ -1768,6 +1807,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     def_nogil(ml, "mlp_heads_bwd", &mlp_heads_bwd, "x"_a, "wpack"_a, "wpack_t"_a, "bpack"_a, "widths"_a, "act_after"_a, "head_widths"_a, "act"_a, "douts"_a,
               "want_x"_a = true, "want_w"_a = true, "want_b"_a = true);
     ml.def("bwd_scratch_bytes", &mlp_bwd_scratch_bytes, "N"_a, "half"_a, "widths"_a, "head_widths"_a);
+    py::module_ ff = m.def_submodule("_ffn", "the tail of a unimatch TransformerLayer in one launch: merge, LayerNorms and FFN (ffn.hip)");
+    def_nogil(ff, "layer_tail_fwd", &layer_tail_fwd, "attn_out"_a, "source"_a, "wpack"_a, "hidden"_a, "ln1_w"_a, "ln1_b"_a, "eps1"_a, "ln2_w"_a = none,
+              "ln2_b"_a = none, "eps2"_a = 1e-5, "out_half"_a = false);
+    def_nogil(ff, "pack_elems", &layer_tail_pack_elems, "hidden"_a, "has_ffn"_a = true);
     py::module_ ls = m.def_submodule("_loss", "SSIM and L1 of a batch of images: the AGM-Net training loss (ssim_batch.hip)");
     def_nogil(ls, "ssim_batch", &ssim_batch, "a"_a, "b"_a, "c_ssim"_a, "c_l1"_a, "want_grad"_a, "want_map"_a, "want_l1"_a);
 

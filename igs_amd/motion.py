@@ -38,6 +38,7 @@ Deviations from the reference lines (INTEGRATION.md lists them):
 """
 import torch
 
+from ._binding import autocast_half as _autocast_half, param_key as _param_key
 from ._cabi import ext as _ext
 
 MAX_K = 100                            # IGS_INTERP_MAX_K
@@ -821,16 +822,6 @@ class _MlpHeadsFn(torch.autograd.Function):
         return (dx, None, None) + tuple(grads)
 
 
-def _autocast_half(fn, x):
-    """True when CUDA autocast to float16 is on for x's device type; bfloat16 autocast is refused."""
-    if not (x.is_cuda and torch.is_autocast_enabled()):
-        return False
-    dt = torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
-    if dt != torch.float16:
-        raise NotImplementedError(f"{fn}: autocast to {dt} is not supported (float16 only)")
-    return True
-
-
 def _mlp_train_launch(x, params, packs, widths, act_after, head_widths, activation):
     if packs[0].dtype != x.dtype:
         x = x.to(packs[0].dtype)                  # (autocast; autograd casts the gradient back)
@@ -901,10 +892,6 @@ def _decoder_spec(renderer, fn):
     if any(m.in_features != width for m in heads):
         raise NotImplementedError(f"{fn}: every output layer must read the MLP's {width} channels")
     return linears, act_after, (kinds.pop() if kinds else "silu"), heads, keys
-
-
-def _param_key(params):
-    return tuple(None if p is None else (p._version, p.data_ptr(), p.dtype, p.device) for p in params)
 
 
 def _child(m, name):

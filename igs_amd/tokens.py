@@ -12,6 +12,9 @@ norm2, then `source + message`, and a three-launch `is_self_attn` test whose res
                                                                         writes both halves of d proj in one launch
     use_native_block_ops(grid_encoder)                                  binds norm1, norm3 and ff.net[0] of every BasicTransformerBlock
     use_native_transformer_layers(feature_transformer)                  binds the forward of every unimatch TransformerLayer
+    layer_tail(attn_out, source, layer)                                 everything behind the layer's attention (merge, LN1, cat, the
+                                                                        GELU MLP, LN2, the residual add) as one launch, forward only
+    use_native_layer_tails(feature_transformer)                         binds a forward that takes layer_tail when nothing needs a gradient
     group_norm_tokens(x, num_groups, weight, bias, eps)                 F.group_norm over [B, C, A] written token-major [B, A, C]: the
                                                                         statistics, then one tile-transposing launch
     add_residual_tokens(tokens, residual)                               tokens [B, A, C] + residual [B, C, A], one launch; a [B, C, A]-shaped
@@ -41,7 +44,8 @@ the figures of section 20.
 
 Not provided: norm types other than nn.GroupNorm with affine parameters at the ends of Transformer1D, gradient checkpointing and 2-D
 attention masks there, fusing proj_in / proj_out; the GELU inside the unimatch MLP (a single eager kernel
-already); splitting the MLP's first weight to avoid the cat (it changes the GEMM's summation order); bfloat16; fusing any GEMM; the ada
+already) and splitting the MLP's first weight to avoid the cat outside layer_tail (which does both); any backward
+of layer_tail, the q / k / v projections, d_model other than 128 and biases there; bfloat16; fusing any other GEMM; the ada
 norms, cross-attention (norm2 / attn2) and the other feed-forward activations of BasicTransformerBlock; attn_type other than 'swin' and
 nhead > 1 of TransformerLayer.
 """
@@ -51,7 +55,9 @@ import types
 import torch
 import torch.nn as nn
 
+from ._binding import autocast_half, param_key
 from ._cabi import ext as _ext
+from .motion import pack_mlp_tile_order
 
 DTYPES = (torch.float32, torch.float16)
 LN_MAX_C = 1024                                                    # IGS_LN_MAX_C (include/igs_rast.h)
@@ -259,12 +265,9 @@ def use_native_block_ops(module):
 
 
 # ---------------------------------------------------------------- the unimatch TransformerLayer
-def _layer_forward(self, source, target, height=None, width=None, shifted_window_attn_mask=None, shifted_window_attn_mask_1d=None,
-                   attn_type="swin", with_shift=False, attn_num_splits=None):
-    """TransformerLayer.forward (igs/models/unimatch/transformer.py:44-146) for attn_type = 'swin': the three projections, the attention
-    function of the layer's own module (looked up now, so whatever use_native_window_attention set there is used), merge, then
-    source + LN1(message) as one launch, or LN1, cat, mlp and source + LN2(message) as one launch.  is_self_attn is not computed: 'swin'
-    never reads it."""
+def _layer_message(self, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits):
+    """The three projections and the attention function of the layer's own module (looked up now, so whatever
+    use_native_window_attention set there is used): the input of the layer's tail."""
     fn = "TransformerLayer"
     if attn_type != "swin":
         raise NotImplementedError(f"{fn}: attn_type = {attn_type!r} is not provided (IGS uses 'swin' only)")
@@ -273,10 +276,13 @@ def _layer_forward(self, source, target, height=None, width=None, shifted_window
     namespace = sys.modules[type(self).__module__]
     query, key, value = getattr(self, LAYER_Q)(source), getattr(self, LAYER_K)(target), getattr(self, LAYER_V)(target)
     if attn_num_splits is not None and attn_num_splits > 1:
-        message = getattr(namespace, ATTN_SPLIT)(query, key, value, num_splits=attn_num_splits, with_shift=with_shift, h=height, w=width,
-                                                 attn_mask=shifted_window_attn_mask)
-    else:
-        message = getattr(namespace, ATTN_FULL)(query, key, value)
+        return getattr(namespace, ATTN_SPLIT)(query, key, value, num_splits=attn_num_splits, with_shift=with_shift, h=height, w=width,
+                                              attn_mask=shifted_window_attn_mask)
+    return getattr(namespace, ATTN_FULL)(query, key, value)
+
+
+def _layer_tail_unfused(self, message, source):
+    """merge, then source + LN1(message) as one launch, or LN1, cat, mlp and source + LN2(message) as one launch."""
     message = getattr(self, LAYER_MERGE)(message)
     n1 = getattr(self, LAYER_NORM1)
     if getattr(self, LAYER_NO_FFN):
@@ -289,16 +295,22 @@ def _layer_forward(self, source, target, height=None, width=None, shifted_window
                       out_dtype=_autocast_out_dtype(torch.promote_types(message.dtype, source.dtype)))
 
 
+def _layer_forward(self, source, target, height=None, width=None, shifted_window_attn_mask=None, shifted_window_attn_mask_1d=None,
+                   attn_type="swin", with_shift=False, attn_num_splits=None):
+    """TransformerLayer.forward (igs/models/unimatch/transformer.py:44-146) for attn_type = 'swin': the three projections, the attention
+    function of the layer's own module (looked up now, so whatever use_native_window_attention set there is used), merge, then
+    source + LN1(message) as one launch, or LN1, cat, mlp and source + LN2(message) as one launch.  is_self_attn is not computed: 'swin'
+    never reads it."""
+    message = _layer_message(self, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits)
+    return _layer_tail_unfused(self, message, source)
+
+
 def _is_layer(m):
     return all(hasattr(m, a) for a in (LAYER_Q, LAYER_K, LAYER_V, LAYER_MERGE, LAYER_NORM1, LAYER_NO_FFN, LAYER_NHEAD))
 
 
-def use_native_transformer_layers(module):
-    """Binds a forward on every unimatch TransformerLayer under `module`, found by q_proj, k_proj, v_proj, merge, norm1, no_ffn, nhead (and
-    mlp, norm2 when it has an FFN); returns how many.  state_dict() keys and the classes are untouched.  Raises NotImplementedError, before
-    anything is changed, for nhead > 1 and for norms that are not nn.LayerNorm over the last dimension; attn_type other than 'swin' raises
-    at the call."""
-    fn = "use_native_transformer_layers"
+def _checked_layers(fn, module):
+    """Every unimatch TransformerLayer under `module`, or NotImplementedError for one that the bound forwards do not serve."""
     layers = [m for m in module.modules() if _is_layer(m)]
     for m in layers:
         if getattr(m, LAYER_NHEAD) > 1:
@@ -309,8 +321,200 @@ def use_native_transformer_layers(module):
         for a in names[:2]:
             if not _layer_norm_ok(getattr(m, a)):
                 raise NotImplementedError(f"{fn}: {a} must be nn.LayerNorm over the last dimension (got {getattr(m, a)})")
+    return layers
+
+
+def use_native_transformer_layers(module):
+    """Binds a forward on every unimatch TransformerLayer under `module`, found by q_proj, k_proj, v_proj, merge, norm1, no_ffn, nhead (and
+    mlp, norm2 when it has an FFN); returns how many.  state_dict() keys and the classes are untouched.  Raises NotImplementedError, before
+    anything is changed, for nhead > 1 and for norms that are not nn.LayerNorm over the last dimension; attn_type other than 'swin' raises
+    at the call."""
+    layers = _checked_layers("use_native_transformer_layers", module)
     for m in layers:
         m.forward = types.MethodType(_layer_forward, m)
+    return len(layers)
+
+
+# ---------------------------------------------------------------- the layer's tail in one launch (ffn.hip)
+TAIL_D = 128                                                       # d_model: the only width ffn.hip (and wattn.hip) serves
+TAIL_MAX_HIDDEN = 2048                                             # IGS_LAYER_TAIL_MAX_HIDDEN
+TAIL_MAX_ROWS = 1 << 24                                            # IGS_LAYER_TAIL_MAX_ROWS
+TAIL_TRIP_ROWS = 128                                               # IGS_LAYER_TAIL_TRIP_ROWS
+TAIL_CACHE = "_igs_layer_tail_pack"
+# Per compute dtype, whether the forward that use_native_layer_tails binds takes the fused kernel when nothing needs a gradient (True) or
+# today's tail (False; layer_tail with an explicit compute_dtype still runs the kernel).  DESIGN.md 27 has the measurement that set
+# each: the fused tail against the unfused native tail at [32768, 128], hidden 1024.
+LAYER_TAIL_FUSED = {torch.float32: True, torch.float16: True}
+# A layer WITH FFN takes the fused kernel only when its rows fill at least this share of the kernel's last round of workgroups.  The kernel
+# holds one wave per SIMD and a wave streams the whole FFN past its 32 rows, so a launch costs a fixed time per round of compute units x
+# 128 rows (0.32 ms float32, 0.14 ms float16 measured) however few of them are there: [16384, 128] fills half a round of 256 compute
+# units and measured 0.67 x (float32) and 0.91 x (float16) of the unfused tail, [32768, 128] fills it and measured 1.05 x and 1.10 x.
+# Layers without FFN are not held to it, and float32 ones take the fused kernel although it buys no time there: 0.99 x at [32768, 128] and
+# 0.94 x at [16384, 128] with overlapping min - max ranges, i.e. level within the timing noise; it is kept for half the peak memory
+# (merge's result is never stored) and one launch less.  float16 ones gain 1.21 - 1.24 x.
+LAYER_TAIL_FFN_MIN_FILL = {torch.float32: 0.95, torch.float16: 0.95}
+
+
+def _tail_spec(fn, layer):
+    """(merge, norm1, Linear 256 -> hidden or None, Linear hidden -> 128 or None, norm2 or None) of a layer that ffn.hip serves, or
+    NotImplementedError."""
+    merge, n1 = getattr(layer, LAYER_MERGE, None), getattr(layer, LAYER_NORM1, None)
+    if not isinstance(merge, nn.Linear) or (merge.in_features, merge.out_features) != (TAIL_D, TAIL_D):
+        raise NotImplementedError(f"{fn}: {LAYER_MERGE} must be nn.Linear({TAIL_D}, {TAIL_D}): d_model other than {TAIL_D} is not provided (got {merge})")
+    linears, norms = [(merge, LAYER_MERGE)], [(n1, LAYER_NORM1)]
+    l0 = l2 = n2 = None
+    if not getattr(layer, LAYER_NO_FFN):
+        mlp, n2 = getattr(layer, LAYER_MLP, None), getattr(layer, LAYER_NORM2, None)
+        mods = list(mlp) if isinstance(mlp, nn.Sequential) else []
+        if (len(mods) != 3 or not (isinstance(mods[0], nn.Linear) and isinstance(mods[1], nn.GELU) and isinstance(mods[2], nn.Linear))
+                or getattr(mods[1], GELU_ONLY_ATTRS[0], "none") != "none"):
+            raise NotImplementedError(f"{fn}: {LAYER_MLP} must be exactly nn.Sequential(Linear, GELU(approximate='none'), Linear) (got {mlp})")
+        l0, l2 = mods[0], mods[2]
+        hidden = l0.out_features
+        if l0.in_features != 2 * TAIL_D or l2.in_features != hidden or l2.out_features != TAIL_D:
+            raise NotImplementedError(f"{fn}: {LAYER_MLP} must map {2 * TAIL_D} -> hidden -> {TAIL_D} (got {l0.in_features} -> {hidden}, "
+                                      f"{l2.in_features} -> {l2.out_features})")
+        if hidden % 32 or not 32 <= hidden <= TAIL_MAX_HIDDEN:
+            raise NotImplementedError(f"{fn}: hidden = {hidden} must be a multiple of 32 in 32..{TAIL_MAX_HIDDEN}")
+        linears += [(l0, f"{LAYER_MLP}[0]"), (l2, f"{LAYER_MLP}[2]")]
+        norms.append((n2, LAYER_NORM2))
+    for lin, name in linears:
+        if lin.bias is not None:
+            raise NotImplementedError(f"{fn}: {name} has a bias: biases are not provided")
+    for n, name in norms:
+        if not _layer_norm_ok(n) or tuple(n.normalized_shape) != (TAIL_D,) or n.weight is None:
+            raise NotImplementedError(f"{fn}: {name} must be nn.LayerNorm({TAIL_D}) with weight and bias (got {n})")
+    for p in _tail_params(layer):
+        if p.dtype not in DTYPES:
+            raise NotImplementedError(f"{fn}: parameters must be float32 or float16 (got {p.dtype})")
+    return merge, n1, l0, l2, n2
+
+
+def _tail_params(layer):
+    """The parameters the tail reads: merge, norm1 and, with an FFN, the two Linears of mlp and norm2."""
+    n1 = getattr(layer, LAYER_NORM1)
+    params = [getattr(layer, LAYER_MERGE).weight, n1.weight, n1.bias]
+    if not getattr(layer, LAYER_NO_FFN):
+        mlp, n2 = getattr(layer, LAYER_MLP), getattr(layer, LAYER_NORM2)
+        params += [mlp[0].weight, mlp[2].weight, n2.weight, n2.bias]
+    return params
+
+
+def pack_layer_tail(layer, dtype=torch.float32):
+    """The weights of a layer's tail in `dtype` as igs_layer_tail_fwd takes them (include/igs_rast.h), one flat tensor of 1024-element tiles in
+    pack_mlp_tile_order's per-tile layout: merge (16 tiles, output tile outermost), then with an FFN mlp[0] split by output tile (hidden / 32
+    x 8 tiles) and mlp[2] with its INPUT tile outermost (hidden / 32 x 4 tiles), so that the kernel finds everything hidden units
+    32 j .. 32 j + 31 need in two contiguous pieces.  Plain tensor ops: works on any device."""
+    merge, _, l0, l2, _ = _tail_spec("pack_layer_tail", layer)
+    if dtype not in DTYPES:
+        raise NotImplementedError(f"pack_layer_tail: dtype must be float32 or float16 (got {dtype})")
+    parts = [pack_mlp_tile_order(merge.weight.detach().to(dtype))]
+    if l0 is not None:
+        ht = l0.out_features // 32
+        parts.append(pack_mlp_tile_order(l0.weight.detach().to(dtype)))
+        parts.append(pack_mlp_tile_order(l2.weight.detach().to(dtype)).view(TAIL_D // 32, ht, -1).transpose(0, 1).reshape(-1))
+    return torch.cat(parts).contiguous()
+
+
+def _tail_compute_dtype(fn, attn_out):
+    return torch.float16 if autocast_half(fn, attn_out) or attn_out.dtype == torch.float16 else torch.float32
+
+
+def layer_tail(attn_out, source, layer, packed=None, compute_dtype=None):
+    """Everything a unimatch TransformerLayer does behind its attention, in one launch and forward only (igs_layer_tail_fwd, ffn.hip):
+    source + LN1(merge(attn_out)) for a layer without FFN, source + LN2(mlp(cat(source, LN1(merge(attn_out))))) with one; neither merge's
+    result, the cat nor the [rows, hidden] activations reach memory.  attn_out, source: [..., 128] float32 / float16 on one GPU (rows with
+    stride 1 are read in place through a row stride, anything else is copied once).  compute_dtype: torch.float32 (exact float32 matrix
+    instructions) or torch.float16 (half operands, float32 accumulation; LayerNorms, GELU and the residual add stay float32); default
+    float16 under autocast to half or when attn_out is half, float32 otherwise.  packed: pack_layer_tail(layer, compute_dtype), packed
+    here when absent.  The result is contiguous, in the dtype the unfused bound forward gives: float32 under autocast, the promoted dtype
+    of attn_out and source otherwise.  Raises NotImplementedError when grad is enabled and an input or a parameter of the tail requires
+    grad, for a Linear with a bias, an mlp that is not Sequential(Linear, GELU(approximate='none'), Linear), d_model other than 128, a
+    hidden that is not a multiple of 32 in 32..2048, and bfloat16 / float64; RuntimeError for CPU tensors; ValueError for shapes."""
+    fn = "layer_tail"
+    merge, n1, l0, l2, n2 = _tail_spec(fn, layer)
+    if attn_out.dim() < 1 or attn_out.shape[-1] != TAIL_D or tuple(source.shape) != tuple(attn_out.shape):
+        raise ValueError(f"{fn}: attn_out and source must both be [..., {TAIL_D}] (got {list(attn_out.shape)} and {list(source.shape)})")
+    if attn_out.numel() // TAIL_D > TAIL_MAX_ROWS:
+        raise ValueError(f"{fn}: {attn_out.numel() // TAIL_D} rows is above the supported {TAIL_MAX_ROWS}")
+    params = _tail_params(layer)
+    named = [(attn_out, "attn_out"), (source, "source")] + [(p, "a parameter") for p in params]
+    for t, name in named[:2]:
+        if t.dtype not in DTYPES:
+            raise NotImplementedError(f"{fn}: {name} must be float32 or float16 (got {t.dtype})")
+    if torch.is_grad_enabled() and any(t.requires_grad for t, _ in named):
+        raise NotImplementedError(f"{fn}: forward only -- call it under torch.no_grad(), and train with use_native_transformer_layers")
+    if compute_dtype is None:
+        compute_dtype = _tail_compute_dtype(fn, attn_out)
+    if compute_dtype not in DTYPES:
+        raise NotImplementedError(f"{fn}: compute_dtype must be float32 or float16 (got {compute_dtype})")
+    if packed is not None and packed.dtype != compute_dtype:
+        raise ValueError(f"{fn}: packed holds {packed.dtype} weights, compute_dtype is {compute_dtype}")
+    _refuse(fn, named)
+    if packed is None:
+        packed = pack_layer_tail(layer, compute_dtype)
+    out_dtype = _autocast_out_dtype(torch.promote_types(attn_out.dtype, source.dtype))
+    ln2 = (None, None, 1e-5) if n2 is None else (n2.weight.detach().float(), n2.bias.detach().float(), float(n2.eps))
+    out = _ext()._ffn.layer_tail_fwd(_rows(attn_out.detach()), _rows(source.detach()), packed, 0 if l0 is None else l0.out_features,
+                                     n1.weight.detach().float(), n1.bias.detach().float(), float(n1.eps), *ln2, out_dtype == torch.float16)
+    return out.view(attn_out.shape)
+
+
+_TAIL_CUS = {}                                                     # device index -> compute units, asked once
+
+
+def _tail_fill(attn_out):
+    """The share of the fused FFN kernel's last round of workgroups (one of TAIL_TRIP_ROWS rows per compute unit) that these rows fill."""
+    rows = attn_out.numel() // max(attn_out.shape[-1], 1)
+    if rows == 0 or not attn_out.is_cuda:
+        return 0.0
+    index = attn_out.device.index
+    groups = _TAIL_CUS.get(index)
+    if groups is None:
+        groups = _TAIL_CUS[index] = torch.cuda.get_device_properties(attn_out.device).multi_processor_count
+    trips = -(-rows // TAIL_TRIP_ROWS)
+    return rows / float(-(-trips // groups) * groups * TAIL_TRIP_ROWS)
+
+
+def _layer_tail_forward(self, source, target, height=None, width=None, shifted_window_attn_mask=None, shifted_window_attn_mask_1d=None,
+                        attn_type="swin", with_shift=False, attn_num_splits=None):
+    """TransformerLayer.forward as use_native_layer_tails binds it: _layer_forward's projections and attention, then layer_tail when
+    nothing needs a gradient (and LAYER_TAIL_FUSED and LAYER_TAIL_FFN_MIN_FILL take the call), _layer_forward's own tail otherwise."""
+    fn = "TransformerLayer"
+    message = _layer_message(self, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits)
+    params = _tail_params(self)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in [message, source] + params):
+        return _layer_tail_unfused(self, message, source)
+    dtype = _tail_compute_dtype(fn, message)
+    if not LAYER_TAIL_FUSED[dtype] or (not getattr(self, LAYER_NO_FFN) and _tail_fill(message) < LAYER_TAIL_FFN_MIN_FILL[dtype]):
+        return _layer_tail_unfused(self, message, source)
+    key = param_key(params)
+    cache = self.__dict__.setdefault(TAIL_CACHE, {})                             # one pack per compute dtype
+    entry = cache.get(dtype)
+    if entry is None or entry["key"] != key:
+        entry = cache[dtype] = dict(key=key, pack=pack_layer_tail(self, dtype))
+    return layer_tail(message, source, self, packed=entry["pack"], compute_dtype=dtype)
+
+
+def use_native_layer_tails(module):
+    """Binds a forward on every unimatch TransformerLayer under `module` (found as use_native_transformer_layers finds them) that does the
+    three projections and the attention lookup as that binder's forward does and then, when nothing needs a gradient, runs the whole tail
+    as one launch (layer_tail); with grad enabled and anything requiring it, the tail is use_native_transformer_layers' own, with autograd.
+    So is the tail of a layer with FFN whose rows fill less than LAYER_TAIL_FFN_MIN_FILL of the kernel's last round of workgroups (the
+    kernel's time does not shrink with the rows below compute units x 128), and of a compute dtype that LAYER_TAIL_FUSED turns off.
+    Returns how many layers were bound; state_dict() keys and the classes are untouched; composes with use_native_window_attention.  The
+    packed weights are kept on the layer, one pack per compute dtype, and rebuilt when a parameter's _version, data_ptr, dtype or device
+    changes.  Compute dtype:
+    float16 under autocast to half or when the attention's output is half, float32 otherwise; the result has the dtype of the unfused bound
+    forward.  Raises NotImplementedError, before anything is changed, for everything use_native_transformer_layers refuses and for
+    everything layer_tail refuses about a layer (biases, another mlp, d_model other than 128, hidden out of range, bfloat16 / float64
+    parameters)."""
+    fn = "use_native_layer_tails"
+    layers = _checked_layers(fn, module)
+    for m in layers:
+        _tail_spec(fn, m)
+    for m in layers:
+        m.forward = types.MethodType(_layer_tail_forward, m)
     return len(layers)
 
 

@@ -1132,6 +1132,42 @@ int igs_mlp_heads_bwd(void* stream, long long N, int dtype, int act, int n_hidde
                       const int* head_widths, const void* x, long long x_rs, const void* wpack, const void* wpack_t, const float* bpack,
                       const void* const* douts, void* scratch, long long scratch_bytes, void* dx, float* dw, float* db);
 
+/* The tail of a unimatch TransformerLayer in one launch (ffn.hip): everything behind the attention
+ * (igs/models/unimatch/transformer.py:34-40, 117-146).  Per row t of a (the attention's output) and s (the layer's source), 128 channels:
+ *     m = Wm a;  n1 = LN1(m);  has_ffn == 0: out = s + n1;  has_ffn != 0: h = gelu(W1 [s ; n1]),  y = W2 h,  out = s + LN2(y),
+ * with Wm [128, 128], W1 [hidden, 256] (columns 0..127 multiply s, 128..255 multiply n1), W2 [128, hidden], no biases, gelu the exact
+ * (erf) one and LN(v) = (v - mean) / sqrt(var + eps) * weight + bias with float32 statistics and the biased variance taken from centred
+ * values.  Forward only.  Runs on `stream`, reads nothing back, allocates nothing, uses no atomics: two runs agree bit for bit, and a
+ * row's result depends on that row and the weights only (not on T, on the row's position or on the other rows), so a NaN stays in its row.
+ *   - a, s and out each have their own dtype code (IGS_DTYPE_F32 / IGS_DTYPE_F16; widened on load, rounded once on store) and their own row
+ *     stride in elements (>= 128; stride 1 inside a row), so slices of wider buffers are read and written in place.  Four-element accesses
+ *     are used for an operand whose base lies on its dtype's four-element grid and whose stride is a multiple of 4, scalar ones otherwise.
+ *   - compute_dtype is the matrix operand type.  IGS_DTYPE_F32: v_mfma_f32_32x32x2_f32, an exact float32 fma chain, no half value anywhere.
+ *     IGS_DTYPE_F16: v_mfma_f32_32x32x16_f16 with float32 accumulation; the only roundings to half are those of the three operands a,
+ *     [s ; n1] and h (after the float32 GELU).  The LayerNorms, the GELU and the residual add are float32 in both; the residual reads s
+ *     itself, not the rounded operand.
+ *   - wpack, in compute_dtype, 16-byte aligned, igs_layer_tail_pack_elems(hidden, has_ffn) elements (-1 for a hidden out of range;
+ *     hidden is ignored without FFN), in tiles of 1024 elements in igs_mlp_heads_fwd's per-tile layout (tile (ot, kt) of W is [chunk][lane 64][E]
+ *     with E = 8 (half) or 4 (float), element e = chunk E + j of lane (r, h) = W[32 ot + r][32 kt + (e & 3) + 8 (e >> 2) + 4 h]):
+ *       Wm:  16 tiles, output tile outermost: tile 4 ot + kt;
+ *       W1:  hidden / 32 x 8 tiles, output tile outermost: tile 8 j + kt (has_ffn only);
+ *       W2:  hidden / 32 x 4 tiles, INPUT tile outermost: tile 4 j + ot, so that the 12 tiles of hidden units 32 j .. 32 j + 31 are two
+ *            contiguous pieces (has_ffn only).
+ *   - ln1_w, ln1_b, ln2_w, ln2_b: float32 [128]; ln2_* and eps2 are not read without FFN.
+ *   - The launch: workgroups of 4 waves take trips of IGS_LAYER_TAIL_TRIP_ROWS rows (32 per wave); the grid is
+ *     min(ceil(T / IGS_LAYER_TAIL_TRIP_ROWS), compute units x (has_ffn ? 1 : 2)) workgroups, each looping over its trips.
+ *   - Refused with IGS_RAST_E_INVALID and a message before any HIP call: an unknown dtype code; T < 0 or > IGS_LAYER_TAIL_MAX_ROWS; with FFN a
+ *     hidden that is not a multiple of 32 in 32 .. IGS_LAYER_TAIL_MAX_HIDDEN; a row stride below 128 or above IGS_TOKENS_MAX_STRIDE; an eps
+ *     that is not finite and >= 0; with T > 0 a NULL required pointer, a pointer not aligned to its element size, a wpack not aligned to
+ *     16 bytes, an out that overlaps a or s.  T == 0 returns 0 without a launch. */
+#define IGS_LAYER_TAIL_MAX_HIDDEN 2048
+#define IGS_LAYER_TAIL_MAX_ROWS (1LL << 24)
+#define IGS_LAYER_TAIL_TRIP_ROWS 128
+long long igs_layer_tail_pack_elems(int hidden, int has_ffn);
+int igs_layer_tail_fwd(void* stream, long long T, int compute_dtype, int has_ffn, int hidden, const void* a, int a_dtype, long long a_stride,
+                       const void* s, int s_dtype, long long s_stride, const void* wpack, const float* ln1_w, const float* ln1_b, float eps1,
+                       const float* ln2_w, const float* ln2_b, float eps2, void* out, int out_dtype, long long out_stride);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).
