@@ -146,6 +146,9 @@ SIGNATURES = {
     # cond_fused.hip
     "igs_condition3d_pack_elems": (_ll, [_i] * 3),
     "igs_condition3d_fwd": (_i, [_vp] + [_i] * 8 + [_vp] + [_ll] * 4 + [_vp] * 2 + [_i] + [_vp] * 4 + [_f] + [_vp]),
+    # cond_fused_bwd.hip
+    "igs_condition3d_bwd_scratch_bytes": (_ll, [_i] * 5),
+    "igs_condition3d_bwd": (_i, [_vp] + [_i] * 8 + [_vp] + [_ll] * 4 + [_vp] * 2 + [_i] + [_vp] * 5 + [_f] + [_vp] * 2 + [_ll] + [_vp] * 7),
     # upconv.hip
     "igs_upconv_pack_elems": (_ll, [_i] * 3),
     "igs_upconv_fwd": (_i, [_vp] + [_i] * 6 + [_vp] + [_ll] * 4 + [_i] + [_vp] * 3),

@@ -1,5 +1,6 @@
 // cond_common.h -- one pixel's 33 conditioning channels of IGS.condition3D, shared by ray_condition_kernel (cond.hip), which stores
 // them, and condition3d_fused_kernel (cond_fused.hip), which keeps them in registers: the same statements, so the same bits.
+// cond_fused.hip and cond_fused_bwd.hip also share how an element of x is loaded and widened (CfRaw, cf_load, cf_widen).
 // Device only.  include/igs_rast.h (igs_ray_condition_fwd) defines the channels.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -52,3 +53,12 @@ __device__ __forceinline__ void cond_pixel(const float* __restrict__ r, const fl
     const float v10 = dm[(size_t)y1 * Wd + x0], v11 = dm[(size_t)y1 * Wd + x1];
     t[32] = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
 }
+
+// an element of x as it is loaded (float16: its 16 bits), and widened
+template <typename TX> struct CfRaw;
+template <> struct CfRaw<float> { typedef float type; };
+template <> struct CfRaw<_Float16> { typedef unsigned short type; };
+__device__ __forceinline__ float cf_load(const float* p) { return *p; }
+__device__ __forceinline__ unsigned short cf_load(const _Float16* p) { return *(const unsigned short*)p; }
+__device__ __forceinline__ float cf_widen(float v) { return v; }
+__device__ __forceinline__ float cf_widen(unsigned short v) { return (float)__builtin_bit_cast(_Float16, v); }

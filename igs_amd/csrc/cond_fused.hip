@@ -2,7 +2,8 @@
 // x [N, C, H, W] the 33 conditioning channels (cond_common.h, the statements of ray_condition_kernel), ModLN's MLP
 // Linear(33, hidden) . SiLU . Linear(hidden, 2 C) on the matrix cores, LayerNorm over the pixel's C channels and the modulation
 //     out = ((x - mu) r weight + bias) (1 + scale) + shift.
-// Neither the condition, the hidden activations nor the modulation reaches memory.  Forward only.  include/igs_rast.h states the
+// Neither the condition, the hidden activations nor the modulation reaches memory.  Forward only (cond_fused_bwd.hip is the backward,
+// which recomputes this forward with the same statements).  include/igs_rast.h states the
 // contract (igs_condition3d_fwd), DESIGN.md section 15.7 the budget and the figures.
 //
 // Tile layout: mlp.hip's.  One wave owns 32 consecutive pixels of ONE image (the last group of an image is masked per lane, so a group
@@ -42,15 +43,6 @@ struct CondFusedArgs {
     const float* nb;
     float* out;
 };
-
-// an element of x as it is loaded (float16: its 16 bits), and widened
-template <typename TX> struct CfRaw;
-template <> struct CfRaw<float> { typedef float type; };
-template <> struct CfRaw<_Float16> { typedef unsigned short type; };
-__device__ __forceinline__ float cf_load(const float* p) { return *p; }
-__device__ __forceinline__ unsigned short cf_load(const _Float16* p) { return *(const unsigned short*)p; }
-__device__ __forceinline__ float cf_widen(float v) { return v; }
-__device__ __forceinline__ float cf_widen(unsigned short v) { return (float)__builtin_bit_cast(_Float16, v); }
 
 template <typename T, typename TX>
 __global__ __launch_bounds__(CF_THREADS, 2) void condition3d_fused_kernel(const CondFusedArgs a)

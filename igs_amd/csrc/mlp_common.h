@@ -1,5 +1,6 @@
-// mlp_common.h -- what the kernels that chain Linears on 32x32 MFMA tiles share (mlp.hip, cond_fused.hip): the operand registers of
-// 32 data rows, the tile product over a packed weight tile, the finite SiLU and the compute-unit count.  mlp.hip states the tile layout.
+// mlp_common.h -- what the kernels that chain Linears on 32x32 MFMA tiles share (mlp.hip, cond_fused.hip, cond_fused_bwd.hip): the operand registers of
+// 32 data rows, the tile product over a packed weight tile, the finite SiLU and its derivative, the weight-gradient product over rows and the
+// compute-unit count.  mlp.hip states the tile layout.
 #pragma once
 #include "attn_common.h"
 
@@ -51,6 +52,39 @@ __device__ __forceinline__ float mlp_silu(float v)
     float e = attn_exp2(t > 126.f ? 126.f : t);
     e = fmaf(e, tl * 0.6931471805599453f, e);
     return v * __builtin_amdgcn_rcpf(1.f + e);
+}
+
+// d silu(v) / d v = s (1 + v (1 - s)), s = sigmoid(v), on mlp_silu's clamped evaluation of e = exp(-v); 1 - s is taken as e s (no
+// cancellation where s is close to 1) and the result as fma(v e s, s, s).  For finite v every term is finite: e <= 2^126 (1 + small),
+// s >= 2^-127, e s <= 1, |v e s| <= |v|.  s is within 6 u of sigmoid, e s within 10 u, t = v e s within 11 u; |s t| <= 0.224, so the
+// result is within 8 u |silu'| + 3 u of silu'(v) (tests/decoder_grad_restatement.py: SILUP_C, SILUP_ABS).
+__device__ __forceinline__ float mlp_silu_grad(float v)
+{
+    const float L = -1.4426950408889634f, Ll = -1.9259629911266175e-8f;
+    const float c = __builtin_amdgcn_fmed3f(v, -128.f, 128.f);
+    const float t = c * L;
+    const float tl = fmaf(c, L, -t) + c * Ll;
+    float e = attn_exp2(t > 126.f ? 126.f : t);
+    e = fmaf(e, tl * 0.6931471805599453f, e);
+    const float s = __builtin_amdgcn_rcpf(1.f + e);
+    return fmaf(v * (e * s), s, s);
+}
+
+// sixteen rows of a product over rows: element j of lane half h is row n0 + 8 h + j (half: one v_mfma_f32_32x32x16_f16) or row
+// n0 + 2 j + h (float: the j-th of eight v_mfma_f32_32x32x2_f32)
+template <typename T> __device__ __forceinline__ constexpr int mlp_wgrad_row(int j, int h) { return AttnCfg<T>::HALF ? 8 * h + j : 2 * j + h; }
+__device__ __forceinline__ attn_acc mlp_wgrad_mm(_Float16, const float (&av)[8], const float (&bv)[8], attn_acc o)
+{
+    attn_h8 a8, b8;
+#pragma unroll
+    for (int j = 0; j < 8; j++) { a8[j] = (_Float16)av[j]; b8[j] = (_Float16)bv[j]; }
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a8, b8, o, 0, 0, 0);
+}
+__device__ __forceinline__ attn_acc mlp_wgrad_mm(float, const float (&av)[8], const float (&bv)[8], attn_acc o)
+{
+#pragma unroll
+    for (int j = 0; j < 8; j++) o = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], o, 0, 0, 0);
+    return o;
 }
 
 __host__ __device__ static inline int mlp_tiles(int c) { return (c + 31) / 32; }

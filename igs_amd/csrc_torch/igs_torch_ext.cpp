@@ -15,6 +15,7 @@
 //   lifting             lift.hip                motion_lift_fwd / _bwd
 //   condition3D         cond.hip                cond_ray_fwd, modln_fwd / _bwd
 //                       cond_fused.hip          _cond.condition3d_fwd, _cond.pack_elems: the forward in one launch, ModLN's MLP included
+//                       cond_fused_bwd.hip      _cond.condition3d_bwd, _cond.bwd_scratch_bytes: its backward, the forward recomputed
 //   upsample + conv     upconv.hip              _upconv.upconv_fwd, _upconv.pack_elems: 2x bilinear upsample and 3x3 convolution in one launch
 //                       upconv_bwd.hip          _upconv.upconv_bwd: its backward, d x / d weight / d bias from x and d out
 //   attention           attn.hip                attn_fwd / _bwd on [B, H, A, 64] views of any acceptable strides
@@ -873,6 +874,63 @@ Tensor condition3d_fwd(const Tensor& x, const Tensor& rays, const Tensor& depth,
                               x.stride(2), x.stride(3), rc.data_ptr<float>(), dc.data_ptr<float>(), mdt, wpack.data_ptr(), bpack.data_ptr<float>(),
                               wc.data_ptr<float>(), bc.data_ptr<float>(), (float)eps, out.data_ptr<float>()), "igs_condition3d_fwd");
     return out;
+}
+int64_t cond_fused_bwd_scratch_bytes(int64_t N, int64_t C, int64_t hidden, int64_t H, int64_t W)
+{
+    if (N < 0 || N > INT_MAX || C < 1 || C > INT_MAX || hidden < 1 || hidden > INT_MAX || H < 1 || H > INT_MAX || W < 1 || W > INT_MAX) return -1;
+    return igs_condition3d_bwd_scratch_bytes((int)N, (int)C, (int)hidden, (int)H, (int)W);
+}
+// (d x [N, C, H, W] in x's dtype, d W1 [hidden, 33], d b1 [hidden], d W2 [2C, hidden], d b2 [2C], d weight [C], d bias [C] float32), each None
+// unless wanted.  The inputs of condition3d_fwd, wpack_t as igs_condition3d_bwd takes it, and grad_out [N, C, H, W] float32 contiguous
+std::tuple<OptTensor, OptTensor, OptTensor, OptTensor, OptTensor, OptTensor, OptTensor>
+condition3d_bwd(const Tensor& x, const Tensor& rays, const Tensor& depth, const Tensor& wpack, const Tensor& wpack_t, const Tensor& bpack, int64_t hidden,
+                const Tensor& weight, const Tensor& bias, double eps, const Tensor& grad_out, bool want_x, bool want_w1, bool want_b1, bool want_w2,
+                bool want_b2, bool want_weight, bool want_bias)
+{
+    const char* fn = "condition3d_bwd";
+    const int xdt = dtype_code(x, fn, "x"), mdt = dtype_code(wpack, fn, "wpack");
+    if (x.dim() != 4) throw RasterizerError(std::string(fn) + ": x must have shape [N, C, H, W] (got " + c10::str(x.sizes()) + ")");
+    const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+    expect(rays, fn, "rays", at::kFloat, {N, H, W, 6});
+    expect(depth, fn, "depth", at::kFloat, {N, -1, -1});
+    expect(weight, fn, "weight", at::kFloat, {C});
+    expect(bias, fn, "bias", at::kFloat, {C});
+    expect(grad_out, fn, "grad_out", at::kFloat, {N, C, H, W});
+    const int64_t Hd = depth.size(1), Wd = depth.size(2);
+    if (H < 1 || W < 1 || Hd < 1 || Wd < 1 || H > IGS_COND_MAX_HW || W > IGS_COND_MAX_HW || Hd > IGS_COND_MAX_HW || Wd > IGS_COND_MAX_HW ||
+        N * H * W > IGS_COND_MAX_PIXELS)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (1 <= H, W, Hd, Wd <= 8192, N * H * W <= 2^24)");
+    const int64_t elems = C >= 1 && C <= INT_MAX && hidden >= 1 && hidden <= INT_MAX ? igs_condition3d_pack_elems((int)C, (int)hidden, mdt) : -1;
+    if (elems < 0) throw RasterizerError(std::string(fn) + ": C and hidden must be in 1..128 (got " + std::to_string(C) + ", " + std::to_string(hidden) + ")");
+    const int64_t ht = (hidden + 31) / 32, ct = (C + 31) / 32;
+    expect(wpack, fn, "wpack", wpack.scalar_type(), {elems});
+    expect(wpack_t, fn, "wpack_t", wpack.scalar_type(), {2 * ct * ht * 1024});
+    expect(bpack, fn, "bpack", at::kFloat, {3, IGS_COND_MLP_MAX_WIDTH});
+    if (!wpack.is_contiguous() || !wpack_t.is_contiguous() || !bpack.is_contiguous() || !grad_out.is_contiguous())
+        throw RasterizerError(std::string(fn) + ": wpack, wpack_t, bpack and grad_out must be contiguous");
+    const GpuCall c(x, fn, "x", {{rays, "rays"}, {depth, "depth"}, {wpack, "wpack"}, {wpack_t, "wpack_t"}, {bpack, "bpack"}, {weight, "weight"},
+                                 {bias, "bias"}, {grad_out, "grad_out"}});
+    OptTensor dx, dw1, db1, dw2, db2, dnw, dnb;
+    const auto fo = x.options().dtype(at::kFloat);
+    const bool empty = N == 0;                                   // (no pixel: the sums are zero and nothing is launched)
+    auto make = [&](at::IntArrayRef shape) { return empty ? at::zeros(shape, fo) : at::empty(shape, fo); };
+    if (want_x) dx = at::empty({N, C, H, W}, x.options());
+    if (want_w1) dw1 = make({hidden, 33});
+    if (want_b1) db1 = make({hidden});
+    if (want_w2) dw2 = make({2 * C, hidden});
+    if (want_b2) db2 = make({2 * C});
+    if (want_weight) dnw = make({C});
+    if (want_bias) dnb = make({C});
+    if (empty || !(want_x || want_w1 || want_b1 || want_w2 || want_b2 || want_weight || want_bias)) return {dx, dw1, db1, dw2, db2, dnw, dnb};
+    const Tensor rc = rays.contiguous(), dc = depth.contiguous(), wc = weight.contiguous(), bc = bias.contiguous();
+    const Tensor scratch = at::empty({igs_condition3d_bwd_scratch_bytes((int)N, (int)C, (int)hidden, (int)H, (int)W)}, x.options().dtype(at::kByte));
+    check(igs_condition3d_bwd(c.stream(), (int)N, (int)C, (int)hidden, (int)H, (int)W, (int)Hd, (int)Wd, xdt, x.data_ptr(), x.stride(0), x.stride(1),
+                              x.stride(2), x.stride(3), rc.data_ptr<float>(), dc.data_ptr<float>(), mdt, wpack.data_ptr(), wpack_t.data_ptr(),
+                              bpack.data_ptr<float>(), wc.data_ptr<float>(), bc.data_ptr<float>(), (float)eps, grad_out.data_ptr<float>(),
+                              scratch.data_ptr(), scratch.numel(), ptr_or_null(dx), ptr_or_null<float>(dw1), ptr_or_null<float>(db1),
+                              ptr_or_null<float>(dw2), ptr_or_null<float>(db2), ptr_or_null<float>(dnw), ptr_or_null<float>(dnb)),
+          "igs_condition3d_bwd");
+    return {dx, dw1, db1, dw2, db2, dnw, dnb};
 }
 
 // ---- 2x bilinear upsample + 3x3 convolution in one launch (upconv.hip) ----
@@ -1794,9 +1852,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
               "want_weight"_a = true, "want_bias"_a = true);
     def_nogil(gn, "tokens_add_residual", &tokens_add_residual, "tokens"_a, "residual"_a, "out_half"_a = false);
     // ... and the residual decoder
-    py::module_ cf = m.def_submodule("_cond", "condition3D's forward in one launch, ModLN's MLP included (cond_fused.hip)");
+    py::module_ cf = m.def_submodule("_cond", "condition3D in one launch, ModLN's MLP included, and its backward (cond_fused.hip, cond_fused_bwd.hip)");
     def_nogil(cf, "condition3d_fwd", &condition3d_fwd, "x"_a, "rays"_a, "depth"_a, "wpack"_a, "bpack"_a, "hidden"_a, "weight"_a, "bias"_a, "eps"_a = 1e-6);
     def_nogil(cf, "pack_elems", &cond_fused_pack_elems, "C"_a, "hidden"_a, "half"_a = false);
+    def_nogil(cf, "condition3d_bwd", &condition3d_bwd, "x"_a, "rays"_a, "depth"_a, "wpack"_a, "wpack_t"_a, "bpack"_a, "hidden"_a, "weight"_a, "bias"_a,
+              "eps"_a, "grad_out"_a, "want_x"_a = true, "want_w1"_a = true, "want_b1"_a = true, "want_w2"_a = true, "want_b2"_a = true,
+              "want_weight"_a = true, "want_bias"_a = true);
+    def_nogil(cf, "bwd_scratch_bytes", &cond_fused_bwd_scratch_bytes, "N"_a, "C"_a, "hidden"_a, "H"_a, "W"_a);
     py::module_ uc = m.def_submodule("_upconv", "2x bilinear upsample + 3x3 convolution in one launch (upconv.hip)");
     def_nogil(uc, "upconv_fwd", &upconv_fwd, "x"_a, "wpack"_a, "bpack"_a, "Cout"_a);
     def_nogil(uc, "upconv_bwd", &upconv_bwd, "x"_a, "wpack_t"_a, "dout"_a, "want_x"_a, "want_w"_a, "want_b"_a);

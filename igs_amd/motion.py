@@ -15,7 +15,9 @@ anchors (igs/models/grid_encoder.py:66-88 over igs/utils/ops.py:444-477; igs_amd
 `ray_condition` / `modln` / `condition3d` are the step in front of the lift: IGS.condition3D (igs/IGS.py:185-210 with ray_to_plucker,
 rsh_cart_3 and ModLN; igs_amd/csrc/cond.hip).  The ray embedding and the fused LayerNorm + adaLN modulation are native, ModLN's small MLP
 between them stays PyTorch: the path with autograd.  `condition3d_fused` / `use_native_condition3d` are the same stage's forward in one
-launch, the MLP on the matrix cores included (igs_amd/csrc/cond_fused.hip): forward only, for the streaming path under torch.no_grad().
+launch, the MLP on the matrix cores included (igs_amd/csrc/cond_fused.hip): forward only, for the streaming path under torch.no_grad();
+`condition3d_fused_autograd` / `use_native_condition3d(model, training=True)` put a recomputing native backward behind that launch
+(igs_amd/csrc/cond_fused_bwd.hip).
 
 `upsample_conv` / `pack_upsample_conv` are the step in front of condition3D: the 2x bilinear upsample and the 3x3 convolution of the
 motion features (igs/IGS.py:132-134, up_sample True) in one launch on the matrix cores, the upsampled map never stored
@@ -307,6 +309,12 @@ MODLN_NAME = "ModLN"                                            # IGS.ModLN (IGS
 # What use_native_condition3d sends to the fused kernel: per MLP dtype the largest N * H * W it takes (None: no limit, 0: never).
 # DESIGN.md 15.7 has the measurements this follows: the fused forward is the faster one in every measured case.
 COND_FUSED_MAX_PIXELS = {torch.float32: None, torch.float16: None}
+COND_FUSED_TRAIN_CACHE = "_igs_condition3d_train_pack"
+# Per MLP dtype, whether use_native_condition3d(model, training=True) sends a call that needs a gradient to condition3d_fused_autograd
+# (True) or to condition3d (False).  DESIGN.md 15.8 has the rule and the measurements this follows: at N = 16 views of the shipped shape
+# the native forward + backward took 3.84 ms against 2.09 ms (float32) and 2.92 against 2.08 ms (float16), so it is taken only on request
+# (an explicit mlp_dtype on condition3d_fused_autograd); what it buys is memory (203 MB against 985 / 565 MB) and a reproducible backward.
+COND_FUSED_BWD_NATIVE = {torch.float32: False, torch.float16: False}
 
 
 def _cond_mlp_spec(fn, modln_module, C):
@@ -330,10 +338,12 @@ def _cond_params(modln_module):
     return [mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias, norm.weight, norm.bias]
 
 
-def pack_condition_mlp(mlp, dtype=torch.float32):
+def pack_condition_mlp(mlp, dtype=torch.float32, transposed=False):
     """(wpack in `dtype`, bpack float32 [3, 128]) as igs_condition3d_fwd takes them (include/igs_rast.h), from
     mlp = nn.Sequential(Linear(33, hidden), SiLU, Linear(hidden, 2C)): W1, W2[:C] (shift) and W2[C:] (scale), each in
-    pack_mlp_tile_order, one after another; the biases b1, b2[:C], b2[C:] zero-padded (an absent bias: zeros).  Plain tensor ops."""
+    pack_mlp_tile_order, one after another; the biases b1, b2[:C], b2[C:] zero-padded (an absent bias: zeros).  transposed=True:
+    (wpack, bpack, wpack_t), wpack_t = W2^T as igs_condition3d_bwd takes it: one Linear [hidden, 2 * 32 ct] in pack_mlp_tile_order whose
+    input 32 ct s + c is channel c of the shift (s = 0) or the scale (s = 1) half.  Plain tensor ops."""
     l0, l2 = mlp[0], mlp[2]
     hidden, C = l0.out_features, l2.out_features // 2
     W1, W2 = l0.weight.detach().to(dtype), l2.weight.detach().to(dtype)
@@ -344,19 +354,17 @@ def pack_condition_mlp(mlp, dtype=torch.float32):
     if l2.bias is not None:
         bpack[1, :C] = l2.bias.detach().float()[:C]
         bpack[2, :C] = l2.bias.detach().float()[C:]
-    return wpack, bpack
+    if not transposed:
+        return wpack, bpack
+    cw = 32 * _tiles(C)
+    M = W2.new_zeros(hidden, 2 * cw)
+    M[:, :C] = W2[:C].t()
+    M[:, cw:cw + C] = W2[C:].t()
+    return wpack, bpack, pack_mlp_tile_order(M).contiguous()
 
 
-def condition3d_fused(motion_feature, rays, depth, modln_module, packed=None, mlp_dtype=None):
-    """condition3d's result in one launch, forward only: the ray / depth condition, ModLN's MLP and the modulated LayerNorm per pixel,
-    with neither cond, the hidden activations nor mod stored (igs_condition3d_fwd, cond_fused.hip).  motion_feature [B*V, C, H, W] float32
-    / float16 (plane-contiguous NCHW is read in place, anything else is copied), rays [B, V, H, W, 6], depth [B, V, Hd, Wd] float32;
-    out float32, NCHW-contiguous.  modln_module: .norm as condition3d takes it, .mlp = nn.Sequential(Linear(33, hidden), SiLU,
-    Linear(hidden, 2C)) with C, hidden <= 128.  mlp_dtype: torch.float32 (an exact float32 fma chain) or torch.float16 (half operands,
-    float32 accumulation; mod is not rounded to half); default float16 under autocast to half, float32 otherwise.  packed:
-    pack_condition_mlp(modln_module.mlp, mlp_dtype), packed here when absent.  The argument checks are condition3d's; another .mlp
-    structure, C or hidden out of range, or anything that requires grad under enabled grad raise NotImplementedError."""
-    fn = "condition3d_fused"
+def _cond_fused_args(fn, motion_feature, rays, depth, modln_module):
+    """(norm, (N, C, H, W), Linear(33, hidden)) after the checks condition3d_fused and condition3d_fused_autograd share."""
     if motion_feature.dim() != 4:
         raise ValueError(f"{fn}: motion_feature must be [B*V, C, H, W] (got {list(motion_feature.shape)})")
     norm = modln_module.norm
@@ -380,6 +388,20 @@ def condition3d_fused(motion_feature, rays, depth, modln_module, packed=None, ml
     if norm.weight.dtype != torch.float32 or norm.bias.dtype != torch.float32:
         raise NotImplementedError(f"{fn}: the LayerNorm's weight and bias must be float32 (got {norm.weight.dtype}, {norm.bias.dtype})")
     l0, _ = _cond_mlp_spec(fn, modln_module, C)
+    return norm, (N, C, H, W), l0
+
+
+def condition3d_fused(motion_feature, rays, depth, modln_module, packed=None, mlp_dtype=None):
+    """condition3d's result in one launch, forward only: the ray / depth condition, ModLN's MLP and the modulated LayerNorm per pixel,
+    with neither cond, the hidden activations nor mod stored (igs_condition3d_fwd, cond_fused.hip).  motion_feature [B*V, C, H, W] float32
+    / float16 (plane-contiguous NCHW is read in place, anything else is copied), rays [B, V, H, W, 6], depth [B, V, Hd, Wd] float32;
+    out float32, NCHW-contiguous.  modln_module: .norm as condition3d takes it, .mlp = nn.Sequential(Linear(33, hidden), SiLU,
+    Linear(hidden, 2C)) with C, hidden <= 128.  mlp_dtype: torch.float32 (an exact float32 fma chain) or torch.float16 (half operands,
+    float32 accumulation; mod is not rounded to half); default float16 under autocast to half, float32 otherwise.  packed:
+    pack_condition_mlp(modln_module.mlp, mlp_dtype), packed here when absent.  The argument checks are condition3d's; another .mlp
+    structure, C or hidden out of range, or anything that requires grad under enabled grad raise NotImplementedError."""
+    fn = "condition3d_fused"
+    norm, (N, C, H, W), l0 = _cond_fused_args(fn, motion_feature, rays, depth, modln_module)
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [motion_feature, rays, depth] + _cond_params(modln_module)):
         raise NotImplementedError(f"{fn}: forward only -- call it under torch.no_grad(), and train with condition3d")
     if not (motion_feature.is_cuda and rays.is_cuda and depth.is_cuda):
@@ -398,9 +420,83 @@ def condition3d_fused(motion_feature, rays, depth, modln_module, packed=None, ml
                                   norm.weight.detach(), norm.bias.detach(), float(norm.eps))
 
 
-def _condition3d_bound(self, motion_feature, rays, depth):
+class _Condition3dFused(torch.autograd.Function):
+    """igs_condition3d_fwd with igs_condition3d_bwd behind it.  Saves x as the kernels read it, rays, depth, the packs and the LayerNorm's
+    affine: neither cond, the hidden activations, mod nor the statistics."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, nw, nb, rays, depth, wpack, bpack, wpack_t, hidden, eps):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, rays, depth, wpack, bpack, wpack_t, nw, nb)
+        ctx.hidden, ctx.eps = hidden, eps
+        ctx.param_dtypes = [None if t is None else t.dtype for t in (w1, b1, w2, b2, nw, nb)]
+        return _ext()._cond.condition3d_fwd(x, rays, depth, wpack, bpack, hidden, nw.detach(), nb.detach(), eps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 14
+        x, rays, depth, wpack, bpack, wpack_t, nw, nb = ctx.saved_tensors
+        if g.dtype != torch.float32:
+            g = g.float()
+        if not g.is_contiguous():
+            g = g.contiguous()                   # (the one copy of a strided d out)
+        grads = list(_ext()._cond.condition3d_bwd(x, rays, depth, wpack, wpack_t, bpack, ctx.hidden, nw.detach(), nb.detach(), ctx.eps, g,
+                                                  *ctx.needs_input_grad[:7]))
+        for i, dt in enumerate(ctx.param_dtypes):    # accumulated in float32, cast once
+            if grads[i + 1] is not None and grads[i + 1].dtype != dt:
+                grads[i + 1] = grads[i + 1].to(dt)
+        return (*grads, None, None, None, None, None, None, None)
+
+
+def condition3d_fused_autograd(motion_feature, rays, depth, modln_module, packed=None, mlp_dtype=None):
+    """condition3d_fused for training: the same checks, sizes, dtypes and value, and a native backward.  When grad is disabled or neither
+    motion_feature nor a parameter of the module requires it this IS condition3d_fused(...).  Otherwise the forward is igs_condition3d_fwd
+    and the backward igs_condition3d_bwd (cond_fused_bwd.hip): d motion_feature in its dtype, the gradients of mlp[0] / mlp[2]'s weights and
+    biases and of norm.weight / norm.bias accumulated in float32 and cast once to each parameter's dtype.  Saved: motion_feature as the
+    kernels read it (itself where it is plane-contiguous NCHW, a contiguous copy otherwise), rays, depth, the packs and the LayerNorm's
+    affine; cond, the hidden activations and mod are recomputed.  Once differentiable, deterministic (no atomics).  rays or depth that
+    require grad raise NotImplementedError.  `packed`, if given, is pack_condition_mlp(modln_module.mlp, mlp_dtype, transposed=True);
+    otherwise the three packs are kept on the module under COND_FUSED_TRAIN_CACHE and rebuilt when a parameter's _version, data_ptr,
+    dtype or device changes (every optimiser step).  Refusals as condition3d_fused's; there is no CPU fallback."""
+    fn = "condition3d_fused_autograd"
+    norm, (N, C, H, W), l0 = _cond_fused_args(fn, motion_feature, rays, depth, modln_module)
+    if packed is not None and len(packed) != 3:
+        raise ValueError(f"{fn}: packed must be pack_condition_mlp(mlp, mlp_dtype, transposed=True)")
+    if torch.is_grad_enabled() and (rays.requires_grad or depth.requires_grad):
+        raise NotImplementedError(f"{fn}: gradients to rays and depth are not provided")
+    params = _cond_params(modln_module)
+    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [motion_feature] + params)):
+        return condition3d_fused(motion_feature, rays, depth, modln_module, packed=None if packed is None else tuple(packed[:2]),
+                                 mlp_dtype=mlp_dtype)
+    if mlp_dtype is None:
+        mlp_dtype = torch.float16 if _autocast_half(fn, motion_feature) else torch.float32
+    if mlp_dtype not in FEATURE_DTYPES:
+        raise NotImplementedError(f"{fn}: mlp_dtype must be float32 or float16 (got {mlp_dtype})")
+    if packed is not None and (packed[0].dtype != mlp_dtype or packed[2].dtype != mlp_dtype):
+        raise ValueError(f"{fn}: packed holds {packed[0].dtype} weights, mlp_dtype is {mlp_dtype}")
+    if not (motion_feature.is_cuda and rays.is_cuda and depth.is_cuda):
+        raise RuntimeError(f"{fn}: tensors must be on a GPU (no CPU fallback)")
+    if packed is None:
+        key = (_param_key(params[:4]), mlp_dtype)
+        cache = modln_module.__dict__.get(COND_FUSED_TRAIN_CACHE)
+        if cache is None or cache["key"] != key:
+            cache = dict(key=key, pack=pack_condition_mlp(modln_module.mlp, mlp_dtype, transposed=True))
+            modln_module.__dict__[COND_FUSED_TRAIN_CACHE] = cache
+        packed = cache["pack"]
+    wpack, bpack, wpack_t = packed
+    x = motion_feature
+    if not _plane_contiguous(x) or (C > 1 and x.stride(1) > COND_FUSED_MAX_STRIDE) or x.stride(0) < 0 or x.stride(1) < 0:
+        x = x.contiguous()
+    return _Condition3dFused.apply(x, *params, rays.reshape(N, *rays.shape[2:]), depth.reshape(N, *depth.shape[2:]), wpack, bpack, wpack_t,
+                                   l0.out_features, float(norm.eps))
+
+
+def _condition3d_bound(self, motion_feature, rays, depth, training=False):
     """IGS.condition3D as use_native_condition3d binds it: the fused forward when nothing needs a gradient and the module qualifies,
-    condition3d (ray_condition -> the PyTorch MLP -> modln, with autograd) otherwise."""
+    condition3d (ray_condition -> the PyTorch MLP -> modln, with autograd) otherwise.  training: a call that needs a gradient goes to
+    condition3d_fused_autograd where COND_FUSED_BWD_NATIVE says so for its MLP dtype."""
     fn = "condition3D"
     module = _child(self, MODLN_NAME)
     try:
@@ -408,7 +504,16 @@ def _condition3d_bound(self, motion_feature, rays, depth):
     except (AttributeError, IndexError, TypeError):
         return condition3d(motion_feature, rays, depth, module)
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [motion_feature, rays, depth] + params):
-        return condition3d(motion_feature, rays, depth, module)
+        if not training or rays.requires_grad or depth.requires_grad:
+            return condition3d(motion_feature, rays, depth, module)
+        try:
+            _cond_mlp_spec(fn, module, motion_feature.shape[1] if motion_feature.dim() == 4 else -1)
+        except NotImplementedError:
+            return condition3d(motion_feature, rays, depth, module)
+        dtype = torch.float16 if _autocast_half(fn, motion_feature) else torch.float32
+        if not COND_FUSED_BWD_NATIVE[dtype]:
+            return condition3d(motion_feature, rays, depth, module)
+        return condition3d_fused_autograd(motion_feature, rays, depth, module, mlp_dtype=dtype)
     try:
         _cond_mlp_spec(fn, module, motion_feature.shape[1] if motion_feature.dim() == 4 else -1)
     except NotImplementedError:
@@ -425,11 +530,17 @@ def _condition3d_bound(self, motion_feature, rays, depth):
     return condition3d_fused(motion_feature, rays, depth, module, packed=cache["pack"], mlp_dtype=dtype)
 
 
-def use_native_condition3d(model):
+def _condition3d_bound_training(self, motion_feature, rays, depth):
+    return _condition3d_bound(self, motion_feature, rays, depth, training=True)
+
+
+def use_native_condition3d(model, training=False):
     """Binds condition3D(motion_feature, rays, depth) on this IGS-shaped instance (IGS.py:185-210) and returns the instance; the class and
     state_dict() keys are untouched.  A call under torch.no_grad() (or with nothing that requires grad) on a module whose .ModLN.mlp is
     Linear(33, hidden) . SiLU . Linear(hidden, 2C) with C, hidden <= 128 takes condition3d_fused -- float16 weights under autocast to half,
-    float32 otherwise, within COND_FUSED_MAX_PIXELS -- and every other call is condition3d, exactly today's training path.  The packed
+    float32 otherwise, within COND_FUSED_MAX_PIXELS -- and every other call is condition3d, exactly today's training path.  training=True
+    binds a variant that sends a call that needs a gradient (to motion_feature or a parameter, not to rays or depth) to
+    condition3d_fused_autograd where COND_FUSED_BWD_NATIVE[mlp dtype] is True, and to condition3d where it is False.  The packed
     weights are kept on the ModLN module and rebuilt when a parameter's _version, data_ptr, dtype or device changes.  Raises
     NotImplementedError, before anything is changed, for cfg.local_ray true or cfg.use_condition3d false."""
     import types
@@ -440,7 +551,7 @@ def use_native_condition3d(model):
         raise NotImplementedError("use_native_condition3d: cfg.use_condition3d is False: the model has no ModLN to bind")
     if _child(model, MODLN_NAME) is None:
         raise NotImplementedError(f"use_native_condition3d: the model has no {MODLN_NAME} module")
-    model.condition3D = types.MethodType(_condition3d_bound, model)
+    model.condition3D = types.MethodType(_condition3d_bound_training if training else _condition3d_bound, model)
     return model
 
 

@@ -815,6 +815,41 @@ int igs_condition3d_fwd(void* stream, int N, int C, int hidden, int H, int W, in
                         long long xs_c, long long xs_h, long long xs_w, const float* rays, const float* depth, int mlp_dtype, const void* wpack,
                         const float* bpack, const float* weight, const float* bias, float eps, float* out);
 
+/* The backward of igs_condition3d_fwd (cond_fused_bwd.hip).  The forward is recomputed from x, rays, depth and the
+ * packs; with g = gout[:, p] the upstream gradient of a pixel and n = (x - mu) r weight + bias:
+ *     d shift = g, d scale = g n, d n = g (1 + scale);  d weight += d n xh, d bias += d n;  d xh = d n weight,
+ *     d x = r (d xh - mean_C(d xh) - xh mean_C(d xh xh));  d h = W2[:C]^T d shift + W2[C:]^T d scale, d z1 = d h silu'(z1);
+ *     d W2 += [d shift ; d scale] (x) h, d b2 += [d shift ; d scale], d W1 += d z1 (x) cond, d b1 += d z1.
+ * rays and depth get no gradient.  Every output may be NULL and is then neither computed nor stored: with only dx no weight-gradient or
+ * reduce launch happens, without dx nothing of d x is computed, without dW1 and db1 the product with W2^T is left out.
+ *   - x, rays, depth, mlp_dtype, wpack, bpack, weight, bias, eps: as igs_condition3d_fwd takes them, under the same limits and stride rule.
+ *     gout [N, C, H, W] float32 contiguous.
+ *   - wpack_t, in mlp_dtype: W2^T as ONE Linear in igs_mlp_heads_fwd's tile order, ht x 2 ct tiles with ht = ceil(hidden / 32),
+ *     ct = ceil(C / 32): output j = hidden unit j, input 32 ct s + c = channel c of W2[:C] (s = 0) or of W2[C:] (s = 1), that is
+ *     M[j][32 ct s + c] = W2[s C + c][j], zero elsewhere; 2 ct ht 1024 elements.  W1^T is never needed.
+ *   - Outputs: dx [N, C, H, W] contiguous in x_dtype, rounded once; float32 row-major dW1 [hidden, 33], db1 [hidden], dW2 [2 C, hidden],
+ *     db2 [2 C], dweight [C], dbias [C] -- nn.Linear's and nn.LayerNorm's layouts.
+ *   - Numerics.  IGS_DTYPE_F32: v_mfma_f32_32x32x2_f32 everywhere, every output a float32 fma chain in a fixed order (the depth column of
+ *     d W1 runs through the same product as the other 32).  IGS_DTYPE_F16: float32 accumulation, silu', LayerNorm backward and parameter
+ *     sums; a value is rounded to half once, only as a matrix operand: cond and h as in the forward, g and g n for the product with W2^T
+ *     and for d W2, d z1 for d W1.  silu' is igs_mlp_heads_bwd's clamped evaluation: finite inputs give finite results.
+ *   - No float atomics: per-slice partials in pixel order, then a reduce launch in slice order; two runs agree bit for bit, and d x of an
+ *     image depends on no other image.  A NaN in x or a ray of one pixel makes that pixel's d x NaN and leaves every other pixel's d x as
+ *     it was; the parameter gradients become NaN.
+ *   - scratch: as many bytes as igs_condition3d_bwd_scratch_bytes returns for these sizes (-1: out of range), aligned to 16.  The pixels are
+ *     walked in chunks of IGS_COND_BWD_CHUNK_ROWS rows (a row is a lane of a 32-pixel group of one image, so an image takes
+ *     32 ceil(H W / 32) rows): 7 float32 [rows][128] slots of one chunk plus at most IGS_COND_BWD_CHUNK_ROWS / 256 partials of the
+ *     parameter gradients.  Above one chunk the size does not depend on N, H, W.
+ *   - Refused with IGS_RAST_E_INVALID and a message before any HIP call: what igs_condition3d_fwd refuses, a misaligned output, wpack_t or
+ *     scratch, scratch_bytes below the required size.  N == 0 returns 0 without a launch (the caller zero-fills). */
+#define IGS_COND_BWD_CHUNK_ROWS 16384
+long long igs_condition3d_bwd_scratch_bytes(int N, int C, int hidden, int H, int W);
+int igs_condition3d_bwd(void* stream, int N, int C, int hidden, int H, int W, int Hd, int Wd, int x_dtype, const void* x, long long xs_n,
+                        long long xs_c, long long xs_h, long long xs_w, const float* rays, const float* depth, int mlp_dtype, const void* wpack,
+                        const void* wpack_t, const float* bpack, const float* weight, const float* bias, float eps, const float* gout,
+                        void* scratch, long long scratch_bytes, void* dx, float* dW1, float* db1, float* dW2, float* db2, float* dweight,
+                        float* dbias);
+
 /* The 2x bilinear upsample and the 3x3 convolution of the motion features in one launch (upconv.hip; DESIGN.md section 25;
  * igs/IGS.py:132-134 with up_sample True).  For x [N, Cin, H, W]:
  *     up[n, c, Y, X]  = the bilinear sample of x[n, c] at ((Y + 0.5) / 2 - 0.5, (X + 0.5) / 2 - 0.5), the source clamped at 0 and the

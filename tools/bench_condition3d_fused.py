@@ -10,7 +10,15 @@ float16 features under autocast (the fused side then runs its float16 instance, 
 The last line states the gate: for float32, B = 1, forward, the fused median is below the three-step median and the min-max ranges do not
 overlap; every other case is recorded as measured.
 
-usage: python tools/bench_condition3d_fused.py [--reps 20] [--trace] [--out profiles/condition3d_fused_bench.jsonl]
+  --train    forward + backward instead: condition3d_fused_autograd (cond_fused_bwd.hip, the packs kept as the training binder keeps them)
+             against condition3d forward + backward, the training path without it, with gradients to the features, the MLP's parameters
+             and the LayerNorm's affine; N = 4 and N = 16 views, float32 and float16 features under autocast; case "fwd_bwd", sides
+             "fused_autograd" | "three_step", "peak_mb" the rise of max_memory_allocated over one forward + backward.  The last line
+             ("train_gate") states per dtype whether the native median is below the three-step median with disjoint min-max ranges at
+             N = 16: the rule COND_FUSED_BWD_NATIVE follows.  With --out the lines replace the file's earlier fwd_bwd lines and leave
+             the forward's lines as they are.
+
+usage: python tools/bench_condition3d_fused.py [--reps 20] [--trace] [--train] [--out profiles/condition3d_fused_bench.jsonl]
   --trace: 3 calls per fused case and no timing (for a rocprofv3 --kernel-trace --stats run)
 """
 import argparse
@@ -29,13 +37,78 @@ import torch  # noqa: E402
 from bench_condition3d import peak, timed_pair  # noqa: E402
 
 
+def train(args):
+    import condition3d_restatement as CR
+    from igs_amd import motion
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    V, C, H, W, Hd, Wd = 4, 128, 128, 128, 1014, 1352
+    module = CR.AdaLNModule(C).to(dev)
+    lines, verdicts = [], {}
+    for B in (1, 4):
+        N = B * V
+        rays = torch.cat([torch.randn(B, V, H, W, 3, generator=g), torch.randn(B, V, H, W, 3, generator=g) * 1.7], -1).to(dev)
+        depth = (1.0 + 5.0 * torch.rand(B, V, Hd, Wd, generator=g)).to(dev)
+        gout = torch.randn(N, C, H, W, generator=g).to(dev)
+        for dt in (torch.float32, torch.float16):
+            x = torch.randn(N, C, H, W, generator=g).to(dt).to(dev).requires_grad_(True)
+            cast = (lambda: torch.autocast("cuda", dtype=torch.float16)) if dt == torch.float16 else contextlib.nullcontext
+            sides = dict(fused_autograd=lambda f, dt=dt: motion.condition3d_fused_autograd(f, rays, depth, module, mlp_dtype=dt),
+                         three_step=lambda f: motion.condition3d(f, rays, depth, module))
+
+            def make(side, x=x, cast=cast, sides=sides, gout=gout):
+                fn = sides[side]
+
+                def fwd_bwd():
+                    x.grad = None
+                    module.zero_grad(set_to_none=True)
+                    with cast():
+                        out = fn(x)
+                    out.backward(gout)
+
+                return fwd_bwd
+
+            fa, fb = make("fused_autograd"), make("three_step")
+            if args.trace:
+                for _ in range(3):
+                    fa()
+                torch.cuda.synchronize()
+                continue
+            ra, rb = timed_pair(fa, fb, args.reps)
+            case = dict(N=N, dtype=str(dt).replace("torch.", ""), C=C, H=H, W=W, case="fwd_bwd")
+            for side, r, fn in (("fused_autograd", ra, fa), ("three_step", rb, fb)):
+                lines.append(dict(case, side=side, ms=round(r[0], 4), ms_min=round(r[1], 4), ms_max=round(r[2], 4), reps=args.reps,
+                                  peak_mb=round(peak(fn), 1)))
+                print(json.dumps(lines[-1]), flush=True)
+            if N == 16:
+                verdicts[case["dtype"]] = dict(faster=bool(ra[0] < rb[0]), disjoint=bool(ra[2] < rb[1]), speedup=round(rb[0] / ra[0], 2),
+                                               native=bool(ra[0] < rb[0] and ra[2] < rb[1]))
+            del x
+    if not args.trace:
+        lines.append(dict(case="train_gate", N=16, verdicts=verdicts))
+        print(json.dumps(lines[-1]), flush=True)
+    if args.out and lines:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        kept = []
+        if os.path.exists(args.out):
+            kept = [ln for ln in open(args.out).read().splitlines() if ln.strip() and json.loads(ln).get("case") not in ("fwd_bwd", "train_gate")]
+        with open(args.out, "w") as f:
+            for ln in kept:
+                f.write(ln + "\n")
+            for ln in lines:
+                f.write(json.dumps(ln) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--train", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_condition3d_fused needs a GPU"
+    if args.train:
+        return train(args)
     import condition3d_restatement as CR
     from igs_amd import motion
     dev = torch.device("cuda:0")
@@ -94,9 +167,14 @@ def main():
         print(json.dumps(lines[-1]), flush=True)
     if args.out and lines:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        kept = []                                    # the --train lines of an earlier run stay
+        if os.path.exists(args.out):
+            kept = [ln for ln in open(args.out).read().splitlines() if ln.strip() and json.loads(ln).get("case") in ("fwd_bwd", "train_gate")]
         with open(args.out, "w") as f:
             for ln in lines:
                 f.write(json.dumps(ln) + "\n")
+            for ln in kept:
+                f.write(ln + "\n")
 
 
 if __name__ == "__main__":
