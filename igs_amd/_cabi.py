@@ -186,6 +186,10 @@ SIGNATURES = {
     # ffn.hip
     "igs_layer_tail_pack_elems": (_ll, [_i, _i]),
     "igs_layer_tail_fwd": (_i, [_vp, _ll, _i, _i, _i] + [_vp, _i, _ll] * 2 + [_vp, _vp, _vp, _f, _vp, _vp, _f] + [_vp, _i, _ll]),
+    # ffn_bwd.hip
+    "igs_layer_tail_bwd_scratch_bytes": (_ll, [_ll, _i, _i, _i]),
+    "igs_layer_tail_bwd": (_i, [_vp, _ll, _i, _i, _i] + [_vp, _i, _ll] * 3 + [_vp, _vp, _vp, _vp, _f, _vp, _vp, _f] + [_vp, _ll]
+                           + [_vp, _i, _ll] * 2 + [_vp] * 7),
     # ssim_batch.hip
     "igs_ssim_batch_scratch_bytes": (_ll, [_i] * 5),
     "igs_ssim_batch_fwd_bwd": (_i, [_vp] + [_i] * 4 + [_vp, _vp, _f, _f] + [_vp] * 5),

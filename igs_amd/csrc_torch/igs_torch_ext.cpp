@@ -25,7 +25,7 @@
 //   transformer ends    gnorm.hip               _gnorm.group_norm_tokens_fwd / _bwd, _gnorm.tokens_add_residual: [B, C, A] in, [B, A, C] out
 //   residual decoder    mlp.hip                 _mlp.mlp_heads_fwd, _mlp.pack_elems: [N, C0] rows with a row stride in, one [N, ch] per head out;
 //                                               _mlp.mlp_heads_bwd, _mlp.bwd_scratch_bytes: d x and flat float32 d w / d b from x alone
-//   layer tail          ffn.hip                 _ffn.layer_tail_fwd, _ffn.pack_elems: merge, LayerNorms and FFN of a unimatch TransformerLayer on [T, 128] rows
+//   layer tail          ffn.hip                 _ffn.layer_tail_fwd, _ffn.layer_tail_bwd, _ffn.pack_elems, _ffn.bwd_scratch_bytes: merge, LayerNorms and FFN of a unimatch TransformerLayer on [T, 128] rows
 //   deform              motion.hip              motion_deform_fwd / _bwd
 //   Adam                refine_ops.hip          adam_step_multi
 //   losses              refine_ops, loss_ops    l1_mean; ssim_mean
@@ -1528,6 +1528,70 @@ Tensor layer_tail_fwd(const Tensor& attn_out, const Tensor& source, const Tensor
     return out;
 }
 
+int64_t layer_tail_bwd_scratch_bytes(int64_t T, bool half, int64_t hidden)
+{
+    return igs_layer_tail_bwd_scratch_bytes(T, half ? IGS_DTYPE_F16 : IGS_DTYPE_F32, hidden != 0 ? 1 : 0, (int)std::min<int64_t>(hidden, INT_MAX));
+}
+// (d attn_out, d source [T, 128] contiguous, float16 when da_half / ds_half, else float32; d merge [128, 128], d ln1_w, d ln1_b [128],
+// d mlp[0] [hidden, 256], d mlp[2] [128, hidden], d ln2_w, d ln2_b [128], float32), each None unless its `want` entry is set (in that
+// order; the last four need an FFN).  attn_out, source, wpack, ln*: as layer_tail_fwd read them; wpack_t: the transposed pack; dout: [T, 128] rows
+std::vector<OptTensor> layer_tail_bwd(const Tensor& attn_out, const Tensor& source, const Tensor& dout, const Tensor& wpack, const Tensor& wpack_t,
+                                      int64_t hidden, const Tensor& ln1_w, const Tensor& ln1_b, double eps1, const OptTensor& ln2_w,
+                                      const OptTensor& ln2_b, double eps2, const std::vector<bool>& want, bool da_half, bool ds_half)
+{
+    const char* fn = "layer_tail_bwd";
+    const int adt = token_rows_check(fn, attn_out, "attn_out"), sdt = token_rows_check(fn, source, "source"), gdt = token_rows_check(fn, dout, "dout");
+    const int cdt = dtype_code(wpack, fn, "wpack");
+    const int64_t T = attn_out.size(0);
+    if (attn_out.size(1) != 128 || source.sizes() != attn_out.sizes() || dout.sizes() != attn_out.sizes())
+        throw RasterizerError(std::string(fn) + ": attn_out, source and dout must all be [T, 128] (got " + c10::str(attn_out.sizes()) + ", " +
+                              c10::str(source.sizes()) + " and " + c10::str(dout.sizes()) + ")");
+    const bool has_ffn = hidden != 0;
+    const int64_t elems = layer_tail_pack_elems(hidden, has_ffn);
+    if (hidden < 0 || elems < 0 || T > IGS_LAYER_TAIL_MAX_ROWS)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (hidden a multiple of 32 in 32.." + std::to_string(IGS_LAYER_TAIL_MAX_HIDDEN) + ", T <= 2^24)");
+    if (want.size() != 9) throw RasterizerError(std::string(fn) + ": want needs nine entries");
+    expect(wpack, fn, "wpack", wpack.scalar_type(), {elems});
+    expect(wpack_t, fn, "wpack_t", wpack.scalar_type(), {elems});
+    if (!wpack.is_contiguous() || !wpack_t.is_contiguous()) throw RasterizerError(std::string(fn) + ": wpack and wpack_t must be contiguous");
+    expect(ln1_w, fn, "ln1_w", at::kFloat, {128});
+    expect(ln1_b, fn, "ln1_b", at::kFloat, {128});
+    if (has_ffn != (ln2_w.has_value() && ln2_b.has_value())) throw RasterizerError(std::string(fn) + ": ln2_w and ln2_b go with the FFN (both or neither)");
+    token_param_check(fn, ln2_w, "ln2_w", 128);
+    token_param_check(fn, ln2_b, "ln2_b", 128);
+    const GpuCall c(attn_out, fn, "attn_out", {{source, "source"}, {dout, "dout"}, {wpack, "wpack"}, {wpack_t, "wpack_t"}, {ln1_w, "ln1_w"}, {ln1_b, "ln1_b"}});
+    if (has_ffn) same_device(attn_out, fn, {{*ln2_w, "ln2_w"}, {*ln2_b, "ln2_b"}});
+    const auto fo = attn_out.options().dtype(at::kFloat);
+    std::vector<OptTensor> out(9);
+    if (want[0]) out[0] = at::empty({T, 128}, attn_out.options().dtype(da_half ? at::kHalf : at::kFloat));
+    if (want[1]) out[1] = at::empty({T, 128}, attn_out.options().dtype(ds_half ? at::kHalf : at::kFloat));
+    if (want[2]) out[2] = at::empty({128, 128}, fo);
+    if (want[3]) out[3] = at::empty({128}, fo);
+    if (want[4]) out[4] = at::empty({128}, fo);
+    if (has_ffn) {
+        if (want[5]) out[5] = at::empty({hidden, 256}, fo);
+        if (want[6]) out[6] = at::empty({128, hidden}, fo);
+        if (want[7]) out[7] = at::empty({128}, fo);
+        if (want[8]) out[8] = at::empty({128}, fo);
+    }
+    bool any = false;
+    for (const OptTensor& t : out) any = any || t.has_value();
+    if (!any) return out;
+    const Tensor w1 = ln1_w.contiguous(), b1 = ln1_b.contiguous();
+    OptTensor w2, b2;
+    if (has_ffn) { w2 = ln2_w->contiguous(); b2 = ln2_b->contiguous(); }
+    const Tensor scratch = at::empty({layer_tail_bwd_scratch_bytes(T, cdt == IGS_DTYPE_F16, hidden)}, attn_out.options().dtype(at::kByte));
+    check(igs_layer_tail_bwd(c.stream(), T, cdt, has_ffn ? 1 : 0, (int)hidden, attn_out.data_ptr(), adt, token_row_stride(attn_out), source.data_ptr(), sdt,
+                             token_row_stride(source), dout.data_ptr(), gdt, token_row_stride(dout), wpack.data_ptr(), wpack_t.data_ptr(),
+                             w1.data_ptr<float>(), b1.data_ptr<float>(), (float)eps1, ptr_or_null<float>(w2), ptr_or_null<float>(b2), (float)eps2,
+                             scratch.data_ptr(), scratch.numel(), ptr_or_null(out[0]), da_half ? IGS_DTYPE_F16 : IGS_DTYPE_F32, 128, ptr_or_null(out[1]),
+                             ds_half ? IGS_DTYPE_F16 : IGS_DTYPE_F32, 128, ptr_or_null<float>(out[2]), ptr_or_null<float>(out[3]),
+                             ptr_or_null<float>(out[4]), ptr_or_null<float>(out[5]), ptr_or_null<float>(out[6]), ptr_or_null<float>(out[7]),
+                             ptr_or_null<float>(out[8])),
+          "igs_layer_tail_bwd");
+    return out;
+}
+
 // ---- the Gaussian deform (motion.hip) ----
 void deform_checks(const char* fn, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot, int* dt)
 {
@@ -1873,6 +1937,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     def_nogil(ff, "layer_tail_fwd", &layer_tail_fwd, "attn_out"_a, "source"_a, "wpack"_a, "hidden"_a, "ln1_w"_a, "ln1_b"_a, "eps1"_a, "ln2_w"_a = none,
               "ln2_b"_a = none, "eps2"_a = 1e-5, "out_half"_a = false);
     def_nogil(ff, "pack_elems", &layer_tail_pack_elems, "hidden"_a, "has_ffn"_a = true);
+    def_nogil(ff, "layer_tail_bwd", &layer_tail_bwd, "attn_out"_a, "source"_a, "dout"_a, "wpack"_a, "wpack_t"_a, "hidden"_a, "ln1_w"_a, "ln1_b"_a, "eps1"_a,
+              "ln2_w"_a, "ln2_b"_a, "eps2"_a, "want"_a, "da_half"_a = false, "ds_half"_a = false);
+    ff.def("bwd_scratch_bytes", &layer_tail_bwd_scratch_bytes, "T"_a, "half"_a, "hidden"_a);
     py::module_ ls = m.def_submodule("_loss", "SSIM and L1 of a batch of images: the AGM-Net training loss (ssim_batch.hip)");
     def_nogil(ls, "ssim_batch", &ssim_batch, "a"_a, "b"_a, "c_ssim"_a, "c_l1"_a, "want_grad"_a, "want_map"_a, "want_l1"_a);
 

@@ -15,6 +15,7 @@ norm2, then `source + message`, and a three-launch `is_self_attn` test whose res
     layer_tail(attn_out, source, layer)                                 everything behind the layer's attention (merge, LN1, cat, the
                                                                         GELU MLP, LN2, the residual add) as one launch, forward only
     use_native_layer_tails(feature_transformer)                         binds a forward that takes layer_tail when nothing needs a gradient
+    layer_tail_autograd(attn_out, source, layer)                        layer_tail with the recomputing native backward (ffn_bwd.hip) behind it
     group_norm_tokens(x, num_groups, weight, bias, eps)                 F.group_norm over [B, C, A] written token-major [B, A, C]: the
                                                                         statistics, then one tile-transposing launch
     add_residual_tokens(tokens, residual)                               tokens [B, A, C] + residual [B, C, A], one launch; a [B, C, A]-shaped
@@ -44,7 +45,7 @@ the figures of section 20.
 
 Not provided: norm types other than nn.GroupNorm with affine parameters at the ends of Transformer1D, gradient checkpointing and 2-D
 attention masks there, fusing proj_in / proj_out; the GELU inside the unimatch MLP (a single eager kernel
-already) and splitting the MLP's first weight to avoid the cat outside layer_tail (which does both); any backward
+already) and splitting the MLP's first weight to avoid the cat outside layer_tail (which does both); a double backward
 of layer_tail, the q / k / v projections, d_model other than 128 and biases there; bfloat16; fusing any other GEMM; the ada
 norms, cross-attention (norm2 / attn2) and the other feed-forward activations of BasicTransformerBlock; attn_type other than 'swin' and
 nhead > 1 of TransformerLayer.
@@ -353,6 +354,13 @@ LAYER_TAIL_FUSED = {torch.float32: True, torch.float16: True}
 # 0.94 x at [16384, 128] with overlapping min - max ranges, i.e. level within the timing noise; it is kept for half the peak memory
 # (merge's result is never stored) and one launch less.  float16 ones gain 1.21 - 1.24 x.
 LAYER_TAIL_FFN_MIN_FILL = {torch.float32: 0.95, torch.float16: 0.95}
+# Per compute dtype, whether a call that needs a gradient takes layer_tail_autograd (the fused forward and the recomputing backward of
+# ffn_bwd.hip) under use_native_layer_tails(training=True).  An entry is True only where the native training step's median is lower than
+# the unfused tail's under autograd and its min - max range does not lie behind it.  Measured ("The backward";
+# profiles/layer_tail_train_bench.jsonl): 0.44 x (float32) and 0.53 x (float16 autocast) at [32768, 128] with the FFN, 0.52 x and 0.77 x
+# without, 0.66 x and 0.75 x over a six-block stand-in, so both are False: the route buys memory (that stand-in trains in 1.3 GB
+# against 3.4 GB in float32) and a reproducible backward, not time.  layer_tail_autograd called directly always runs the kernels.
+LAYER_TAIL_BWD_NATIVE = {torch.float32: False, torch.float16: False}
 
 
 def _tail_spec(fn, layer):
@@ -400,11 +408,13 @@ def _tail_params(layer):
     return params
 
 
-def pack_layer_tail(layer, dtype=torch.float32):
+def pack_layer_tail(layer, dtype=torch.float32, transposed=False):
     """The weights of a layer's tail in `dtype` as igs_layer_tail_fwd takes them (include/igs_rast.h), one flat tensor of 1024-element tiles in
     pack_mlp_tile_order's per-tile layout: merge (16 tiles, output tile outermost), then with an FFN mlp[0] split by output tile (hidden / 32
     x 8 tiles) and mlp[2] with its INPUT tile outermost (hidden / 32 x 4 tiles), so that the kernel finds everything hidden units
-    32 j .. 32 j + 31 need in two contiguous pieces.  Plain tensor ops: works on any device."""
+    32 j .. 32 j + 31 need in two contiguous pieces.  transposed=True: (pack, pack_t), pack_t the transposes as igs_layer_tail_bwd takes them
+    at the same offsets: merge^T, mlp[0]^T with its INPUT tile outermost (tile 8 j + ot), mlp[2]^T with its output tile outermost (tile
+    4 j + kt).  Plain tensor ops: works on any device."""
     merge, _, l0, l2, _ = _tail_spec("pack_layer_tail", layer)
     if dtype not in DTYPES:
         raise NotImplementedError(f"pack_layer_tail: dtype must be float32 or float16 (got {dtype})")
@@ -413,11 +423,43 @@ def pack_layer_tail(layer, dtype=torch.float32):
         ht = l0.out_features // 32
         parts.append(pack_mlp_tile_order(l0.weight.detach().to(dtype)))
         parts.append(pack_mlp_tile_order(l2.weight.detach().to(dtype)).view(TAIL_D // 32, ht, -1).transpose(0, 1).reshape(-1))
-    return torch.cat(parts).contiguous()
+    pack = torch.cat(parts).contiguous()
+    if not transposed:
+        return pack
+    parts = [pack_mlp_tile_order(merge.weight.detach().to(dtype).t().contiguous())]
+    if l0 is not None:
+        parts.append(pack_mlp_tile_order(l0.weight.detach().to(dtype).t().contiguous()).view(2 * TAIL_D // 32, ht, -1).transpose(0, 1).reshape(-1))
+        parts.append(pack_mlp_tile_order(l2.weight.detach().to(dtype).t().contiguous()))
+    return pack, torch.cat(parts).contiguous()
 
 
 def _tail_compute_dtype(fn, attn_out):
     return torch.float16 if autocast_half(fn, attn_out) or attn_out.dtype == torch.float16 else torch.float32
+
+
+def _tail_checks(fn, attn_out, source, layer, packed, packed_t, compute_dtype, forward_only):
+    """The refusals of layer_tail and layer_tail_autograd, in one order; returns _tail_spec's tuple and the compute dtype."""
+    merge, n1, l0, l2, n2 = _tail_spec(fn, layer)
+    if attn_out.dim() < 1 or attn_out.shape[-1] != TAIL_D or tuple(source.shape) != tuple(attn_out.shape):
+        raise ValueError(f"{fn}: attn_out and source must both be [..., {TAIL_D}] (got {list(attn_out.shape)} and {list(source.shape)})")
+    if attn_out.numel() // TAIL_D > TAIL_MAX_ROWS:
+        raise ValueError(f"{fn}: {attn_out.numel() // TAIL_D} rows is above the supported {TAIL_MAX_ROWS}")
+    params = _tail_params(layer)
+    named = [(attn_out, "attn_out"), (source, "source")] + [(p, "a parameter") for p in params]
+    for t, name in named[:2]:
+        if t.dtype not in DTYPES:
+            raise NotImplementedError(f"{fn}: {name} must be float32 or float16 (got {t.dtype})")
+    if forward_only and torch.is_grad_enabled() and any(t.requires_grad for t, _ in named):
+        raise NotImplementedError(f"{fn}: forward only -- call it under torch.no_grad(), and train with use_native_transformer_layers")
+    if compute_dtype is None:
+        compute_dtype = _tail_compute_dtype(fn, attn_out)
+    if compute_dtype not in DTYPES:
+        raise NotImplementedError(f"{fn}: compute_dtype must be float32 or float16 (got {compute_dtype})")
+    for pk in (packed, packed_t):
+        if pk is not None and pk.dtype != compute_dtype:
+            raise ValueError(f"{fn}: packed holds {pk.dtype} weights, compute_dtype is {compute_dtype}")
+    _refuse(fn, named)
+    return merge, n1, l0, l2, n2, compute_dtype
 
 
 def layer_tail(attn_out, source, layer, packed=None, compute_dtype=None):
@@ -432,31 +474,70 @@ def layer_tail(attn_out, source, layer, packed=None, compute_dtype=None):
     grad, for a Linear with a bias, an mlp that is not Sequential(Linear, GELU(approximate='none'), Linear), d_model other than 128, a
     hidden that is not a multiple of 32 in 32..2048, and bfloat16 / float64; RuntimeError for CPU tensors; ValueError for shapes."""
     fn = "layer_tail"
-    merge, n1, l0, l2, n2 = _tail_spec(fn, layer)
-    if attn_out.dim() < 1 or attn_out.shape[-1] != TAIL_D or tuple(source.shape) != tuple(attn_out.shape):
-        raise ValueError(f"{fn}: attn_out and source must both be [..., {TAIL_D}] (got {list(attn_out.shape)} and {list(source.shape)})")
-    if attn_out.numel() // TAIL_D > TAIL_MAX_ROWS:
-        raise ValueError(f"{fn}: {attn_out.numel() // TAIL_D} rows is above the supported {TAIL_MAX_ROWS}")
-    params = _tail_params(layer)
-    named = [(attn_out, "attn_out"), (source, "source")] + [(p, "a parameter") for p in params]
-    for t, name in named[:2]:
-        if t.dtype not in DTYPES:
-            raise NotImplementedError(f"{fn}: {name} must be float32 or float16 (got {t.dtype})")
-    if torch.is_grad_enabled() and any(t.requires_grad for t, _ in named):
-        raise NotImplementedError(f"{fn}: forward only -- call it under torch.no_grad(), and train with use_native_transformer_layers")
-    if compute_dtype is None:
-        compute_dtype = _tail_compute_dtype(fn, attn_out)
-    if compute_dtype not in DTYPES:
-        raise NotImplementedError(f"{fn}: compute_dtype must be float32 or float16 (got {compute_dtype})")
-    if packed is not None and packed.dtype != compute_dtype:
-        raise ValueError(f"{fn}: packed holds {packed.dtype} weights, compute_dtype is {compute_dtype}")
-    _refuse(fn, named)
+    merge, n1, l0, l2, n2, compute_dtype = _tail_checks(fn, attn_out, source, layer, packed, None, compute_dtype, True)
     if packed is None:
         packed = pack_layer_tail(layer, compute_dtype)
     out_dtype = _autocast_out_dtype(torch.promote_types(attn_out.dtype, source.dtype))
     ln2 = (None, None, 1e-5) if n2 is None else (n2.weight.detach().float(), n2.bias.detach().float(), float(n2.eps))
     out = _ext()._ffn.layer_tail_fwd(_rows(attn_out.detach()), _rows(source.detach()), packed, 0 if l0 is None else l0.out_features,
                                      n1.weight.detach().float(), n1.bias.detach().float(), float(n1.eps), *ln2, out_dtype == torch.float16)
+    return out.view(attn_out.shape)
+
+
+class _LayerTail(torch.autograd.Function):
+    """igs_layer_tail_fwd with igs_layer_tail_bwd behind it.  Saves attn_out and source as the kernel read them, the two packs and the
+    LayerNorms' affines: neither merge's result, the cat, the hidden activations, mlp's result nor any statistics."""
+
+    @staticmethod
+    def forward(ctx, a, s, wm, ln1w, ln1b, w1, w2, ln2w, ln2b, pack, pack_t, hidden, eps1, eps2, out_half):
+        ctx.set_materialize_grads(False)
+        f1w, f1b = ln1w.detach().float(), ln1b.detach().float()
+        f2w, f2b = (None, None) if ln2w is None else (ln2w.detach().float(), ln2b.detach().float())
+        ctx.save_for_backward(a, s, pack, pack_t, f1w, f1b, f2w, f2b)
+        ctx.hidden, ctx.eps1, ctx.eps2 = hidden, eps1, eps2
+        ctx.param_dtypes = [None if t is None else t.dtype for t in (wm, ln1w, ln1b, w1, w2, ln2w, ln2b)]
+        return _ext()._ffn.layer_tail_fwd(a, s, pack, hidden, f1w, f1b, eps1, f2w, f2b, eps2, out_half)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 15
+        a, s, pack, pack_t, f1w, f1b, f2w, f2b = ctx.saved_tensors
+        if g.dtype not in DTYPES:
+            g = g.float()
+        want = [bool(n) and (i < 5 or ctx.hidden != 0) for i, n in enumerate(ctx.needs_input_grad[:9])]
+        grads = list(_ext()._ffn.layer_tail_bwd(a, s, _rows(g), pack, pack_t, ctx.hidden, f1w, f1b, ctx.eps1, f2w, f2b, ctx.eps2, want,
+                                                a.dtype == torch.float16, s.dtype == torch.float16))
+        for i, dt in enumerate(ctx.param_dtypes):                  # accumulated in float32, cast once
+            if grads[i + 2] is not None and grads[i + 2].dtype != dt:
+                grads[i + 2] = grads[i + 2].to(dt)
+        return (*grads, None, None, None, None, None, None)
+
+
+def layer_tail_autograd(attn_out, source, layer, packed=None, packed_t=None, compute_dtype=None):
+    """layer_tail for training: the same checks, sizes, dtypes and value, and a native backward.  When grad is disabled or neither an input
+    nor a parameter of the tail requires it this IS the forward kernel alone.  Otherwise the forward is igs_layer_tail_fwd and the backward
+    igs_layer_tail_bwd (ffn_bwd.hip), which recomputes the forward chunk by chunk: gradients for attn_out and source in their dtypes and
+    for merge.weight, norm1.weight / bias, mlp[0].weight, mlp[2].weight and norm2.weight / bias, accumulated in float32 and cast once to
+    each parameter's dtype.  Saved: attn_out and source as the kernel read them (themselves where their rows have stride 1), the two packs
+    and the LayerNorms' affines.  Once differentiable, deterministic (no atomics).  packed, packed_t: pack_layer_tail(layer,
+    compute_dtype, transposed=True), packed here when either is absent.  Refusals as layer_tail's, except that gradients are served."""
+    fn = "layer_tail_autograd"
+    merge, n1, l0, l2, n2, compute_dtype = _tail_checks(fn, attn_out, source, layer, packed, packed_t, compute_dtype, False)
+    if packed is None or packed_t is None:
+        packed, packed_t = pack_layer_tail(layer, compute_dtype, transposed=True)
+    out_half = _autocast_out_dtype(torch.promote_types(attn_out.dtype, source.dtype)) == torch.float16
+    hidden = 0 if l0 is None else l0.out_features
+    a, s = _rows(attn_out), _rows(source)
+    ffn = (None,) * 4 if l0 is None else (l0.weight, l2.weight, n2.weight, n2.bias)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (a, s, merge.weight, n1.weight, n1.bias) + ffn):
+        out = _LayerTail.apply(a, s, merge.weight, n1.weight, n1.bias, *ffn, packed, packed_t, hidden, float(n1.eps),
+                               1e-5 if n2 is None else float(n2.eps), out_half)
+    else:
+        ln2 = (None, None, 1e-5) if n2 is None else (n2.weight.detach().float(), n2.bias.detach().float(), float(n2.eps))
+        out = _ext()._ffn.layer_tail_fwd(a.detach(), s.detach(), packed, hidden, n1.weight.detach().float(), n1.bias.detach().float(),
+                                         float(n1.eps), *ln2, out_half)
     return out.view(attn_out.shape)
 
 
@@ -476,27 +557,55 @@ def _tail_fill(attn_out):
     return rows / float(-(-trips // groups) * groups * TAIL_TRIP_ROWS)
 
 
+def _tail_entry(layer, dtype, params, transposed):
+    """The layer's cached pack(s) for a compute dtype, rebuilt when a parameter changed (param_key)."""
+    key = param_key(params)
+    cache = layer.__dict__.setdefault(TAIL_CACHE, {})                            # one entry per compute dtype
+    entry = cache.get(dtype)
+    if entry is None or entry["key"] != key:
+        entry = cache[dtype] = dict(key=key)
+    if transposed and "pack_t" not in entry:
+        entry["pack"], entry["pack_t"] = pack_layer_tail(layer, dtype, transposed=True)
+    elif "pack" not in entry:
+        entry["pack"] = pack_layer_tail(layer, dtype)
+    return entry
+
+
 def _layer_tail_forward(self, source, target, height=None, width=None, shifted_window_attn_mask=None, shifted_window_attn_mask_1d=None,
                         attn_type="swin", with_shift=False, attn_num_splits=None):
     """TransformerLayer.forward as use_native_layer_tails binds it: _layer_forward's projections and attention, then layer_tail when
     nothing needs a gradient (and LAYER_TAIL_FUSED and LAYER_TAIL_FFN_MIN_FILL take the call), _layer_forward's own tail otherwise."""
+    return _layer_tail_route(self, False, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits)
+
+
+def _layer_tail_forward_training(self, source, target, height=None, width=None, shifted_window_attn_mask=None, shifted_window_attn_mask_1d=None,
+                                 attn_type="swin", with_shift=False, attn_num_splits=None):
+    """_layer_tail_forward as use_native_layer_tails(training=True) binds it: a call that needs a gradient takes layer_tail_autograd where
+    LAYER_TAIL_BWD_NATIVE says so (a layer with FFN still held to LAYER_TAIL_FFN_MIN_FILL), the unfused tail otherwise."""
+    return _layer_tail_route(self, True, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits)
+
+
+def _layer_tail_route(self, training, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits):
     fn = "TransformerLayer"
     message = _layer_message(self, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits)
     params = _tail_params(self)
-    if torch.is_grad_enabled() and any(t.requires_grad for t in [message, source] + params):
+    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in [message, source] + params)
+    if needs_grad and not training:
         return _layer_tail_unfused(self, message, source)
     dtype = _tail_compute_dtype(fn, message)
-    if not LAYER_TAIL_FUSED[dtype] or (not getattr(self, LAYER_NO_FFN) and _tail_fill(message) < LAYER_TAIL_FFN_MIN_FILL[dtype]):
+    if needs_grad and not LAYER_TAIL_BWD_NATIVE[dtype]:
         return _layer_tail_unfused(self, message, source)
-    key = param_key(params)
-    cache = self.__dict__.setdefault(TAIL_CACHE, {})                             # one pack per compute dtype
-    entry = cache.get(dtype)
-    if entry is None or entry["key"] != key:
-        entry = cache[dtype] = dict(key=key, pack=pack_layer_tail(self, dtype))
+    if not needs_grad and not LAYER_TAIL_FUSED[dtype]:
+        return _layer_tail_unfused(self, message, source)
+    if not getattr(self, LAYER_NO_FFN) and _tail_fill(message) < LAYER_TAIL_FFN_MIN_FILL[dtype]:
+        return _layer_tail_unfused(self, message, source)
+    entry = _tail_entry(self, dtype, params, needs_grad)
+    if needs_grad:
+        return layer_tail_autograd(message, source, self, packed=entry["pack"], packed_t=entry["pack_t"], compute_dtype=dtype)
     return layer_tail(message, source, self, packed=entry["pack"], compute_dtype=dtype)
 
 
-def use_native_layer_tails(module):
+def use_native_layer_tails(module, training=False):
     """Binds a forward on every unimatch TransformerLayer under `module` (found as use_native_transformer_layers finds them) that does the
     three projections and the attention lookup as that binder's forward does and then, when nothing needs a gradient, runs the whole tail
     as one launch (layer_tail); with grad enabled and anything requiring it, the tail is use_native_transformer_layers' own, with autograd.
@@ -508,13 +617,18 @@ def use_native_layer_tails(module):
     float16 under autocast to half or when the attention's output is half, float32 otherwise; the result has the dtype of the unfused bound
     forward.  Raises NotImplementedError, before anything is changed, for everything use_native_transformer_layers refuses and for
     everything layer_tail refuses about a layer (biases, another mlp, d_model other than 128, hidden out of range, bfloat16 / float64
-    parameters)."""
+    parameters).
+    training=True: a call that needs a gradient goes to layer_tail_autograd (the fused forward with the recomputing native backward of
+    ffn_bwd.hip behind it) for the compute dtypes that LAYER_TAIL_BWD_NATIVE turns on, a layer with FFN still held to
+    LAYER_TAIL_FFN_MIN_FILL; everything else is routed as with the default.  The transposed pack is cached beside the pack, per compute
+    dtype, and both are rebuilt after every optimiser step (a parameter's _version changes)."""
     fn = "use_native_layer_tails"
     layers = _checked_layers(fn, module)
     for m in layers:
         _tail_spec(fn, m)
+    bound = _layer_tail_forward_training if training else _layer_tail_forward
     for m in layers:
-        m.forward = types.MethodType(_layer_tail_forward, m)
+        m.forward = types.MethodType(bound, m)
     return len(layers)
 
 

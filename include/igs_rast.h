@@ -1203,6 +1203,54 @@ int igs_layer_tail_fwd(void* stream, long long T, int compute_dtype, int has_ffn
                        const void* s, int s_dtype, long long s_stride, const void* wpack, const float* ln1_w, const float* ln1_b, float eps1,
                        const float* ln2_w, const float* ln2_b, float eps2, void* out, int out_dtype, long long out_stride);
 
+/* The backward of igs_layer_tail_fwd (ffn_bwd.hip; DESIGN.md section 27, "The backward"): the forward is recomputed from a and s, nothing of
+ * T rows is kept between the two but the inputs.  Per row, with g = d out, xh = (v - mean) rstd of each LayerNorm and Phi, phi the normal
+ * distribution and density:
+ *     FFN:     d ln2_w = sum_t g xh2;  d ln2_b = sum_t g;  q = g ln2_w;  dy = r2 (q - mean q - xh2 mean(q xh2));  d W2 = sum_t dy h^T;
+ *              dh = W2^T dy;  dz = dh (Phi(z) + z phi(z));  d W1 = sum_t dz [s ; n1]^T;  du = W1^T dz;  ds = g + du[0:128];  dn1 = du[128:256]
+ *     no FFN:  ds = g;  dn1 = g
+ *     both:    d ln1_w = sum_t dn1 xh1;  d ln1_b = sum_t dn1;  p = dn1 ln1_w;  dm = r1 (p - mean p - xh1 mean(p xh1));
+ *              d Wm = sum_t dm a^T;  da = Wm^T dm
+ * Runs on `stream`, reads nothing back, allocates nothing.  No float atomics in memory or LDS; every sum has a fixed order (the rows of a
+ * slice of 512, chunk after chunk, then the slices), two runs agree bit for bit on every output, and a row's da and ds depend on that row
+ * of a, s, g and on the weights only (not on T, on the row's position or on the other rows): a NaN in a row makes that row's da / ds NaN,
+ * leaves every other row's bits as they were, and makes the parameter gradients NaN.  GELU' is finite for every finite z.
+ *   - T, compute_dtype, has_ffn, hidden, a, s, wpack, ln1_*, ln2_*, eps1, eps2 as igs_layer_tail_fwd takes them (s is not read, and may be
+ *     NULL, without FFN).  g: d out, [T, 128] with its own dtype code and row stride.
+ *   - wpack_t, in compute_dtype, 16-byte aligned, igs_layer_tail_pack_elems(hidden, has_ffn) elements: the TRANSPOSES in wpack's per-tile
+ *     layout (element e = chunk E + j of lane (r, h) of tile (ot, kt) of a matrix M is M[32 ot + r][32 kt + (e & 3) + 8 (e >> 2) + 4 h]):
+ *       Wm^T [128, 128]:      16 tiles, output tile outermost: tile 4 ot + kt;
+ *       W1^T [256, hidden]:   hidden / 32 x 8 tiles, INPUT tile outermost: tile 8 j + ot (has_ffn only);
+ *       W2^T [hidden, 128]:   hidden / 32 x 4 tiles, output tile outermost: tile 4 j + kt (has_ffn only),
+ *     so that, as in wpack, the 12 tiles of hidden units 32 j .. 32 j + 31 are two contiguous pieces at the same offsets.
+ *   - Every output may be NULL; every element of a non-NULL output is written; with all of them NULL nothing is launched.  da and ds:
+ *     [T, 128], each with a dtype code and a row stride like the forward's out (rounded once on store); da's product is skipped when da is
+ *     NULL.  d Wm [128, 128], d ln1_w, d ln1_b [128], d W1 [hidden, 256], d W2 [128, hidden], d ln2_w, d ln2_b [128]: float32 whatever the
+ *     dtypes, row-major as nn.Linear and nn.LayerNorm keep them; the last four are not written without FFN.  When no parameter gradient
+ *     is wanted, the stores that only the weight gradients read and the weight-gradient launches are skipped.
+ *   - compute_dtype IGS_DTYPE_F32: v_mfma_f32_32x32x2_f32 everywhere, no half value anywhere.  IGS_DTYPE_F16: v_mfma_f32_32x32x16_f16 with
+ *     float32 accumulation; a value is rounded to half once, only as a matrix operand: a, [s ; n1] and h as in the forward, dy, dz and dm
+ *     for their two products each.  The LayerNorm backwards, GELU' and all parameter sums are float32; the residual part of ds reads g itself.
+ *   - T is walked in chunks of IGS_LAYER_TAIL_BWD_CHUNK_ROWS rows.  scratch: igs_layer_tail_bwd_scratch_bytes(T, compute_dtype, has_ffn,
+ *     hidden) bytes (-1 for sizes out of range), 16-byte aligned, not initialised by the caller: one chunk's spilled values as float32
+ *     (per row 2 hidden + 1152 values with FFN, 512 without) and the slices' partial sums, so it does not grow with T above one chunk.
+ *     The launches: per chunk one over the rows and, when a parameter gradient is wanted, one for the weight gradients; then one reduction.
+ *   - Refused with IGS_RAST_E_INVALID and a message naming igs_layer_tail_bwd before any HIP call: everything igs_layer_tail_fwd refuses
+ *     about codes, T, hidden, strides and eps (g, da and ds included); a parameter gradient not aligned to 4 bytes; with T > 0 a NULL a,
+ *     g, wpack, wpack_t, ln1_w, ln1_b or scratch (with FFN also s, ln2_w, ln2_b), an a, s, g, da or ds not aligned to its element size, a
+ *     wpack, wpack_t or scratch not aligned to 16 bytes, a scratch_bytes below the needed size, a da or ds that overlaps a, s or g.
+ *     T == 0 zero-fills the parameter gradients that are given and launches nothing else. */
+#ifndef IGS_LAYER_TAIL_BWD_CHUNK_ROWS              /* (a build may choose another multiple of 512: DESIGN.md section 27 has the table) */
+#define IGS_LAYER_TAIL_BWD_CHUNK_ROWS 8192
+#endif
+long long igs_layer_tail_bwd_scratch_bytes(long long T, int compute_dtype, int has_ffn, int hidden);
+int igs_layer_tail_bwd(void* stream, long long T, int compute_dtype, int has_ffn, int hidden, const void* a, int a_dtype, long long a_stride,
+                       const void* s, int s_dtype, long long s_stride, const void* g, int g_dtype, long long g_stride, const void* wpack,
+                       const void* wpack_t, const float* ln1_w, const float* ln1_b, float eps1, const float* ln2_w, const float* ln2_b,
+                       float eps2, void* scratch, long long scratch_bytes, void* da, int da_dtype, long long da_stride, void* ds,
+                       int ds_dtype, long long ds_stride, float* dWm, float* dln1_w, float* dln1_b, float* dW1, float* dW2, float* dln2_w,
+                       float* dln2_b);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).

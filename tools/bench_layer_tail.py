@@ -22,7 +22,15 @@ The tool sets no time limit of its own.  --case is the unit to run under one: ea
       && timeout -k 10 300 python tools/bench_layer_tail.py --case transformer --out transformer.jsonl
 and profiles/layer_tail_bench.jsonl is the two files one after the other.
 
-usage: python tools/bench_layer_tail.py [--reps 20] [--case tail|transformer|all] [--out FILE]
+--train times a training step instead (profiles/layer_tail_train_bench.jsonl): the forward plus backward() of the same modules with every
+.grad reset before the step, the inputs and the parameters of the tail requiring grad.
+                 native   layer_tail_autograd (tail) / use_native_layer_tails(training=True) with LAYER_TAIL_BWD_NATIVE forced on and the
+                          fill rule off (transformer): the fused forward, the recomputing backward of ffn_bwd.hip
+                 unfused  today's training path: use_native_transformer_layers' tail under autograd
+The native tail steps run on packs made once; what a step after an optimiser update adds is timed on its own as side "repack" (both
+packs of pack_layer_tail(..., transposed=True)).  peak_mb is the step's peak above the operands, the forward's saved tensors included.
+
+usage: python tools/bench_layer_tail.py [--reps 20] [--case tail|transformer|all] [--train] [--out FILE]
 """
 import argparse
 import json
@@ -73,6 +81,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--case", default="all", choices=("tail", "transformer", "all"))
+    ap.add_argument("--train", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_layer_tail needs a GPU"
@@ -97,7 +106,53 @@ def main():
             m = layer.norm2(layer.mlp(torch.cat([s, m], dim=-1)))
         return s + m
 
-    if args.case in ("tail", "all"):
+    def step(module_params, fn, inputs):
+        """One training step: .grad reset, forward, backward() of the sum against a fixed upstream gradient."""
+        for p in module_params:
+            p.grad = None
+        leaves = [t.detach().requires_grad_(True) for t in inputs]
+        out = fn(*leaves)
+        out = out if torch.is_tensor(out) else torch.cat(list(out), 0)
+        out.backward(torch.ones_like(out))
+        return None
+
+    if args.train and args.case in ("tail", "all"):
+        for half in (False, True):
+            adt = torch.float16 if half else torch.float32
+            cdt = adt
+            for T in (32768, 16384):
+                ring = Ring(lambda i: (torch.randn(T, 128, device=dev).to(adt), torch.randn(T, 128, device=dev)), T * 128 * (4 + (2 if half else 4)))
+                for no_ffn in (False, True):
+                    layer = TR.make_layer(128, no_ffn=no_ffn, seed=1).to(dev)
+                    params = TK._tail_params(layer)
+                    pack, pack_t = TK.pack_layer_tail(layer, cdt, transposed=True)
+                    case = dict(case="tail", mode="train", shape=[T, 128], dtype="float16 (autocast)" if half else "float32", has_ffn=not no_ffn)
+                    native = lambda: step(params, lambda a, s: TK.layer_tail_autograd(a, s, layer, packed=pack, packed_t=pack_t, compute_dtype=cdt), ring.next())
+                    unfused = lambda: step(params, lambda a, s: TK._layer_tail_unfused(layer, a, s), ring.next())
+                    repack = lambda: TK.pack_layer_tail(layer, cdt, transposed=True)
+                    with torch.autocast("cuda", dtype=torch.float16, enabled=half):
+                        record(case, ("native", "unfused", "repack"), [native, unfused, repack])
+                    verdicts.pop()                                     # (the repack is a part of a step, not a rival)
+                del ring
+                torch.cuda.empty_cache()
+
+    if args.train and args.case in ("transformer", "all"):
+        assert AT.use_native_window_attention(TR) == 2
+        TK.LAYER_TAIL_BWD_NATIVE = {torch.float32: True, torch.float16: True}
+        TK.LAYER_TAIL_FFN_MIN_FILL = {torch.float32: 0.0, torch.float16: 0.0}
+        models = [StandInTransformer().to(dev) for _ in range(2)]
+        models[1].load_state_dict(models[0].state_dict())
+        assert TK.use_native_layer_tails(models[0], training=True) == 12 and TK.use_native_transformer_layers(models[1]) == 12
+        ring = Ring(lambda i: (torch.randn(4, 4096, 128, device=dev), torch.randn(4, 4096, 128, device=dev)), 2 * 4 * 4096 * 128 * 4)
+        import window_attention_restatement as WR
+        kw = dict(height=64, width=64, attn_num_splits=2, shifted_window_attn_mask=WR.paint_mask(64, 64, 2).float().to(dev))
+        for half in (False, True):
+            case = dict(case="transformer", mode="train", shape=[8, 4096, 128], dtype="float16 (autocast)" if half else "float32", has_ffn=True)
+            fns = [lambda m=m: step(list(m.parameters()), lambda f0, f1: m(f0, f1, **kw), ring.next()) for m in models]
+            with torch.autocast("cuda", dtype=torch.float16, enabled=half):
+                record(case, ("native", "unfused"), fns)
+
+    if not args.train and args.case in ("tail", "all"):
         for half in (False, True):
             adt = torch.float16 if half else torch.float32
             for T in (32768, 16384):
@@ -125,7 +180,7 @@ def main():
                 del ring
                 torch.cuda.empty_cache()
 
-    if args.case in ("transformer", "all"):
+    if not args.train and args.case in ("transformer", "all"):
         assert AT.use_native_window_attention(TR) == 2
         models = [StandInTransformer().to(dev) for _ in range(2)]
         models[1].load_state_dict(models[0].state_dict())
