@@ -190,6 +190,9 @@ SIGNATURES = {
     "igs_layer_tail_bwd_scratch_bytes": (_ll, [_ll, _i, _i, _i]),
     "igs_layer_tail_bwd": (_i, [_vp, _ll, _i, _i, _i] + [_vp, _i, _ll] * 3 + [_vp, _vp, _vp, _vp, _f, _vp, _vp, _f] + [_vp, _ll]
                            + [_vp, _i, _ll] * 2 + [_vp] * 7),
+    # proj.hip
+    "igs_token_proj_pack_elems": (_ll, [_i]),
+    "igs_token_proj_fwd": (_i, [_vp, _ll, _i, _i] + [_vp, _i, _ll] + [_vp, _vp] + [_vp, _i, _ll]),
     # ssim_batch.hip
     "igs_ssim_batch_scratch_bytes": (_ll, [_i] * 5),
     "igs_ssim_batch_fwd_bwd": (_i, [_vp] + [_i] * 4 + [_vp, _vp, _f, _f] + [_vp] * 5),

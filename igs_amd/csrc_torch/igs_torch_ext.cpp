@@ -26,6 +26,7 @@
 //   residual decoder    mlp.hip                 _mlp.mlp_heads_fwd, _mlp.pack_elems: [N, C0] rows with a row stride in, one [N, ch] per head out;
 //                                               _mlp.mlp_heads_bwd, _mlp.bwd_scratch_bytes: d x and flat float32 d w / d b from x alone
 //   layer tail          ffn.hip                 _ffn.layer_tail_fwd, _ffn.layer_tail_bwd, _ffn.pack_elems, _ffn.bwd_scratch_bytes: merge, LayerNorms and FFN of a unimatch TransformerLayer on [T, 128] rows
+//   projections         proj.hip                _proj.token_proj_fwd, _proj.pack_elems: up to five 128 -> 128 projections of [T, 128] rows side by side in one [T, 128 n] buffer
 //   deform              motion.hip              motion_deform_fwd / _bwd
 //   Adam                refine_ops.hip          adam_step_multi
 //   losses              refine_ops, loss_ops    l1_mean; ssim_mean
@@ -1592,6 +1593,37 @@ std::vector<OptTensor> layer_tail_bwd(const Tensor& attn_out, const Tensor& sour
     return out;
 }
 
+// ---- the q / k / v projections of the unimatch TransformerLayers in one launch (proj.hip; contract in include/igs_rast.h) ----
+int64_t token_proj_pack_elems(int64_t n) { return igs_token_proj_pack_elems((int)std::max<int64_t>(std::min<int64_t>(n, INT_MAX), INT_MIN)); }
+// out [T, 128 n] contiguous, float16 when out_half, else float32: columns 128 j .. of row (t + rot[j]) mod T are W_j x[t].  x: [T, 128] rows
+// (token_rows_check), float32 / float16; wpack in the compute dtype as igs_token_proj_fwd takes it (igs_amd/tokens.py packs and caches it);
+// rot: n values in [0, T), or empty for zeros
+Tensor token_proj_fwd(const Tensor& x, const Tensor& wpack, int64_t n, const std::vector<int64_t>& rot, bool out_half)
+{
+    const char* fn = "token_proj_fwd";
+    const int xdt = token_rows_check(fn, x, "x");
+    const int cdt = dtype_code(wpack, fn, "wpack");
+    const int64_t T = x.size(0);
+    if (x.size(1) != 128) throw RasterizerError(std::string(fn) + ": x must be [T, 128] (got " + c10::str(x.sizes()) + ")");
+    const int64_t elems = token_proj_pack_elems(n);
+    if (elems < 0 || T > IGS_TOKEN_PROJ_MAX_ROWS)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (n in 1.." + std::to_string(IGS_TOKEN_PROJ_MAX_OUT) + ", T <= 2^24)");
+    expect(wpack, fn, "wpack", wpack.scalar_type(), {elems});
+    if (!wpack.is_contiguous()) throw RasterizerError(std::string(fn) + ": wpack must be contiguous");
+    if (!rot.empty() && (int64_t)rot.size() != n) throw RasterizerError(std::string(fn) + ": rot must have one entry per matrix, or none");
+    for (int64_t v : rot)
+        if (v < 0 || (v >= T && !(T == 0 && v == 0))) throw RasterizerError(std::string(fn) + ": a rot entry is outside 0..T-1");
+    const GpuCall c(x, fn, "x", {{wpack, "wpack"}});
+    Tensor out = at::empty({T, 128 * n}, x.options().dtype(out_half ? at::kHalf : at::kFloat));
+    if (T == 0) return out;
+    long long r[IGS_TOKEN_PROJ_MAX_OUT] = {};
+    for (size_t j = 0; j < rot.size(); j++) r[j] = rot[j];
+    check(igs_token_proj_fwd(c.stream(), T, (int)n, cdt, x.data_ptr(), xdt, token_row_stride(x), wpack.data_ptr(), r, out.data_ptr(),
+                             out_half ? IGS_DTYPE_F16 : IGS_DTYPE_F32, 128 * n),
+          "igs_token_proj_fwd");
+    return out;
+}
+
 // ---- the Gaussian deform (motion.hip) ----
 void deform_checks(const char* fn, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot, int* dt)
 {
@@ -1940,6 +1972,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     def_nogil(ff, "layer_tail_bwd", &layer_tail_bwd, "attn_out"_a, "source"_a, "dout"_a, "wpack"_a, "wpack_t"_a, "hidden"_a, "ln1_w"_a, "ln1_b"_a, "eps1"_a,
               "ln2_w"_a, "ln2_b"_a, "eps2"_a, "want"_a, "da_half"_a = false, "ds_half"_a = false);
     ff.def("bwd_scratch_bytes", &layer_tail_bwd_scratch_bytes, "T"_a, "half"_a, "hidden"_a);
+    py::module_ pj = m.def_submodule("_proj", "the q / k / v projections of the unimatch TransformerLayers in one launch (proj.hip)");
+    def_nogil(pj, "token_proj_fwd", &token_proj_fwd, "x"_a, "wpack"_a, "n"_a, "rot"_a = std::vector<int64_t>(), "out_half"_a = false);
+    def_nogil(pj, "pack_elems", &token_proj_pack_elems, "n"_a);
     py::module_ ls = m.def_submodule("_loss", "SSIM and L1 of a batch of images: the AGM-Net training loss (ssim_batch.hip)");
     def_nogil(ls, "ssim_batch", &ssim_batch, "a"_a, "b"_a, "c_ssim"_a, "c_l1"_a, "want_grad"_a, "want_map"_a, "want_l1"_a);
 

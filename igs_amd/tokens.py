@@ -16,6 +16,12 @@ norm2, then `source + message`, and a three-launch `is_self_attn` test whose res
                                                                         GELU MLP, LN2, the residual add) as one launch, forward only
     use_native_layer_tails(feature_transformer)                         binds a forward that takes layer_tail when nothing needs a gradient
     layer_tail_autograd(attn_out, source, layer)                        layer_tail with the recomputing native backward (ffn_bwd.hip) behind it
+    project_tokens(x, weights, rot=None)                                up to five bias-free 128 -> 128 projections of x side by side in
+                                                                        one buffer, one launch, forward only (proj.hip)
+    use_native_layer_heads(feature_transformer)                         binds a forward whose q / k / v projections are one or two such
+                                                                        launches when nothing needs a gradient, then the tail as above
+    use_native_feature_transformer(transformer, bidirectional)          binds the transformer's forward: five projections of a block's
+                                                                        input in one launch, the batch-swapped target never built
     group_norm_tokens(x, num_groups, weight, bias, eps)                 F.group_norm over [B, C, A] written token-major [B, A, C]: the
                                                                         statistics, then one tile-transposing launch
     add_residual_tokens(tokens, residual)                               tokens [B, A, C] + residual [B, C, A], one launch; a [B, C, A]-shaped
@@ -46,7 +52,7 @@ the figures of section 20.
 Not provided: norm types other than nn.GroupNorm with affine parameters at the ends of Transformer1D, gradient checkpointing and 2-D
 attention masks there, fusing proj_in / proj_out; the GELU inside the unimatch MLP (a single eager kernel
 already) and splitting the MLP's first weight to avoid the cat outside layer_tail (which does both); a double backward
-of layer_tail, the q / k / v projections, d_model other than 128 and biases there; bfloat16; fusing any other GEMM; the ada
+of layer_tail, a backward of project_tokens, d_model other than 128 and biases there; bfloat16; fusing any other GEMM; the ada
 norms, cross-attention (norm2 / attn2) and the other feed-forward activations of BasicTransformerBlock; attn_type other than 'swin' and
 nhead > 1 of TransformerLayer.
 """
@@ -266,20 +272,28 @@ def use_native_block_ops(module):
 
 
 # ---------------------------------------------------------------- the unimatch TransformerLayer
-def _layer_message(self, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits):
-    """The three projections and the attention function of the layer's own module (looked up now, so whatever
-    use_native_window_attention set there is used): the input of the layer's tail."""
+def _layer_served(self, attn_type):
     fn = "TransformerLayer"
     if attn_type != "swin":
         raise NotImplementedError(f"{fn}: attn_type = {attn_type!r} is not provided (IGS uses 'swin' only)")
     if getattr(self, LAYER_NHEAD) > 1:
         raise NotImplementedError(f"{fn}: nhead > 1 is not provided")
+
+
+def _layer_attention(self, query, key, value, height, width, shifted_window_attn_mask, with_shift, attn_num_splits):
+    """The attention function of the layer's own module, looked up now, so whatever use_native_window_attention set there is used."""
     namespace = sys.modules[type(self).__module__]
-    query, key, value = getattr(self, LAYER_Q)(source), getattr(self, LAYER_K)(target), getattr(self, LAYER_V)(target)
     if attn_num_splits is not None and attn_num_splits > 1:
         return getattr(namespace, ATTN_SPLIT)(query, key, value, num_splits=attn_num_splits, with_shift=with_shift, h=height, w=width,
                                               attn_mask=shifted_window_attn_mask)
     return getattr(namespace, ATTN_FULL)(query, key, value)
+
+
+def _layer_message(self, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits):
+    """The three projections and the attention: the input of the layer's tail."""
+    _layer_served(self, attn_type)
+    query, key, value = getattr(self, LAYER_Q)(source), getattr(self, LAYER_K)(target), getattr(self, LAYER_V)(target)
+    return _layer_attention(self, query, key, value, height, width, shifted_window_attn_mask, with_shift, attn_num_splits)
 
 
 def _layer_tail_unfused(self, message, source):
@@ -586,8 +600,13 @@ def _layer_tail_forward_training(self, source, target, height=None, width=None, 
 
 
 def _layer_tail_route(self, training, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits):
-    fn = "TransformerLayer"
     message = _layer_message(self, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits)
+    return _tail_route(self, training, message, source)
+
+
+def _tail_route(self, training, message, source):
+    """The layer's tail behind the attention's `message`, by the rules of use_native_layer_tails(module, training)."""
+    fn = "TransformerLayer"
     params = _tail_params(self)
     needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in [message, source] + params)
     if needs_grad and not training:
@@ -630,6 +649,288 @@ def use_native_layer_tails(module, training=False):
     for m in layers:
         m.forward = types.MethodType(bound, m)
     return len(layers)
+
+
+# ---------------------------------------------------------------- the layer's q / k / v projections in one launch (proj.hip)
+PROJ_MAX_OUT = 5                                                   # IGS_TOKEN_PROJ_MAX_OUT
+HEAD_CACHE = "_igs_layer_head_pack"
+FT_LAYERS, BLOCK_SELF, BLOCK_CROSS = "layers", "self_attn", "cross_attn_ffn"
+FT_MASK = "generate_shift_window_attn_mask"
+FT_STATE = "_igs_feature_transformer"
+# Per compute dtype, whether the forwards that use_native_layer_heads and use_native_feature_transformer bind take the fused projections
+# when nothing needs a gradient (True) or the layer's three nn.Linear calls (False; project_tokens itself always runs the kernel), and the
+# fewest outputs a launch must have to be taken: a launch with fewer stays nn.Linear.  DESIGN.md 28 has the measurement that set each
+# (profiles/layer_head_bench.jsonl): the launch against as many F.linear calls at [32768, 128] and [163840, 128].  n = 5 (with the swap
+# copy on the other side) and n = 2 hold at both shapes in both dtypes (1.14 - 1.44 x and 1.07 - 1.27 x float32, 2.26 - 3.07 x and
+# 1.34 - 2.13 x float16 autocast, ranges disjoint), so both dtypes are on.  n = 1 holds at [32768, 128] (1.23 x, 1.58 x) and DOES NOT HOLD
+# at [163840, 128] (1.02 x float32 and 0.94 x float16, ranges overlapping), so a single projection stays nn.Linear in both.  n = 3 in
+# float32 does not hold at [163840, 128] either (0.98 x, ranges overlapping: level) and is 1.35 x ahead at [32768, 128]; it stays on.
+LAYER_HEAD_FUSED = {torch.float32: True, torch.float16: True}
+LAYER_HEAD_MIN_OUTPUTS = {torch.float32: 2, torch.float16: 2}
+
+
+def _proj_weights(fn, weights):
+    """The [128, 128] weight tensors of `weights` (tensors, or bias-free nn.Linear modules), or the refusal."""
+    ws = []
+    for w in weights:
+        if isinstance(w, nn.Linear):
+            if w.bias is not None:
+                raise NotImplementedError(f"{fn}: a projection has a bias: biases are not provided")
+            w = w.weight
+        if not torch.is_tensor(w) or w.dim() != 2 or w.shape[0] != w.shape[1]:
+            raise ValueError(f"{fn}: every weight must be a square [{TAIL_D}, {TAIL_D}] matrix (got {list(w.shape) if torch.is_tensor(w) else type(w)})")
+        if w.shape[0] != TAIL_D:
+            raise NotImplementedError(f"{fn}: a weight is {list(w.shape)}: widths other than {TAIL_D} are not provided")
+        if w.dtype not in DTYPES:
+            raise NotImplementedError(f"{fn}: weights must be float32 or float16 (got {w.dtype})")
+        ws.append(w)
+    if not 1 <= len(ws) <= PROJ_MAX_OUT:
+        raise ValueError(f"{fn}: 1..{PROJ_MAX_OUT} weights are served (got {len(ws)})")
+    return ws
+
+
+def pack_projections(weights, dtype=torch.float32):
+    """n = 1..5 weights [128, 128] (tensors as nn.Linear keeps them, or bias-free nn.Linear modules) in `dtype` as igs_token_proj_fwd takes
+    them (include/igs_rast.h): one flat tensor, matrix after matrix, each 16 tiles of 1024 elements in pack_layer_tail's layout for merge.
+    Plain tensor ops: works on any device."""
+    ws = _proj_weights("pack_projections", weights)
+    if dtype not in DTYPES:
+        raise NotImplementedError(f"pack_projections: dtype must be float32 or float16 (got {dtype})")
+    return torch.cat([pack_mlp_tile_order(w.detach().to(dtype)) for w in ws]).contiguous()
+
+
+def project_tokens(x, weights, rot=None, packed=None, compute_dtype=None):
+    """torch.cat([F.linear(x, W) for W in weights], -1) in one launch and forward only (igs_token_proj_fwd, proj.hip): x [..., 128] is read
+    once, the n = 1..5 results [..., 128 n] are written side by side and the caller slices them (wattn.hip reads such slices in place).
+    rot: n row offsets in [0, rows), rows the product of x's leading sizes: the columns of output j are written rolled by rot[j] rows,
+    torch.roll(F.linear(x, W_j).view(rows, 128), rot[j], 0); rot[j] = rows / 2 is the projection of x with its two batch halves swapped.
+    weights: tensors [128, 128] or bias-free nn.Linear modules.  compute_dtype: torch.float32 (exact float32 matrix instructions) or
+    torch.float16 (half operands, float32 accumulation); default float16 under autocast to half or when x is half, float32 otherwise.  The
+    result is contiguous, float16 when the compute dtype is, float32 otherwise: what nn.Linear returns.  packed:
+    pack_projections(weights, compute_dtype), packed here when absent.  Raises NotImplementedError when grad is enabled and x or a
+    weight requires it, for a bias, widths other than 128 and bfloat16 / float64; RuntimeError for CPU tensors; ValueError for shapes."""
+    fn = "project_tokens"
+    ws = _proj_weights(fn, weights)
+    n = len(ws)
+    if x.dim() < 1 or x.shape[-1] != TAIL_D:
+        raise ValueError(f"{fn}: x must be [..., {TAIL_D}] (got {list(x.shape)})")
+    rows = x.numel() // TAIL_D
+    if rows > TAIL_MAX_ROWS:
+        raise ValueError(f"{fn}: {rows} rows is above the supported {TAIL_MAX_ROWS}")
+    rot = [] if rot is None else [int(r) for r in rot]
+    if rot and (len(rot) != n or any(r < 0 or (r >= rows and not (rows == 0 and r == 0)) for r in rot)):
+        raise ValueError(f"{fn}: rot must hold one offset in 0..{rows - 1} per weight (got {rot})")
+    if x.dtype not in DTYPES:
+        raise NotImplementedError(f"{fn}: x must be float32 or float16 (got {x.dtype})")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in [x] + ws):
+        raise NotImplementedError(f"{fn}: forward only -- call it under torch.no_grad(), and train with the layer's nn.Linear modules")
+    if compute_dtype is None:
+        compute_dtype = _tail_compute_dtype(fn, x)
+    if compute_dtype not in DTYPES:
+        raise NotImplementedError(f"{fn}: compute_dtype must be float32 or float16 (got {compute_dtype})")
+    if packed is not None and packed.dtype != compute_dtype:
+        raise ValueError(f"{fn}: packed holds {packed.dtype} weights, compute_dtype is {compute_dtype}")
+    _refuse(fn, [(x, "x")] + [(w, "a weight") for w in ws])
+    if packed is None:
+        packed = pack_projections(ws, compute_dtype)
+    out = _ext()._proj.token_proj_fwd(_rows(x.detach()), packed, n, rot, compute_dtype == torch.float16)
+    return out.view(x.shape[:-1] + (TAIL_D * n,))
+
+
+def _head_linears(fn, layer):
+    """(q_proj, k_proj, v_proj) of a layer that proj.hip serves, or NotImplementedError."""
+    lins = tuple(getattr(layer, a, None) for a in (LAYER_Q, LAYER_K, LAYER_V))
+    for lin, name in zip(lins, (LAYER_Q, LAYER_K, LAYER_V)):
+        if not isinstance(lin, nn.Linear) or (lin.in_features, lin.out_features) != (TAIL_D, TAIL_D):
+            raise NotImplementedError(f"{fn}: {name} must be nn.Linear({TAIL_D}, {TAIL_D}): d_model other than {TAIL_D} is not provided (got {lin})")
+        if lin.bias is not None:
+            raise NotImplementedError(f"{fn}: {name} has a bias: biases are not provided")
+        if lin.weight.dtype not in DTYPES:
+            raise NotImplementedError(f"{fn}: parameters must be float32 or float16 (got {lin.weight.dtype})")
+    return lins
+
+
+def _head_pack(holder, which, dtype, weights):
+    """The pack of `weights` for a compute dtype, cached on the layer `holder` under the name `which` and rebuilt when a weight changed
+    (param_key)."""
+    key = param_key(weights)
+    cache = holder.__dict__.setdefault(HEAD_CACHE, {})
+    entry = cache.get((which, dtype))
+    if entry is None or entry["key"] != key:
+        entry = cache[(which, dtype)] = dict(key=key, pack=pack_projections(weights, dtype))
+    return entry["pack"]
+
+
+def _head_project(holder, which, x, linears, rot=None):
+    """[..., 128 n]: the products of x with the n Linears' weights, as one launch where LAYER_HEAD_MIN_OUTPUTS allows, as n nn.Linear calls
+    (and the rolls and the cat that rot and the layout ask for) otherwise."""
+    dtype = _tail_compute_dtype("TransformerLayer", x)
+    if len(linears) >= LAYER_HEAD_MIN_OUTPUTS[dtype]:
+        weights = [lin.weight for lin in linears]
+        return project_tokens(x, weights, rot=rot, packed=_head_pack(holder, which, dtype, weights), compute_dtype=dtype)
+    outs = [lin(x) for lin in linears]
+    if rot is not None:
+        outs = [o if r == 0 else torch.roll(o.reshape(-1, TAIL_D), r, 0).view(o.shape) for o, r in zip(outs, rot)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs, -1)
+
+
+def _heads_fused(tensors, weights):
+    """Whether a forward over `tensors` with the projection `weights` takes the fused launches: nothing needs a gradient, the activations
+    are float32 / float16 rows of 128 on a GPU, and LAYER_HEAD_FUSED has the compute dtype on."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in list(tensors) + list(weights)):
+        return False
+    if any(t.dtype not in DTYPES or not t.is_cuda or t.dim() < 1 or t.shape[-1] != TAIL_D for t in tensors):
+        return False
+    return LAYER_HEAD_FUSED[_tail_compute_dtype("TransformerLayer", tensors[0])]
+
+
+def _cols(buf, j):
+    return buf[..., TAIL_D * j: TAIL_D * (j + 1)]
+
+
+def _layer_head_route(self, training, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits):
+    _layer_served(self, attn_type)
+    q, k, v = (getattr(self, a) for a in (LAYER_Q, LAYER_K, LAYER_V))
+    if not _heads_fused([source, target], [q.weight, k.weight, v.weight]):
+        message = _layer_message(self, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits)
+        return _tail_route(self, training, message, source)
+    if source is target:
+        buf = _head_project(self, "qkv", source, (q, k, v))
+        query, key, value = _cols(buf, 0), _cols(buf, 1), _cols(buf, 2)
+    else:
+        query = _head_project(self, "q", source, (q,))
+        buf = _head_project(self, "kv", target, (k, v))
+        key, value = _cols(buf, 0), _cols(buf, 1)
+    message = _layer_attention(self, query, key, value, height, width, shifted_window_attn_mask, with_shift, attn_num_splits)
+    return _tail_route(self, training, message, source)
+
+
+def _layer_head_forward(self, source, target, height=None, width=None, shifted_window_attn_mask=None, shifted_window_attn_mask_1d=None,
+                        attn_type="swin", with_shift=False, attn_num_splits=None):
+    """TransformerLayer.forward as use_native_layer_heads binds it: when nothing needs a gradient the projections are one launch
+    (source is target) or two (q of source, k and v of target) whose column slices the attention reads in place; then the attention
+    lookup and the tail routing of use_native_layer_tails.  With a gradient needed: that binder's forward as it is."""
+    return _layer_head_route(self, False, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits)
+
+
+def _layer_head_forward_training(self, source, target, height=None, width=None, shifted_window_attn_mask=None, shifted_window_attn_mask_1d=None,
+                                 attn_type="swin", with_shift=False, attn_num_splits=None):
+    """_layer_head_forward with the tail routing of use_native_layer_tails(training=True)."""
+    return _layer_head_route(self, True, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits)
+
+
+def use_native_layer_heads(module, training=False):
+    """Binds a forward on every unimatch TransformerLayer under `module` (found as use_native_transformer_layers finds them) that, when
+    nothing needs a gradient, runs q_proj, k_proj and v_proj as one project_tokens launch with n = 3 when `source is target`, as one with
+    n = 1 on source and one with n = 2 on target otherwise, hands the attention column slices of those buffers, and then does exactly what
+    the forward of use_native_layer_tails(module, training) does behind the projections: the same attention lookup, the same tail routing.
+    With grad enabled and an input or a parameter requiring it the three nn.Linear calls run as before.  LAYER_HEAD_FUSED turns the
+    launches off per compute dtype and LAYER_HEAD_MIN_OUTPUTS leaves launches with too few outputs to nn.Linear.  Returns how many layers
+    were bound; state_dict() keys and the classes are untouched.  The packs are kept on the layer per compute dtype and rebuilt when a
+    weight's _version, data_ptr, dtype or device changes.  Raises NotImplementedError, before anything is changed, for everything
+    use_native_layer_tails refuses and for a q_proj / k_proj / v_proj that is not a bias-free nn.Linear(128, 128) in float32 / float16."""
+    fn = "use_native_layer_heads"
+    layers = _checked_layers(fn, module)
+    for m in layers:
+        _tail_spec(fn, m)
+        _head_linears(fn, m)
+    bound = _layer_head_forward_training if training else _layer_head_forward
+    for m in layers:
+        m.forward = types.MethodType(bound, m)
+    return len(layers)
+
+
+def _feature_blocks(fn, transformer):
+    """The blocks of a unimatch feature transformer, each a (self_attn, cross_attn_ffn) pair of layers, or NotImplementedError."""
+    blocks = getattr(transformer, FT_LAYERS, None)
+    if not isinstance(blocks, (nn.ModuleList, list, tuple)) or len(blocks) == 0:
+        raise NotImplementedError(f"{fn}: the transformer must have a non-empty `{FT_LAYERS}` list of blocks")
+    pairs = []
+    for b in blocks:
+        pair = (getattr(b, BLOCK_SELF, None), getattr(b, BLOCK_CROSS, None))
+        if not all(p is not None and _is_layer(p) for p in pair):
+            raise NotImplementedError(f"{fn}: every block must have the TransformerLayers {BLOCK_SELF} and {BLOCK_CROSS}")
+        pairs.append(pair)
+    return pairs
+
+
+def _feature_forward(self, feature0, feature1, attn_type="swin", attn_num_splits=None, **kwargs):
+    """The forward that use_native_feature_transformer binds: FeatureTransformer.forward (igs/models/unimatch/transformer.py:229-301) or
+    FeatureTransformerMy.forward (:328-400) with a block's projections of its input fused, or the forward it was bound over."""
+    state = self.__dict__[FT_STATE]
+    pairs = _feature_blocks("FeatureTransformer", self)
+    weights = [getattr(layer, a).weight for pair in pairs for layer in pair for a in (LAYER_Q, LAYER_K, LAYER_V)]
+    tensors = [feature0, feature1]
+    fused = (attn_type == "swin" and all(torch.is_tensor(t) and t.dim() == 4 and t.shape[1] == TAIL_D for t in tensors)
+             and tuple(feature0.shape) == tuple(feature1.shape) and feature0.dtype == feature1.dtype
+             and _heads_fused([t.permute(0, 2, 3, 1) for t in tensors], weights + [p for pair in pairs for layer in pair for p in _tail_params(layer)]))
+    if not fused:
+        return state["forward"](feature0, feature1, attn_type=attn_type, attn_num_splits=attn_num_splits, **kwargs)
+    for pair in pairs:
+        for layer in pair:
+            _layer_served(layer, attn_type)
+    training, bidirectional = state["training"], state["bidirectional"]
+    b, c, h, w = feature0.shape
+    feature0 = feature0.flatten(-2).permute(0, 2, 1)
+    feature1 = feature1.flatten(-2).permute(0, 2, 1)
+    split = attn_num_splits is not None and attn_num_splits > 1
+    mask = None
+    if split:
+        wh, ww = h // attn_num_splits, w // attn_num_splits
+        mask = getattr(sys.modules[type(self).__module__], FT_MASK)(input_resolution=(h, w), window_size_h=wh, window_size_w=ww,
+                                                                   shift_size_h=wh // 2, shift_size_w=ww // 2, device=feature0.device)
+    if bidirectional:
+        x = torch.cat((feature0, feature1), dim=0)
+    else:
+        x, feature1 = feature0.contiguous(), feature1.contiguous()        # (token-major once, not once per block)
+    rows = x.shape[0] * x.shape[1]
+    for i, (sa, ca) in enumerate(pairs):
+        geom = (h, w, mask, split and i % 2 == 1, attn_num_splits)
+        sq, sk, sv = (getattr(sa, a) for a in (LAYER_Q, LAYER_K, LAYER_V))
+        cq, ck, cv = (getattr(ca, a) for a in (LAYER_Q, LAYER_K, LAYER_V))
+        if bidirectional:                                                  # five products of the block's input; the last two land swapped
+            buf = _head_project(sa, "block", x, (sq, sk, sv, ck, cv), rot=(0, 0, 0, rows // 2, rows // 2))
+            key, value = _cols(buf, 3), _cols(buf, 4)
+        else:
+            buf = _head_project(sa, "qkv", x, (sq, sk, sv))
+            kv = _head_project(ca, "kv", feature1, (ck, cv))
+            key, value = _cols(kv, 0), _cols(kv, 1)
+        x = _tail_route(sa, training, _layer_attention(sa, _cols(buf, 0), _cols(buf, 1), _cols(buf, 2), *geom), x)
+        x = _tail_route(ca, training, _layer_attention(ca, _head_project(ca, "q", x, (cq,)), key, value, *geom), x)
+    if not bidirectional:
+        return x.view(b, h, w, c).permute(0, 3, 1, 2).contiguous()
+    feature0, feature1 = x.chunk(chunks=2, dim=0)
+    return feature0.view(b, h, w, c).permute(0, 3, 1, 2).contiguous(), feature1.view(b, h, w, c).permute(0, 3, 1, 2).contiguous()
+
+
+def use_native_feature_transformer(transformer, bidirectional, training=False):
+    """Binds the forward of a unimatch feature transformer, found by its `layers` list of blocks that each have the TransformerLayers
+    self_attn and cross_attn_ffn, and use_native_layer_heads(transformer, training) on its layers; returns how many layers were bound (two
+    per block).  The reference's two classes have the same attributes, so the caller says which forward it is: bidirectional=True is
+    FeatureTransformer.forward (both features on the batch, each the other's target, two results), False is FeatureTransformerMy.forward
+    (feature1 is every block's target and is never updated, one result).  Under no_grad with attn_type = 'swin' a block is: one
+    project_tokens launch with n = 5 on the block's input (self_attn's q, k, v and cross_attn_ffn's k, v, the last two written with
+    rot = rows / 2, i.e. where the block's batch-swapped target would have put them: that target is never built), self attention and its
+    tail, one launch with n = 1 (cross_attn_ffn's q), cross attention on columns 384..639 of the first buffer and its tail.  With
+    bidirectional=False: n = 3 on the block's input, n = 2 on feature1, n = 1.  The first cat and the final chunk / view / permute /
+    contiguous stay PyTorch; the shift mask comes from generate_shift_window_attn_mask of the module that defines the transformer's class
+    and the attention functions from the module that defines the layers' class, both looked up at the call, so eager and native window
+    attention both work; a launch with fewer outputs than LAYER_HEAD_MIN_OUTPUTS (as shipped: the single q projection) stays nn.Linear;
+    tails are routed as use_native_layer_tails(module, training) routes them.  A call that needs a gradient, another attn_type,
+    or a compute dtype that LAYER_HEAD_FUSED turns off runs the forward that was bound over (whose layers are bound).  Raises
+    NotImplementedError, before anything is changed, for a module without such blocks and for everything use_native_layer_heads refuses."""
+    fn = "use_native_feature_transformer"
+    pairs = _feature_blocks(fn, transformer)
+    for pair in pairs:
+        for layer in pair:
+            _tail_spec(fn, layer)
+            _head_linears(fn, layer)
+    state = transformer.__dict__.get(FT_STATE)
+    original = state["forward"] if state is not None else transformer.forward      # (binding twice keeps the first original)
+    n = use_native_layer_heads(transformer, training)
+    transformer.__dict__[FT_STATE] = dict(forward=original, bidirectional=bool(bidirectional), training=bool(training))
+    transformer.forward = types.MethodType(_feature_forward, transformer)
+    return n
 
 
 # ---------------------------------------------------------------- the two ends of Transformer1D

@@ -1251,6 +1251,39 @@ int igs_layer_tail_bwd(void* stream, long long T, int compute_dtype, int has_ffn
                        int ds_dtype, long long ds_stride, float* dWm, float* dln1_w, float* dln1_b, float* dW1, float* dW2, float* dln2_w,
                        float* dln2_b);
 
+/* Up to IGS_TOKEN_PROJ_MAX_OUT bias-free 128 -> 128 projections of one activation in one launch (proj.hip): the
+ * q_proj / k_proj / v_proj of the unimatch TransformerLayers (igs/models/unimatch/transformer.py:25-27, 104-106).  For j = 0 .. n - 1 and
+ * every row t of x:
+ *     out[(t + rot[j]) mod T][128 j .. 128 j + 127] = W_j x[t],   W_j [128, 128] as nn.Linear keeps it,
+ * so the n results lie side by side in one buffer whose column slices igs_window_attn_fwd reads in place, and rot[j] = T / 2 is the
+ * projection of x with its two batch halves swapped (a FeatureTransformer block's `concat1`, :274-289) without the swap being built.
+ * Forward only.  Runs on `stream`, reads nothing back, allocates nothing, uses no atomics: two runs agree bit for bit, and a row's 128 n
+ * results depend on that row and the weights only (not on T, on the row's position, on rot, or on which workgroup took it), so a NaN
+ * stays in its row.
+ *   - x: [T, 128] and out: [T, >= 128 n], each with its own dtype code (IGS_DTYPE_F32 / IGS_DTYPE_F16; widened on load, rounded once on
+ *     store) and its own row stride in elements (x: >= 128, out: >= 128 n; stride 1 inside a row).  Columns of an out row beyond 128 n are
+ *     not touched.  Four-element accesses are used for an operand whose base lies on its dtype's four-element grid and whose stride is a
+ *     multiple of 4, scalar ones otherwise.
+ *   - compute_dtype is the matrix operand type.  IGS_DTYPE_F32: v_mfma_f32_32x32x2_f32, an exact float32 fma chain over the 128 inputs in
+ *     ascending order, no half value anywhere.  IGS_DTYPE_F16: v_mfma_f32_32x32x16_f16 with float32 accumulation; x is rounded to half
+ *     once, as an operand.
+ *   - wpack, in compute_dtype, 16-byte aligned, igs_token_proj_pack_elems(n) = n x 16 x 1024 elements (-1 for an n out of range): the n
+ *     matrices one after the other, each as igs_layer_tail_fwd's Wm (16 tiles, output tile outermost: tile 4 ot + kt, in that
+ *     function's per-tile layout).
+ *   - rot: n host values, read before the call returns; NULL means all zero.
+ *   - The launch: workgroups of 4 waves take trips of IGS_LAYER_TAIL_TRIP_ROWS rows (32 per wave); the grid is
+ *     min(ceil(T / IGS_LAYER_TAIL_TRIP_ROWS), compute units x (compute_dtype == IGS_DTYPE_F16 ? 2 : 1)) workgroups, each looping over its
+ *     trips.
+ *   - Refused with IGS_RAST_E_INVALID and a message naming igs_token_proj_fwd before any HIP call: an unknown dtype code; n < 1 or
+ *     > IGS_TOKEN_PROJ_MAX_OUT; T < 0 or > IGS_TOKEN_PROJ_MAX_ROWS; an x stride below 128, an out stride below 128 n, either above
+ *     IGS_TOKENS_MAX_STRIDE; a rot[j] outside [0, T) (with T == 0: other than 0); with T > 0 a NULL x, wpack or out, an x or out not
+ *     aligned to its element size, a wpack not aligned to 16 bytes, an out span that overlaps x.  T == 0 returns 0 without a launch. */
+#define IGS_TOKEN_PROJ_MAX_OUT 5
+#define IGS_TOKEN_PROJ_MAX_ROWS (1LL << 24)
+long long igs_token_proj_pack_elems(int n);
+int igs_token_proj_fwd(void* stream, long long T, int n, int compute_dtype, const void* x, int x_dtype, long long x_stride, const void* wpack,
+                       const long long* rot, void* out, int out_dtype, long long out_stride);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).
