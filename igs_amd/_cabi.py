@@ -193,6 +193,8 @@ SIGNATURES = {
     # proj.hip
     "igs_token_proj_pack_elems": (_ll, [_i]),
     "igs_token_proj_fwd": (_i, [_vp, _ll, _i, _i] + [_vp, _i, _ll] + [_vp, _vp] + [_vp, _i, _ll]),
+    "igs_token_proj_bwd_scratch_bytes": (_ll, [_ll, _i]),
+    "igs_token_proj_bwd": (_i, [_vp, _ll, _i, _i] + [_vp, _i, _ll] + [_vp, _i, _vp] + [_vp, _vp] + [_vp, _ll] + [_vp, _i, _ll] + [_vp]),
     # ssim_batch.hip
     "igs_ssim_batch_scratch_bytes": (_ll, [_i] * 5),
     "igs_ssim_batch_fwd_bwd": (_i, [_vp] + [_i] * 4 + [_vp, _vp, _f, _f] + [_vp] * 5),

@@ -18,19 +18,7 @@
 // last read during matrix s - 1, which every wave left through that matrix's barrier.  float32 holds one workgroup of 4 waves per compute
 // unit (128 KB of LDS), float16 two (64 KB each).  A workgroup loops over trips of 128 rows; the grid is at most what the chip holds at
 // once.  Rows past T read row 0 instead and are never stored.
-#include "ffn_common.h"                   // the row loads and stores, the staging, the argument checks
-
-#define PROJ_MAT (FFN_WM_TILES * MLP_TILE)                                       // elements of one packed matrix
-
-template <typename T> struct ProjCfg {
-    enum {
-        HALF = AttnCfg<T>::HALF,
-        QUARTER = PROJ_MAT / 4,                                                    // one output tile's four tiles
-        PIECES = QUARTER * (int)sizeof(T) / 16 / FFN_THREADS,                      // a thread's 16-byte pieces of a quarter: 4 / 2
-        GROUPS_PER_CU = HALF ? 2 : 1,                                              // what the LDS lets a compute unit hold
-        WAVES_PER_SIMD = GROUPS_PER_CU * FFN_WAVES / 4,
-    };
-};
+#include "proj_common.h"                  // PROJ_MAT, ProjCfg; ffn_common.h's row loads and stores, staging and argument checks
 
 struct ProjArgs {
     long long T;

@@ -26,8 +26,9 @@
 //   residual decoder    mlp.hip                 _mlp.mlp_heads_fwd, _mlp.pack_elems: [N, C0] rows with a row stride in, one [N, ch] per head out;
 //                                               _mlp.mlp_heads_bwd, _mlp.bwd_scratch_bytes: d x and flat float32 d w / d b from x alone
 //   layer tail          ffn.hip                 _ffn.layer_tail_fwd, _ffn.layer_tail_bwd, _ffn.pack_elems, _ffn.bwd_scratch_bytes: merge, LayerNorms and FFN of a unimatch TransformerLayer on [T, 128] rows
-//   projections         proj.hip                _proj.token_proj_fwd, _proj.pack_elems: up to five 128 -> 128 projections of [T, 128] rows side by side in one [T, 128 n] buffer
-//   deform              motion.hip              motion_deform_fwd / _bwd
+//   projections         proj.hip                _proj.token_proj_fwd, _proj.pack_elems: up to five 128 -> 128 projections of [T, 128] rows side by side in one [T, 128 n] buffer;
+//                       proj_bwd.hip            _proj.token_proj_bwd, _proj.bwd_scratch_bytes: d x and the float32 d W_j from each output's own gradient rows
+//   deform             motion.hip              motion_deform_fwd / _bwd
 //   Adam                refine_ops.hip          adam_step_multi
 //   losses              refine_ops, loss_ops    l1_mean; ssim_mean
 //   training loss       ssim_batch.hip          _loss.ssim_batch on [N, C, H, W] float32 batches
@@ -1624,6 +1625,68 @@ Tensor token_proj_fwd(const Tensor& x, const Tensor& wpack, int64_t n, const std
     return out;
 }
 
+int64_t token_proj_bwd_scratch_bytes(int64_t T, int64_t n)
+{
+    return igs_token_proj_bwd_scratch_bytes(T, (int)std::max<int64_t>(std::min<int64_t>(n, INT_MAX), INT_MIN));
+}
+// (d x [T, 128] contiguous, float16 when dx_half, else float32, or None unless want_dx; n d W_j [128, 128] float32, each None unless
+// want_dw[j]).  x: as token_proj_fwd read it; grads: n entries, each the gradient of output j as [T, 128] rows (column slices of a wider
+// buffer included), all of one dtype, or None where output j had none; wpack_t: the pack of the transposes; rot: as the forward's
+std::tuple<OptTensor, std::vector<OptTensor>> token_proj_bwd(const Tensor& x, const std::vector<OptTensor>& grads, const Tensor& wpack_t,
+                                                             const std::vector<int64_t>& rot, bool want_dx, const std::vector<bool>& want_dw,
+                                                             bool dx_half)
+{
+    const char* fn = "token_proj_bwd";
+    const int xdt = token_rows_check(fn, x, "x");
+    const int cdt = dtype_code(wpack_t, fn, "wpack_t");
+    const int64_t T = x.size(0), n = (int64_t)grads.size();
+    if (x.size(1) != 128) throw RasterizerError(std::string(fn) + ": x must be [T, 128] (got " + c10::str(x.sizes()) + ")");
+    const int64_t elems = token_proj_pack_elems(n);
+    if (elems < 0 || T > IGS_TOKEN_PROJ_MAX_ROWS)
+        throw RasterizerError(std::string(fn) + ": sizes out of range (n in 1.." + std::to_string(IGS_TOKEN_PROJ_MAX_OUT) + ", T <= 2^24)");
+    expect(wpack_t, fn, "wpack_t", wpack_t.scalar_type(), {elems});
+    if (!wpack_t.is_contiguous()) throw RasterizerError(std::string(fn) + ": wpack_t must be contiguous");
+    if ((int64_t)want_dw.size() != n) throw RasterizerError(std::string(fn) + ": want_dw must have one entry per matrix");
+    if (!rot.empty() && (int64_t)rot.size() != n) throw RasterizerError(std::string(fn) + ": rot must have one entry per matrix, or none");
+    for (int64_t v : rot)
+        if (v < 0 || (v >= T && !(T == 0 && v == 0))) throw RasterizerError(std::string(fn) + ": a rot entry is outside 0..T-1");
+    int gdt = IGS_DTYPE_F32;
+    bool first = true;
+    for (const OptTensor& g : grads) {
+        if (!g) continue;
+        const int dt = token_rows_check(fn, *g, "a gradient");
+        if (g->sizes() != x.sizes()) throw RasterizerError(std::string(fn) + ": a gradient has shape " + c10::str(g->sizes()) + ", expected " + c10::str(x.sizes()));
+        if (!first && dt != gdt) throw RasterizerError(std::string(fn) + ": the gradients must all have one dtype");
+        gdt = dt;
+        first = false;
+    }
+    const GpuCall c(x, fn, "x", {{wpack_t, "wpack_t"}});
+    for (const OptTensor& g : grads)
+        if (g) same_device(x, fn, {{*g, "a gradient"}});
+    OptTensor dx;
+    std::vector<OptTensor> dw(n);
+    const auto fo = x.options().dtype(at::kFloat);
+    bool any_dw = false;
+    if (want_dx) dx = at::empty({T, 128}, x.options().dtype(dx_half ? at::kHalf : at::kFloat));
+    for (int64_t j = 0; j < n; j++)
+        if (want_dw[j]) { dw[j] = at::empty({128, 128}, fo); any_dw = true; }
+    if (!want_dx && !any_dw) return {dx, dw};
+    OptTensor scratch;
+    if (any_dw) scratch = at::empty({token_proj_bwd_scratch_bytes(T, n)}, x.options().dtype(at::kByte));
+    const void* gp[IGS_TOKEN_PROJ_MAX_OUT] = {};
+    float* wp[IGS_TOKEN_PROJ_MAX_OUT] = {};
+    long long gs[IGS_TOKEN_PROJ_MAX_OUT] = {}, r[IGS_TOKEN_PROJ_MAX_OUT] = {};
+    for (int64_t j = 0; j < n; j++) {
+        if (grads[j]) { gp[j] = grads[j]->data_ptr(); gs[j] = token_row_stride(*grads[j]); }
+        wp[j] = ptr_or_null<float>(dw[j]);
+        if (!rot.empty()) r[j] = rot[j];
+    }
+    check(igs_token_proj_bwd(c.stream(), T, (int)n, cdt, x.data_ptr(), xdt, token_row_stride(x), gp, gdt, gs, r, wpack_t.data_ptr(),
+                             ptr_or_null(scratch), scratch ? scratch->numel() : 0, ptr_or_null(dx), dx_half ? IGS_DTYPE_F16 : IGS_DTYPE_F32, 128, wp),
+          "igs_token_proj_bwd");
+    return {dx, dw};
+}
+
 // ---- the Gaussian deform (motion.hip) ----
 void deform_checks(const char* fn, const Tensor& rot, const Tensor& mask, const Tensor& dxyz, const Tensor& drot, int* dt)
 {
@@ -1975,6 +2038,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     py::module_ pj = m.def_submodule("_proj", "the q / k / v projections of the unimatch TransformerLayers in one launch (proj.hip)");
     def_nogil(pj, "token_proj_fwd", &token_proj_fwd, "x"_a, "wpack"_a, "n"_a, "rot"_a = std::vector<int64_t>(), "out_half"_a = false);
     def_nogil(pj, "pack_elems", &token_proj_pack_elems, "n"_a);
+    def_nogil(pj, "token_proj_bwd", &token_proj_bwd, "x"_a, "grads"_a, "wpack_t"_a, "rot"_a, "want_dx"_a, "want_dw"_a, "dx_half"_a = false);
+    def_nogil(pj, "bwd_scratch_bytes", &token_proj_bwd_scratch_bytes, "T"_a, "n"_a);
     py::module_ ls = m.def_submodule("_loss", "SSIM and L1 of a batch of images: the AGM-Net training loss (ssim_batch.hip)");
     def_nogil(ls, "ssim_batch", &ssim_batch, "a"_a, "b"_a, "c_ssim"_a, "c_l1"_a, "want_grad"_a, "want_map"_a, "want_l1"_a);
 

@@ -18,6 +18,8 @@ norm2, then `source + message`, and a three-launch `is_self_attn` test whose res
     layer_tail_autograd(attn_out, source, layer)                        layer_tail with the recomputing native backward (ffn_bwd.hip) behind it
     project_tokens(x, weights, rot=None)                                up to five bias-free 128 -> 128 projections of x side by side in
                                                                         one buffer, one launch, forward only (proj.hip)
+    project_tokens_autograd(x, weights, rot=None)                       the same launch with a native backward (proj_bwd.hip) behind it;
+                                                                        returns the n results as a tuple of column slices
     use_native_layer_heads(feature_transformer)                         binds a forward whose q / k / v projections are one or two such
                                                                         launches when nothing needs a gradient, then the tail as above
     use_native_feature_transformer(transformer, bidirectional)          binds the transformer's forward: five projections of a block's
@@ -52,7 +54,7 @@ the figures of section 20.
 Not provided: norm types other than nn.GroupNorm with affine parameters at the ends of Transformer1D, gradient checkpointing and 2-D
 attention masks there, fusing proj_in / proj_out; the GELU inside the unimatch MLP (a single eager kernel
 already) and splitting the MLP's first weight to avoid the cat outside layer_tail (which does both); a double backward
-of layer_tail, a backward of project_tokens, d_model other than 128 and biases there; bfloat16; fusing any other GEMM; the ada
+of layer_tail or project_tokens_autograd, d_model other than 128 and biases there; bfloat16; fusing any other GEMM; the ada
 norms, cross-attention (norm2 / attn2) and the other feed-forward activations of BasicTransformerBlock; attn_type other than 'swin' and
 nhead > 1 of TransformerLayer.
 """
@@ -667,6 +669,18 @@ FT_STATE = "_igs_feature_transformer"
 # float32 does not hold at [163840, 128] either (0.98 x, ranges overlapping: level) and is 1.35 x ahead at [32768, 128]; it stays on.
 LAYER_HEAD_FUSED = {torch.float32: True, torch.float16: True}
 LAYER_HEAD_MIN_OUTPUTS = {torch.float32: 2, torch.float16: 2}
+# Per compute dtype, whether a call that needs a gradient takes project_tokens_autograd (the fused forward with proj_bwd.hip behind it) under
+# use_native_layer_heads(training=True) and use_native_feature_transformer(training=True), and the fewest outputs such a launch must have.
+# A case holds only where the native forward + backward is ahead of as many F.linear calls under autograd (plus the swap cat for n = 5)
+# with disjoint min - max ranges.  Measured ("The backward"; profiles/layer_head_train_bench.jsonl) at [32768, 128] and
+# [163840, 128]: n = 5 holds everywhere (2.07 x and 2.05 x float32, 2.50 x and 2.15 x float16 autocast), n = 3 too (1.68 x, 1.67 x, 1.86 x,
+# 1.28 x), so both dtypes are on.  n = 2 holds in float32 (1.32 x, 1.35 x) and at [32768, 128] under autocast (1.43 x) and DOES NOT HOLD at
+# [163840, 128] under autocast (0.91 x: 1.046 ms (1.033 - 1.073) against 0.947 (0.933 - 0.964), slower), so float16 asks for three outputs.
+# n = 1 DOES NOT HOLD anywhere (0.88 x, 0.79 x float32; 0.90 x, 0.50 x float16: the weight-gradient launch costs a wave's walk over its
+# slice however few outputs there are), so a single projection stays nn.Linear in both.  project_tokens_autograd called directly always
+# runs the kernels.
+LAYER_HEAD_BWD_NATIVE = {torch.float32: True, torch.float16: True}
+LAYER_HEAD_BWD_MIN_OUTPUTS = {torch.float32: 2, torch.float16: 3}
 
 
 def _proj_weights(fn, weights):
@@ -689,14 +703,48 @@ def _proj_weights(fn, weights):
     return ws
 
 
-def pack_projections(weights, dtype=torch.float32):
+def pack_projections(weights, dtype=torch.float32, transposed=False):
     """n = 1..5 weights [128, 128] (tensors as nn.Linear keeps them, or bias-free nn.Linear modules) in `dtype` as igs_token_proj_fwd takes
     them (include/igs_rast.h): one flat tensor, matrix after matrix, each 16 tiles of 1024 elements in pack_layer_tail's layout for merge.
-    Plain tensor ops: works on any device."""
+    transposed=True: (pack, pack_t), pack_t the same pack of the transposes W_j^T as igs_token_proj_bwd takes it.  Plain tensor ops: works
+    on any device."""
     ws = _proj_weights("pack_projections", weights)
     if dtype not in DTYPES:
         raise NotImplementedError(f"pack_projections: dtype must be float32 or float16 (got {dtype})")
-    return torch.cat([pack_mlp_tile_order(w.detach().to(dtype)) for w in ws]).contiguous()
+    pack = torch.cat([pack_mlp_tile_order(w.detach().to(dtype)) for w in ws]).contiguous()
+    if not transposed:
+        return pack
+    return pack, torch.cat([pack_mlp_tile_order(w.detach().to(dtype).t().contiguous()) for w in ws]).contiguous()
+
+
+def _proj_checks(fn, x, weights, rot, packed, packed_t, compute_dtype, forward_only):
+    """The refusals of project_tokens and project_tokens_autograd, in one order; returns the weight tensors, the offsets as a list (empty:
+    none) and the compute dtype."""
+    ws = _proj_weights(fn, weights)
+    n = len(ws)
+    if x.dim() < 1 or x.shape[-1] != TAIL_D:
+        raise ValueError(f"{fn}: x must be [..., {TAIL_D}] (got {list(x.shape)})")
+    rows = x.numel() // TAIL_D
+    if rows > TAIL_MAX_ROWS:
+        raise ValueError(f"{fn}: {rows} rows is above the supported {TAIL_MAX_ROWS}")
+    rot = [] if rot is None else [int(r) for r in rot]
+    if rot and (len(rot) != n or any(r < 0 or (r >= rows and not (rows == 0 and r == 0)) for r in rot)):
+        raise ValueError(f"{fn}: rot must hold one offset in 0..{rows - 1} per weight (got {rot})")
+    if x.dtype not in DTYPES:
+        raise NotImplementedError(f"{fn}: x must be float32 or float16 (got {x.dtype})")
+    if forward_only and torch.is_grad_enabled() and any(t.requires_grad for t in [x] + ws):
+        raise NotImplementedError(f"{fn}: forward only -- call it under torch.no_grad(), and train with project_tokens_autograd")
+    if compute_dtype is None:
+        compute_dtype = _tail_compute_dtype(fn, x)
+    if compute_dtype not in DTYPES:
+        raise NotImplementedError(f"{fn}: compute_dtype must be float32 or float16 (got {compute_dtype})")
+    for pk in (packed, packed_t):
+        if pk is not None and pk.dtype != compute_dtype:
+            raise ValueError(f"{fn}: packed holds {pk.dtype} weights, compute_dtype is {compute_dtype}")
+        if pk is not None and pk.numel() != n * 16 * 1024:
+            raise ValueError(f"{fn}: packed holds {pk.numel()} elements, {n} matrices are {n * 16 * 1024}")
+    _refuse(fn, [(x, "x")] + [(w, "a weight") for w in ws])
+    return ws, rot, compute_dtype
 
 
 def project_tokens(x, weights, rot=None, packed=None, compute_dtype=None):
@@ -710,31 +758,64 @@ def project_tokens(x, weights, rot=None, packed=None, compute_dtype=None):
     pack_projections(weights, compute_dtype), packed here when absent.  Raises NotImplementedError when grad is enabled and x or a
     weight requires it, for a bias, widths other than 128 and bfloat16 / float64; RuntimeError for CPU tensors; ValueError for shapes."""
     fn = "project_tokens"
-    ws = _proj_weights(fn, weights)
-    n = len(ws)
-    if x.dim() < 1 or x.shape[-1] != TAIL_D:
-        raise ValueError(f"{fn}: x must be [..., {TAIL_D}] (got {list(x.shape)})")
-    rows = x.numel() // TAIL_D
-    if rows > TAIL_MAX_ROWS:
-        raise ValueError(f"{fn}: {rows} rows is above the supported {TAIL_MAX_ROWS}")
-    rot = [] if rot is None else [int(r) for r in rot]
-    if rot and (len(rot) != n or any(r < 0 or (r >= rows and not (rows == 0 and r == 0)) for r in rot)):
-        raise ValueError(f"{fn}: rot must hold one offset in 0..{rows - 1} per weight (got {rot})")
-    if x.dtype not in DTYPES:
-        raise NotImplementedError(f"{fn}: x must be float32 or float16 (got {x.dtype})")
-    if torch.is_grad_enabled() and any(t.requires_grad for t in [x] + ws):
-        raise NotImplementedError(f"{fn}: forward only -- call it under torch.no_grad(), and train with the layer's nn.Linear modules")
-    if compute_dtype is None:
-        compute_dtype = _tail_compute_dtype(fn, x)
-    if compute_dtype not in DTYPES:
-        raise NotImplementedError(f"{fn}: compute_dtype must be float32 or float16 (got {compute_dtype})")
-    if packed is not None and packed.dtype != compute_dtype:
-        raise ValueError(f"{fn}: packed holds {packed.dtype} weights, compute_dtype is {compute_dtype}")
-    _refuse(fn, [(x, "x")] + [(w, "a weight") for w in ws])
+    ws, rot, compute_dtype = _proj_checks(fn, x, weights, rot, packed, None, compute_dtype, True)
     if packed is None:
         packed = pack_projections(ws, compute_dtype)
-    out = _ext()._proj.token_proj_fwd(_rows(x.detach()), packed, n, rot, compute_dtype == torch.float16)
-    return out.view(x.shape[:-1] + (TAIL_D * n,))
+    out = _ext()._proj.token_proj_fwd(_rows(x.detach()), packed, len(ws), rot, compute_dtype == torch.float16)
+    return out.view(x.shape[:-1] + (TAIL_D * len(ws),))
+
+
+class _ProjectTokens(torch.autograd.Function):
+    """igs_token_proj_fwd with igs_token_proj_bwd behind it.  Returns the n column slices of the one buffer as n outputs, so that each
+    output's gradient arrives on its own (None for an unused one).  Saves x as the kernel read it and the transposed pack."""
+
+    @staticmethod
+    def forward(ctx, x, pack, pack_t, rot, out_half, *ws):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, pack_t)
+        ctx.rot, ctx.param_dtypes = rot, [w.dtype for w in ws]
+        buf = _ext()._proj.token_proj_fwd(x, pack, len(ws), rot, out_half)
+        return tuple(_cols(buf, j) for j in range(len(ws)))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gs):
+        n = len(gs)
+        if all(g is None for g in gs):
+            return (None,) * (5 + n)
+        x, pack_t = ctx.saved_tensors
+        dts = {g.dtype for g in gs if g is not None}
+        to = None if len(dts) == 1 and dts <= set(DTYPES) else torch.float32     # the C call takes one dtype for all of them
+        # rows with stride 1 inside and at least 128 between them are read in place; anything else (an expanded gradient) is copied once
+        gs = [None if g is None else _rows(g if to is None else g.to(to)) for g in gs]
+        dx, dws = _ext()._proj.token_proj_bwd(x, gs, pack_t, ctx.rot, bool(ctx.needs_input_grad[0]), [bool(w) for w in ctx.needs_input_grad[5:]],
+                                              x.dtype == torch.float16)
+        dws = [d if d is None or d.dtype == dt else d.to(dt) for d, dt in zip(dws, ctx.param_dtypes)]      # accumulated in float32, cast once
+        return (dx, None, None, None, None, *dws)
+
+
+def project_tokens_autograd(x, weights, rot=None, packed=None, packed_t=None, compute_dtype=None):
+    """project_tokens for training: the same checks, sizes, dtypes and values, returned as a tuple of the n results [..., 128], which are
+    the column slices of one [rows, 128 n] buffer (wattn.hip reads them in place), and a native backward.  When grad is disabled or neither
+    x nor a weight requires it this IS project_tokens plus the slicing.  Otherwise the forward is igs_token_proj_fwd and the backward
+    igs_token_proj_bwd (proj_bwd.hip): each output's gradient arrives on its own and is read in place with its stride and the roll (an
+    unused output's is skipped), d x comes back in x's dtype (no launch for it when x needs none) and each d W_j, accumulated in float32,
+    is cast once to its weight's dtype.  Saved: x as the kernel read it (itself where its rows have stride 1) and the transposed pack.
+    Once differentiable, deterministic (no atomics).  packed, packed_t: pack_projections(weights, compute_dtype, transposed=True), packed
+    here when either is absent; a wrong dtype or length raises ValueError.  Refusals as project_tokens', except that gradients are
+    served."""
+    fn = "project_tokens_autograd"
+    ws, rot, compute_dtype = _proj_checks(fn, x, weights, rot, packed, packed_t, compute_dtype, False)
+    n, shape = len(ws), x.shape[:-1] + (TAIL_D,)
+    if not (torch.is_grad_enabled() and any(t.requires_grad for t in [x] + ws)):
+        if packed is None:
+            packed = pack_projections(ws, compute_dtype)
+        buf = _ext()._proj.token_proj_fwd(_rows(x.detach()), packed, n, rot, compute_dtype == torch.float16)
+        return tuple(_cols(buf, j).view(shape) for j in range(n))
+    if packed is None or packed_t is None:
+        packed, packed_t = pack_projections(ws, compute_dtype, transposed=True)
+    outs = _ProjectTokens.apply(_rows(x), packed, packed_t, rot, compute_dtype == torch.float16, *ws)
+    return tuple(o.view(shape) for o in outs)
 
 
 def _head_linears(fn, layer):
@@ -750,38 +831,55 @@ def _head_linears(fn, layer):
     return lins
 
 
-def _head_pack(holder, which, dtype, weights):
-    """The pack of `weights` for a compute dtype, cached on the layer `holder` under the name `which` and rebuilt when a weight changed
-    (param_key)."""
+def _head_pack(holder, which, dtype, weights, transposed=False):
+    """The pack of `weights` for a compute dtype (transposed: the pack and the pack of the transposes), cached on the layer `holder` under
+    the name `which` and rebuilt when a weight changed (param_key)."""
     key = param_key(weights)
     cache = holder.__dict__.setdefault(HEAD_CACHE, {})
     entry = cache.get((which, dtype))
     if entry is None or entry["key"] != key:
-        entry = cache[(which, dtype)] = dict(key=key, pack=pack_projections(weights, dtype))
-    return entry["pack"]
+        entry = cache[(which, dtype)] = dict(key=key)
+    if transposed and "pack_t" not in entry:
+        pack, entry["pack_t"] = pack_projections(weights, dtype, transposed=True)
+        entry.setdefault("pack", pack)
+    elif "pack" not in entry:
+        entry["pack"] = pack_projections(weights, dtype)
+    return (entry["pack"], entry["pack_t"]) if transposed else entry["pack"]
 
 
 def _head_project(holder, which, x, linears, rot=None):
-    """[..., 128 n]: the products of x with the n Linears' weights, as one launch where LAYER_HEAD_MIN_OUTPUTS allows, as n nn.Linear calls
-    (and the rolls and the cat that rot and the layout ask for) otherwise."""
+    """The n products [..., 128] of x with the n Linears' weights.  One launch whose buffer's column slices are returned where
+    LAYER_HEAD_MIN_OUTPUTS allows (project_tokens; with a gradient needed: LAYER_HEAD_BWD_MIN_OUTPUTS and project_tokens_autograd), n
+    nn.Linear calls (and the rolls and the cat that rot and the layout ask for) otherwise."""
     dtype = _tail_compute_dtype("TransformerLayer", x)
-    if len(linears) >= LAYER_HEAD_MIN_OUTPUTS[dtype]:
-        weights = [lin.weight for lin in linears]
-        return project_tokens(x, weights, rot=rot, packed=_head_pack(holder, which, dtype, weights), compute_dtype=dtype)
+    weights = [lin.weight for lin in linears]
+    n = len(linears)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in [x] + weights):
+        if n >= LAYER_HEAD_BWD_MIN_OUTPUTS[dtype]:
+            pack, pack_t = _head_pack(holder, which, dtype, weights, transposed=True)
+            return project_tokens_autograd(x, weights, rot=rot, packed=pack, packed_t=pack_t, compute_dtype=dtype)
+    elif n >= LAYER_HEAD_MIN_OUTPUTS[dtype]:
+        buf = project_tokens(x, weights, rot=rot, packed=_head_pack(holder, which, dtype, weights), compute_dtype=dtype)
+        return tuple(_cols(buf, j) for j in range(n))
     outs = [lin(x) for lin in linears]
     if rot is not None:
         outs = [o if r == 0 else torch.roll(o.reshape(-1, TAIL_D), r, 0).view(o.shape) for o, r in zip(outs, rot)]
-    return outs[0] if len(outs) == 1 else torch.cat(outs, -1)
+    if n == 1:
+        return (outs[0],)
+    buf = torch.cat(outs, -1)
+    return tuple(_cols(buf, j) for j in range(n))
 
 
-def _heads_fused(tensors, weights):
-    """Whether a forward over `tensors` with the projection `weights` takes the fused launches: nothing needs a gradient, the activations
-    are float32 / float16 rows of 128 on a GPU, and LAYER_HEAD_FUSED has the compute dtype on."""
-    if torch.is_grad_enabled() and any(t.requires_grad for t in list(tensors) + list(weights)):
+def _heads_fused(tensors, weights, training=False):
+    """Whether a forward over `tensors` with the projection `weights` takes the fused launches: the activations are float32 / float16 rows
+    of 128 on a GPU and, when nothing needs a gradient, LAYER_HEAD_FUSED has the compute dtype on; when something does, the forward was
+    bound with training=True and LAYER_HEAD_BWD_NATIVE has it on."""
+    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in list(tensors) + list(weights))
+    if needs_grad and not training:
         return False
     if any(t.dtype not in DTYPES or not t.is_cuda or t.dim() < 1 or t.shape[-1] != TAIL_D for t in tensors):
         return False
-    return LAYER_HEAD_FUSED[_tail_compute_dtype("TransformerLayer", tensors[0])]
+    return (LAYER_HEAD_BWD_NATIVE if needs_grad else LAYER_HEAD_FUSED)[_tail_compute_dtype("TransformerLayer", tensors[0])]
 
 
 def _cols(buf, j):
@@ -791,16 +889,14 @@ def _cols(buf, j):
 def _layer_head_route(self, training, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits):
     _layer_served(self, attn_type)
     q, k, v = (getattr(self, a) for a in (LAYER_Q, LAYER_K, LAYER_V))
-    if not _heads_fused([source, target], [q.weight, k.weight, v.weight]):
+    if not _heads_fused([source, target], [q.weight, k.weight, v.weight], training):
         message = _layer_message(self, source, target, height, width, shifted_window_attn_mask, attn_type, with_shift, attn_num_splits)
         return _tail_route(self, training, message, source)
     if source is target:
-        buf = _head_project(self, "qkv", source, (q, k, v))
-        query, key, value = _cols(buf, 0), _cols(buf, 1), _cols(buf, 2)
+        query, key, value = _head_project(self, "qkv", source, (q, k, v))
     else:
-        query = _head_project(self, "q", source, (q,))
-        buf = _head_project(self, "kv", target, (k, v))
-        key, value = _cols(buf, 0), _cols(buf, 1)
+        (query,) = _head_project(self, "q", source, (q,))
+        key, value = _head_project(self, "kv", target, (k, v))
     message = _layer_attention(self, query, key, value, height, width, shifted_window_attn_mask, with_shift, attn_num_splits)
     return _tail_route(self, training, message, source)
 
@@ -828,7 +924,10 @@ def use_native_layer_heads(module, training=False):
     launches off per compute dtype and LAYER_HEAD_MIN_OUTPUTS leaves launches with too few outputs to nn.Linear.  Returns how many layers
     were bound; state_dict() keys and the classes are untouched.  The packs are kept on the layer per compute dtype and rebuilt when a
     weight's _version, data_ptr, dtype or device changes.  Raises NotImplementedError, before anything is changed, for everything
-    use_native_layer_tails refuses and for a q_proj / k_proj / v_proj that is not a bias-free nn.Linear(128, 128) in float32 / float16."""
+    use_native_layer_tails refuses and for a q_proj / k_proj / v_proj that is not a bias-free nn.Linear(128, 128) in float32 / float16.
+    training=True: a call that needs a gradient takes the same launches through project_tokens_autograd (proj_bwd.hip behind them) for the
+    compute dtypes that LAYER_HEAD_BWD_NATIVE turns on, a launch with fewer outputs than LAYER_HEAD_BWD_MIN_OUTPUTS staying nn.Linear; the
+    transposed pack is cached beside the pack.  Everything else is routed as with the default."""
     fn = "use_native_layer_heads"
     layers = _checked_layers(fn, module)
     for m in layers:
@@ -863,7 +962,8 @@ def _feature_forward(self, feature0, feature1, attn_type="swin", attn_num_splits
     tensors = [feature0, feature1]
     fused = (attn_type == "swin" and all(torch.is_tensor(t) and t.dim() == 4 and t.shape[1] == TAIL_D for t in tensors)
              and tuple(feature0.shape) == tuple(feature1.shape) and feature0.dtype == feature1.dtype
-             and _heads_fused([t.permute(0, 2, 3, 1) for t in tensors], weights + [p for pair in pairs for layer in pair for p in _tail_params(layer)]))
+             and _heads_fused([t.permute(0, 2, 3, 1) for t in tensors], weights + [p for pair in pairs for layer in pair for p in _tail_params(layer)],
+                              state["training"]))
     if not fused:
         return state["forward"](feature0, feature1, attn_type=attn_type, attn_num_splits=attn_num_splits, **kwargs)
     for pair in pairs:
@@ -889,14 +989,12 @@ def _feature_forward(self, feature0, feature1, attn_type="swin", attn_num_splits
         sq, sk, sv = (getattr(sa, a) for a in (LAYER_Q, LAYER_K, LAYER_V))
         cq, ck, cv = (getattr(ca, a) for a in (LAYER_Q, LAYER_K, LAYER_V))
         if bidirectional:                                                  # five products of the block's input; the last two land swapped
-            buf = _head_project(sa, "block", x, (sq, sk, sv, ck, cv), rot=(0, 0, 0, rows // 2, rows // 2))
-            key, value = _cols(buf, 3), _cols(buf, 4)
+            q, k, v, key, value = _head_project(sa, "block", x, (sq, sk, sv, ck, cv), rot=(0, 0, 0, rows // 2, rows // 2))
         else:
-            buf = _head_project(sa, "qkv", x, (sq, sk, sv))
-            kv = _head_project(ca, "kv", feature1, (ck, cv))
-            key, value = _cols(kv, 0), _cols(kv, 1)
-        x = _tail_route(sa, training, _layer_attention(sa, _cols(buf, 0), _cols(buf, 1), _cols(buf, 2), *geom), x)
-        x = _tail_route(ca, training, _layer_attention(ca, _head_project(ca, "q", x, (cq,)), key, value, *geom), x)
+            q, k, v = _head_project(sa, "qkv", x, (sq, sk, sv))
+            key, value = _head_project(ca, "kv", feature1, (ck, cv))
+        x = _tail_route(sa, training, _layer_attention(sa, q, k, v, *geom), x)
+        x = _tail_route(ca, training, _layer_attention(ca, _head_project(ca, "q", x, (cq,))[0], key, value, *geom), x)
     if not bidirectional:
         return x.view(b, h, w, c).permute(0, 3, 1, 2).contiguous()
     feature0, feature1 = x.chunk(chunks=2, dim=0)
@@ -918,7 +1016,10 @@ def use_native_feature_transformer(transformer, bidirectional, training=False):
     attention both work; a launch with fewer outputs than LAYER_HEAD_MIN_OUTPUTS (as shipped: the single q projection) stays nn.Linear;
     tails are routed as use_native_layer_tails(module, training) routes them.  A call that needs a gradient, another attn_type,
     or a compute dtype that LAYER_HEAD_FUSED turns off runs the forward that was bound over (whose layers are bound).  Raises
-    NotImplementedError, before anything is changed, for a module without such blocks and for everything use_native_layer_heads refuses."""
+    NotImplementedError, before anything is changed, for a module without such blocks and for everything use_native_layer_heads refuses.
+    training=True: a call that needs a gradient runs the same block loop for the compute dtypes that LAYER_HEAD_BWD_NATIVE turns on, its
+    launches through project_tokens_autograd (n = 5 with rot, or n = 3 / 2 / 1; fewer outputs than LAYER_HEAD_BWD_MIN_OUTPUTS stay
+    nn.Linear), its tails as use_native_layer_tails(training=True) routes them; a feature1 that needs no gradient gets no d x launch."""
     fn = "use_native_feature_transformer"
     pairs = _feature_blocks(fn, transformer)
     for pair in pairs:

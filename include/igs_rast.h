@@ -1284,6 +1284,41 @@ long long igs_token_proj_pack_elems(int n);
 int igs_token_proj_fwd(void* stream, long long T, int n, int compute_dtype, const void* x, int x_dtype, long long x_stride, const void* wpack,
                        const long long* rot, void* out, int out_dtype, long long out_stride);
 
+/* The backward of igs_token_proj_fwd (proj_bwd.hip; DESIGN.md section 28, "The backward").  Per row t of x and output j, g_j[t] is the
+ * upstream gradient of what the forward wrote for input row t, i.e. row (t + rot[j]) mod T of g[j]:
+ *     d x[t] = sum_j W_j^T g_j[t]   (j ascending, one accumulator chain),      d W_j = sum_t g_j[t] (x) x[t]   (t ascending).
+ * Runs on `stream`, reads nothing back, allocates nothing.  No float atomics: every sum has a fixed order (the rows of a slice, then the
+ * slices), two runs agree bit for bit, and a row's d x depends on that row's gradients and the weights only (not on T, the row's
+ * position, rot or x): a NaN in a row of a g[j] makes that row's d x and d W_j NaN, one in a row of x makes every wanted d W_j NaN, and
+ * either leaves every other row's d x as it was.
+ *   - T, n, compute_dtype, x, rot as igs_token_proj_fwd takes them.  g: n pointers to [T, 128] rows, all of g_dtype, each with its own row
+ *     stride g_stride[j] >= 128 (column slices of the forward's buffer are read in place); g[j] == NULL means that output j had no
+ *     gradient: it is skipped, and g_stride[j] is not read.  The array g itself may be NULL (no output had one).
+ *   - wpack_t, in compute_dtype, 16-byte aligned, igs_token_proj_pack_elems(n) elements: the pack of the TRANSPOSES, matrix j being W_j^T in
+ *     wpack's layout (16 tiles, output tile outermost).  Read only when dx is wanted.
+ *   - dx: [T, 128] with its dtype code and row stride (rounded once on store), or NULL: then the d x kernel is not launched.  With every
+ *     g[j] NULL it is written as zeros.  dW: n pointers to [128, 128] float32, row-major as nn.Linear keeps its weight, 16-byte aligned, or
+ *     NULL where not wanted; the array itself may be NULL.  A dW[j] whose g[j] is NULL is written as zeros.
+ *   - compute_dtype IGS_DTYPE_F32: v_mfma_f32_32x32x2_f32, operands widened on load, no half value anywhere.  IGS_DTYPE_F16:
+ *     v_mfma_f32_32x32x16_f16 with float32 accumulation; x, g and W^T are rounded to half once, as operands; d W is never rounded to half.
+ *   - The launches: for dx one launch by igs_token_proj_fwd's rule; for the weight gradients one launch in which a wave owns (slice of
+ *     rows, output, input tile) and one reduction.  A slice is 512 rows, or, where that would give more than
+ *     IGS_TOKEN_PROJ_BWD_MAX_SLICES slices, ceil(T / IGS_TOKEN_PROJ_BWD_MAX_SLICES) rows rounded up to a multiple of 128.  scratch:
+ *     igs_token_proj_bwd_scratch_bytes(T, n) = min(ceil(T / 512), IGS_TOKEN_PROJ_BWD_MAX_SLICES) x n x 65536 bytes (-1 for a T or n out of
+ *     range), 16-byte aligned, not initialised by the caller, read and written only when a dW[j] is wanted.
+ *   - Refused with IGS_RAST_E_INVALID and a message naming igs_token_proj_bwd before any HIP call: an unknown dtype code; n, T out of range;
+ *     a row stride (x, dx, a non-NULL g[j]'s) below 128 or above IGS_TOKENS_MAX_STRIDE; a rot[j] outside [0, T); a dW[j] not aligned to 16
+ *     bytes; with T > 0 and something wanted: a NULL x or scratch while some dW[j] is wanted, a NULL wpack_t while dx is wanted, a NULL
+ *     g_stride beside a non-NULL g[j], an x, g[j] or dx not aligned to its element size, a wpack_t or scratch not aligned to 16 bytes, a
+ *     scratch_bytes below the needed size, and any output (dx, a dW[j], the scratch) that overlaps an input (x, a g[j], wpack_t) or
+ *     another output.  T == 0 zero-fills the dW[j] that are given and writes no dx; with dx and every dW[j] NULL the call returns 0 and
+ *     launches nothing. */
+#define IGS_TOKEN_PROJ_BWD_MAX_SLICES 64
+long long igs_token_proj_bwd_scratch_bytes(long long T, int n);
+int igs_token_proj_bwd(void* stream, long long T, int n, int compute_dtype, const void* x, int x_dtype, long long x_stride,
+                       const void* const* g, int g_dtype, const long long* g_stride, const long long* rot, const void* wpack_t,
+                       void* scratch, long long scratch_bytes, void* dx, int dx_dtype, long long dx_stride, float* const* dW);
+
 /* Densification support (igs/models/gaussian_model.py:586-663,865-868; driven by infer_batch.py:308-321).
  * igs_densify_stats: per-step statistics of add_densification_stats + the max_radii2D update, for Gaussians with radii > 0:
  *   grad_accum += ||dL_dmean2D[:2]||, denom += 1, max_radii = max(max_radii, radii).

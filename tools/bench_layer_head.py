@@ -14,11 +14,16 @@ GPU, under no_grad.  JSON lines:
                  heads, q eager the same with LAYER_HEAD_MIN_OUTPUTS = 2 (the cross layer's q stays nn.Linear)
                  tails          use_native_window_attention + use_native_layer_tails alone
 
+  train         (--train only, written to its own file) forward + backward of one project_tokens_autograd call with n outputs (proj.hip and
+                proj_bwd.hip) against n F.linear calls under autograd, plus the swap cat for n = 5, on the same rows and the same upstream
+                gradients, one per output; x and every weight require a gradient; n = 1, 2, 3, 5 at both shapes
+
 The sides of a case alternate inside one process; the operands rotate through more than twice the Infinity Cache.  float16 is autocast to
 half on float32 rows, as the shipped models run.  The last line is {"case": "summary", "ratios": [...]}: for every case the other side's
 median over the native one's and whether the two min - max ranges are disjoint.
 
 usage: python tools/bench_layer_head.py [--reps 20] [--case launch|transformer|all] [--out FILE]
+       python tools/bench_layer_head.py --train [--reps 20] [--out profiles/layer_head_train_bench.jsonl]
 """
 import argparse
 import json
@@ -41,8 +46,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--case", default="all", choices=("launch", "transformer", "all"))
+    ap.add_argument("--train", action="store_true", help="time forward + backward instead (the case 'train' alone)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.train:
+        args.case = "train"
+        args.out = args.out or os.path.join(ROOT, "profiles", "layer_head_train_bench.jsonl")
     assert torch.cuda.is_available(), "bench_layer_head needs a GPU"
     import layer_head_restatement as LH
     import token_ops_restatement as TR
@@ -84,6 +93,42 @@ def main():
                     with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16, enabled=half):
                         record(case, ("native", "eager"), [native, eager])
             del ring
+            torch.cuda.empty_cache()
+
+    if args.case == "train":
+        for T in (32768, 163840):
+            xs = Ring(lambda i: torch.randn(T, 128, device=dev).requires_grad_(True), T * 128 * 4)
+            for half in (False, True):
+                cdt = torch.float16 if half else torch.float32
+                gs = Ring(lambda i: [torch.randn(T, 128, device=dev, dtype=cdt) for _ in range(5)], 5 * T * 128 * (2 if half else 4))
+                for n in (5, 3, 2, 1):
+                    ws = [torch.nn.Parameter(w) for w in LH.make_weights(n, n, torch.float32, dev)]
+                    pack, pack_t = TK.pack_projections(ws, cdt, transposed=True)
+                    rot = (0, 0, 0, T // 2, T // 2) if n == 5 else None
+                    case = dict(case="train", shape=[T, 128], dtype="float16 (autocast)" if half else "float32", n=n)
+
+                    def step(forward):
+                        x, g = xs.next(), gs.next()[:n]
+                        with torch.autocast("cuda", dtype=torch.float16, enabled=half):
+                            outs = forward(x)
+                        torch.autograd.backward(list(outs), g)
+                        x.grad = None
+                        for w in ws:
+                            w.grad = None
+
+                    def native_forward(x):
+                        return TK.project_tokens_autograd(x, ws, rot=rot, packed=pack, packed_t=pack_t, compute_dtype=cdt)
+
+                    def eager_forward(x):
+                        if n == 5:
+                            swapped = torch.cat(x.chunk(2, 0)[::-1], 0)
+                            return [F.linear(x, w) for w in ws[:3]] + [F.linear(swapped, w) for w in ws[3:]]
+                        return [F.linear(x, w) for w in ws]
+
+                    record(case, ("native", "eager"), [lambda: step(native_forward), lambda: step(eager_forward)])
+                del gs
+                torch.cuda.empty_cache()
+            del xs
             torch.cuda.empty_cache()
 
     if args.case in ("transformer", "all"):
